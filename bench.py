@@ -2,6 +2,7 @@
 """bench.py — frames/s of the detect(+camshift) hot path on N MI355X, ONE compact JSON line on rank 0.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--scaling weak|strong] [--feeds K]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N ...
 
@@ -21,17 +22,25 @@ Workloads (BASELINE.json configs) — benchlib/detect.py, c3.py, c5.py:
   c4  1280x720 detect, 128 frames per GPU (weak) or 1024 frames in total (--scaling strong: 1024 / N per GPU);
   c3  256 streams of 320x240: detect once + initTracker + 60 camshift track() calls per step;
   c5  --feeds K live 1920x1080 feeds per GPU (one batch of K frames per time step), detect every 30th frame.
-The default run (c2) also measures c4 (weak + strong), c3, c5, the depth-1 / PCIe-inclusive / single-frame variants, the
-JavaScript host and the exchange step's cost, each with its own bounded budget.  The LINE carries the contract's keys
-for the headline plus scalars of the sub-records (value_720p, c3_value, c5_value, ...: benchlib/line.py, < 4 KB,
-asserted); the full record tree — every sub-record with its own `roofline`, `cpu_baseline`, configuration and
-notes — is written to bench_sub.json (and gpurun_out/bench_sub.json).  --no-sub skips the sub-records (profiler runs).
+A plain run sets up, warms up, times exactly K steps (one block: barrier + synchronize on both sides, max over ranks),
+writes the outputs if asked and prints the line: the contract's keys, with `roofline` and `cpu_baseline` null.
 
-Timing: the K timed steps (barrier + synchronize on both sides, max over ranks) are repeated R times back to back
-("rounds"; R is chosen so that the timed work is ~0.4 s, K stays what the caller passed) and the MEDIAN block is
-reported, with the spread (`ms_per_step_min` / `ms_per_step_max`): a 20-step block of C2 is 5 ms of GPU time, far too
-short to quote on its own.  "dominant kernel" of a roofline = the kernel with the largest device time per step (the
-sum over its launches).
+--full adds everything else: the headline's dominant-kernel roofline and CPU baselines, and for the default workload (c2)
+c4 (weak + strong), c3, c5, the depth-1 / PCIe-inclusive / single-frame variants, the JavaScript host and the exchange
+step's cost, each with its own bounded budget.  The LINE then carries the contract's keys for the headline plus scalars
+of the sub-records (value_720p, c3_value, c5_value, ...: benchlib/line.py, < 4 KB, asserted); the full record tree —
+every sub-record with its own `roofline`, `cpu_baseline`, configuration and notes — is written to bench_sub.json.
+--no-sub skips the sub-records (profiler runs).  Timing under --full: the K timed steps are repeated R times back to
+back ("rounds"; R is chosen so that the timed work is ~0.4 s, K stays what the caller passed) and the MEDIAN block is
+reported, with the spread (`ms_per_step_min` / `ms_per_step_max`); --rounds R sets R for either kind of run.
+"dominant kernel" of a roofline = the kernel with the largest device time per step (the sum over its launches).
+
+--dump-outputs DIR: after the timed steps, what the last one returned to its caller, as DIR/<name>.npy in float64
+(benchlib/dump.py; record arrays become one row per frame / stream, one column per field): c2 / c4 `best_faces`
+(x, y, width, height, confidence, neighbors per frame) and `raw_hits` (the step's raw hit count; with an exchange step
+also `gathered_records`), c3 `best_faces` and `track_objects` of the 60th track() call (x, y, width, height, angle,
+sw_x, sw_y, sw_width, sw_height per stream), c5 the last step's `best_faces` or `track_objects`.  The inputs are
+seeded: the same arguments give the same inputs on every run.
 """
 import argparse
 import os
@@ -42,6 +51,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from benchlib.common import DEFAULT_STEPS, GEOM, SUB_STEPS, Env, device_copy_ceiling, free_port  # noqa: E402
+from benchlib.dump import write as write_outputs  # noqa: E402
 
 
 def parse():
@@ -72,12 +82,29 @@ def parse():
     ap.add_argument("--options", default="", help="ht_config.options of every context (result-preserving schedule A/B)")
     ap.add_argument("--force-launcher", action="store_true",
                     help="start the rank(s) through torch.distributed.run even for --gpus 1 (RCCL init + all-gather)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: auto rounds, rooflines, CPU baselines, depth-1 / PCIe / single-frame "
+                         "variants, in-run parity, the sub-records and the side file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float64)")
     a = ap.parse_args()
     if a.steps <= 0:
         a.steps = DEFAULT_STEPS[a.workload]
     if a.warmup < 0:
         a.warmup = max(3, a.steps // 10) if a.workload != "c5" else 1
+    if a.rounds <= 0 and not a.full:
+        a.rounds = 1  # a plain run times exactly --steps steps, once
     return a
+
+
+def strip_outputs(tree):
+    """pops every record's `_outputs` (arrays, not JSON); returns the top-level one"""
+    if not isinstance(tree, dict):
+        return None
+    out = tree.pop("_outputs", None)
+    for v in tree.values():
+        strip_outputs(v)
+    return out
 
 
 def sub_records(env, a, prim, t_budget):
@@ -214,6 +241,9 @@ def main():
         init_s = init_group(torch, dist, "gloo", rank, world, local) if world > 1 else None
         prim = stub_bench(Env(torch, dist, rank, world, local, stub=True), a)
         if rank == 0:
+            outputs = strip_outputs(prim)
+            if a.dump_outputs:
+                write_outputs(a.dump_outputs, outputs)
             line = bl.compose("STUB — launcher / collective plumbing only, not a measurement", prim, {}, world,
                               dict(backend="gloo", rccl_init_s=init_s))
             line["data"] = "stub"
@@ -237,34 +267,42 @@ def main():
     from benchlib.c5 import stream_bench
     from benchlib.detect import detect_bench
 
+    # a plain run: set up, warm up, time the steps, dump, print the line; everything else only with --full
+    lean = not a.full
     sub = {}
     if a.workload == "c5":
         prim = stream_bench(env, a, feeds=max(1, a.feeds), steps=a.steps, warm_cycles=max(a.warmup, 1),
-                            cpu_seconds=a.cpu_seconds)
+                            cpu_seconds=a.cpu_seconds, lean=lean)
         metric = ("frames/sec streaming 1920x1080 feeds (detect every 30th frame, camshift between); frames resident in "
                   "HBM")
     elif a.workload == "c3":
-        prim = c3_bench(env, a, a.steps, a.warmup, a.cpu_seconds)
+        prim = c3_bench(env, a, a.steps, a.warmup, a.cpu_seconds, lean=lean)
         metric = "frames/sec (1 full-cascade detect + 60 camshift track per stream) at 320x240"
     else:
         prim = detect_bench(env, a, a.workload, a.steps, a.warmup, scaling=a.scaling, frames_per_gpu=a.frames,
                             cpu_seconds=a.cpu_seconds, prewarm=a.prewarm, gather=gather,
-                            extras=world == 1 and not a.no_sub)
+                            extras=world == 1 and not a.no_sub, lean=lean)
         W, H, _ = GEOM[a.workload]
         metric = f"frames/sec full-cascade detect at {W}x{H}"
-        if a.workload == "c2" and a.scaling == "weak" and not a.no_sub:
+        if a.full and a.workload == "c2" and a.scaling == "weak" and not a.no_sub:
             sub = sub_records(env, a, prim, t_run)
     if rank == 0:
-        copy_gbs = device_copy_ceiling(torch)
-        for r in [prim] + [v for v in sub.values() if isinstance(v, dict)]:
-            if r.get("roofline"):
-                r["roofline"]["device_copy_gbs"] = round(copy_gbs, 1)
-                r["roofline"]["frac_of_device_copy"] = round(r["roofline"]["achieved"] / copy_gbs, 5)
-        extra = dict(rccl_init_s=rccl_init_s, device_copy_gbs=round(copy_gbs, 1),
-                     bench_wall_s=round(time.perf_counter() - t_run, 1))
+        outputs = strip_outputs(prim)
+        strip_outputs(sub)
+        if a.dump_outputs:
+            write_outputs(a.dump_outputs, outputs)
+        extra = dict(rccl_init_s=rccl_init_s)
+        if a.full:
+            copy_gbs = device_copy_ceiling(torch)
+            for r in [prim] + [v for v in sub.values() if isinstance(v, dict)]:
+                if r.get("roofline"):
+                    r["roofline"]["device_copy_gbs"] = round(copy_gbs, 1)
+                    r["roofline"]["frac_of_device_copy"] = round(r["roofline"]["achieved"] / copy_gbs, 5)
+            extra["device_copy_gbs"] = round(copy_gbs, 1)
+        extra["bench_wall_s"] = round(time.perf_counter() - t_run, 1)
         line = bl.compose(metric, prim, sub, world, extra)
         full = dict(line=dict(line), primary=prim, sub=sub)
-        bl.emit(line, full, line_out, write_sub=not a.no_sub)
+        bl.emit(line, full, line_out, write_sub=a.full and not a.no_sub)
     if dist.is_initialized():
         dist.destroy_process_group()
 

@@ -29,7 +29,10 @@ def track_exact(g, sw, to):
                abs(float(g["angle"]) - to["angle"]) < 1e-6)
 
 
-def c3_bench(env, a, steps, warmup, cpu_seconds=0.0):
+def c3_bench(env, a, steps, warmup, cpu_seconds=0.0, lean=False):
+    """lean: the record of the timed steps only (no roofline pass, parity check or CPU baseline).  The record's `_outputs`
+    hold what the last timed step returned to the caller: the best faces of its detect and the track objects of its 60th
+    track() call."""
     torch, rank, world, local = env.torch, env.rank, env.world, env.local
     from headtrackr_amd import synth
     from headtrackr_amd.api import Context
@@ -93,10 +96,19 @@ def c3_bench(env, a, steps, warmup, cpu_seconds=0.0):
     dts = env.timed_rounds(block, steps, a.rounds)
     dt, spread = round_stats(dts, steps)
     total_frames = world * nf * steps * (CALLS + 1)  # every processed frame: 1 detected + 60 tracked per stream
+    outputs = dict(best_faces=np.array(state["best"], copy=True), track_objects=np.array(state["tracked"], copy=True))
     if rank != 0:
         for cx in ctxs:
             cx.close()
         return None
+    if lean:
+        for cx in ctxs:
+            cx.close()
+        return {"value": round(total_frames / dt, 2), "unit": "frames/s", "steps": steps, "warmup": warmup, **spread,
+                "scaling": "weak", "config": {"workload": WORKLOAD_TEXT["c3"], "streams_per_gpu": nf,
+                                              "track_calls_per_step": CALLS, "width": W, "height": H,
+                                              "steps_in_flight": depth},
+                "roofline": None, "cpu_baseline": None, "_outputs": outputs}
     # Which form of k_cs_track_fused did the timed region launch (the library takes the 512-thread form, two workgroups per CU, when
     # another context of the device has work in flight at launch time)?  The library counts the launches per form (pseudo-timers of
     # ht_kernel_times, reset before the timed region).
@@ -184,6 +196,7 @@ def c3_bench(env, a, steps, warmup, cpu_seconds=0.0):
                                       "the device has work in flight; roofline = the majority form's launch alone on the chip"},
         "track_calls_per_s_device": round(nf / (call_ms * 1e-3), 1),
         "detected": int((state["best"]["neighbors"] > 0).sum()), "alive": int((state["tracked"]["width"] > 0).sum()),
+        "_outputs": outputs,
     }
     if world == 1 and cpu_seconds > 0:
         f = int(np.argmax(state["best"]["neighbors"] > 0))

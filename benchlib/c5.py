@@ -20,7 +20,7 @@ def init_rects(best, K):
             (W // 4, H // 4, W // 2, H // 2) for f in range(K)]
 
 
-def stream_bench(env, a, feeds=1, steps=300, warm_cycles=1, cpu_seconds=0.0):
+def stream_bench(env, a, feeds=1, steps=300, warm_cycles=1, cpu_seconds=0.0, lean=False):
     """`feeds` live 1920x1080 feeds per GPU.  The feeds of a GPU are frame-synchronous cameras: their frames of one
     time step form ONE batch of `feeds` frames on one context (one tracker stream per feed), so a step of K feeds costs
     the host the same handful of launches as a step of one feed.  Step 0, 30, 60, ...: full-cascade detect of every
@@ -30,7 +30,9 @@ def stream_bench(env, a, feeds=1, steps=300, warm_cycles=1, cpu_seconds=0.0):
       pcie_inclusive   every frame travels host -> GPU in the step (pinned buffer, double-buffered: step i+1 crosses
                        PCIe on the copy stream while step i is processed) — bounded by the link: 8.3 MB per frame;
     plus the per-step end-to-end latency distribution, PCIe included, strictly in turn (upload, process, result).
-    Returns the record on rank 0."""
+    lean: the resident timed steps only (no latency pass, PCIe variant, rooflines, CPU baseline or parity check).
+    Returns the record on rank 0; its `_outputs` hold what the last timed step returned to the caller (the best faces
+    of a detect step or the track objects of a track step)."""
     torch, rank, world, local = env.torch, env.rank, env.world, env.local
     from headtrackr_amd import synth
     from headtrackr_amd.api import Context
@@ -78,7 +80,7 @@ def stream_bench(env, a, feeds=1, steps=300, warm_cycles=1, cpu_seconds=0.0):
     for i in range(max(warm_cycles, 1) * 30 + 1):
         step_in_turn(i)
     lat = {"detect": [], "track": []}
-    for i in range(steps):  # latency pass (not a timed region)
+    for i in range(0 if lean else steps):  # latency pass (not a timed region)
         step_in_turn(i)
     last = {}
 
@@ -122,6 +124,17 @@ def stream_bench(env, a, feeds=1, steps=300, warm_cycles=1, cpu_seconds=0.0):
     rounds = a.rounds if a.workload == "c5" else 3
     block_resident(31)
     dt, spread = round_stats(env.timed_rounds(block_resident, steps, rounds, target_s=0.5), steps)
+    lr = last["r"]
+    outputs = {("best_faces" if is_detect(steps - 1) else "track_objects"): np.array(lr, copy=True)}
+    if lean:
+        ctx.close()
+        if rank != 0:
+            return None
+        return {"value": round(world * K * steps / dt, 2), "unit": "frames/s", "steps": steps, "warmup": warm_cycles,
+                **spread, "scaling": "weak",
+                "config": {"workload": f"C5: {K} frame-synchronous 1920x1080 RGBA feed(s) per GPU as one batch of {K} "
+                                       "frames per time step", "feeds_per_gpu": K, "width": W, "height": H},
+                "roofline": None, "cpu_baseline": None, "_outputs": outputs}
     block_pcie(31)
     dt_p, spread_p = round_stats(env.timed_rounds(block_pcie, steps, rounds, target_s=0.5), steps)
     graph_launches = ctx.graph_launches
@@ -177,7 +190,6 @@ def stream_bench(env, a, feeds=1, steps=300, warm_cycles=1, cpu_seconds=0.0):
                           f"track ({ct['value']} calls/s: {ct['sample']})")
     fps = world * K * steps / dt
     fps_p = world * K * steps / dt_p
-    lr = last["r"]
     # parity in the same run (after the timed regions): one 31-step cycle exactly as timed above — bind a new set every
     # step, detect (graph replay by now) + initTracker on step 0 / 30, enqueue-only track + collect otherwise — every
     # feed against the oracle
@@ -232,6 +244,6 @@ def stream_bench(env, a, feeds=1, steps=300, warm_cycles=1, cpu_seconds=0.0):
         "last_track": [float(lr["x"][0]), float(lr["y"][0]), float(lr["width"][0]), float(lr["height"][0])],
         "roofline": roofline, "camshift_roofline": cs_roofline,
         "device_ms": {"detect_step": round(det_ms, 4), "track_step": round(cs_ms, 4), "per_30_step_cycle": dev_ms},
-        "cpu_baseline": cpu, "vs_cpu": round(fps / cpu["value"], 1) if cpu else None}
+        "cpu_baseline": cpu, "vs_cpu": round(fps / cpu["value"], 1) if cpu else None, "_outputs": outputs}
     ctx.close()
     return rec

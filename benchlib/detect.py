@@ -15,10 +15,12 @@ def arena_estimate(W, H):
 
 
 def detect_bench(env, a, name, steps, warmup, scaling="weak", frames_per_gpu=0, cpu_seconds=0.0, prewarm=0.0,
-                 full=True, gather=None, unique=0, extras=True):
+                 full=True, gather=None, unique=0, extras=True, lean=False):
     """One detect workload: K timed steps (barrier + synchronize on both sides, max over ranks), then — on rank 0 —
     the live HIP-event roofline of the dominant kernel and the CPU baseline.  extras: the depth-1 and PCIe-inclusive
-    variants of the same step (bounded, after the timed region).  Returns the record (rank 0) or None."""
+    variants of the same step (bounded, after the timed region).  lean: the record of the timed steps only
+    (no profiling pass, no CPU baseline, no extras).  Returns the record (rank 0) or None; its `_outputs` hold what
+    the last timed step returned to the caller."""
     torch, dist, rank, world, local = env.torch, env.dist, env.rank, env.world, env.local
     from headtrackr_amd import distributed as hd
     from headtrackr_amd import native, synth
@@ -112,6 +114,10 @@ def detect_bench(env, a, name, steps, warmup, scaling="weak", frames_per_gpu=0, 
     dt, spread = round_stats(dts, steps)
     fps = total * steps / dt
     rank_ms = env.gather_scalar(float(np.median(env.last_own)) / steps * 1e3)  # every rank's own median block
+    # the last timed step's results as its caller received them (the best-face buffers are reused by later steps)
+    outputs = dict(best_faces=np.array(state["best"], copy=True), raw_hits=np.array([state["nhits"]], dtype=np.float64))
+    if gather_on:
+        outputs["gathered_records"] = state["gathered"].cpu().numpy().reshape(-1, hd.RECORD_F64)
 
     gather_ok = None
     if gather_on:  # outside the timed region: the gathered tensor must be the concatenation of every rank's records
@@ -130,6 +136,25 @@ def detect_bench(env, a, name, steps, warmup, scaling="weak", frames_per_gpu=0, 
         for cx in ctxs:
             cx.close()
         return None
+    par = (f"frames block-sharded over {world} GPU(s), all-gather of {nf_max}x64B best-face rect records (verified "
+           "against the per-rank results)") if world > 1 else "1 GPU"
+    rec = {
+        "value": round(fps, 2), "unit": "frames/s", "steps": steps, "warmup": warmup, **spread, "scaling": scaling,
+        "config": {"workload": WORKLOAD_TEXT[name], "frames_per_gpu": nf, "frames_total": total,
+                   "batches_in_flight": depth, "width": W, "height": H, "unique_frames": uniq,
+                   "frame_mix": "1/3 LCG noise, 1/3 smooth, 1/3 faces", "parallelism": par},
+        "roofline": None, "cpu_baseline": None,
+        "rank_ms_per_step_min": round(min(rank_ms), 4), "rank_ms_per_step_max": round(max(rank_ms), 4),
+        "_outputs": outputs,
+    }
+    if gather_ok is not None:
+        rec["allgather_verified"] = bool(gather_ok)
+    rec["hits_per_step"] = int(state["nhits"])
+    rec["faces_per_step"] = int((state["best"]["neighbors"] > 0).sum())
+    if lean:
+        for cx in ctxs:
+            cx.close()
+        return rec
 
     # ---- roofline of the dominant kernel: live HIP-event timing on the ctx stream ---------------------------------
     ctx.profile(True)
@@ -160,18 +185,7 @@ def detect_bench(env, a, name, steps, warmup, scaling="weak", frames_per_gpu=0, 
         roofline["co_dominant"][k]["traffic"] = traffic.get(k)
     dev_ms = sum(per_step.values())
     wall_ms = dt / steps * 1e3
-    par = (f"frames block-sharded over {world} GPU(s), all-gather of {nf_max}x64B best-face rect records (verified "
-           "against the per-rank results)") if world > 1 else "1 GPU"
-    rec = {
-        "value": round(fps, 2), "unit": "frames/s", "steps": steps, "warmup": warmup, **spread, "scaling": scaling,
-        "config": {"workload": WORKLOAD_TEXT[name], "frames_per_gpu": nf, "frames_total": total,
-                   "batches_in_flight": depth, "width": W, "height": H, "unique_frames": uniq,
-                   "frame_mix": "1/3 LCG noise, 1/3 smooth, 1/3 faces", "parallelism": par},
-        "roofline": roofline,
-        "rank_ms_per_step_min": round(min(rank_ms), 4), "rank_ms_per_step_max": round(max(rank_ms), 4),
-    }
-    if gather_ok is not None:
-        rec["allgather_verified"] = bool(gather_ok)
+    rec["roofline"] = roofline
     # each kernel against its OWN algorithmic bytes (per step): gray 5*W*H, pyramid build 2*(P - W*H) (every derived
     # plane written once, its source read once), tile scan P (every plane read once)
     own = {"gray": 5 * W * H * nf, "resample": 2 * (P - W * H) * nf, "scan_tiles": P * nf}
@@ -194,8 +208,6 @@ def detect_bench(env, a, name, steps, warmup, scaling="weak", frames_per_gpu=0, 
             frac_wall=round(valu / (wall_ms * 1e-3) / VALU_PEAK_WAVE_INSTS_PER_S, 4),
             frac_device=round(valu / (dev_ms * 1e-3) / VALU_PEAK_WAVE_INSTS_PER_S, 4),
             source="SQ_INSTS_VALU per step from " + TRAFFIC_SOURCE + "; peak = 1024 SIMDs x 2.4 GHz / 4")
-    rec["hits_per_step"] = int(state["nhits"])
-    rec["faces_per_step"] = int((state["best"]["neighbors"] > 0).sum())
     if full:
         ctx.detect_enqueue(a.flags | 16)  # one extra untimed pass with HT_SCAN_STATS for the survival curve
         ctx.detect_collect(cap=1 << 17)

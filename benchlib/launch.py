@@ -67,4 +67,5 @@ def stub_bench(env, a):
     return {"value": round(total * a.steps / dt, 2), "unit": "frames/s", "steps": a.steps, "warmup": a.warmup, **spread,
             "scaling": "weak", "config": {"workload": "stub", "frames_per_gpu": nf, "frames_total": total},
             "allgather_verified": bool(ok), "rank_ms_per_step_min": round(min(rank_ms), 4),
-            "rank_ms_per_step_max": round(max(rank_ms), 4), "roofline": None, "cpu_baseline": None}
+            "rank_ms_per_step_max": round(max(rank_ms), 4), "roofline": None, "cpu_baseline": None,
+            "_outputs": dict(best_faces=best, gathered_records=got.reshape(-1, hd.RECORD_F64))}

@@ -96,7 +96,7 @@ def test_bench_gpus_n_launches_n_ranks():
     """`python bench.py --gpus 2` — the one command the driver uses — must start 2 ranks itself: launcher -> torch.distributed.run ->
     rank environment -> barriers / max over ranks -> all-gather of the best-face records (verified) -> ONE line with n_gpus 2.
     HT_BENCH_STUB=1 swaps RCCL for gloo and the detect step for a stand-in, so the plumbing runs without GPUs."""
-    r, line = _bench(["--gpus", "2", "--steps", "4", "--warmup", "1"], {"HT_BENCH_STUB": "1"})
+    r, line = _bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--full"], {"HT_BENCH_STUB": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     assert line["n_gpus"] == 2 and line["ranks"] == 2 and line["launched_by_bench"] is True
     assert line["allgather_verified"] is True and line["steps"] == 4 and line["rounds"] >= 3
@@ -104,6 +104,26 @@ def test_bench_gpus_n_launches_n_ranks():
     assert line["config"]["frames_total"] == 2 * line["config"]["frames_per_gpu"]
     assert line["rank_ms_per_step_min"] <= line["rank_ms_per_step_max"] and line["data"] == "stub"
     assert len(r.stdout.strip().splitlines()[-1]) < 2000  # the one line stays a headline (benchlib/line.py)
+
+
+def test_plain_bench_times_exactly_steps_and_dumps_the_same_outputs(tmp_path):
+    """A plain run (no --full) times --steps steps once, and --dump-outputs DIR writes what the last timed step returned (float64 .npy,
+    rank 0): the same arguments give the same files."""
+    import numpy as np
+
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        r, line = _bench(["--gpus", "2", "--steps", "5", "--warmup", "1", "--dump-outputs", str(d)], {"HT_BENCH_STUB": "1"})
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert line["steps"] == 5 and line["rounds"] == 1 and line["ms_per_step"] > 0
+        assert line["ms_per_step_min"] == line["ms_per_step"] == line["ms_per_step_max"] and "sub_file" not in line
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    assert sorted(dumps[0]) == ["best_faces.npy", "gathered_records.npy"]
+    for name, arr in dumps[0].items():
+        assert arr.dtype == np.float64 and arr.size > 0
+        assert np.array_equal(arr, dumps[1][name]), name
+    assert dumps[0]["best_faces.npy"].shape == (line["config"]["frames_per_gpu"], 6)  # x, y, width, height, confidence, neighbors
 
 
 def test_bench_gpus_8_stub_is_cheap_and_loud():

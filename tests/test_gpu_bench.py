@@ -33,7 +33,7 @@ def test_launcher_path_with_rccl_on_one_gpu():
     step all-gathers its 128 best-face records through ncclAllGather, rank 0 verifies the gathered table — the N > 1 code path,
     world size 1."""
     txt, line = _run(["--gpus", "1", "--force-launcher", "--workload", "c4", "--no-sub", "--steps", "10", "--warmup", "3",
-                      "--cpu-seconds", "0", "--rounds", "3"])
+                      "--cpu-seconds", "0", "--rounds", "3", "--full"])
     assert line["n_gpus"] == 1 and line["ranks"] == 1 and line["launched_by_bench"] is True
     assert line["allgather_verified"] is True and line["rccl_init_s"] > 0
     assert line["config"]["frames_per_gpu"] == 128 and line["config"]["width"] == 1280
@@ -42,11 +42,44 @@ def test_launcher_path_with_rccl_on_one_gpu():
     assert len(txt) < 4000
 
 
+def test_plain_run_times_exactly_steps_and_dumps_what_the_last_step_returned(tmp_path):
+    """`--gpus 1 --steps K --warmup W` without --full: one block of exactly K timed steps, the contract's headline keys and nothing measured
+    beyond them; --dump-outputs writes the last step's best face per frame (the same on a second run, and the oracle's on the frames)."""
+    import numpy as np
+
+    from headtrackr_amd import synth
+    from headtrackr_amd.cascade import load_cascade
+    from oracle import ht_oracle as ho
+
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        txt, line = _run(["--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(d)], timeout=300)
+        for key in CONTRACT:
+            assert key in line, key
+        assert line["steps"] == 7 and line["warmup"] == 2 and line["rounds"] == 1 and line["dtype"] == "u8"
+        assert line["higher_is_better"] is True and line["unit"] == "frames/s" and line["ms_per_step"] > 0
+        assert abs(line["value"] - 256 / line["ms_per_step"] * 1e3) <= 1e-3 * line["value"]
+        assert line["roofline"] is None and line["cpu_baseline"] is None and "sub_file" not in line and "value_720p" not in line
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    assert sorted(dumps[0]) == ["best_faces.npy", "raw_hits.npy"]
+    for name, arr in dumps[0].items():
+        assert arr.dtype == np.float64 and np.array_equal(arr, dumps[1][name]), name
+    best = dumps[0]["best_faces.npy"]  # x, y, width, height, confidence, neighbors per frame
+    assert best.shape == (256, 6) and (best[:, 5] > 0).sum() > 0
+    frames = synth.mixed_batch(256, 320, 240, seed0=1234)
+    pick = [f for f in range(0, 256, 37)]
+    want = ho.best_faces(frames[pick], load_cascade().blob, 1)
+    for j, f in enumerate(pick):
+        for c, k in enumerate(("x", "y", "width", "height", "confidence", "neighbors")):
+            assert best[f, c] == float(want[k][j]), (f, k, best[f], want[j])
+
+
 def test_default_line_is_compact_and_complete(tmp_path):
-    """the driver's command shape (`--gpus 1 --steps K --warmup W`, all sub-records) with a short CPU budget: the line stays under
+    """the driver's command shape (`--gpus 1 --steps K --warmup W`, all sub-records, --full) with a short CPU budget: the line stays under
     4 KB with every contract key, roofline and cpu_baseline of the headline, the scalars of the sub-records, parity of its own run;
     the full tree is in bench_sub.json."""
-    txt, line = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "1.5"], timeout=900)
+    txt, line = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "1.5", "--full"], timeout=900)
     assert len(txt.encode()) < 4000, len(txt)
     for k in CONTRACT:
         assert k in line, k

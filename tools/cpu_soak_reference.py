@@ -9,7 +9,11 @@ tests/test_oracle_golden.py: input CRC, whitebalance, gray bytes, every pyramid 
 confidence, grouped rects; camshift search window / x / y / width / height exact and the angle to 1e-12.  On the same reference
 output the PRODUCT's host-side code is checked too (no GPU needed): ht_group_rects of libheadtrackr_hip.so, and through
 tests/js/facade_cpu.js the JS facade's grouping, Smoother and headposition.Tracker on random sequences.
-Needs /root/reference and node (this container, not the GPU box).  Exit 1 on the first mismatch, with the case's generator spec."""
+Needs the reference and node.  Exit 1 on the first mismatch, with the case's generator spec.
+
+    tools/cpu_soak_reference.py --record FILE BATCHES SEED   the reference's output of the first BATCHES batches of SEED, into FILE
+    tools/cpu_soak_reference.py --replay FILE                the same checks against FILE's recorded output instead of a live reference
+                                                             (node only: tests/golden/soak_seed*.json, tests/test_reference_soak.py)"""
 import importlib.util
 import json
 import os
@@ -31,14 +35,25 @@ def load(path, name):
     return m
 
 
-BUDGET = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
-SEED = int(sys.argv[2]) if len(sys.argv) > 2 else int(time.time()) & 0x7FFFFFFF
+RECORD = REPLAY = None
+if len(sys.argv) > 1 and sys.argv[1] == "--record":
+    RECORD, BATCHES, SEED = sys.argv[2], int(sys.argv[3]), int(sys.argv[4])
+elif len(sys.argv) > 1 and sys.argv[1] == "--replay":
+    with open(sys.argv[2]) as fh:
+        REPLAY = json.load(fh)
+    SEED = REPLAY["seed"]
+else:
+    BUDGET = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
+    SEED = int(sys.argv[2]) if len(sys.argv) > 2 else int(time.time()) & 0x7FFFFFFF
 rng = np.random.default_rng(SEED)
 mg = load(os.path.join(ROOT, "tests", "golden", "make_golden.py"), "make_golden")
 tg = load(os.path.join(ROOT, "tests", "test_oracle_golden.py"), "test_oracle_golden")
 cascade = load_cascade()
 # the JS facade's state machines need the oracle as a Node addon (tests/test_js_host.py builds it: tests/js/oracle_addon.node)
 MOCK = os.path.exists(os.path.join(ROOT, "tests", "js", "oracle_addon.node"))
+# a recording holds the facade cases whenever it was made with the addon; a replay generates them to keep the random stream in
+# step, and checks them where the addon exists
+FACADE = REPLAY["facade"] if REPLAY else MOCK
 
 
 def rand_gen(w, h):
@@ -250,34 +265,50 @@ def main():
     t0 = time.time()
     tot = dict(detect=0, planes=0, raw=0, grouped=0, camshift=0, calls=0, post=0, facade_checks=0, facade_frames=0, sizes=set())
     batch_no = 0
+    recorded = []
+
+    def more():
+        if REPLAY:
+            return batch_no < len(REPLAY["batches"])
+        if RECORD:
+            return batch_no < BATCHES
+        return time.time() - t0 < BUDGET
+
     with tempfile.TemporaryDirectory() as td:
         mg.OUT = td
-        while time.time() - t0 < BUDGET:
+        while more():
             cases = [detect_case(batch_no * 100 + i) for i in range(16)] + [camshift_case(batch_no * 100 + i) for i in range(8)]
             for i in range(4):
                 cases += post_cases(batch_no * 100 + i)
-            if MOCK:
+            if FACADE:
                 for i in range(2):
                     cases += facade_cases(batch_no * 100 + i)
-            sys.stdout.flush()
-            sys.stderr.flush()
-            keep, null = (os.dup(1), os.dup(2)), os.open(os.devnull, os.O_WRONLY)
-            os.dup2(null, 1)  # the harness (a child process) prints a line per case
-            os.dup2(null, 2)
-            try:
-                mg.run(cases, "soak.json")
-            finally:
+            if REPLAY:
+                res = REPLAY["batches"][batch_no]
+                assert [c["name"] for c in res["cases"]] == [c["name"] for c in cases], "recording does not match the seed's cases"
+            else:
                 sys.stdout.flush()
-                os.dup2(keep[0], 1)
-                os.dup2(keep[1], 2)
-                for fd in keep + (null,):
-                    os.close(fd)
-            with open(os.path.join(td, "soak.json")) as f:
-                res = json.load(f)
+                sys.stderr.flush()
+                keep, null = (os.dup(1), os.dup(2)), os.open(os.devnull, os.O_WRONLY)
+                os.dup2(null, 1)  # the harness (a child process) prints a line per case
+                os.dup2(null, 2)
+                try:
+                    mg.run(cases, "soak.json")
+                finally:
+                    sys.stdout.flush()
+                    os.dup2(keep[0], 1)
+                    os.dup2(keep[1], 2)
+                    for fd in keep + (null,):
+                        os.close(fd)
+                with open(os.path.join(td, "soak.json")) as f:
+                    res = json.load(f)
+                res.pop("vote_template", None)  # pinned by tests/golden/detect.json
+                if RECORD:
+                    recorded.append(json.loads(json.dumps(res)))  # the checks below add fields to res
             try:
                 check_product_host(td, res)
                 tot["post"] += 8
-                if MOCK:
+                if FACADE and MOCK:
                     chk, frames = check_facade(td, cases, res)
                     tot["facade_checks"] += chk
                     tot["facade_frames"] += frames
@@ -303,13 +334,17 @@ def main():
                     print("MISMATCH oracle vs reference:", json.dumps(spec), "\n", e)
                     return 1
             batch_no += 1
-    print(f"oracle vs reference JS soak, seed {SEED}, {time.time() - t0:.0f} s: {tot['detect']} detect cases + {tot['camshift']} camshift set-ups over "
+    if RECORD:
+        with open(RECORD, "w") as fh:
+            json.dump(dict(seed=SEED, facade=FACADE, batches=recorded), fh, separators=(",", ":"))
+    print(f"oracle vs reference JS soak ({'recorded output' if REPLAY else 'live'}), seed {SEED}, {time.time() - t0:.0f} s: {tot['detect']} detect cases + {tot['camshift']} camshift set-ups over "
           f"{len(tot['sizes'])} geometries; {tot['planes']} pyramid planes (size + CRC), {tot['raw']} raw rects incl. confidence bits, "
           f"{tot['grouped']} grouped faces, {tot['calls']} track() calls (window / x / y / width / height exact, angle to 1e-12): all identical.  "
           f"Product host code on the same reference output: ht_group_rects (C) and the JS facade's seq construction + ccv._group on every raw list, "
           f"{tot['post']} random Smoother / headposition sequences through headtrackr_amd/js: all identical"
           + (f"; facetrackr.Tracker / headtrackr.Tracker body / main.js loop on {tot['facade_frames']} frames of random sequences through the "
-             f"unchanged facade on the oracle-backed mock addon (tests/js/parity_cpu.js): {tot['facade_checks']} checks, all passed" if MOCK else ""))
+             f"unchanged facade on the oracle-backed mock addon (tests/js/parity_cpu.js): {tot['facade_checks']} checks, all passed"
+             if FACADE and MOCK else ""))
     return 0
 
 

@@ -8,11 +8,11 @@ t0=$(date +%s)
 timeout 1500 python -m pytest tests -m gpu -q --no-header -p no:cacheprovider --durations=5 > $OUT/pytest_gpu.log 2>&1; echo "pytest exit $? ($(( $(date +%s) - t0 )) s)"; grep -E "passed|failed|camshift parity" $OUT/pytest_gpu.log | tail -3
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
 t0=$(date +%s)
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench driver-style exit $? ($(( $(date +%s) - t0 )) s, $(wc -c < $OUT/bench_driver.json) bytes)"; cut -c1-200 $OUT/bench_driver.json
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench driver-style exit $? ($(( $(date +%s) - t0 )) s, $(wc -c < $OUT/bench_driver.json) bytes)"; cut -c1-200 $OUT/bench_driver.json
 cp $OUT/bench_sub.json $OUT/bench_driver_sub.json 2>/dev/null
-timeout 900 python bench.py --no-sub --cpu-seconds 0 > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench flag-less (c2 only) exit $?"; cut -c1-200 $OUT/bench_default.json
+timeout 900 python bench.py --full --no-sub --cpu-seconds 0 > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench flag-less (c2 only) exit $?"; cut -c1-200 $OUT/bench_default.json
 for d in 2 3 4; do
-  timeout 200 python bench.py --workload c3 --no-sub --cpu-seconds 0 --pipeline $d 2>/dev/null | python -c "
+  timeout 200 python bench.py --full --workload c3 --no-sub --cpu-seconds 0 --pipeline $d 2>/dev/null | python -c "
 import sys, json
 j = json.loads(sys.stdin.readline())
 print('c3 steps in flight $d:', j['value'], 'frames/s', j['ms_per_step'], 'ms/step', j.get('parity_exact'))" | tee -a $OUT/c3_depth.txt
