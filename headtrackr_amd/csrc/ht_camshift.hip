@@ -44,25 +44,16 @@ namespace {
 #endif
 
 constexpr int CS_NT = 512;          // threads of the mean-shift workgroup
-#ifndef HT_HIST_NT
-#define HT_HIST_NT 1024
-#endif
-constexpr int HIST_NT = HT_HIST_NT;
+constexpr int HIST_NT = 1024;
 // Partial histograms per stream: enough chunks to put ~256 workgroups of 1024 threads on the chip (a single 1080p stream gets 127,
 // eight of them 32 each, a batch of >= 32 streams 8 each), each chunk >= 16384 pixels and a multiple of 4 * HIST_NT.  Round 5, same box,
 // the C5 track step of 8 / 1 feeds (tools/gpu_cs_step.py): 256 threads x ~1024 workgroups 39.1 / 27.8 us, 512 x 512: 36.5 / 24.6,
 // 1024 x 512: 36.4 / 24.2, 1024 x 256: 35.8 / 24.0 (a quarter of the chunk histograms to write and to sum), 8 loads in flight per
 // thread instead of 4: 39.4 / 26.8.
-#ifndef HT_HIST_MAXCHUNKS
-#define HT_HIST_MAXCHUNKS 128
-#endif
-#ifndef HT_HIST_UNROLL
-#define HT_HIST_UNROLL 4
-#endif
-#ifndef HT_HIST_TARGET_WGS
-#define HT_HIST_TARGET_WGS 256  // workgroups of a k_cs_hist launch, all streams together
-#endif
-inline uint32_t hist_max_chunks(int nstreams) { return (uint32_t)std::min(HT_HIST_MAXCHUNKS, std::max(8, HT_HIST_TARGET_WGS / std::max(nstreams, 1))); }
+constexpr int HIST_MAXCHUNKS = 128;
+constexpr int HIST_UNROLL = 4;
+constexpr int HIST_TARGET_WGS = 256;  // workgroups of a k_cs_hist launch, all streams together
+inline uint32_t hist_max_chunks(int nstreams) { return (uint32_t)std::min(HIST_MAXCHUNKS, std::max(8, HIST_TARGET_WGS / std::max(nstreams, 1))); }
 inline void hist_chunks(uint32_t npix, uint32_t max_chunks, uint32_t *chunk_px, uint32_t *nchunks) {
     uint32_t n = std::min<uint32_t>((npix + 16383u) / 16384u, max_chunks);
     n = std::max<uint32_t>(n, 1u);
@@ -76,12 +67,8 @@ inline void hist_chunks(uint32_t npix, uint32_t max_chunks, uint32_t *chunk_px, 
 // bins): with t = px & 0xf0f0f0 = r<<4 | g<<12 | b<<20 (r, g, b the 4-bit fields), t + (t << 12) puts g at bit 24 next to b at bit 20
 // (all fields of the sum are disjoint: no carries; b << 32 leaves the register), t << 24 puts r at bit 28, and the bin is bits 20-31.
 __device__ __forceinline__ uint32_t cs_bin(uint32_t px) {
-#ifdef HT_CS_BIN_FIELDS  // A/B (tools/build_alt.py): the field-by-field form
-    return ((px & 0xf0u) << 4) | ((px >> 8) & 0xf0u) | ((px >> 20) & 0xfu);
-#else
     const uint32_t t = px & 0x00f0f0f0u;
     return ((t << 24) | (t + (t << 12))) >> 20;  // v_and, v_mul_u32_u24 0x1001, v_lshl_or_b32, v_lshrrev
-#endif
 }
 
 // A batch of PREDICATED loads (`v = ok ? p[i] : 0`) followed by cs_bin: the optimiser folds the bin's first instruction (`& 0xf0f0f0`, which maps
@@ -213,28 +200,28 @@ __global__ __launch_bounds__(HIST_NT) void k_cs_hist(const uint8_t *__restrict__
     const uint32_t nquad = (end - beg) / 4;
     const uint4 *img4 = reinterpret_cast<const uint4 *>(frame + (size_t)beg * 4);
     const uint32_t iters = chunk_px / (4 * HIST_NT);
-    // HT_HIST_UNROLL loads of a thread in flight before the first bin is counted, written out: the wave-level merge below is convergent code,
+    // HIST_UNROLL loads of a thread in flight before the first bin is counted, written out: the wave-level merge below is convergent code,
     // which keeps the optimiser from unrolling the loop itself (`#pragma unroll` was refused), and with ONE 16-byte load in flight per
     // thread the pass was a chain of chunk_px / 1024 memory round trips (16 x ~1.3 us at 1080p = the kernel's whole duration)
-    for (uint32_t it0 = 0; it0 < iters; it0 += HT_HIST_UNROLL) {
-        uint4 pv[HT_HIST_UNROLL];
-        bool onv[HT_HIST_UNROLL];
+    for (uint32_t it0 = 0; it0 < iters; it0 += HIST_UNROLL) {
+        uint4 pv[HIST_UNROLL];
+        bool onv[HIST_UNROLL];
 #pragma unroll
-        for (int u = 0; u < HT_HIST_UNROLL; u++) {
+        for (int u = 0; u < HIST_UNROLL; u++) {
             const uint32_t i = (it0 + (uint32_t)u) * HIST_NT + threadIdx.x;
             onv[u] = it0 + (uint32_t)u < iters && i < nquad;
             pv[u] = make_uint4(0u, 0u, 0u, 0u);
             if (onv[u]) pv[u] = img4[i];
         }
 #pragma unroll
-        for (int u = 0; u < HT_HIST_UNROLL; u++) {
+        for (int u = 0; u < HIST_UNROLL; u++) {
             CS_BATCH_LOADED(pv[u].x);
             CS_BATCH_LOADED(pv[u].y);
             CS_BATCH_LOADED(pv[u].z);
             CS_BATCH_LOADED(pv[u].w);
         }
 #pragma unroll
-        for (int u = 0; u < HT_HIST_UNROLL; u++) {
+        for (int u = 0; u < HIST_UNROLL; u++) {
             if (it0 + (uint32_t)u >= iters) break;  // workgroup-uniform
             const uint4 p = pv[u];
             const bool on = onv[u];

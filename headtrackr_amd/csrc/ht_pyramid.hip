@@ -129,11 +129,8 @@ __global__ __launch_bounds__(256) void k_gray_inplace(uint8_t *__restrict__ fram
 //   3. every thread produces 4 pixels from LDS bytes: top/bot/v lerps, v_rndne_f64 (round half to even), one dword store.
 // Tiles whose source span does not fit (only the last 1-3 pixel levels, where the ratio can reach 6) read HBM directly.
 constexpr int RS_TW = 64;                   // destination tile width; its height is 16 * RPT (RPT rows per thread)
-#ifndef HT_RS_PITCH
-#define HT_RS_PITCH 160
-#endif
 constexpr int RS_ROWB = 160;                // LDS source tile: payload bytes per row (64 * 2.04 + 2, dword aligned start; 10 threads x 16 bytes)
-constexpr int RS_SP = HT_RS_PITCH;          // ... and its row pitch (a multiple of 16: rows are written as 16-byte chunks)
+constexpr int RS_SP = 160;                  // ... and its row pitch (a multiple of 16: rows are written as 16-byte chunks)
 static_assert(RS_SP >= RS_ROWB && RS_SP % 16 == 0, "RS_SP");
 // A workgroup's latency chain (taps -> barrier -> HBM loads -> barrier -> LDS reads -> store) is fixed, so the tile
 // height decides how much of it is amortised: with 16 rows (1 row per thread) the 260k waves of one C2 generation run
@@ -223,24 +220,11 @@ __device__ __forceinline__ uint32_t rs_pixel_f64(const uint8_t *p, const uint8_t
 // ties (a quarter of all pixels) would all take the fallback: it is computed in integers instead, RNE included.
 constexpr float RS_EPS = 1.0f / 8192.0f;
 
-#ifndef HT_RS_WPS
-#define HT_RS_WPS 6  // waves per SIMD the register allocator must leave room for (6: <= 80 VGPRs, 5: <= 96)
-#endif
+constexpr int RS_WPS = 6;  // waves per SIMD the register allocator must leave room for (6: <= 80 VGPRs, 5: <= 96)
 // Measured on one box, device ms per step of the pyramid generations 1-5 at 128 x 720p / bench frames/s (profiles/r03_resample_ab.txt):
 // round-2 loop 0.503 / 110.9 k; flat loop 6 waves 0.472 / 116.0 k; + packed 0.472 / 116.3 k; flat loop with the next row's taps in flight
-// (needs 5 waves: 84 VGPRs) 0.490 / 112.9 k; the same + packed 0.491 / 112.3 k.
-#ifndef HT_RS_ROWPF
-#define HT_RS_ROWPF 0  // 1 = the 16 taps of the next row are in flight while a row is evaluated (32 tap registers: needs HT_RS_WPS 5), 0 = one row at a time
-#endif
-#ifndef HT_RS_PACKED
-#define HT_RS_PACKED 1  // 1 = top / bot of a pixel as one packed pair (v_pk_add_f32 + v_pk_fma_f32: 4.5 cycles for two, tools/micro/valu_rate_bench.hip)
-#endif
-#if defined(HT_RS_EXPERIMENT) && HT_RS_EXPERIMENT && !defined(HT_DEBUG_KNOBS)
-#error "HT_RS_EXPERIMENT builds compute wrong results by design: only together with -DHT_DEBUG_KNOBS (tools/build_alt.py)"
-#endif
-#ifndef HT_RS_EXPERIMENT
-#define HT_RS_EXPERIMENT 0  // timing experiments only (results are wrong): 1 = no pixel arithmetic, 2 = no source loads after the first frame, 3 = no stores
-#endif
+// (needs 5 waves: 84 VGPRs) 0.490 / 112.9 k; the same + packed 0.491 / 112.3 k.  Hence one row of taps at a time, and top / bot of a
+// pixel as one packed pair (v_pk_add_f32 + v_pk_fma_f32: 4.5 cycles for two, tools/micro/valu_rate_bench.hip).
 #if defined(HT_RS_PHASES)  // tools/gpu_rs_phases.py: shader-clock stamps of every phase of every frame iteration, plain stores into per-workgroup slots
 __device__ unsigned long long g_rs_tl[16384][8][8];  // [slot][frame iteration & 7][stamp]
 __device__ unsigned long long g_rs_launch[1024][4];  // per launch (keyed by its tiles per frame): workgroups, sum of workgroup lifetimes
@@ -292,7 +276,7 @@ __device__ unsigned long long g_rs_timeline[1 << 16][8];
 // extent and tap tables are computed once, and the source tile of frame f+1 is loaded (into registers) while the pixels
 // of frame f are computed from LDS.  Frames of a group are consecutive, so they stay inside one XCD's share of the batch.
 template <int RPT>
-__global__ __launch_bounds__(256, HT_RS_WPS) void k_resample(const HtResampleJob *__restrict__ tiles, uint8_t *__restrict__ arena,
+__global__ __launch_bounds__(256, RS_WPS) void k_resample(const HtResampleJob *__restrict__ tiles, uint8_t *__restrict__ arena,
                                                   uint64_t arena_stride, uint32_t blocks_per_frame, uint32_t ngroups,
                                                   uint32_t nframes, uint32_t group_frames) {
     constexpr int TH = 16 * RPT;          // destination rows per tile (at most)
@@ -301,10 +285,9 @@ __global__ __launch_bounds__(256, HT_RS_WPS) void k_resample(const HtResampleJob
     __shared__ RsTap s_col[RS_TW], s_row[TH];
     uint32_t gidx, blk;
     if (!xcd_item(blocks_per_frame, ngroups, &gidx, &blk)) return;
-#ifndef HT_RS_PRIO
-#define HT_RS_PRIO 1  // measured: 1 -> resample -1 % / -1.4 %; 2 (also every frame's LDS write + load issue ahead of the pixel arithmetic): no better
-#endif
-    if (HT_RS_PRIO) __builtin_amdgcn_s_setprio(3);  // record, extent, first loads, tap tables: ahead of other wavefronts' pixel arithmetic
+    // record, extent, first loads, tap tables: ahead of other wavefronts' pixel arithmetic (measured: resample -1 % / -1.4 %; every
+    // frame's LDS write + load issue at high priority as well: no better)
+    __builtin_amdgcn_s_setprio(3);
 #ifdef HT_RS_PHASES
     const uint32_t rs_slot = (blockIdx.x ^ (blocks_per_frame * 2654435761u)) & 16383u;  // different launches mostly land in different slots
     uint32_t rs_iter = 0;
@@ -364,8 +347,8 @@ __global__ __launch_bounds__(256, HT_RS_WPS) void k_resample(const HtResampleJob
         //   * everything that depends only on the tile geometry is computed ONCE per workgroup (row offsets, row weights as
         //     binary32, byte mask, store predicates);
         //   * the loop is specialised on the number of passes (NP) and on the box mode, and a row is straight-line code: every tap
-        //     is loaded from CLAMPED coordinates whether or not its pixel is drawn (the byte mask zeroes what lies outside dw x dh),
-        //     and the 16 taps of row q + 1 are in flight while row q is evaluated (~16 VALU instructions per pixel);
+        //     is loaded from CLAMPED coordinates whether or not its pixel is drawn (the byte mask zeroes what lies outside dw x dh):
+        //     ~16 VALU instructions per pixel;
         //   * global memory is addressed through a buffer descriptor of the frame (scalar registers) + 32-bit per-thread offsets +
         //     a scalar offset: no 64-bit per-thread address arithmetic, nothing for loop strength reduction to turn into per-thread
         //     induction variables;
@@ -402,7 +385,7 @@ __global__ __launch_bounds__(256, HT_RS_WPS) void k_resample(const HtResampleJob
             RS_TILE_TO_LDS();
         }
         __syncthreads();
-        if (HT_RS_PRIO == 1) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
         RS_STAMP(1);
         const int cbase = x0 - X0;  // first column of this thread inside the tile
         int ia[4];
@@ -411,10 +394,6 @@ __global__ __launch_bounds__(256, HT_RS_WPS) void k_resample(const HtResampleJob
         for (int k = 0; k < 4; k++) {
             const RsTap *ct = &s_col[min(cbase + k, ncols - 1)];
             ia[k] = ct->a - xa, ctf[k] = (float)ct->t;
-        }
-        if (HT_RS_EXPERIMENT == 4) {  // timing experiment (wrong results): conflict-free tap addresses — what would halving the LDS cycles buy?
-#pragma unroll
-            for (int k = 0; k < 4; k++) ia[k] = (tid & 31) * 4 + ((tid >> 5) & 1) * 1280 + k * 160 * 2;
         }
         // the right taps are read at p + 1 — with a "1" the optimiser cannot see: hipcc otherwise fuses p[0] and p[1] into ONE
         // ds_read_u16 at an arbitrary byte address (see rs_pixel_f64)
@@ -437,7 +416,7 @@ __global__ __launch_bounds__(256, HT_RS_WPS) void k_resample(const HtResampleJob
             for (int q = 0; q < NP; q++) {
                 const int y = yt + 16 * q;
                 const RsTap *ry = &s_row[min(y - Y0, nrows - 1)];
-                roff[q] = HT_RS_EXPERIMENT == 4 ? (uint32_t)(q * 3 * RS_SP) : (uint32_t)((ry->a - ya) * RS_SP);
+                roff[q] = (uint32_t)((ry->a - ya) * RS_SP);
                 rtf[q] = (float)ry->t;
                 rv[q] = y < dh;  // a drawn row (pxmask is 0 where the thread has no drawn column)
                 st[q] = y < ch && x0 < dst_stride;
@@ -451,7 +430,7 @@ __global__ __launch_bounds__(256, HT_RS_WPS) void k_resample(const HtResampleJob
                 for (int q = 0; q < NP; q++) asm volatile("" : "+v"(roff[q]));
                 RS_STAMP(2);
                 uint4 v0, v1, v2;
-                if (f + 1 < f1 && HT_RS_EXPERIMENT != 2) {  // the next frame's source tile (scalar offset = one arena): in flight during this frame's pixels
+                if (f + 1 < f1) {  // the next frame's source tile (scalar offset = one arena): in flight during this frame's pixels
                     v0 = rs_buf_load16(fr, soff0, (uint32_t)arena_stride);
                     v1 = rs_buf_load16(fr, soff1, (uint32_t)arena_stride);
                     v2 = rs_buf_load16(fr, soff2, (uint32_t)arena_stride);
@@ -459,10 +438,7 @@ __global__ __launch_bounds__(256, HT_RS_WPS) void k_resample(const HtResampleJob
                 RS_STAMP(3);
                 RS_WSTAMP(0);
                 uint32_t o[NP];
-                if (HT_RS_EXPERIMENT == 1) {  // timing experiment (wrong results): no pixel arithmetic, one LDS read per row
-#pragma unroll
-                    for (int q = 0; q < NP; q++) o[q] = *reinterpret_cast<const uint32_t *>(s_src + roff[q] + (ia8 & ~3));
-                } else if (BOX) {
+                if (BOX) {
                     // exact 2:1 in both directions: (a + b + c + d) / 4 with round half to even.  The 4 pixels of a thread are 8 consecutive
                     // bytes of two source rows: two ds_read_b64 per row instead of 16 byte reads; v_perm_b32 gathers a pixel's four bytes,
                     // v_sad_u8 adds them, and RNE(sum / 4) is exact in binary32 (sum <= 1020).
@@ -486,40 +462,25 @@ __global__ __launch_bounds__(256, HT_RS_WPS) void k_resample(const HtResampleJob
                     // binary32 first — top = p00 + tx * (p01 - p00), bot likewise, v = top + ty * (bot - top): three v_fma_f32 —, stored
                     // with v_cvt_pk_u8_f32 (its input is already integral), and the distance to the nearest rounding boundary is tested once
                     // per row (max of the four |v - r|).
-                    uint32_t T[2][16];
-#define RS_TAPS(q_, buf_)                                                                                   \
-    do {                                                                                                    \
-        const uint8_t *row_ = s_src + roff[q_];                                                             \
-        _Pragma("unroll") for (int k = 0; k < 4; k++) {                                                     \
-            const uint8_t *p_ = row_ + ia[k];                                                               \
-            T[buf_][4 * k] = p_[0], T[buf_][4 * k + 1] = RS_LD1(p_ + 1), T[buf_][4 * k + 2] = p_[RS_SP], T[buf_][4 * k + 3] = RS_LD1(p_ + RS_SP + 1); \
-        }                                                                                                   \
-    } while (0)
-                    if (HT_RS_ROWPF) {
-                        RS_TAPS(0, 0);
-                        __builtin_amdgcn_sched_barrier(0);  // row 0's taps first: its arithmetic only waits for them
-                    }
+                    uint32_t T[16];
 #pragma unroll
                     for (int q = 0; q < NP; q++) {
-                        if (HT_RS_ROWPF) {
-                            if (q + 1 < NP) RS_TAPS(q + 1, (q + 1) & 1);
-                        } else {
-                            RS_TAPS(q, q & 1);
+                        const uint8_t *row_ = s_src + roff[q];
+#pragma unroll
+                        for (int k = 0; k < 4; k++) {
+                            const uint8_t *p_ = row_ + ia[k];
+                            T[4 * k] = p_[0], T[4 * k + 1] = RS_LD1(p_ + 1), T[4 * k + 2] = p_[RS_SP], T[4 * k + 3] = RS_LD1(p_ + RS_SP + 1);
                         }
                         __builtin_amdgcn_sched_barrier(0);  // the loads above are not sunk into the arithmetic below
                         float d[4];
                         uint32_t oq = 0;
 #pragma unroll
                         for (int k = 0; k < 4; k++) {
-                            const float p00 = (float)T[q & 1][4 * k], p01 = (float)T[q & 1][4 * k + 1], p10 = (float)T[q & 1][4 * k + 2], p11 = (float)T[q & 1][4 * k + 3];
-#if HT_RS_PACKED  // top and bot of a pixel as one packed pair: v_pk_add_f32 + v_pk_fma_f32 instead of two v_sub_f32 + two v_fma_f32
+                            const float p00 = (float)T[4 * k], p01 = (float)T[4 * k + 1], p10 = (float)T[4 * k + 2], p11 = (float)T[4 * k + 3];
+                            // top and bot of a pixel as one packed pair: v_pk_add_f32 + v_pk_fma_f32 instead of two v_sub_f32 + two v_fma_f32
                             const rs_f2 lo2 = {p00, p10}, hi2 = {p01, p11}, ct2 = {ctf[k], ctf[k]};
                             const rs_f2 tb = __builtin_elementwise_fma(ct2, hi2 - lo2, lo2);
                             const float top = tb.x, bot = tb.y;
-#else
-                            const float top = __builtin_fmaf(ctf[k], p01 - p00, p00);
-                            const float bot = __builtin_fmaf(ctf[k], p11 - p10, p10);
-#endif
                             const float v = __builtin_fmaf(rtf[q], bot - top, top);
                             const float r = __builtin_rintf(v);
                             d[k] = v - r;
@@ -545,7 +506,6 @@ __global__ __launch_bounds__(256, HT_RS_WPS) void k_resample(const HtResampleJob
                         }
                         o[q] = rv[q] ? (oq & pxmask) : 0u;
                     }
-#undef RS_TAPS
                 }
 #ifdef HT_RS_TIMELINE
 #pragma unroll
@@ -559,25 +519,25 @@ __global__ __launch_bounds__(256, HT_RS_WPS) void k_resample(const HtResampleJob
                 // issued after the next tile has been written to LDS, so whoever waits for loads next (vmcnt cannot tell loads from older
                 // stores) finds them a whole pixel phase old.
                 // pixels outside the drawn dw x dh rect stay transparent black (ccv.js:135-145 draws 2 px short on the variants)
-#define RS_STORE_ROWS()                                                                                                                             \
-    _Pragma("unroll") for (int q = 0; q < NP; q++) if (st[q] && (HT_RS_EXPERIMENT != 3 || o[q] == 0x12345678u))                                     \
+#define RS_WRITE_ROWS()                                                                                                                             \
+    _Pragma("unroll") for (int q = 0; q < NP; q++) if (st[q])                                                                                      \
         __builtin_amdgcn_raw_buffer_store_b32(o[q], fr, doff, (uint32_t)(16 * q * dst_stride), 0)
                 if (f + 1 < f1) {
                     RS_LDS_BARRIER();  // every wave is done reading this frame's tile
                     RS_STAMP(5);
                     RS_WSTAMP(2);
-                    if (HT_RS_EXPERIMENT != 2) RS_TILE_TO_LDS();
-                    RS_STORE_ROWS();
+                    RS_TILE_TO_LDS();
+                    RS_WRITE_ROWS();
                     RS_LDS_BARRIER();
                     RS_WSTAMP(3);
 #ifdef HT_RS_PHASES
                     if (rs_iter == 2u && (threadIdx.x & 63u) == 0) g_rs_tw[rs_slot & 4095u][threadIdx.x >> 6][4] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));  // HW_ID
 #endif
                 } else {
-                    RS_STORE_ROWS();
+                    RS_WRITE_ROWS();
                     RS_STAMP(5);
                 }
-#undef RS_STORE_ROWS
+#undef RS_WRITE_ROWS
                 RS_STAMP(6);
 #ifdef HT_RS_PHASES
                 rs_iter++;
@@ -644,9 +604,7 @@ __global__ __launch_bounds__(256, HT_RS_WPS) void k_resample(const HtResampleJob
 // compute.  16 KB of bands + 3 KB of tap tables per workgroup and <= 64 VGPRs: 8 workgroups per CU (k_resample: 7 by registers).
 // The host fills in each tile record's band extents (ht_context.hip, the binary64 operations of rs_tap); a tile whose bands do not fit takes
 // the HBM-tap path exactly like k_resample's.
-#ifndef HT_RSB_WPS
-#define HT_RSB_WPS 8
-#endif
+constexpr int RSB_WPS = 8;
 constexpr int RSB_BAND = 4096;  // LDS bytes per wavefront = four 1 KB LDS-DMA instructions = 25.6 rows of RS_SP bytes
 #if defined(HT_RS_PHASES)  // tools/gpu_rsb_phases.py: shader-clock sums per phase of a WAVEFRONT's frame iteration (there is no workgroup phase in the loop)
 __device__ unsigned long long g_rsb_ph[256][8];  // per shard (blockIdx & 255): [0] iterations, [1] pixels, [2] DMA issue, [3] wait for the band, [4] stores, [5] workgroups, [6] record -> first loop top
@@ -663,7 +621,7 @@ __device__ unsigned long long g_rsb_ph[256][8];  // per shard (blockIdx & 255): 
 #endif
 typedef __attribute__((address_space(3))) void rs_lds_void;
 template <int RPT>
-__global__ __launch_bounds__(256, HT_RSB_WPS) void k_resample_bands(const HtResampleJob *__restrict__ tiles, uint8_t *__restrict__ arena,
+__global__ __launch_bounds__(256, RSB_WPS) void k_resample_bands(const HtResampleJob *__restrict__ tiles, uint8_t *__restrict__ arena,
                                                                     uint64_t arena_stride, uint32_t blocks_per_frame, uint32_t ngroups,
                                                                     uint32_t nframes, uint32_t group_frames) {
     constexpr int TH = 16 * RPT;
@@ -896,16 +854,9 @@ __global__ __launch_bounds__(256, HT_RSB_WPS) void k_resample_bands(const HtResa
 // empty grids whose cost is launch + latency chain (C2: 48 us for 6 % of the pixels).  Here ONE workgroup per frame walks
 // those generations in order: a thread produces 4 destination pixels straight from HBM/L2 (own tap evaluation, no LDS
 // staging), generations are separated by a workgroup barrier.  Same arithmetic as k_resample's HBM-tap path.
-#ifndef HT_TAIL_NT
-#define HT_TAIL_NT 1024
-#endif
-#ifndef HT_TAIL_U
-#define HT_TAIL_U 1  // groups per thread in flight: 1 = 68 VGPRs; 2-6 (96-240 VGPRs) measured no faster
-#endif
-constexpr int TAIL_NT = HT_TAIL_NT;
-#ifndef HT_TAIL_SMALL_WPS
-#define HT_TAIL_SMALL_WPS 8  // waves per SIMD the small-footprint tail leaves room for (8: <= 64 VGPRs)
-#endif
+constexpr int TAIL_NT = 1024;
+constexpr int TAIL_U = 1;  // groups per thread in flight: 1 = 68 VGPRs; 2-6 (96-240 VGPRs) measured no faster
+constexpr int TAIL_SMALL_WPS = 8;  // waves per SIMD the small-footprint tail leaves room for (8: <= 64 VGPRs)
 // Taps come from tables the host built once per geometry (compact {a, (float)t} for the binary32 estimate, full binary64 form for the
 // fallback) and the pixels take the same binary32-estimate / integer-box-mean / binary64-fallback route as k_resample: the tail
 // used to spend ~135 binary64 instructions per group of 4 pixels on re-deriving taps and on the lerps.
@@ -942,8 +893,9 @@ __global__ __launch_bounds__(TAIL_NT, WPS) void k_resample_tail(const HtResample
         __syncthreads();
         // TAIL_U groups per thread in flight: a group is a chain job lookup (LDS) -> taps (L2) -> source bytes (L2) -> store, and a
         // thread that walks its groups one at a time pays that chain once per group (the late generations are pure latency);
-        // the phases below are separate loops over the TAIL_U groups so that every load of a phase is issued before the first use
-        constexpr int TAIL_U = HT_TAIL_U;
+        // the phases below are separate loops over the TAIL_U groups so that every load of a phase is issued before the first use.
+        // (Written for one group without the phase loops, the kernel compiles to other machine code: kept until the pyramid's PMC
+        // constants in profiles/traffic.json are measured again.)
         for (uint32_t i0 = (uint32_t)tid; i0 < total; i0 += TAIL_U * TAIL_NT) {
             bool live[TAIL_U], draw[TAIL_U];
             uint32_t doff[TAIL_U], mode[TAIL_U], tcol[TAIL_U], trow[TAIL_U];
@@ -1189,7 +1141,7 @@ ht_status ht_launch_pyramid(ht_ctx *c, uint32_t flags) {
     if (c->tail_first_gen > 0 && c->tail_first_gen <= dbg_maxgen) {
         HtProfScope ps(c, c->rs_gennames ? "resample_tail" : "resample");
         if (c->tail_table == 2)
-            hipLaunchKernelGGL((k_resample_tail<false, HT_TAIL_SMALL_WPS>), dim3(((uint32_t)c->nframes + 7u) & ~7u), dim3(TAIL_NT), 0, c->stream, c->d_tail_jobs,
+            hipLaunchKernelGGL((k_resample_tail<false, TAIL_SMALL_WPS>), dim3(((uint32_t)c->nframes + 7u) & ~7u), dim3(TAIL_NT), 0, c->stream, c->d_tail_jobs,
                                c->d_tail_prefix, c->d_tail_tapref, c->d_tail_taps_fast, c->d_tail_taps, c->h_tail, c->d_arena, c->arena_stride, (uint32_t)c->nframes);
         else if (c->tail_table)
             hipLaunchKernelGGL((k_resample_tail<true, 4>), dim3(((uint32_t)c->nframes + 7u) & ~7u), dim3(TAIL_NT), 0, c->stream, c->d_tail_jobs, c->d_tail_prefix,

@@ -35,28 +35,18 @@ namespace {
 
 // tile geometry (window = 24x24, see ht_scan_tile_tables for the check)
 constexpr int TXH = 64;                 // tile width  in half-window steps X'
-#ifndef HT_TILE_TYH
-#define HT_TILE_TYH 32
-#endif
-#ifndef HT_TILE_WPS
-#define HT_TILE_WPS 6  // waves per SIMD the register allocator must leave room for: 6 workgroups per CU (80 VGPRs, no spills; 26.4 KB of LDS
-                       // each now that the survivor queue lives in the unused tails of the plane-1/2 rows).  Measured: 4 -> 5 workgroups
-                       // -15 %, 5 -> 6 another -7 % (C2) / -6 % (C4) on the tile kernel.
-#endif
-constexpr int TYH = HT_TILE_TYH;        // tile height in half-window steps Y'
-#ifndef HT_TILE_NT
-#define HT_TILE_NT 256
-#endif
-constexpr int NT = HT_TILE_NT;          // threads per workgroup (256: 4 waves/SIMD at <=128 VGPRs; 512: 8 waves/SIMD at <=64)
-#ifndef HT_TILE_PITCH
-#define HT_TILE_PITCH 152
-#endif
+constexpr int TYH = 32;                 // tile height in half-window steps Y'
+constexpr int NT = 256;                 // threads per workgroup (256: 4 waves/SIMD at <=128 VGPRs; 512: 8 waves/SIMD at <=64)
+// waves per SIMD the register allocator must leave room for: 6 workgroups per CU (80 VGPRs, no spills; 26.4 KB of LDS each now that the
+// survivor queue lives in the unused tails of the plane-1/2 rows).  Measured: 4 -> 5 workgroups -15 %, 5 -> 6 another -7 % (C2) / -6 % (C4)
+// on the tile kernel.
+constexpr int TILE_WPS = 6;
 // plane-0 bytes per LDS row: 2*TXH + 24 = 152 are needed.  A window's base address steps by 2*PITCH0 bytes per half-step row, i.e.
 // PITCH0/2 dwords: 152 -> 76 = 12 (mod 32 banks), so 8 consecutive rows start in 8 different 4-bank slots (0,12,24,4,16,28,8,20).
 // With 160 the step was 16 (mod 32): rows r and r+2 aliased, and compacted survivors — which cluster in 2-D blobs — hit the
 // same banks from every other row (36 % of the kernel's LDS cycles were bank conflicts; tools/sim_scan_lds.py models
 // 61 % -> 44 % overhead over conflict-free).  Multiple of 8: rows are staged as 16-byte loads split into two 8-byte LDS writes.
-constexpr int PITCH0 = HT_TILE_PITCH;
+constexpr int PITCH0 = 152;
 static_assert(PITCH0 >= 2 * TXH + 24 && PITCH0 % 8 == 0, "PITCH0");
 constexpr int ROWS0 = 2 * TYH + 22;     // 86
 constexpr int P0_BYTES = PITCH0 * ROWS0;  // 13760
@@ -154,7 +144,7 @@ __device__ __forceinline__ double eval_stage_lds(const uint8_t *lds, uint32_t B,
 #endif
 
 template <bool GEN>
-__global__ __launch_bounds__(NT, HT_TILE_WPS) void k_scan_tiles(const uint8_t *__restrict__ arena, uint64_t arena_stride,
+__global__ __launch_bounds__(NT, TILE_WPS) void k_scan_tiles(const uint8_t *__restrict__ arena, uint64_t arena_stride,
                                                    const HtTileRec *__restrict__ tile_recs, const HtTileFeature *__restrict__ feats,
                                                    const HtPackedFeature *__restrict__ fp_feats, const HtDevStage *__restrict__ stages, int nstages, int split, uint32_t deep_bias,
                                                    int stop_stage, int force_exact, uint32_t tiles_per_frame, uint32_t total_tiles, HtQueueEntry *__restrict__ queue,
@@ -169,35 +159,17 @@ __global__ __launch_bounds__(NT, HT_TILE_WPS) void k_scan_tiles(const uint8_t *_
 #define QB(qi_, i_) (*reinterpret_cast<uint16_t *>(&lds[P12_BASE + 160 + ((uint32_t)(i_) >> 6) * G_PITCH + (((uint32_t)(i_)&63u) << 1)]))  // qi_: always 0 (one queue)
     __shared__ uint32_t s_nout;
     __shared__ uint32_t s_qbase;
-#ifndef HT_TILE_WAVEQ
-#define HT_TILE_WAVEQ 1
-#endif
-#ifndef HT_TILE_FPAR
-#define HT_TILE_FPAR 1  // feature-parallel sparse phase (0: always the four feature slices)
-#endif
-#ifndef HT_TILE_MERGE_FROM
-#define HT_TILE_MERGE_FROM 2  // the first stage after which the wavefronts compare their survivor counts
-#endif
-#if HT_TILE_WAVEQ
+    constexpr int MERGE_FROM = 2;  // the first stage after which the wavefronts compare their survivor counts
     // Wave-private layout of the same row tails (see "wave-private cascade" below): rows [8w, 8w + 8) = wavefront w's queue of
     // window ids (a wavefront enumerates at most MAXWIN / 4 = 512 windows), rows 32-37 = three buffers of 64 per-survivor integer
     // stage sums (36 dwords of tail per row: 32 used), row 38 = the wavefronts' survivor counts (two parities x 4).
     constexpr int WQ_ROWS = MAXWIN / NT, WQ_CAP = WQ_ROWS * 64;
-    static_assert(NT != 256 || GH >= 4 * WQ_ROWS + 11, "wave-private queues do not fit the row tails");
+    static_assert(NT == 256 && GH >= 4 * WQ_ROWS + 11, "wave-private queues: four wavefronts, queues in the row tails");
     // rows 39-42: per wavefront the LDS bases of the tile's surviving windows in rank order (feature-parallel sparse phase)
 #define FPB(w_, i_) (*reinterpret_cast<uint16_t *>(&lds[P12_BASE + 160 + (4 * WQ_ROWS + 7 + (w_)) * G_PITCH + (((uint32_t)(i_)&63u) << 1)]))
 #define QW(w_, e_) QB(0, (w_) * WQ_CAP + (e_))
 #define SF(b_, l_) (*reinterpret_cast<uint32_t *>(&lds[P12_BASE + 160 + (4 * WQ_ROWS + 2 * (b_) + ((l_) >> 5)) * G_PITCH + (((l_)&31u) << 2)]))
 #define SCNT(p_) (reinterpret_cast<uint32_t *>(&lds[P12_BASE + 160 + (4 * WQ_ROWS + 6) * G_PITCH + (p_) * 16]))
-    constexpr bool WAVEQ = GEN && NT == 256;
-#else
-    constexpr bool WAVEQ = false;
-#define QW(w_, e_) QB(0, 0)
-#define SF(b_, l_) (*SCNT(0))
-#define SCNT(p_) (&s_qbase)
-#define FPB(w_, i_) (*reinterpret_cast<uint16_t *>(&s_qbase))
-    constexpr int WQ_CAP = 0;
-#endif
 
     // XCD-aware tile order: consecutive tiles (same frame / scale, shared halos) stay on one XCD's L2.
     const uint32_t nb = gridDim.x, chunk = nb >> 3;  // gridDim.x is a multiple of 8
@@ -221,11 +193,9 @@ __global__ __launch_bounds__(NT, HT_TILE_WPS) void k_scan_tiles(const uint8_t *_
 #ifdef HT_TILE_TIMELINE
     unsigned long long tl_prev = __builtin_readcyclecounter();
 #endif
-#ifndef HT_TILE_PRIO
-#define HT_TILE_PRIO 1  // measured: 1 -> scan_tiles -2.1 % (C2) / -2.9 % (C4); 2 (also the sparse stages at high priority): the same
-#endif
     // wave priority: the short dependent chain that gets the tile's loads out runs ahead of other wavefronts' stage-0 bursts
-    if (HT_TILE_PRIO) __builtin_amdgcn_s_setprio(3);
+    // (measured: scan_tiles -2.1 % (C2) / -2.9 % (C4); the sparse stages at high priority as well: no further gain)
+    __builtin_amdgcn_s_setprio(3);
 
     // ---- stage the three planes into LDS --------------------------------------------------------------------
     // All global loads of a thread are issued before the first LDS write (fixed trip counts, predicated), so one
@@ -308,9 +278,9 @@ __global__ __launch_bounds__(NT, HT_TILE_WPS) void k_scan_tiles(const uint8_t *_
         }
     }
     if (tid == 0) s_nout = 0;
-    if (WAVEQ && tid < 192u) SF(tid >> 6, tid & 63u) = 0u;
+    if (GEN && tid < 192u) SF(tid >> 6, tid & 63u) = 0u;
     __syncthreads();
-    if (HT_TILE_PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     TL_STAMP(0);
 
     // ---- cascade with per-stage compaction -------------------------------------------------------------------
@@ -320,7 +290,7 @@ __global__ __launch_bounds__(NT, HT_TILE_WPS) void k_scan_tiles(const uint8_t *_
     // reservation by LDS atomic, queue write, counter read — each one waits behind the ~24 wavefronts' queued LDS traffic of the
     // CU) and 4-5 workgroup barriers.  Here a wavefront keeps the survivors of ITS windows in a queue of its own: compaction is
     // ballot + popcount in registers, no atomics and no barriers; per stage it pays two round trips (ids, feature pixels).
-    // After stage HT_TILE_MERGE_FROM the four wavefronts publish their counts (one barrier); once <= 64 windows are left in the
+    // After stage MERGE_FROM the four wavefronts publish their counts (one barrier); once <= 64 windows are left in the
     // tile every wavefront pulls all of them into registers (lane = survivor, the same in all four wavefronts) and the
     // stages are evaluated in four feature slices whose integer partial sums meet in LDS: one atomic add, one barrier and one
     // read per stage, no queue.  Window sets and stage decisions are exactly those of the shared-queue code below, which still
@@ -330,78 +300,45 @@ __global__ __launch_bounds__(NT, HT_TILE_WPS) void k_scan_tiles(const uint8_t *_
     bool pushed = (split >= nstages);
     int s_first = 0;
     const int wq_lim = min(min(split, nstages - 1), (int)HT_GEN_STAGES);  // stages [0, wq_lim) run wave-private
-    if (WAVEQ && wq_lim >= 1) {
+    if (GEN && wq_lim >= 1) {
         const uint32_t wv = tid >> 6;
         if (stop_stage == 0) return;
         uint32_t wq = 0;  // survivors of this wavefront's windows (wave-uniform)
         {
             const HtDevStage st0 = stages[0];
-#ifndef HT_TILE_BLOCKASSIGN
-#define HT_TILE_BLOCKASSIGN 1
-#endif
             // A wavefront takes a contiguous quarter of the tile's 64-window batches (= adjacent rows).  With the batches dealt out
             // round-robin its survivors came from every 4th row, whose LDS bank phases (12 banks per row) collide more often once
             // compacted: tools/sim_scan_lds.py counts 6.6 % fewer LDS cycles for the whole kernel with contiguous rows.
-            const uint32_t nbat = (n_in + 63u) >> 6, per = HT_TILE_BLOCKASSIGN ? (nbat + 3u) >> 2 : 0u;
-            const uint32_t b_lo = HT_TILE_BLOCKASSIGN ? wv * per : 0u, b_hi = HT_TILE_BLOCKASSIGN ? min(b_lo + per, nbat) : nbat;
-#ifndef HT_TILE_PAIR
-#define HT_TILE_PAIR 1
-#endif
+            const uint32_t nbat = (n_in + 63u) >> 6, per = (nbat + 3u) >> 2;
+            const uint32_t b_lo = wv * per, b_hi = min(b_lo + per, nbat);
             // pair mode: a lane evaluates the two ADJACENT windows (X', X'+1) of a pass's 128 consecutive ids from shared aligned dword
             // reads (ht_gen_stage_0_pair: 30 LDS reads per pair instead of 2 x 22; stage 0 is LDS-throughput bound)
-            constexpr bool PAIR = HT_TILE_PAIR && HT_TILE_BLOCKASSIGN && PITCH0 == HT_GEN_PAIR_PITCH0 && P12_BASE == HT_GEN_PAIR_P12;
-            for (uint32_t bt = b_lo; bt < b_hi; bt += (HT_TILE_BLOCKASSIGN ? 2u : 8u)) {
+            static_assert(PITCH0 == HT_GEN_PAIR_PITCH0 && P12_BASE == HT_GEN_PAIR_P12, "ht_gen_stage_0_pair was generated for another tile layout");
+            for (uint32_t bt = b_lo; bt < b_hi; bt += 2u) {
                 uint32_t id[2], xx[2], yy[2], Fv[2];
                 bool valid[2];
-                if (PAIR) {
-                    // Order of the walk: window PAIRS in vertical strips of 4 pairs (8 half-steps), row by row inside a strip.  A pair's
-                    // dword reads are `base + constant` with base / 4 = 76 * Y' + X' / 2, and a wave64 ds_read_b32 is served in two
-                    // groups of 32 lanes over 32 banks: 8 consecutive rows x 4 consecutive pairs are 32 different banks (76 = 12 mod 32:
-                    // the rows start at banks 0, 12, 24, 4, 16, 28, 8, 20), so every group is conflict-free.  Walking whole rows
-                    // (pair n = row-major) put rows of tw2 / 2 < 32 pairs — all but 2 of the 19 scales at 320x240 — into groups that
-                    // wrap to the next row 12 banks on: 2 cycles instead of 1 for nearly every one of stage 0's reads
-                    // (tools/sim_scan_lds2.py: stage 0 at 1.86 LDS cycles per conflict-free cycle, 1.14 in strips; the PMC counters
-                    // had 37 % of the kernel's LDS cycles as bank conflicts).  Window ids keep their meaning (Y' * tw2 + X').
-                    const uint32_t lim = min(b_hi * 64u, n_in);
-                    const uint32_t pn = bt * 32u + lane;  // pair index in walking order
-                    const bool in0 = 2u * pn < lim;
-                    const uint32_t pn0 = in0 ? pn : 0u;
-#ifndef HT_TILE_STRIPS
-#define HT_TILE_STRIPS 1
-#endif
-                    if (HT_TILE_STRIPS) {
-                        const uint32_t strip = __umul24(pn0, R.strip_magic) >> 24, rem = pn0 - __umul24(strip, 4u * (uint32_t)th);
-                        yy[0] = yy[1] = rem >> 2;
-                        xx[0] = 8u * strip + 2u * (rem & 3u);
-                        id[0] = __umul24(yy[0], (uint32_t)S.tw2) + xx[0];
-                    } else {
-                        id[0] = 2u * pn0;  // ids come in even / odd pairs of one row: tw2 is even
-                        yy[0] = yy[1] = __umul24(id[0], S.div_magic) >> 20;
-                        xx[0] = id[0] - __umul24(yy[0], (uint32_t)S.tw2);
-                    }
-                    id[1] = id[0] + 1u;
-                    xx[1] = xx[0] + 1u;
-                    valid[0] = in0 && xx[0] < (uint32_t)tw;
-                    valid[1] = in0 && xx[1] < (uint32_t)tw;
-#ifndef HT_TILE_PAIRPK
-#define HT_TILE_PAIRPK 1  // both windows of the pair in the two 16-bit halves of one register (v_perm_b32 gather, v_pk_min/max_u16); 0: one 32-bit chain per window
-#endif
-                    if (HT_TILE_PAIRPK) ht_gen_stage_0_pair(lds + (valid[0] ? 2u * (yy[0] * PITCH0 + xx[0]) : 0u), Fv[0], Fv[1]);
-                    else ht_gen_stage_0_pair_u32(lds + (valid[0] ? 2u * (yy[0] * PITCH0 + xx[0]) : 0u), Fv[0], Fv[1]);
-                } else {
-#pragma unroll
-                    for (int u = 0; u < 2; u++) {
-                        const uint32_t bu = HT_TILE_BLOCKASSIGN ? bt + (uint32_t)u : bt + 4u * (uint32_t)u + wv;
-                        const uint32_t pos = bu * 64u + lane;
-                        valid[u] = bu < b_hi && pos < n_in;
-                        id[u] = valid[u] ? pos : 0u;
-                        yy[u] = __umul24(id[u], S.div_magic) >> 20;  // 24-bit multiplies (id < 2^11, magic < 2^18); v_mul_lo_u32 measures at the same 4 cycles per wave64 (tools/micro/valu_rate_bench.hip)
-                        xx[u] = id[u] - __umul24(yy[u], (uint32_t)S.tw2);
-                        valid[u] = valid[u] && xx[u] < (uint32_t)tw;
-                    }
-                    if (!HT_TILE_BLOCKASSIGN && bt + wv >= nbat) break;  // round-robin: this wavefront's batches are exhausted
-                    ht_gen_stage_0_x2(lds + (valid[0] ? 2u * (yy[0] * PITCH0 + xx[0]) : 0u), lds + (valid[1] ? 2u * (yy[1] * PITCH0 + xx[1]) : 0u), Fv[0], Fv[1]);
-                }
+                // Order of the walk: window PAIRS in vertical strips of 4 pairs (8 half-steps), row by row inside a strip.  A pair's
+                // dword reads are `base + constant` with base / 4 = 76 * Y' + X' / 2, and a wave64 ds_read_b32 is served in two
+                // groups of 32 lanes over 32 banks: 8 consecutive rows x 4 consecutive pairs are 32 different banks (76 = 12 mod 32:
+                // the rows start at banks 0, 12, 24, 4, 16, 28, 8, 20), so every group is conflict-free.  Walking whole rows
+                // (pair n = row-major) put rows of tw2 / 2 < 32 pairs — all but 2 of the 19 scales at 320x240 — into groups that
+                // wrap to the next row 12 banks on: 2 cycles instead of 1 for nearly every one of stage 0's reads
+                // (tools/sim_scan_lds2.py: stage 0 at 1.86 LDS cycles per conflict-free cycle, 1.14 in strips; the PMC counters
+                // had 37 % of the kernel's LDS cycles as bank conflicts).  Window ids keep their meaning (Y' * tw2 + X').
+                const uint32_t lim = min(b_hi * 64u, n_in);
+                const uint32_t pn = bt * 32u + lane;  // pair index in walking order
+                const bool in0 = 2u * pn < lim;
+                const uint32_t pn0 = in0 ? pn : 0u;
+                const uint32_t strip = __umul24(pn0, R.strip_magic) >> 24, rem = pn0 - __umul24(strip, 4u * (uint32_t)th);
+                yy[0] = yy[1] = rem >> 2;
+                xx[0] = 8u * strip + 2u * (rem & 3u);
+                id[0] = __umul24(yy[0], (uint32_t)S.tw2) + xx[0];
+                id[1] = id[0] + 1u;
+                xx[1] = xx[0] + 1u;
+                valid[0] = in0 && xx[0] < (uint32_t)tw;
+                valid[1] = in0 && xx[1] < (uint32_t)tw;
+                // both windows of the pair in the two 16-bit halves of one register (v_perm_b32 gather, v_pk_min/max_u16)
+                ht_gen_stage_0_pair(lds + (valid[0] ? 2u * (yy[0] * PITCH0 + xx[0]) : 0u), Fv[0], Fv[1]);
                 bool pass[2];
                 pass[0] = (Fv[0] >= HT_GEN_FMIN[0]) & valid[0];
                 pass[1] = (Fv[1] >= HT_GEN_FMIN[0]) & valid[1];
@@ -419,13 +356,12 @@ __global__ __launch_bounds__(NT, HT_TILE_WPS) void k_scan_tiles(const uint8_t *_
             if (tid == 0 && my_stats) atomicAdd(&my_stats[0], (unsigned long long)(uint32_t)(tw * th));
         }
         // -- stages 1.. on the wavefront's own queue, until the tile is down to one wavefront of windows
-        if (HT_TILE_PRIO == 3) __builtin_amdgcn_s_setprio(3);
         int s = 1;
         uint32_t total = 0;
         uint4 cn = make_uint4(0u, 0u, 0u, 0u);
         bool gather = false;
         for (;; s++) {
-            if (s > HT_TILE_MERGE_FROM || s == wq_lim) {
+            if (s > MERGE_FROM || s == wq_lim) {
                 if (lane == 0) SCNT(s & 1)[wv] = wq;
                 __syncthreads();
                 cn = *reinterpret_cast<const uint4 *>(SCNT(s & 1));
@@ -446,6 +382,7 @@ __global__ __launch_bounds__(NT, HT_TILE_WPS) void k_scan_tiles(const uint8_t *_
             for (uint32_t b = 0; b < wq; b += 64) {
                 const bool valid = b + lane < wq;
                 const uint32_t wid = valid ? (uint32_t)QW(wv, b + lane) : 0u;
+                // 24-bit multiplies (id < 2^11, magic < 2^18); v_mul_lo_u32 measures at the same 4 cycles per wave64 (tools/micro/valu_rate_bench.hip)
                 const uint32_t yy = __umul24(wid, S.div_magic) >> 20, xx = wid - __umul24(yy, (uint32_t)S.tw2);
                 const uint32_t Bw = 2u * (yy * PITCH0 + xx);
                 const uint32_t Fv = ht_gen_stage(s, lds + (valid ? Bw : 0u));
@@ -461,7 +398,7 @@ __global__ __launch_bounds__(NT, HT_TILE_WPS) void k_scan_tiles(const uint8_t *_
             }
             wq = out;
         }
-        if (HT_TILE_PRIO) __builtin_amdgcn_s_setprio(HT_TILE_PRIO > 1 ? 3 : 0);
+        __builtin_amdgcn_s_setprio(0);  // already 0 since the staging barrier; kept: the code object is the one profiles/traffic.json was measured on
         if (gather) {
             // -- <= 64 windows left in the tile: lane = survivor in every wavefront, stages in four feature slices
             const uint32_t o1 = cn.x, o2 = o1 + cn.y, o3 = o2 + cn.z;
@@ -486,7 +423,7 @@ __global__ __launch_bounds__(NT, HT_TILE_WPS) void k_scan_tiles(const uint8_t *_
                 if (tid == 0 && my_stats) atomicAdd(&my_stats[s], (unsigned long long)n_alive);
                 const uint32_t bi = (uint32_t)s % 3u;
                 const uint32_t nf = HT_GEN_NFEAT[s], npairs = n_alive * nf;
-                const bool fpar = HT_TILE_FPAR && fp_feats != nullptr && npairs <= HT_GEN_FP_MAXPAIRS[s];
+                const bool fpar = fp_feats != nullptr && npairs <= HT_GEN_FP_MAXPAIRS[s];
                 uint32_t fslot = lane;  // the window's entry of the sum buffer: its lane, or its rank among the survivors
                 if (fpar) {
                     fslot = __builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0u));
@@ -903,10 +840,7 @@ __global__ __launch_bounds__(64 * DEEP_WAVES) void k_scan_deep(const uint8_t *__
 // is copied into LDS once per workgroup (one 1024-thread workgroup per CU); every wavefront then owns a window at a time
 // exactly like k_scan_deep, but feature records and pixels both come from LDS.
 constexpr uint32_t DEEP_LDS_TABLE_BYTES = 64 * 1024;
-#ifndef HT_DEEPL_WAVES
-#define HT_DEEPL_WAVES 12  // 12 waves x 2 workgroups per CU (2 x 77 KB of LDS) beat 16 x 1: measured 0.044 vs 0.055 ms on C2
-#endif
-constexpr int DEEPL_WAVES = HT_DEEPL_WAVES;
+constexpr int DEEPL_WAVES = 12;  // 12 waves x 2 workgroups per CU (2 x 77 KB of LDS) beat 16 x 1: measured 0.044 vs 0.055 ms on C2
 
 __device__ __forceinline__ bool packed_fire(const uint8_t *patch, const uint4 A, const uint32_t B0) {
     // A = off[0..7], B0 = off[8..9]
@@ -1021,14 +955,11 @@ __global__ __launch_bounds__(64 * DEEPL_WAVES, (2 * DEEPL_WAVES + 3) / 4) void k
     // e += nwaves the launch lasted as long as the wavefront that drew three full survivors (0.055 ms).  The counter is read one
     // window ahead (the atomic's round trip is hidden behind the window being evaluated); HT_DEEP_CTRS counters, each handing out
     // every HT_DEEP_CTRS-th entry to the wavefronts that share it (see ht_internal.h).
-#ifndef HT_DEEP_DYNAMIC
-#define HT_DEEP_DYNAMIC 1
-#endif
     const uint32_t *my_ctr = reinterpret_cast<const uint32_t *>(queue + queue_cap) + (wave & (HT_DEEP_CTRS - 1u)) * 64u;
     for (uint32_t e = wave; e < n;) {
         e = (uint32_t)__builtin_amdgcn_readfirstlane((int)e);  // the queue entry is a scalar load
         uint32_t nxt = 0;
-        if (HT_DEEP_DYNAMIC && lane == 0) {
+        if (lane == 0) {
             // written out: atomicAdd() is turned into a wave-aggregated add whose result is waited for on the spot (~2 us per window);
             // the compiler's own s_waitcnt vmcnt(k) stay correct with one more (older) operation in the in-order queue
             const uint32_t zero = 0u, one = 1u;
@@ -1043,7 +974,7 @@ __global__ __launch_bounds__(64 * DEEPL_WAVES, (2 * DEEPL_WAVES + 3) / 4) void k
         const uint32_t o0 = ent.o0, o1 = ent.o1, o2 = ent.o2;
         const int s0 = (int)ent.s0, s1 = (int)ent.s1, s2 = (int)ent.s2;
         const DeepEntry cur = ent;  // this window (frame, x, y, scale, q, first stage); `ent` becomes the next one below
-        uint32_t e_next = n;
+        uint32_t e_next;
         {
             uint32_t pa[5], pb[3], pc = 0;
 #pragma unroll
@@ -1076,13 +1007,9 @@ __global__ __launch_bounds__(64 * DEEPL_WAVES, (2 * DEEPL_WAVES + 3) / 4) void k
             // the next entry's index has arrived with the gathers (issued before them): parked in the patch's spare bytes, not in a
             // register that would live across the stage passes (at 80 VGPRs that one register was 9 spills)
             static_assert(PATCH2 + 36 <= 760 && PATCH_BYTES >= 764, "spare bytes of the patch");
-            if (HT_DEEP_DYNAMIC) {
-                if (lane == 0) asm volatile("s_waitcnt vmcnt(0)" : "+v"(nxt) : : "memory");  // the gathers before it in the queue have been consumed above
-                // the k-th entry handed out by counter c is nwaves + HT_DEEP_CTRS * k + c; requested now, it arrives during the stage passes
-                e_next = nwaves + HT_DEEP_CTRS * (uint32_t)__builtin_amdgcn_readlane((int)nxt, 0) + (wave & (HT_DEEP_CTRS - 1u));
-            } else {
-                e_next = e + nwaves;
-            }
+            if (lane == 0) asm volatile("s_waitcnt vmcnt(0)" : "+v"(nxt) : : "memory");  // the gathers before it in the queue have been consumed above
+            // the k-th entry handed out by counter c is nwaves + HT_DEEP_CTRS * k + c; requested now, it arrives during the stage passes
+            e_next = nwaves + HT_DEEP_CTRS * (uint32_t)__builtin_amdgcn_readlane((int)nxt, 0) + (wave & (HT_DEEP_CTRS - 1u));
             if (e_next < n) ent = deep_entry(queue, e_next);  // two scalar loads (wave-uniform index), in flight during the stage passes
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

@@ -173,8 +173,9 @@ def test_integer_stage_decisions_equal_the_sequential_binary64_sums(cascade):
         assert ties < len(pats)
 
 
-def test_resample_binary32_estimate_stays_inside_its_error_budget():
-    """ht_pyramid.hip evaluates every pyramid pixel in binary32 first (three fused multiply-adds) and trusts the rounded estimate only when
+def test_resample_packed_binary32_estimate_stays_inside_its_error_budget():
+    """ht_pyramid.hip evaluates every pyramid pixel in binary32 first (three fused multiply-adds; in k_resample / k_resample_bands the
+    horizontal two as one packed pair, which rounds each lane like a scalar fma) and trusts the rounded estimate only when
     it is at least RS_EPS away from a rounding boundary; otherwise the declared binary64 sequence (oracle/canvas_shim.js resample) decides.
     The source bounds |estimate - declared| by 6.9e-5 < RS_EPS = 2^-13 analytically; here the same two computations are restated with numpy
     (fma32(a, b, c) = fl32(a * b + c) with the product exact in binary64) on 24 M random tap / weight combinations, a third of them steered
@@ -187,7 +188,12 @@ def test_resample_binary32_estimate_stays_inside_its_error_budget():
     m = re.search(r"constexpr float RS_EPS = 1\.0f / (\d+)\.0f;", src)
     assert m, "RS_EPS moved"
     eps = 1.0 / int(m.group(1))
-    assert "__builtin_fmaf(ctf[k], p01 - p00, p00)" in src and "__builtin_fmaf(rtf[q], bot - top, top)" in src  # what is restated below
+    # what is restated below, in every kernel that takes the binary32 route: the LDS kernels (top and bot as one packed pair of fused
+    # multiply-adds, then the vertical one) and the tail kernel (three scalar ones)
+    assert src.count("lo2 = {p00, p10}, hi2 = {p01, p11}, ct2 = {ctf[k], ctf[k]}") == 2 and src.count("__builtin_elementwise_fma(ct2, hi2 - lo2, lo2)") == 2
+    assert src.count("__builtin_fmaf(rtf[q], bot - top, top)") == 2
+    assert "__builtin_fmaf(ctap[u][k].tf, (float)p01[u][k] - a00, a00)" in src and "__builtin_fmaf(ctap[u][k].tf, (float)p11[u][k] - a10, a10)" in src
+    assert "__builtin_fmaf(rtap[u].tf, bot - top, top)" in src
     f32, f64 = np.float32, np.float64
 
     def fma32(a, b, c):  # a, b, c binary32; a * b is exact in binary64 (24 + 24 bits), one more rounding to binary32

@@ -2,7 +2,15 @@
 """tools/build_alt.py NAME DEFINE[=V] ...   build an instrumented variant of the library into alt/NAME.so (objects in a temp dir, the
                                            product library is not touched) and record the hash of the sources it was built from;
 tools/build_alt.py --check NAME            exit 1 unless alt/NAME.so was built from the sources as they are NOW.
-tools/gpu_final.sh refuses a stale variant: round 2 committed "timelines" that were the tracebacks of stale builds."""
+tools/gpu_final.sh refuses a stale variant: round 2 committed "timelines" that were the tracebacks of stale builds.
+
+The defines the sources know: the shader-clock instrumentation and the debug option keys, e.g.
+
+    python tools/build_alt.py tltl HT_TILE_TIMELINE      # k_scan_tiles phase times (tools/gpu_tile_timeline.py)
+    python tools/build_alt.py dltl HT_DEEP_TIMELINE      # k_scan_deep_lds stamps (tools/gpu_deep_timeline.py)
+    python tools/build_alt.py cstl HT_CS_TIMELINE        # k_cs_track_fused stamps (tools/gpu_cs_timeline.py)
+    python tools/build_alt.py rsph HT_RS_PHASES          # resample phase stamps (tools/gpu_rs_phases.py, gpu_rsb_phases.py)
+    python tools/build_alt.py dbg HT_DEBUG_KNOBS         # option keys that make results incomplete (stop_stage, cs_iters, rs_maxgen)"""
 import hashlib
 import json
 import os

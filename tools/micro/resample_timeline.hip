@@ -8,9 +8,10 @@
 #include <vector>
 
 // host-side symbols of the library that the included launchers reference (unused here)
-HtProfScope::HtProfScope(ht_ctx *c, const char *) : ctx(c) {}
+HtProfScope::HtProfScope(ht_ctx *c, const char *, hipStream_t) : ctx(c) {}
 HtProfScope::~HtProfScope() {}
 ht_status ht_fail(ht_ctx *, ht_status st, const std::string &) { return st; }
+ht_status ht_launch_scan_early(ht_ctx *, uint32_t) { return HT_OK; }
 
 int main(int argc, char **argv) {
     const int W = argc > 1 ? atoi(argv[1]) : 320, H = argc > 2 ? atoi(argv[2]) : 240, N = argc > 3 ? atoi(argv[3]) : 256;
