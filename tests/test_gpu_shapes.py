@@ -295,13 +295,16 @@ def test_fused_track_kernel_forms_return_the_same_bits(cascade):
             d.free()
 
 
-@pytest.mark.parametrize("fused", [0, 1024, 512], ids=["chunked", "fused", "fused512"])
+@pytest.mark.parametrize("fused", [0, 1024, 512, "cluster"], ids=["chunked", "fused", "fused512", "cluster"])
 def test_camshift_histograms_bin_for_bin(fused):
     """camshift.Histogram (camshift.js:49-72): the model histogram of initTracker and the full-frame histogram of track(),
     read back from the device, equal the oracle's in every one of the 4096 bins — incl. a rect reaching outside the frame
-    (transparent black -> bin 0), an odd pixel count, and a frame cut into many chunk histograms; on both schedules (the
+    (transparent black -> bin 0), an odd pixel count, and a frame cut into many chunk histograms; on every schedule (the
     single-launch kernel keeps its histogram in LDS and only writes it out with option cs_keep_hist)."""
-    opts = f"cs_fused_min={1 if fused else 1000000},cs_keep_hist=1" + (f",cs_fused_nt={fused}" if fused else "")
+    if fused == "cluster":  # chunk histograms -> LUT kernel -> cluster mean-shift, forced for every frame size
+        opts = "cs_fused_min=1000000,cs_cluster_min_px=1,cs_keep_hist=1"
+    else:
+        opts = f"cs_fused_min={1 if fused else 1000000},cs_keep_hist=1" + (f",cs_fused_nt={fused}" if fused else "")
     for (w, h, rect) in [(320, 240, (100, 60, 90, 80)), (321, 243, (-10, -5, 60, 70)), (1280, 720, (1200, 650, 200, 200))]:
         a = synth.blob_frame(w, h, w // 2, h // 2, w // 6, h // 8, (4, 3, 5), (200, 60, 40), seed=5)
         b = synth.blob_frame(w, h, w // 2 + 3, h // 2 + 2, w // 6, h // 8, (4, 3, 5), (200, 60, 40), seed=6)
