@@ -285,6 +285,23 @@ class Context:
         self._check(self._lib.ht_camshift_debug_hist(self._h, stream, model.ctypes.data, cur.ctypes.data if current else None))
         return model, cur
 
+    _BP_KINDS = {"rgba8": native.HT_BP_RGBA8, "f64": native.HT_BP_F64}
+
+    def camshift_backproject(self, n: int, first: int = 0, kind: str = "rgba8") -> np.ndarray:
+        """Back-projection (camshift.js:172-196, 314-353) of bound frames [0, n) through the models of streams [first, first + n):
+        kind "rgba8" -> uint8 [n, H, W, 4], the bytes of getBackProjectionImg().data; "f64" -> float64 [n, H, W], getPdf()[x][y] at
+        [y, x].  Computed on the device; changes no tracker state."""
+        k = self._BP_KINDS.get(kind, kind)  # an unknown kind reaches the library, which reports it
+        shape = (n, self.height, self.width) if k == native.HT_BP_F64 else (n, self.height, self.width, 4)
+        out = np.zeros(shape if n > 0 else (0,), dtype=np.float64 if k == native.HT_BP_F64 else np.uint8)
+        self._check(self._lib.ht_camshift_backproject(self._h, first, n, int(k), out.ctypes.data, 0))
+        return out
+
+    def camshift_backproject_device(self, dev_ptr: int, n: int, first: int = 0, kind: str = "rgba8", stride: int = 0):
+        """The same into device memory at dev_ptr (frames `stride` bytes apart, 0 = packed; pointer and stride multiples of the
+        element size): enqueued on the context's stream, no copy, no wait."""
+        self._check(self._lib.ht_camshift_backproject_device(self._h, first, n, int(self._BP_KINDS.get(kind, kind)), dev_ptr, stride))
+
     # -- measurement --------------------------------------------------------------------------------------------
     def profile(self, on: bool = True):
         self._check(self._lib.ht_profile(self._h, int(on)))

@@ -990,6 +990,14 @@ ht_status cs_check_err(ht_ctx *c, const char *where) {
 }
 }  // namespace
 
+// the histogram pass for callers outside this unit (ht_backproject.hip): host code only, the kernel stays here
+void ht_cs_hist_plan(uint32_t npix, int nstreams, uint32_t *chunk_px, uint32_t *nchunks) { hist_chunks(npix, hist_max_chunks(nstreams), chunk_px, nchunks); }
+ht_status ht_cs_hist_launch(ht_ctx *c, const uint8_t *frames, size_t frame_stride, int n, uint32_t npix, uint32_t chunk_px, uint32_t nchunks, uint32_t *hist) {
+    hipLaunchKernelGGL(k_cs_hist, dim3(nchunks, n), dim3(HIST_NT), 0, c->stream, frames, frame_stride, npix, chunk_px, hist);
+    HT_HIP(c, hipGetLastError());
+    return HT_OK;
+}
+
 extern "C" ht_status ht_camshift_reserve(ht_ctx *c, int32_t nstreams) {
     if (!c || nstreams <= 0) return HT_ERR_INVALID;
     HT_HIP(c, hipSetDevice(c->device));

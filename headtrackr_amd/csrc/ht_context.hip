@@ -522,6 +522,7 @@ extern "C" void ht_destroy(ht_ctx *c) {
     if (c->d_cs_seq_out) (void)hipFree(c->d_cs_seq_out);
     if (c->d_cs_lut) (void)hipFree(c->d_cs_lut);
     if (c->d_cs_parts) (void)hipFree(c->d_cs_parts);
+    ht_backproject_free(c);
     if (c->d_gather) (void)hipFree(c->d_gather);
     for (auto &a : release) {
         if (a.orphan) {  // whatever a context that has meanwhile re-bound elsewhere still had enqueued against it has to be through

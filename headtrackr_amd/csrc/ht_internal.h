@@ -422,6 +422,14 @@ struct ht_ctx {
     int cs_last_first = 0, cs_last_n = 0, cs_last_chunks = 0;  // layout of d_cs_hist after the last track call (debug read-back)
     const uint32_t *cs_last_hist = nullptr;                    // ... and which half of d_cs_hist it used
 
+    // back-projection (ht_backproject.hip): scratch of its own, grown on demand, so that a call between two track steps leaves d_cs_hist,
+    // d_cs_lut and the exchange slots alone.  Capacities in elements.
+    uint32_t *d_bp_hist = nullptr;    // [frames][chunks][4096] chunk histograms of the bound frames
+    double *d_bp_lut_w = nullptr;     // [frames][4096] weights (HT_BP_F64)
+    uint32_t *d_bp_lut_px = nullptr;  // [frames][4096] expanded pixels v, v, v, 255 (HT_BP_RGBA8)
+    uint8_t *d_bp_out = nullptr;      // staging of the host form's result
+    size_t bp_hist_cap = 0, bp_lut_w_cap = 0, bp_lut_px_cap = 0, bp_out_cap = 0;
+
     std::vector<std::pair<void *, size_t>> user_allocs;  // ht_device_alloc buffers still alive (pointer, bytes): freed by ht_destroy at the latest
 
     // multi-GPU exchange buffer (ht_allgather_best_faces)
@@ -463,6 +471,11 @@ struct HtProfScope {
 // implemented in the .hip files ---------------------------------------------------------------------------
 void ht_cluster_gate_forget(const ht_ctx *ctx);             // ht_camshift.hip
 void ht_capture_mark(ht_ctx *ctx, bool on);                 // ht_camshift.hip: ctx->capturing, ordered against fused_threads' stream queries
+// ht_camshift.hip: the chunk plan of the full-frame histogram pass for a call of nstreams frames, and k_cs_hist on n frames into
+// hist[n][nchunks][4096] (for ht_backproject.hip, which must not carry a copy of the kernel)
+void ht_cs_hist_plan(uint32_t npix, int nstreams, uint32_t *chunk_px, uint32_t *nchunks);
+ht_status ht_cs_hist_launch(ht_ctx *ctx, const uint8_t *frames, size_t frame_stride, int n, uint32_t npix, uint32_t chunk_px, uint32_t nchunks, uint32_t *hist);
+void ht_backproject_free(ht_ctx *ctx);                      // ht_backproject.hip: its scratch (ht_destroy)
 ht_status ht_launch_pyramid(ht_ctx *ctx, uint32_t flags);   // ht_pyramid.hip
 ht_status ht_launch_scan(ht_ctx *ctx, uint32_t flags);      // ht_scan.hip
 ht_status ht_launch_scan_early(ht_ctx *ctx, uint32_t flags); // ht_scan.hip: called by ht_launch_pyramid after generation early_gen

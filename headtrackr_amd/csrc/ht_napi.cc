@@ -30,6 +30,8 @@
 //   camshiftTrackCollect(ctx, n) -> Float64Array(9n)
 //   camshiftTrackSequence(ctx, first, n, calcAngles, dev, Float64Array byteOffsets[ncalls], frameStride, outAll, fetch) -> Float64Array | undefined
 //   camshiftSequenceCollect(ctx, n, ncalls, outAll) -> Float64Array
+//   camshiftBackProject(ctx, n, first, kind) -> Uint8Array(4 n w h) (BP_RGBA8) | Float64Array(n w h) (BP_F64): back-projection of the bound frames
+//   camshiftBackProjectDevice(ctx, n, first, kind, dev, byteOffset, stride)   the same into a deviceAlloc() buffer, enqueue only
 //   framesBound(ctx), framesEnqueued(ctx), graphLaunches(ctx)
 #include <node_api.h>
 
@@ -1067,6 +1069,66 @@ napi_value CamshiftSequenceCollect(napi_env env, napi_callback_info info) {
     return trackobjs_result(env, out);
 }
 
+// camshiftBackProject(ctx, n, first, kind) -> Uint8Array(n*w*h*4) | Float64Array(n*w*h): ht_camshift_backproject of the bound frames
+napi_value CamshiftBackProject(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Locked L;
+    int32_t n = 0, first = 0, kind = 0;
+    if (too_few(env, argc, 4) || !lock_ctx(env, argv[0], &L)) return nullptr;
+    if (!get_i32(env, argv[1], &n) || !get_i32(env, argv[2], &first) || !get_i32(env, argv[3], &kind) || n <= 0 || (kind != HT_BP_RGBA8 && kind != HT_BP_F64)) {
+        napi_throw_type_error(env, nullptr, "camshiftBackProject(ctx, n, first, kind = BP_RGBA8 | BP_F64)");
+        return nullptr;
+    }
+    ht_plane_info pl;  // level 0 of the pyramid is the frame itself
+    if (ht_plane(L.ctx, 0, 0, &pl) != HT_OK || pl.width <= 0 || pl.height <= 0) {
+        napi_throw_error(env, nullptr, "camshiftBackProject: no geometry (setGeometry first)");
+        return nullptr;
+    }
+    const size_t elem = kind == HT_BP_F64 ? 8 : 4, count = (size_t)n * (size_t)pl.width * (size_t)pl.height;
+    napi_value ab, ta;
+    void *p = nullptr;
+    NAPI_OK(napi_create_arraybuffer(env, count * elem, &p, &ab));
+    // the stride is passed explicitly: the library refuses one that is smaller than ITS frame, so the buffer can never be too small
+    ht_status st = ht_camshift_backproject(L.ctx, first, n, kind, p, (size_t)pl.width * (size_t)pl.height * elem);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_backproject");
+    if (kind == HT_BP_F64) NAPI_OK(napi_create_typedarray(env, napi_float64_array, count, ab, 0, &ta));
+    else NAPI_OK(napi_create_typedarray(env, napi_uint8_array, count * 4, ab, 0, &ta));
+    return ta;
+}
+
+// camshiftBackProjectDevice(ctx, n, first, kind, dev, byteOffset, stride): the same into a deviceAlloc() buffer, enqueue only
+napi_value CamshiftBackProjectDevice(napi_env env, napi_callback_info info) {
+    size_t argc = 7;
+    napi_value argv[7];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Locked L;
+    DevBuf *d = nullptr;
+    int32_t n = 0, first = 0, kind = 0;
+    size_t off = 0, stride = 0;
+    if (too_few(env, argc, 7) || !lock_ctx(env, argv[0], &L)) return nullptr;
+    if (!get_i32(env, argv[1], &n) || !get_i32(env, argv[2], &first) || !get_i32(env, argv[3], &kind) || n <= 0 || (kind != HT_BP_RGBA8 && kind != HT_BP_F64)) {
+        napi_throw_type_error(env, nullptr, "camshiftBackProjectDevice(ctx, n, first, kind = BP_RGBA8 | BP_F64, dev, byteOffset, stride)");
+        return nullptr;
+    }
+    if (!get_devbuf(env, argv[4], &d)) return nullptr;
+    ht_plane_info pl;
+    if (ht_plane(L.ctx, 0, 0, &pl) != HT_OK || pl.width <= 0 || pl.height <= 0) {
+        napi_throw_error(env, nullptr, "camshiftBackProjectDevice: no geometry (setGeometry first)");
+        return nullptr;
+    }
+    const size_t frame = (size_t)pl.width * (size_t)pl.height * (kind == HT_BP_F64 ? 8 : 4);
+    if (!get_offset(env, argv[5], &off) || !get_offset(env, argv[6], &stride) || (stride != 0 && stride < frame) ||
+        off + (size_t)(n - 1) * (stride ? stride : frame) + frame > d->bytes) {
+        napi_throw_range_error(env, nullptr, "camshiftBackProjectDevice(ctx, n, first, kind, dev, byteOffset, stride): outside the device buffer");
+        return nullptr;
+    }
+    ht_status st = ht_camshift_backproject_device(L.ctx, first, n, kind, static_cast<char *>(d->ptr) + off, stride ? stride : frame);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_backproject_device");
+    return nullptr;
+}
+
 napi_value ctx_counter(napi_env env, napi_callback_info info, int which) {
     size_t argc = 1;
     napi_value argv[1];
@@ -1099,6 +1161,7 @@ napi_value Init(napi_env env, napi_value exports) {
                {"detectWhitebalance", DetectWhitebalance}, {"whitebalanceBound", WhitebalanceBound},
                {"camshiftInitBound", CamshiftInitBound}, {"camshiftTrackBound", CamshiftTrackBound}, {"camshiftTrackCollect", CamshiftTrackCollect},
                {"camshiftTrackSequence", CamshiftTrackSequence}, {"camshiftSequenceCollect", CamshiftSequenceCollect},
+               {"camshiftBackProject", CamshiftBackProject}, {"camshiftBackProjectDevice", CamshiftBackProjectDevice},
                {"framesBound", FramesBound},     {"framesEnqueued", FramesEnqueued}, {"graphLaunches", GraphLaunches}};
     for (auto &f : fns) {
         napi_value fn;
@@ -1116,6 +1179,10 @@ napi_value Init(napi_env env, napi_value exports) {
     napi_set_named_property(env, exports, "DETECT_WHITEBALANCE", v);
     napi_create_int32(env, HT_SCAN_STATS, &v);
     napi_set_named_property(env, exports, "SCAN_STATS", v);
+    napi_create_int32(env, HT_BP_RGBA8, &v);
+    napi_set_named_property(env, exports, "BP_RGBA8", v);
+    napi_create_int32(env, HT_BP_F64, &v);
+    napi_set_named_property(env, exports, "BP_F64", v);
     return exports;
 }
 

@@ -350,6 +350,10 @@ headtrackr.ccv.detect_objects_batch = function (frames, n, w, h, cascade, interv
  *     detectStep(set) (= detectStepEnqueue + detectStepFinish) / trackStep(set) / trackEnqueue(set) + trackCollect() / ingest(pinned) / swap()   K frame-synchronous live feeds, one time step per call (below)
  *     initTrackers(rects, set) / trackSequence(sets[], calcAngles, outAll) -> Float64Array(9 n [* calls]): n camshift streams,
  *                                           one track() per listed frame set, ONE host call (ht_camshift_track_sequence)
+ *     backProjection(set, kind)            -> Uint8Array(4 n w h) ('rgba8', default: getBackProjectionImg().data per frame) or
+ *                                           Float64Array(n w h) ('f64': getPdf()[x][y] at [y][x]) of the n frames of `set` (-1: whatever is
+ *                                           bound, as after swap()) through the batch's trackers, computed on the device
+ *                                           (ht_camshift_backproject); tracker state is untouched; throws before initTrackers / detectStep
  *     destroy() */
 headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
   opts = opts || {};
@@ -460,6 +464,12 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     A.camshiftTrackBound(ctxs[0], n, 0, calcAngles === false ? 0 : 1, false);
   };
   this.trackCollect = function () { return A.camshiftTrackCollect(ctxs[0], n); };
+  this.backProjection = function (set, kind) {
+    if (!trackers) throw new Error('DeviceBatch.backProjection: no trackers yet (initTrackers or detectStep first)');
+    if (kind !== undefined && kind !== 'rgba8' && kind !== 'f64') throw new RangeError("DeviceBatch.backProjection: kind is 'rgba8' or 'f64'");
+    bind0(set === undefined ? 0 : set);
+    return A.camshiftBackProject(ctxs[0], n, 0, kind === 'f64' ? A.BP_F64 : A.BP_RGBA8);
+  };
   this.graphLaunches = function () { return ctxs.reduce(function (s, c) { return s + A.graphLaunches(c); }, 0); };
   /* the frame buffer is shared by all `depth` contexts: the others go first (ht_device_free refuses while they have it bound) */
   this.destroy = function () { for (let i = ctxs.length - 1; i >= 1; i--) A.destroy(ctxs[i]); A.deviceFree(ctxs[0], dev); A.destroy(ctxs[0]); ctxs.length = 0; };
@@ -576,8 +586,8 @@ headtrackr.camshift.Tracker = function (params) { /* camshift.js:148-354 */
     try { this._trackImg(canvas.getContext('2d').getImageData(0, 0, canvas.width, canvas.height)); } finally { unbindFrames(); }
   };
 
-  /* debug getters: the back-projection is never materialised on the device (only these two functions can observe it),
-   * so it is rebuilt here on demand from the last frame (camshift.js:172-196, 314-353) */
+  /* debug getters (camshift.js:172-196, 314-353).  getPdf's result is an array of W arrays of boxed numbers — a W x H JavaScript loop
+   * whatever the source —, so it is rebuilt here from the last frame; getBackProjectionImg's bytes come from the device (below) */
   this.getPdf = function () {
     if (!lastFrame || !modelFrame) return undefined;
     const w = lastFrame.width, h = lastFrame.height, d = lastFrame.data;
@@ -607,6 +617,18 @@ headtrackr.camshift.Tracker = function (params) { /* camshift.js:148-354 */
   };
 
   this.getBackProjectionImg = function () {
+    /* device route (ht_camshift_backproject): the last frame through this tracker's model.  Inside facetrackr's detectCS the frame is
+     * still bound from _trackImg and bindFrame is a no-op; a stand-alone call uploads it again and drops the marker like every public
+     * entry point.  An addon without the entry point (the CPU test doubles) takes the host loop below. */
+    if (lastFrame && modelFrame && modelFrame.width > 0 && modelFrame.height > 0 && typeof addon().camshiftBackProject === 'function') {
+      const mine = csPool.ctx.boundImg !== lastFrame;
+      try {
+        bindFrame(csPool.ctx, lastFrame, headtrackr.cascade, 5);
+        const img = canvasCtx.createImageData(lastFrame.width, lastFrame.height);
+        img.data.set(addon().camshiftBackProject(csPool.ctx.handle, 1, slot, addon().BP_RGBA8));
+        return img;
+      } finally { if (mine) unbindFrames(); }
+    }
     const pdf = this.getPdf();
     const w = lastFrame.width, h = lastFrame.height;
     const img = canvasCtx.createImageData(w, h), out = img.data;

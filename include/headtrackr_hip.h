@@ -263,6 +263,19 @@ ht_status ht_camshift_stats(ht_ctx *ctx, int32_t first, int32_t n, uint64_t *win
  * (camshift.js:268), 4096 bins each (camshift.Histogram, camshift.js:49-72).  Either pointer may be NULL. */
 ht_status ht_camshift_debug_hist(ht_ctx *ctx, int32_t stream, uint32_t *model, uint32_t *current);
 
+/* Output kinds of the back-projection calls: 4 bytes (v, v, v, 255) per pixel, v = floor(255 * pdf) — the bytes of
+ * getBackProjectionImg().data (camshift.js:177-196) —, or one binary64 per pixel: getPdf()[x][y] stored at [y][x]. */
+enum { HT_BP_RGBA8 = 0, HT_BP_F64 = 1 };
+/* back-projection (camshift.js:172-196, 314-353) of bound frames [0, n) through the models of streams [first, first+n): per frame the
+ * weights w[b] = cur[b] ? min(model[b] / cur[b], 1) : 0 of its own histogram against the stream's model, looked up for every pixel; rows
+ * packed, frames out_stride bytes apart (0 = packed).  When the bound frame is the frame of the stream's last track() this is the
+ * reference's _pdf.  Needs nothing a track call leaves behind and changes no tracker state; a reserved stream that was never
+ * initialised yields zeros.  Waits for its result.  Every byte equals the reference's (integer and single binary64 operations only). */
+ht_status ht_camshift_backproject(ht_ctx *ctx, int32_t first, int32_t n, int32_t kind, void *out_host, size_t out_stride);
+/* The same into device memory (pointer and stride multiples of the element size: 4 bytes for HT_BP_RGBA8, 8 for HT_BP_F64): enqueued on the
+ * ctx stream behind the outstanding track steps, never copies or waits. */
+ht_status ht_camshift_backproject_device(ht_ctx *ctx, int32_t first, int32_t n, int32_t kind, void *out_dev, size_t out_stride);
+
 /* ---- multi-GPU: fixed-size result records, all-gathered over RCCL/xGMI ------------------------------------ */
 
 /* Single-process helper for hosts that drive several GPUs from one process (the Node addon): ctxs[i] are contexts
