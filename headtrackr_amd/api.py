@@ -111,6 +111,41 @@ class Context:
         self._check(self._lib.ht_bind_frames_device(self._h, dev_ptr, n, frame_stride or self.width * self.height * 4))
         self.nframes = n
 
+    def device_download(self, dev_ptr: int, nbytes: int) -> np.ndarray:
+        """nbytes of device memory at dev_ptr as a uint8 array, copied behind everything enqueued on the context's stream so far"""
+        out = np.empty(nbytes, dtype=np.uint8)
+        self._check(self._lib.ht_device_download(self._h, out.ctypes.data, dev_ptr, nbytes))
+        return out
+
+    # -- ingest: the loop's video -> canvas drawImage (main.js:170) ----------------------------------------------
+    @staticmethod
+    def _cs_rect(rect):
+        if rect is None:
+            return None
+        r = np.zeros(1, dtype=native.CS_RECT_DTYPE)
+        r[0] = tuple(int(v) for v in rect)
+        return r
+
+    def draw_frames(self, src: np.ndarray, rect=None):
+        """drawImage(video, sx, sy, sw, sh, 0, 0, W, H) for a host array src, uint8 [n, sh, sw, 4], onto the context's W x H geometry
+        (rect = (x, y, width, height) inside the source, None = the whole frame): scaled on the device, result bound like upload()."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        n, h, w, c = src.shape
+        assert c == 4
+        r = self._cs_rect(rect)
+        self._check(self._lib.ht_draw_frames(self._h, src.ctypes.data, n, w, h, 0, r.ctypes.data if r is not None else None))
+        self.nframes = n
+
+    def draw_frames_device(self, ptr: int, n: int, sw: int, sh: int, pitch: int = 0, stride: int = 0, rect=None, dst: int | None = None,
+                           dst_stride: int = 0):
+        """The same for n device-resident source frames of sw x sh pixels at ptr (rows `pitch` bytes, frames `stride` bytes apart,
+        0 = packed).  dst None: into the context's own frame buffer, which becomes the bound frames; otherwise into device memory at
+        dst (frames dst_stride apart), binding untouched.  Enqueued on the context's stream, no copy, no wait."""
+        r = self._cs_rect(rect)
+        self._check(self._lib.ht_draw_frames_device(self._h, ptr, n, sw, sh, pitch, stride, r.ctypes.data if r is not None else None, dst, dst_stride))
+        if dst is None:
+            self.nframes = n
+
     # -- detect -----------------------------------------------------------------------------------------------
     def detect_enqueue(self, flags: int = HT_INPUT_RGBA):
         self._check(self._lib.ht_detect_enqueue(self._h, flags))

@@ -44,7 +44,8 @@ def _newer(target: str, deps) -> bool:
 
 def build_lib(force: bool = False, verbose: bool = False) -> str:
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
-    deps = srcs + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".inc"))]
+    # (.hip: ht_ingest.hip is compiled as part of ht_backproject.hip, which includes it)
+    deps = srcs + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".inc", ".hip"))]
     deps += [os.path.join(ROOT, "include", "headtrackr_hip.h"), os.path.abspath(__file__)]
     if force or _newer(LIB, deps):
         objs, procs = [], []

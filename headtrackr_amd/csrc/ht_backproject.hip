@@ -12,6 +12,9 @@
 // workgroup copies its frame's LUT into LDS and streams its chunk of pixels through it.  Everything is an integer operation or ONE
 // correctly rounded binary64 operation, so the output is the reference's, byte for byte.
 //
+// This unit also compiles ht_ingest.hip (the video -> canvas draw, included at the end of this file; its names are prefixed ig_ / IG_
+// and share this file's anonymous namespace): the library keeps ONE code object besides the three fingerprinted ones.
+//
 // A translation unit of its own on purpose: profiles/traffic.json ties the committed hardware counters to the machine code of the
 // pyramid, scan and camshift code objects (benchlib/fingerprint.py), which must not change for a debug surface.  The fingerprint finds
 // a unit by a kernel-name substring; no kernel here may carry one of those markers in its name.
@@ -238,3 +241,7 @@ void ht_backproject_free(ht_ctx *c) {  // ht_destroy (the stream has been synchr
     c->d_bp_hist = nullptr, c->d_bp_lut_px = nullptr, c->d_bp_lut_w = nullptr, c->d_bp_out = nullptr;
     c->bp_hist_cap = c->bp_lut_w_cap = c->bp_lut_px_cap = c->bp_out_cap = 0;
 }
+
+// The video -> canvas draw (ht_draw_frames / ht_draw_frames_device, k_draw_frames) is compiled as part of this unit: the library keeps one
+// code object besides the three that profiles/traffic.json fingerprints, and tests/test_backproject_cpu.py counts them.
+#include "ht_ingest.hip"

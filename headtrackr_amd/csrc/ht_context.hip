@@ -523,6 +523,7 @@ extern "C" void ht_destroy(ht_ctx *c) {
     if (c->d_cs_lut) (void)hipFree(c->d_cs_lut);
     if (c->d_cs_parts) (void)hipFree(c->d_cs_parts);
     ht_backproject_free(c);
+    ht_ingest_free(c);
     if (c->d_gather) (void)hipFree(c->d_gather);
     for (auto &a : release) {
         if (a.orphan) {  // whatever a context that has meanwhile re-bound elsewhere still had enqueued against it has to be through
@@ -886,24 +887,35 @@ extern "C" ht_status ht_upload_frames(ht_ctx *c, const uint8_t *host_rgba, int32
         return ht_fail(c, HT_ERR_INVALID, "ht_upload_frames: bad frame count or stride");
     HT_HIP(c, hipSetDevice(c->device));
     const size_t need = fbytes * (size_t)n;
-    if (c->d_frames_own_bytes < need) {
-        HT_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->d_frames_own) (void)hipFree(c->d_frames_own);
-        c->d_frames_own = nullptr;
-        c->d_frames_own_bytes = 0;
-        if (hipMalloc(&c->d_frames_own, need) != hipSuccess) return ht_fail(c, HT_ERR_NOMEM, "ht_upload_frames: hipMalloc failed");
-        c->d_frames_own_bytes = need;
-    }
+    const ht_status st = ht_frames_own_reserve(c, need, "ht_upload_frames");
+    if (st != HT_OK) return st;
     if (frame_stride == fbytes) {
         HT_HIP(c, hipMemcpyAsync(c->d_frames_own, host_rgba, need, hipMemcpyHostToDevice, c->stream));
     } else {
         HT_HIP(c, hipMemcpy2DAsync(c->d_frames_own, fbytes, host_rgba, frame_stride, fbytes, (size_t)n, hipMemcpyHostToDevice, c->stream));
     }
+    ht_frames_bind_own(c, n);
+    return HT_OK;
+}
+
+// The context's own frame buffer, grown on demand (what ht_upload_frames and the bind form of ht_draw_frames_device write), and the
+// binding of its first n frames.
+ht_status ht_frames_own_reserve(ht_ctx *c, size_t need, const char *fn) {
+    if (c->d_frames_own_bytes >= need) return HT_OK;
+    HT_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->d_frames == c->d_frames_own) c->d_frames = nullptr, c->nframes = 0;  // bound inside the buffer that goes away (the caller binds the new one)
+    if (c->d_frames_own) (void)hipFree(c->d_frames_own);
+    c->d_frames_own = nullptr;
+    c->d_frames_own_bytes = 0;
+    if (hipMalloc(&c->d_frames_own, need) != hipSuccess) return (void)hipGetLastError(), ht_fail(c, HT_ERR_NOMEM, std::string(fn) + ": hipMalloc failed");
+    c->d_frames_own_bytes = need;
+    return HT_OK;
+}
+void ht_frames_bind_own(ht_ctx *c, int n) {
     c->d_frames = c->d_frames_own;
-    c->frame_stride = fbytes;
+    c->frame_stride = (size_t)c->W * c->H * 4;
     c->nframes = n;
     sweep_orphans(c);
-    return HT_OK;
 }
 
 extern "C" ht_status ht_upload_frames_async(ht_ctx *c, const uint8_t *host_rgba, int32_t n, size_t frame_stride) {
@@ -1022,6 +1034,15 @@ extern "C" ht_status ht_device_upload(ht_ctx *c, void *dst_dev, const void *src_
     if (bytes == 0) return HT_OK;
     HT_HIP(c, hipSetDevice(c->device));
     HT_HIP(c, hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, c->stream));
+    HT_HIP(c, hipStreamSynchronize(c->stream));
+    return HT_OK;
+}
+
+extern "C" ht_status ht_device_download(ht_ctx *c, void *dst_host, const void *src_dev, size_t bytes) {
+    if (!c || !dst_host || !src_dev) return HT_ERR_INVALID;
+    if (bytes == 0) return HT_OK;
+    HT_HIP(c, hipSetDevice(c->device));
+    HT_HIP(c, hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, c->stream));
     HT_HIP(c, hipStreamSynchronize(c->stream));
     return HT_OK;
 }

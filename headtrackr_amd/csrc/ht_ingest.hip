@@ -1,0 +1,214 @@
+// ht_ingest.hip — the loop's video -> canvas copy on the device (reference: src/main.js:170, 312).
+//
+//   canvasContext.drawImage(videoElement, 0, 0, canvasElement.width, canvasElement.height)
+//
+// A source frame of any size (or a rectangle of it: the 9-argument drawImage) is scaled onto the W x H work canvas that every later
+// stage reads.  The filter is the resampler DECLARED in oracle/canvas_shim.js — the one the pyramid kernels implement for gray planes —
+// on all four channels: ratios divided on the host, taps by rs_tap (ht_resample_tap.h), then per channel top / bot / v with explicit
+// __dmul_rn / __dadd_rn (never contracted) and a round-half-even store, the sequence of rs_pixels4 (ht_pyramid.hip).  Same size and
+// whole rect is an exact copy by that arithmetic (t = 0, u = 1 everywhere).
+//
+// One launch covers all n frames: grid (tile column, tile row, frame), a tile = 64 x 16 destination pixels, 256 threads.  80 threads
+// compute the tile's 64 column and 16 row taps into LDS (once per tile, not per pixel); then every thread produces 4 pixels of its
+// column, 4 rows apart: all 8 source reads (two rows x one 8-byte tap pair each) are issued before the first use, a pixel is stored as
+// one dword, a wavefront stores 256 contiguous bytes of a destination row.  Source pixels are NOT staged in LDS: neighbouring lanes'
+// tap pairs overlap or abut for ratios <= 2 and fall into the same 64-byte lines up to ratio 16, which the vector cache serves
+// (DESIGN.md §2.3 gives the reasoning; it is not backed by a measurement yet, profiles/ingest.txt lists what is open).
+//
+// A file of its own, compiled into the back-projection unit's code object (ht_backproject.hip includes it at its end): profiles/traffic.json
+// ties the committed hardware counters to the machine code of the pyramid, scan and camshift code objects, which this code must not touch
+// (benchlib/fingerprint.py finds a unit by a kernel-name substring; no kernel here may carry one), and the library keeps exactly one
+// code object besides those three (tests/test_backproject_cpu.py).
+#include <algorithm>
+#include <string>
+
+#include "ht_internal.h"
+#include "ht_resample_tap.h"
+
+namespace {
+
+constexpr int IG_TW = 64, IG_TH = 16, IG_NT = 256, IG_RPT = IG_TH / (IG_NT / IG_TW);  // 4 rows per thread
+
+// two neighbouring RGBA pixels as one access; the address is only pixel-aligned (legal for global memory on gfx950)
+typedef uint32_t ig_u32x2 __attribute__((ext_vector_type(2), aligned(4)));
+
+// one channel of one pixel: the declared sequence (rs_pixels4, ht_pyramid.hip), values within [0, 255]
+__device__ __forceinline__ uint32_t ig_channel(uint32_t p00, uint32_t p01, uint32_t p10, uint32_t p11, int sh, double cu, double ct, double ru, double rt) {
+    const double s00 = (double)((p00 >> sh) & 0xffu), s01 = (double)((p01 >> sh) & 0xffu);
+    const double s10 = (double)((p10 >> sh) & 0xffu), s11 = (double)((p11 >> sh) & 0xffu);
+    const double top = __dadd_rn(__dmul_rn(s00, cu), __dmul_rn(s01, ct));
+    const double bot = __dadd_rn(__dmul_rn(s10, cu), __dmul_rn(s11, ct));
+    const double vv = __dadd_rn(__dmul_rn(top, ru), __dmul_rn(bot, rt));
+    return (uint32_t)(int)__builtin_rint(vv) << sh;  // Uint8ClampedArray: round half to even
+}
+
+// src: frame 0 of the source, rows src_pitch bytes, frames src_stride bytes apart; (sx, sy, sw, sh): the source rect, inside the frame;
+// dst: dw x dh packed rows, frames dst_stride bytes apart; rx = sw / dw, ry = sh / dh from the host.
+__global__ __launch_bounds__(IG_NT) void k_draw_frames(const uint8_t *__restrict__ src, size_t src_pitch, size_t src_stride, uint8_t *__restrict__ dst,
+                                                       size_t dst_stride, int sx, int sy, int sw, int sh, int dw, int dh, double rx, double ry) {
+    __shared__ RsTap s_col[IG_TW], s_row[IG_TH];
+    const int X0 = blockIdx.x * IG_TW, Y0 = blockIdx.y * IG_TH;
+    if (threadIdx.x < IG_TW) s_col[threadIdx.x] = rs_tap(min(X0 + (int)threadIdx.x, dw - 1), rx, sw, sx);
+    else if (threadIdx.x < IG_TW + IG_TH) s_row[threadIdx.x - IG_TW] = rs_tap(min(Y0 + (int)threadIdx.x - IG_TW, dh - 1), ry, sh, sy);
+    __syncthreads();
+    const int col = threadIdx.x & (IG_TW - 1), r0 = threadIdx.x / IG_TW, x = X0 + col;
+    if (x >= dw) return;
+    const RsTap cx = s_col[col];
+    // the tap pair (a, b) as ONE 8-byte read: b == a + 1 unless a is the rect's last column (then b == a and the pair is read one
+    // pixel to the left, both taps taking its right half); a 1-pixel-wide rect has no pair and is read pixel by pixel
+    const bool pair = sw >= 2;
+    const int xa = pair ? min(cx.a, sx + sw - 2) : cx.a;
+    const bool right = cx.a != xa;
+    const uint8_t *frame = src + (size_t)blockIdx.z * src_stride + (size_t)xa * 4;
+    ig_u32x2 top2[IG_RPT], bot2[IG_RPT];
+    double ru[IG_RPT], rt[IG_RPT];
+    bool on[IG_RPT];
+#pragma unroll
+    for (int k = 0; k < IG_RPT; k++) {
+        const int j = r0 + k * (IG_NT / IG_TW);
+        on[k] = Y0 + j < dh;
+        const RsTap ty = s_row[j];
+        ru[k] = ty.u, rt[k] = ty.t;
+        top2[k] = bot2[k] = ig_u32x2{0u, 0u};
+        if (on[k]) {
+            const uint8_t *pa = frame + (size_t)ty.a * src_pitch, *pb = frame + (size_t)ty.b * src_pitch;
+            if (pair) {
+                top2[k] = *reinterpret_cast<const ig_u32x2 *>(pa);
+                bot2[k] = *reinterpret_cast<const ig_u32x2 *>(pb);
+            } else {
+                top2[k].x = top2[k].y = *reinterpret_cast<const uint32_t *>(pa);
+                bot2[k].x = bot2[k].y = *reinterpret_cast<const uint32_t *>(pb);
+            }
+        }
+    }
+    uint32_t *out = reinterpret_cast<uint32_t *>(dst + (size_t)blockIdx.z * dst_stride) + x;
+#pragma unroll
+    for (int k = 0; k < IG_RPT; k++) {
+        if (!on[k]) continue;
+        const uint32_t p00 = right ? top2[k].y : top2[k].x, p01 = top2[k].y, p10 = right ? bot2[k].y : bot2[k].x, p11 = bot2[k].y;
+        uint32_t o = 0;
+#pragma unroll
+        for (int ch = 0; ch < 4; ch++) o |= ig_channel(p00, p01, p10, p11, 8 * ch, cx.u, cx.t, ru[k], rt[k]);
+        out[(size_t)(Y0 + r0 + k * (IG_NT / IG_TW)) * dw] = o;
+    }
+}
+
+struct IgPlan {  // a validated call
+    int32_t sx, sy, sw, sh;
+    size_t pitch, sstride;  // effective source pitch / frame stride
+    size_t src_bytes;       // extent of the n source frames from src
+    size_t fbytes;          // bytes of one destination frame
+};
+
+// the checks both entry points share (the source described as the device will see it)
+ht_status ig_check(ht_ctx *c, const char *fn, int32_t n, int32_t src_width, int32_t src_height, size_t src_pitch, size_t src_frame_stride,
+                   const ht_cs_rect *rect, IgPlan *p) {
+    const std::string f(fn);
+    if (c->W == 0) return ht_fail(c, HT_ERR_STATE, f + ": call ht_set_geometry first");
+    if (n <= 0) return ht_fail(c, HT_ERR_INVALID, f + ": bad frame count");
+    if (src_width <= 0 || src_height <= 0 || src_width > 16384 || src_height > 16384)
+        return ht_fail(c, HT_ERR_INVALID, f + ": source width/height must be 1..16384");
+    p->pitch = src_pitch ? src_pitch : (size_t)src_width * 4;
+    if ((p->pitch & 3) || p->pitch < (size_t)src_width * 4) return ht_fail(c, HT_ERR_INVALID, f + ": source pitch smaller than a row or not a multiple of 4");
+    p->sstride = src_frame_stride ? src_frame_stride : p->pitch * (size_t)src_height;
+    if ((p->sstride & 3) || p->sstride < p->pitch * (size_t)src_height)
+        return ht_fail(c, HT_ERR_INVALID, f + ": source frame stride smaller than a frame or not a multiple of 4");
+    p->sx = p->sy = 0, p->sw = src_width, p->sh = src_height;
+    if (rect) {
+        if (rect->x < 0 || rect->y < 0 || rect->width <= 0 || rect->height <= 0 || rect->width > src_width - rect->x || rect->height > src_height - rect->y)
+            return ht_fail(c, HT_ERR_INVALID, f + ": source rect must lie wholly inside the source frame");
+        p->sx = rect->x, p->sy = rect->y, p->sw = rect->width, p->sh = rect->height;
+    }
+    p->src_bytes = (size_t)(n - 1) * p->sstride + p->pitch * (size_t)src_height;
+    p->fbytes = (size_t)c->W * c->H * 4;
+    return HT_OK;
+}
+
+bool ig_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return a && b && pa < pb + nb && pb < pa + na;
+}
+
+ht_status ig_launch(ht_ctx *c, const IgPlan &p, const uint8_t *src, int32_t n, uint8_t *dst, size_t dstride) {
+    HtProfScope ps(c, "draw_frames");
+    const double rx = (double)p.sw / (double)c->W, ry = (double)p.sh / (double)c->H;  // canvas_shim.js: one binary64 division each
+    const dim3 grid((c->W + IG_TW - 1) / IG_TW, (c->H + IG_TH - 1) / IG_TH, n);
+    hipLaunchKernelGGL(k_draw_frames, grid, dim3(IG_NT), 0, c->stream, src, p.pitch, p.sstride, dst, dstride, p.sx, p.sy, p.sw, p.sh, c->W, c->H, rx, ry);
+    HT_HIP(c, hipGetLastError());
+    return HT_OK;
+}
+
+// draws into the context's own frame buffer and binds the result.  Every argument error is reported before anything is touched; a HIP
+// failure here (the buffer has to grow and hipMalloc fails: HT_ERR_NOMEM; a failed launch: HT_ERR_HIP) leaves the context usable but,
+// when the buffer had to grow, without bound frames — the old buffer, and with it the old frames, is gone by then; the launch is ordered on the ctx stream behind every earlier reader
+// of that buffer (all of this context's work runs on that stream)
+ht_status ig_draw_bound(ht_ctx *c, const char *fn, const IgPlan &p, const uint8_t *src, int32_t n) {
+    ht_status st = ht_frames_own_reserve(c, p.fbytes * (size_t)n, fn);
+    if (st != HT_OK) return st;
+    if ((st = ig_launch(c, p, src, n, c->d_frames_own, p.fbytes)) != HT_OK) return st;
+    ht_frames_bind_own(c, n);
+    return HT_OK;
+}
+
+}  // namespace
+
+extern "C" ht_status ht_draw_frames_device(ht_ctx *c, const void *src_dev, int32_t n, int32_t src_width, int32_t src_height, size_t src_pitch,
+                                           size_t src_frame_stride, const ht_cs_rect *src_rect, void *dst_dev, size_t dst_frame_stride) {
+    if (!c) return HT_ERR_INVALID;
+    HtRange range("ht_draw_frames_device");
+    const char *fn = "ht_draw_frames_device";
+    IgPlan p;
+    ht_status st = ig_check(c, fn, n, src_width, src_height, src_pitch, src_frame_stride, src_rect, &p);
+    if (st != HT_OK) return st;
+    if (!src_dev || ((uintptr_t)src_dev & 3) || ((uintptr_t)dst_dev & 3))
+        return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": NULL source or misaligned pointer (4-byte alignment required)");
+    const uint8_t *src = static_cast<const uint8_t *>(src_dev);
+    HT_HIP(c, hipSetDevice(c->device));
+    if (!dst_dev) {
+        if (n > c->max_batch) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": more frames than the geometry's batch capacity");
+        // the buffer as it is now (it may be freed and reallocated for this call) and as far as this call writes it.  Defensive only: the
+        // library hands this buffer's address to nobody, so no caller can name a pointer into it except by accident
+        if (ig_overlap(src, p.src_bytes, c->d_frames_own, std::max(c->d_frames_own_bytes, p.fbytes * (size_t)n)))
+            return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": the source lies inside the context's own frame buffer");
+        return ig_draw_bound(c, fn, p, src, n);
+    }
+    const size_t dstride = dst_frame_stride ? dst_frame_stride : p.fbytes;
+    if ((dstride & 3) || dstride < p.fbytes) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": destination frame stride smaller than a frame or not a multiple of 4");
+    if (ig_overlap(src, p.src_bytes, dst_dev, (size_t)(n - 1) * dstride + p.fbytes))
+        return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": source and destination overlap");
+    return ig_launch(c, p, src, n, static_cast<uint8_t *>(dst_dev), dstride);
+}
+
+extern "C" ht_status ht_draw_frames(ht_ctx *c, const uint8_t *host_rgba, int32_t n, int32_t src_width, int32_t src_height, size_t src_frame_stride,
+                                    const ht_cs_rect *src_rect) {
+    if (!c) return HT_ERR_INVALID;
+    HtRange range("ht_draw_frames");
+    const char *fn = "ht_draw_frames";
+    IgPlan p;
+    const size_t sbytes = (size_t)(src_width > 0 ? src_width : 0) * (size_t)(src_height > 0 ? src_height : 0) * 4;
+    if (src_frame_stride && src_frame_stride < sbytes) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": source frame stride smaller than a frame");
+    ht_status st = ig_check(c, fn, n, src_width, src_height, 0, 0, src_rect, &p);  // staged packed: the caller's stride is applied by the copy
+    if (st != HT_OK) return st;
+    if (!host_rgba) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": NULL source");
+    if (n > c->max_batch) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": more frames than the geometry's batch capacity");
+    HT_HIP(c, hipSetDevice(c->device));
+    const size_t need = sbytes * (size_t)n;
+    if (c->ingest_src_cap < need) {  // a reallocation waits for the work in flight first, like every reallocation of the library
+        HT_HIP(c, hipStreamSynchronize(c->stream));
+        if (c->d_ingest_src) (void)hipFree(c->d_ingest_src);
+        c->d_ingest_src = nullptr, c->ingest_src_cap = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&c->d_ingest_src), need) != hipSuccess) {
+            (void)hipGetLastError();
+            return ht_fail(c, HT_ERR_NOMEM, std::string(fn) + ": hipMalloc failed (source staging)");
+        }
+        c->ingest_src_cap = need;
+    }
+    if (!src_frame_stride || src_frame_stride == sbytes) HT_HIP(c, hipMemcpyAsync(c->d_ingest_src, host_rgba, need, hipMemcpyHostToDevice, c->stream));
+    else HT_HIP(c, hipMemcpy2DAsync(c->d_ingest_src, sbytes, host_rgba, src_frame_stride, sbytes, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    return ig_draw_bound(c, fn, p, c->d_ingest_src, n);
+}
+
+void ht_ingest_free(ht_ctx *c) {  // ht_destroy (the stream has been synchronised)
+    if (c->d_ingest_src) (void)hipFree(c->d_ingest_src);
+    c->d_ingest_src = nullptr, c->ingest_src_cap = 0;
+}

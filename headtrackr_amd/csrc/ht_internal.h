@@ -430,6 +430,10 @@ struct ht_ctx {
     uint8_t *d_bp_out = nullptr;      // staging of the host form's result
     size_t bp_hist_cap = 0, bp_lut_w_cap = 0, bp_lut_px_cap = 0, bp_out_cap = 0;
 
+    // ingest (ht_ingest.hip): device staging of ht_draw_frames' host-resident source frames, grown on demand
+    uint8_t *d_ingest_src = nullptr;
+    size_t ingest_src_cap = 0;
+
     std::vector<std::pair<void *, size_t>> user_allocs;  // ht_device_alloc buffers still alive (pointer, bytes): freed by ht_destroy at the latest
 
     // multi-GPU exchange buffer (ht_allgather_best_faces)
@@ -476,6 +480,9 @@ void ht_capture_mark(ht_ctx *ctx, bool on);                 // ht_camshift.hip: 
 void ht_cs_hist_plan(uint32_t npix, int nstreams, uint32_t *chunk_px, uint32_t *nchunks);
 ht_status ht_cs_hist_launch(ht_ctx *ctx, const uint8_t *frames, size_t frame_stride, int n, uint32_t npix, uint32_t chunk_px, uint32_t nchunks, uint32_t *hist);
 void ht_backproject_free(ht_ctx *ctx);                      // ht_backproject.hip: its scratch (ht_destroy)
+void ht_ingest_free(ht_ctx *ctx);                           // ht_ingest.hip: the host form's source staging (ht_destroy)
+ht_status ht_frames_own_reserve(ht_ctx *ctx, size_t need, const char *fn);  // ht_context.hip: the context's own frame buffer holds >= need bytes
+void ht_frames_bind_own(ht_ctx *ctx, int n);                // ht_context.hip: binds its first n frames (packed), as after ht_upload_frames
 ht_status ht_launch_pyramid(ht_ctx *ctx, uint32_t flags);   // ht_pyramid.hip
 ht_status ht_launch_scan(ht_ctx *ctx, uint32_t flags);      // ht_scan.hip
 ht_status ht_launch_scan_early(ht_ctx *ctx, uint32_t flags); // ht_scan.hip: called by ht_launch_pyramid after generation early_gen

@@ -20,6 +20,7 @@
 // The pipelined path (what the throughput numbers are made of; every C-ABI export has a JS name):
 //   hostAlloc(bytes) -> Uint8Array over PINNED host memory (ht_host_alloc)         deviceAlloc(ctx, bytes) -> device buffer (external)
 //   deviceUpload(ctx, dev, byteOffset, Uint8Array)      deviceFree(ctx, dev)
+//   deviceDownload(ctx, dev, byteOffset, Uint8Array)    ht_device_download: fills the array from the buffer, behind the enqueued work; waits
 //   upload(ctx, rgba, n, w, h)            ht_upload_frames: bind host frames once, then any number of *Bound calls on them
 //   bindDevice(ctx, dev, byteOffset, n)   ht_bind_frames_device
 //   uploadAsync(ctx, rgba, n) / swapFrames(ctx)          double-buffered ingest (rgba should come from hostAlloc)
@@ -32,6 +33,10 @@
 //   camshiftSequenceCollect(ctx, n, ncalls, outAll) -> Float64Array
 //   camshiftBackProject(ctx, n, first, kind) -> Uint8Array(4 n w h) (BP_RGBA8) | Float64Array(n w h) (BP_F64): back-projection of the bound frames
 //   camshiftBackProjectDevice(ctx, n, first, kind, dev, byteOffset, stride)   the same into a deviceAlloc() buffer, enqueue only
+//   drawFrames(ctx, Uint8Array rgba, n, sw, sh, Int32Array rect[4] | null)   ht_draw_frames: the loop's video -> canvas drawImage (main.js:170) of n host
+//        frames of sw x sh onto the context's geometry, on the device; the result becomes the bound frames
+//   drawFramesDevice(ctx, srcDev, srcOffset, n, sw, sh, pitch, stride, rect | null, dstDev | null, dstOffset, dstStride, wait)   ht_draw_frames_device between
+//        deviceAlloc() buffers (dstDev null: into the context's own buffer, bound); wait = true ends with ht_synchronize
 //   framesBound(ctx), framesEnqueued(ctx), graphLaunches(ctx)
 #include <node_api.h>
 
@@ -793,6 +798,24 @@ napi_value DeviceUpload(napi_env env, napi_callback_info info) {
     return nullptr;
 }
 
+napi_value DeviceDownload(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Locked L;
+    DevBuf *d = nullptr;
+    uint8_t *dst = nullptr;
+    size_t len = 0, off = 0;
+    if (too_few(env, argc, 4) || !lock_ctx(env, argv[0], &L) || !get_devbuf(env, argv[1], &d)) return nullptr;
+    if (!get_offset(env, argv[2], &off) || !get_bytes(env, argv[3], &dst, &len) || off > d->bytes || len > d->bytes - off) {
+        napi_throw_range_error(env, nullptr, "deviceDownload(ctx, dev, byteOffset, Uint8Array): outside the device buffer");
+        return nullptr;
+    }
+    ht_status st = ht_device_download(L.ctx, dst, static_cast<char *>(d->ptr) + off, len);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_device_download");
+    return nullptr;
+}
+
 napi_value Upload(napi_env env, napi_callback_info info) {
     size_t argc = 5;
     napi_value argv[5];
@@ -1129,6 +1152,93 @@ napi_value CamshiftBackProjectDevice(napi_env env, napi_callback_info info) {
     return nullptr;
 }
 
+// rect argument of the draw calls: null / undefined (the whole source frame) or an Int32Array [x, y, width, height]
+bool get_rect(napi_env env, napi_value v, ht_cs_rect *r, const ht_cs_rect **out) {
+    napi_valuetype vt;
+    *out = nullptr;
+    if (napi_typeof(env, v, &vt) == napi_ok && (vt == napi_null || vt == napi_undefined)) return true;
+    napi_typedarray_type t;
+    size_t len, off;
+    void *p;
+    napi_value ab;
+    if (napi_get_typedarray_info(env, v, &t, &len, &p, &ab, &off) != napi_ok || t != napi_int32_array || len < 4) return false;
+    memcpy(r, p, sizeof(*r));
+    *out = r;
+    return true;
+}
+
+// drawFrames(ctx, rgba, n, sw, sh, rect | null): ht_draw_frames — n host frames of sw x sh drawn onto the context's geometry and bound
+napi_value DrawFrames(napi_env env, napi_callback_info info) {
+    size_t argc = 6;
+    napi_value argv[6];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    FrameArgs a;
+    ht_cs_rect r;
+    const ht_cs_rect *rp = nullptr;
+    if (too_few(env, argc, 5) || !parse_frames(env, argv, &a)) return nullptr;
+    if (argc > 5 && !get_rect(env, argv[5], &r, &rp)) {
+        napi_throw_type_error(env, nullptr, "drawFrames(ctx, Uint8Array rgba, n, sw, sh, Int32Array rect[4] | null)");
+        return nullptr;
+    }
+    ht_status st = ht_draw_frames(a.ctx, a.rgba, a.n, a.w, a.h, 0, rp);
+    if (st != HT_OK) return throw_ht(env, a.ctx, st, "ht_draw_frames");
+    return nullptr;
+}
+
+// drawFramesDevice(ctx, srcDev, srcOffset, n, sw, sh, pitch, stride, rect | null, dstDev | null, dstOffset, dstStride, wait): ht_draw_frames_device
+napi_value DrawFramesDevice(napi_env env, napi_callback_info info) {
+    size_t argc = 13;
+    napi_value argv[13];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    static const char *usage = "drawFramesDevice(ctx, srcDev, srcOffset, n, sw, sh, pitch, stride, rect | null, dstDev | null, dstOffset, dstStride, wait)";
+    Locked L;
+    DevBuf *src = nullptr, *dst = nullptr;
+    int32_t n = 0, sw = 0, sh = 0;
+    size_t soff = 0, pitch = 0, stride = 0, doff = 0, dstride = 0;
+    ht_cs_rect r;
+    const ht_cs_rect *rp = nullptr;
+    bool wait = false;
+    if (too_few(env, argc, 12) || !lock_ctx(env, argv[0], &L) || !get_devbuf(env, argv[1], &src)) return nullptr;
+    napi_valuetype vt;
+    if (napi_typeof(env, argv[9], &vt) != napi_ok) return nullptr;
+    if (vt != napi_null && vt != napi_undefined && !get_devbuf(env, argv[9], &dst)) return nullptr;
+    if (!get_offset(env, argv[2], &soff) || !get_i32(env, argv[3], &n) || !get_i32(env, argv[4], &sw) || !get_i32(env, argv[5], &sh) || !get_offset(env, argv[6], &pitch) ||
+        !get_offset(env, argv[7], &stride) || !get_rect(env, argv[8], &r, &rp) || !get_offset(env, argv[10], &doff) || !get_offset(env, argv[11], &dstride) || n <= 0 ||
+        sw <= 0 || sh <= 0) {
+        napi_throw_type_error(env, nullptr, usage);
+        return nullptr;
+    }
+    if (argc > 12) napi_get_value_bool(env, argv[12], &wait);
+    // the ranges must lie inside the buffers the handles stand for (the library cannot know their sizes); what it checks itself — strides smaller
+    // than a frame, alignment, overlap — is left to it
+    // no product below can wrap: a factor is first bounded by a division through the buffer size it has to fit into
+    const auto frames_fit = [](size_t off, size_t n, size_t stride, size_t frame, size_t bytes) {  // off + (n - 1) stride + frame <= bytes
+        if (off > bytes || frame > bytes - off) return false;
+        return n == 1 || stride <= (bytes - off - frame) / (n - 1);
+    };
+    const size_t p = pitch ? pitch : (size_t)sw * 4;
+    bool inside = p <= src->bytes / (size_t)sh;  // p * sh: one source frame
+    const size_t sframe = inside ? p * (size_t)sh : 0, ss = stride ? stride : sframe;
+    inside = inside && frames_fit(soff, (size_t)n, ss, sframe, src->bytes);
+    if (dst) {
+        ht_plane_info pl;  // level 0 of the pyramid is the frame itself
+        if (ht_plane(L.ctx, 0, 0, &pl) != HT_OK || pl.width <= 0 || pl.height <= 0) {
+            napi_throw_error(env, nullptr, "drawFramesDevice: no geometry (setGeometry first)");
+            return nullptr;
+        }
+        const size_t fb = (size_t)pl.width * (size_t)pl.height * 4;  // <= 16384 * 16384 * 4
+        inside = inside && frames_fit(doff, (size_t)n, dstride ? dstride : fb, fb, dst->bytes);
+    }
+    if (!inside) {
+        napi_throw_range_error(env, nullptr, (std::string(usage) + ": outside the device buffer").c_str());
+        return nullptr;
+    }
+    ht_status st = ht_draw_frames_device(L.ctx, static_cast<char *>(src->ptr) + soff, n, sw, sh, pitch, stride, rp, dst ? static_cast<char *>(dst->ptr) + doff : nullptr, dstride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_draw_frames_device");
+    if (wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
+    return nullptr;
+}
+
 napi_value ctx_counter(napi_env env, napi_callback_info info, int which) {
     size_t argc = 1;
     napi_value argv[1];
@@ -1155,13 +1265,14 @@ napi_value Init(napi_env env, napi_value exports) {
                {"camshiftInit", CamshiftInit},   {"camshiftTrack", CamshiftTrack}, {"info", Info},
                {"deviceCount", DeviceCount},     {"allgatherBest", AllgatherBest},
                {"exitNow", ExitNow},
-               {"hostAlloc", HostAlloc},         {"hostFree", HostFree},       {"deviceAlloc", DeviceAlloc}, {"deviceFree", DeviceFree}, {"deviceUpload", DeviceUpload},
+               {"hostAlloc", HostAlloc},         {"hostFree", HostFree},       {"deviceAlloc", DeviceAlloc}, {"deviceFree", DeviceFree}, {"deviceUpload", DeviceUpload}, {"deviceDownload", DeviceDownload},
                {"upload", Upload},               {"bindDevice", BindDevice},   {"uploadAsync", UploadAsync}, {"swapFrames", SwapFrames},
                {"detectEnqueue", DetectEnqueue}, {"detectCollect", DetectCollect}, {"collectBest", CollectBest},
                {"detectWhitebalance", DetectWhitebalance}, {"whitebalanceBound", WhitebalanceBound},
                {"camshiftInitBound", CamshiftInitBound}, {"camshiftTrackBound", CamshiftTrackBound}, {"camshiftTrackCollect", CamshiftTrackCollect},
                {"camshiftTrackSequence", CamshiftTrackSequence}, {"camshiftSequenceCollect", CamshiftSequenceCollect},
                {"camshiftBackProject", CamshiftBackProject}, {"camshiftBackProjectDevice", CamshiftBackProjectDevice},
+               {"drawFrames", DrawFrames},       {"drawFramesDevice", DrawFramesDevice},
                {"framesBound", FramesBound},     {"framesEnqueued", FramesEnqueued}, {"graphLaunches", GraphLaunches}};
     for (auto &f : fns) {
         napi_value fn;

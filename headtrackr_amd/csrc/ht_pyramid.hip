@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "ht_internal.h"
+#include "ht_resample_tap.h"
 
 namespace {
 
@@ -142,21 +143,7 @@ __device__ __forceinline__ uint4 rs_buf_load16(__amdgpu_buffer_rsrc_t r, uint32_
     const rs_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
     return make_uint4(v.x, v.y, v.z, v.w);
 }
-typedef HtTap RsTap;  // {t, u: weights of b and a; a, b: source coordinates, absolute incl. the source rect origin}
-
-__device__ __forceinline__ RsTap rs_tap(int i, double r, int s, int origin) {
-    double f = __dadd_rn(__dmul_rn((double)i + 0.5, r), -0.5);
-    f = f < 0.0 ? 0.0 : f;
-    const double fmax = (double)(s - 1);
-    f = f > fmax ? fmax : f;
-    const double af = floor(f);
-    RsTap tp;
-    tp.a = origin + (int)af;
-    tp.b = origin + min((int)af + 1, s - 1);
-    tp.t = __dadd_rn(f, -af);
-    tp.u = __dadd_rn(1.0, -tp.t);
-    return tp;
-}
+// RsTap / rs_tap(i, r, s, origin): one tap of the declared resampler, ht_resample_tap.h (shared with ht_ingest.hip)
 
 // 4 destination pixels of one row from two source rows (r0/r1 either in LDS or in HBM: two instantiations, so the loads
 // are ds_read_u8 / global_load_ubyte rather than flat loads).  The 4 column taps live in registers (loaded once per thread,

@@ -20,6 +20,7 @@
  *                                        collect-best / re-enqueue), fused whitebalance, camshift call sequences — the JS form
  *                                        of the loop bench.py times; every C-ABI export has a JS name (INTEGRATION.md)
  *   hostAlloc(bytes)                     pinned host memory for frames that cross PCIe every call
+ *   ccv.drawFrames(video, canvas[, rect])  the loop's video -> canvas drawImage (main.js:170) scaled on the device -> ht_draw_frames_device
  *
  * "canvas" is anything with width, height and getContext('2d') -> {getImageData, putImageData, drawImage,
  * createImageData}; ./canvas.js provides one for Node.  Failure conventions are the reference's: empty arrays,
@@ -135,6 +136,34 @@ headtrackr.ccv.grayscale = function (canvas) { /* ccv.js:22-32, in place, return
     c.boundImg = null;
   }
   ctx.putImageData(img, 0, 0);
+  return canvas;
+};
+
+/* The loop's video -> canvas copy (main.js:170, 312) between two canvas-like objects, on the device: drawImage(video, 0, 0, canvas.width,
+ * canvas.height), or with rect = [sx, sy, sw, sh] (wholly inside the video) the 9-argument form.  The video's pixels are uploaded, scaled
+ * with the declared resampler (ht_draw_frames_device) and copied back into the canvas: the bytes canvas.js's drawImage writes.  With an
+ * addon that lacks the calls the canvas's own drawImage does it. */
+headtrackr.ccv.drawFrames = function (video, canvas, rect) {
+  const w = canvas.width, h = canvas.height, vw = video.width, vh = video.height, ctx2d = canvas.getContext('2d'), A = addon();
+  if (typeof A.drawFramesDevice !== 'function' || typeof A.deviceDownload !== 'function' || !(w > 0 && h > 0 && vw > 0 && vh > 0)) {
+    if (rect) ctx2d.drawImage(video, rect[0], rect[1], rect[2], rect[3], 0, 0, w, h); else ctx2d.drawImage(video, 0, 0, w, h);
+    return canvas;
+  }
+  const c = contextFor(headtrackr.cascade, 5);
+  ensureGeometry(c, w, h, 1, headtrackr.cascade, 5);
+  const src = video.getContext('2d').getImageData(0, 0, vw, vh), out = ctx2d.createImageData(w, h);
+  const grow = function (key, bytes) { /* two device buffers per context, kept between calls */
+    if (!c[key] || c[key + 'Bytes'] < bytes) {
+      if (c[key]) A.deviceFree(c.handle, c[key]);
+      c[key] = A.deviceAlloc(c.handle, bytes); c[key + 'Bytes'] = bytes;
+    }
+    return c[key];
+  };
+  const dsrc = grow('drawSrc', vw * vh * 4), ddst = grow('drawDst', w * h * 4);
+  A.deviceUpload(c.handle, dsrc, 0, src.data);
+  A.drawFramesDevice(c.handle, dsrc, 0, 1, vw, vh, 0, 0, rect ? Int32Array.from(rect) : null, ddst, 0, 0, false);
+  A.deviceDownload(c.handle, ddst, 0, out.data); /* behind the draw on the context's stream; waits */
+  ctx2d.putImageData(out, 0, 0);
   return canvas;
 };
 
@@ -354,6 +383,14 @@ headtrackr.ccv.detect_objects_batch = function (frames, n, w, h, cascade, interv
  *                                           Float64Array(n w h) ('f64': getPdf()[x][y] at [y][x]) of the n frames of `set` (-1: whatever is
  *                                           bound, as after swap()) through the batch's trackers, computed on the device
  *                                           (ht_camshift_backproject); tracker state is untouched; throws before initTrackers / detectStep
+ *   opts.source = {width, height, sets}: a second device buffer of `sets` SOURCE-size frame sets (n frames of width x height each) and the
+ *   loop's video -> canvas drawImage (main.js:170) between the two buffers, on the device (ht_draw_frames_device):
+ *     uploadSource(frames, sset = 0)       host -> HBM once (frames: Uint8Array of n*width*height*4 bytes)
+ *     draw(sset, set, rect)                source set `sset` scaled onto work set `set` (rect: Int32Array [x, y, width, height] inside a source
+ *                                           frame, default the whole frame); enqueue only, except that with depth > 1 it waits — the other
+ *                                           contexts read the work set on streams of their own
+ *     drawBound(sset, rect)                the same into context 0's own frame buffer, which becomes its bound frames: follow with the step
+ *                                           functions at set = -1
  *     destroy() */
 headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
   opts = opts || {};
@@ -470,9 +507,27 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     bind0(set === undefined ? 0 : set);
     return A.camshiftBackProject(ctxs[0], n, 0, kind === 'f64' ? A.BP_F64 : A.BP_RGBA8);
   };
+  const source = opts.source || null;
+  const ssetBytes = source ? n * source.width * source.height * 4 : 0;
+  const sdev = source ? A.deviceAlloc(ctxs[0], Math.max(1, source.sets || 1) * ssetBytes) : null;
+  const needSource = function (what) { if (!sdev) throw new Error('DeviceBatch.' + what + ': created without opts.source'); };
+  this.uploadSource = function (frames, sset) {
+    needSource('uploadSource');
+    if (frames.length < ssetBytes) throw new RangeError('DeviceBatch.uploadSource: need n*width*height*4 bytes');
+    A.deviceUpload(ctxs[0], sdev, (sset || 0) * ssetBytes, frames.subarray(0, ssetBytes));
+  };
+  this.draw = function (sset, set, rect) {
+    needSource('draw');
+    A.drawFramesDevice(ctxs[0], sdev, (sset || 0) * ssetBytes, n, source.width, source.height, 0, 0, rect || null, dev, (set || 0) * setBytes, 0, depth > 1);
+  };
+  this.drawBound = function (sset, rect) {
+    needSource('drawBound');
+    A.drawFramesDevice(ctxs[0], sdev, (sset || 0) * ssetBytes, n, source.width, source.height, 0, 0, rect || null, null, 0, 0, false);
+    bound = -1;
+  };
   this.graphLaunches = function () { return ctxs.reduce(function (s, c) { return s + A.graphLaunches(c); }, 0); };
   /* the frame buffer is shared by all `depth` contexts: the others go first (ht_device_free refuses while they have it bound) */
-  this.destroy = function () { for (let i = ctxs.length - 1; i >= 1; i--) A.destroy(ctxs[i]); A.deviceFree(ctxs[0], dev); A.destroy(ctxs[0]); ctxs.length = 0; };
+  this.destroy = function () { for (let i = ctxs.length - 1; i >= 1; i--) A.destroy(ctxs[i]); if (sdev) A.deviceFree(ctxs[0], sdev); A.deviceFree(ctxs[0], dev); A.destroy(ctxs[0]); ctxs.length = 0; };
 };
 
 /* ---- whitebalance ----------------------------------------------------------------------------------------------------- */

@@ -64,7 +64,7 @@ class PlaneInfo(C.Structure):
 # every symbol include/headtrackr_hip.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = [
     "ht_create", "ht_destroy", "ht_last_error", "ht_abi_version", "ht_set_geometry", "ht_num_levels", "ht_plane",
-    "ht_windows_per_frame", "ht_pyramid_bytes_per_frame", "ht_upload_frames", "ht_upload_frames_async", "ht_swap_frames", "ht_bind_frames_device", "ht_frames_bound", "ht_frames_enqueued", "ht_host_alloc", "ht_host_free", "ht_device_alloc", "ht_device_free", "ht_device_upload", "ht_detect_enqueue",
+    "ht_windows_per_frame", "ht_pyramid_bytes_per_frame", "ht_upload_frames", "ht_upload_frames_async", "ht_swap_frames", "ht_bind_frames_device", "ht_frames_bound", "ht_frames_enqueued", "ht_host_alloc", "ht_host_free", "ht_device_alloc", "ht_device_free", "ht_device_upload", "ht_device_download", "ht_draw_frames_device", "ht_draw_frames", "ht_detect_enqueue",
     "ht_detect_collect", "ht_detect_batch", "ht_pyramid_readback", "ht_stage_counts", "ht_grayscale_batch",
     "ht_whitebalance_batch", "ht_detect_whitebalance", "ht_hits_to_rects", "ht_group_rects", "ht_best_faces", "ht_detect_collect_best", "ht_detect_collect_best_requeue", "ht_camshift_reserve", "ht_camshift_init_batch",
     "ht_camshift_track_batch", "ht_camshift_track_collect", "ht_camshift_track_sequence", "ht_camshift_sequence_collect", "ht_camshift_stats", "ht_camshift_debug_hist", "ht_camshift_backproject", "ht_camshift_backproject_device", "ht_allgather_records", "ht_allgather_best_faces", "ht_device_count", "ht_profile", "ht_kernel_times", "ht_stream", "ht_graph_launches", "ht_synchronize",
@@ -121,6 +121,12 @@ def lib():
     L.ht_device_free.argtypes = [vp, vp]
     L.ht_device_upload.restype = i32
     L.ht_device_upload.argtypes = [vp, vp, vp, sz]
+    L.ht_device_download.restype = i32
+    L.ht_device_download.argtypes = [vp, vp, vp, sz]
+    L.ht_draw_frames_device.restype = i32
+    L.ht_draw_frames_device.argtypes = [vp, vp, i32, i32, i32, sz, sz, vp, vp, sz]
+    L.ht_draw_frames.restype = i32
+    L.ht_draw_frames.argtypes = [vp, u8p, i32, i32, i32, sz, vp]
     L.ht_detect_enqueue.restype = i32
     L.ht_detect_enqueue.argtypes = [vp, u32]
     L.ht_detect_collect.restype = i32

@@ -170,7 +170,9 @@ int32_t ht_frames_enqueued(const ht_ctx *ctx);
 
 /* Memory for hosts that have no HIP binding of their own (the Node addon): pinned host buffers — frames in them cross PCIe at link
  * speed and may be handed to ht_upload_frames_async — and device buffers for frames that stay resident in HBM across calls
- * (ht_bind_frames_device, ht_camshift_track_sequence).  ht_device_upload copies host -> device and returns when src may be reused. */
+ * (ht_bind_frames_device, ht_camshift_track_sequence).  ht_device_upload copies host -> device and returns when src may be reused;
+ * ht_device_download copies device -> host behind everything enqueued on the ctx stream so far (e.g. an ht_draw_frames_device into that
+ * buffer) and returns when dst_host holds the bytes. */
 ht_status ht_host_alloc(size_t bytes, void **out);
 void ht_host_free(void *p);
 ht_status ht_device_alloc(ht_ctx *ctx, size_t bytes, void **out);
@@ -178,6 +180,23 @@ ht_status ht_device_alloc(ht_ctx *ctx, size_t bytes, void **out);
  * context still has frames bound inside it (ht_bind_frames_device): rebind or destroy that context first. */
 ht_status ht_device_free(ht_ctx *ctx, void *p);
 ht_status ht_device_upload(ht_ctx *ctx, void *dst_dev, const void *src_host, size_t bytes);
+ht_status ht_device_download(ht_ctx *ctx, void *dst_host, const void *src_dev, size_t bytes);
+
+/* ---- ingest: the loop's video -> canvas copy (main.js:170, 312) ------------------------------------------ */
+
+/* drawImage(video, sx,sy,sw,sh, 0,0,W,H) for n frames. W x H = the context's geometry. src_rect NULL = whole source frame (the 5-argument
+ * form main.js uses). One rect for all n frames. Declared resampler of oracle/canvas_shim.js on all four channels, every byte equal.
+ * dst_dev NULL: the result goes into the context's own frame buffer and becomes the bound frames (ht_frames_bound() == n), exactly as
+ * after ht_upload_frames. Otherwise into the caller's buffer, frames dst_frame_stride apart (0 = packed), binding untouched.
+ * Enqueued on the ctx stream; never copies to the host, never waits.  Argument errors change nothing; HT_ERR_NOMEM / HT_ERR_HIP from the
+ * bind form when the context's buffer has to grow leave the context usable but without bound frames (the same holds for ht_upload_frames). */
+ht_status ht_draw_frames_device(ht_ctx *ctx, const void *src_dev, int32_t n, int32_t src_width, int32_t src_height,
+                                size_t src_pitch /* bytes per source row, 0 = packed */, size_t src_frame_stride /* 0 = packed */,
+                                const ht_cs_rect *src_rect, void *dst_dev, size_t dst_frame_stride);
+/* The same for host-resident source frames (rows packed). Staged through a context-owned device buffer that grows on demand.
+ * Result bound as above. Same completion contract as ht_upload_frames (host_rgba reusable on return). */
+ht_status ht_draw_frames(ht_ctx *ctx, const uint8_t *host_rgba, int32_t n, int32_t src_width, int32_t src_height,
+                         size_t src_frame_stride, const ht_cs_rect *src_rect);
 
 /* ---- detect: ccv.grayscale + ccv.detect_objects (ccv.js:22-32, 109-246) ---------------------------------- */
 
