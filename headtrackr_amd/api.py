@@ -285,6 +285,34 @@ class Context:
         self._check(self._lib.ht_camshift_track_collect(self._h, n, out.ctypes.data))
         return out
 
+    @staticmethod
+    def _pairs(pairs):
+        if isinstance(pairs, np.ndarray) and pairs.dtype == native.PAIR_DTYPE:
+            return np.ascontiguousarray(pairs)
+        p = np.zeros(len(pairs), dtype=native.PAIR_DTYPE)
+        for i, (s, f) in enumerate(pairs):
+            p[i] = (s, f)
+        return p
+
+    def camshift_init_pairs(self, pairs, rects):
+        """initTracker of stream pairs[i][0] on BOUND frame pairs[i][1] with rects[i] = (x, y, w, h): any reserved streams in any order,
+        frames may repeat (several trackers on one frame)."""
+        p = self._pairs(pairs)
+        if len(rects) != len(p):
+            raise ValueError("camshift_init_pairs: one rect per pair")
+        r = np.zeros(len(rects), dtype=native.CS_RECT_DTYPE)
+        for i, (x, y, w, h) in enumerate(rects):
+            r[i] = (x, y, w, h)
+        self._check(self._lib.ht_camshift_init_pairs(self._h, p.ctypes.data, len(p), r.ctypes.data))
+
+    def camshift_track_pairs(self, pairs, calc_angles: bool = True, fetch: bool = True):
+        """One track() of stream pairs[i][0] on bound frame pairs[i][1]; track objects in pair order.  The full-frame histogram is computed
+        once per distinct frame.  fetch=False: enqueue only, collected with camshift_track_collect(len(pairs))."""
+        p = self._pairs(pairs)
+        out = np.zeros(len(p), dtype=native.CS_TRACKOBJ_DTYPE)
+        self._check(self._lib.ht_camshift_track_pairs(self._h, p.ctypes.data, len(p), int(calc_angles), out.ctypes.data if fetch else None))
+        return out
+
     def camshift_track_sequence(self, dev_ptrs, n: int, calc_angles: bool = True, first: int = 0, frame_stride: int | None = None,
                                 fetch: str = "last", keep_all: bool = False):
         """len(dev_ptrs) successive track() calls in one host call; call k reads the n device-resident frames at dev_ptrs[k].

@@ -13,7 +13,8 @@
 // correctly rounded binary64 operation, so the output is the reference's, byte for byte.
 //
 // This unit also compiles ht_ingest.hip (the video -> canvas draw, included at the end of this file; its names are prefixed ig_ / IG_
-// and share this file's anonymous namespace): the library keeps ONE code object besides the three fingerprinted ones.
+// and share this file's anonymous namespace) and ht_cs_pairs.hip (camshift on (stream, frame) pairs, k_csp_*): the library keeps ONE code
+// object besides the three fingerprinted ones.
 //
 // A translation unit of its own on purpose: profiles/traffic.json ties the committed hardware counters to the machine code of the
 // pyramid, scan and camshift code objects (benchlib/fingerprint.py), which must not change for a debug surface.  The fingerprint finds
@@ -245,3 +246,7 @@ void ht_backproject_free(ht_ctx *c) {  // ht_destroy (the stream has been synchr
 // The video -> canvas draw (ht_draw_frames / ht_draw_frames_device, k_draw_frames) is compiled as part of this unit: the library keeps one
 // code object besides the three that profiles/traffic.json fingerprints, and tests/test_backproject_cpu.py counts them.
 #include "ht_ingest.hip"
+
+// So are the pair forms of the camshift calls (ht_camshift_init_pairs / ht_camshift_track_pairs, k_csp_*): new kernels must not enter the
+// fingerprinted camshift object, and the library keeps four code objects.
+#include "ht_cs_pairs.hip"

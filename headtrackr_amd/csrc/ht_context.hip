@@ -323,6 +323,7 @@ static bool apply_options(ht_ctx *c, const std::string &opts, std::string &why) 
         else if (key == "deep_v") c->dbg_deep_v = iv;
         else if (key == "cs_flags") c->cs_flags = iv != 0;
         else if (key == "cs_sync_ring") c->cs_sync_ring = iv != 0;
+        else if (key == "cs_pairs_force") c->cs_pairs_force = iv != 0;
         else if (key == "fp_sparse") c->fp_sparse = iv != 0;
         else if (key == "deep_grid") c->deep_grid = std::max(1, iv);
         else if (key == "split") c->opt_split = std::max(1, iv);
@@ -524,6 +525,7 @@ extern "C" void ht_destroy(ht_ctx *c) {
     if (c->d_cs_parts) (void)hipFree(c->d_cs_parts);
     ht_backproject_free(c);
     ht_ingest_free(c);
+    ht_cs_pairs_free(c);
     if (c->d_gather) (void)hipFree(c->d_gather);
     for (auto &a : release) {
         if (a.orphan) {  // whatever a context that has meanwhile re-bound elsewhere still had enqueued against it has to be through

@@ -430,6 +430,23 @@ struct ht_ctx {
     uint8_t *d_bp_out = nullptr;      // staging of the host form's result
     size_t bp_hist_cap = 0, bp_lut_w_cap = 0, bp_lut_px_cap = 0, bp_out_cap = 0;
 
+    // camshift on (stream, frame) pairs (ht_cs_pairs.hip): the call's pair table {stream, frame, histogram slot, rect} + list of distinct
+    // frames goes through a small ring of pinned staging buffers into ONE device table (copies and kernels are ordered by the stream);
+    // the chunk histograms of the distinct frames have scratch of their own, grown on demand.  Capacities in elements.
+    static constexpr int HT_CSP_STAGE = 4;
+    int32_t *d_csp_tab = nullptr;
+    size_t csp_tab_cap = 0;
+    int32_t *h_csp_tab[HT_CSP_STAGE] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev_csp_tab[HT_CSP_STAGE] = {nullptr, nullptr, nullptr, nullptr};  // the staging buffer's copy has left it
+    size_t h_csp_tab_cap = 0;
+    int csp_stage_next = 0;
+    uint32_t *d_csp_hist = nullptr;  // [distinct frames][chunks][4096]
+    size_t csp_hist_cap = 0;
+    bool csp_attr_set = false;       // > 64 KB dynamic LDS enabled for k_csp_meanshift on this context's device
+    bool cs_pairs_force = false;     // option cs_pairs_force=1: identity layouts (first + i, i) go through the pair kernels too (tests, A/B)
+    std::vector<int32_t> cs_pair_slot;  // after a pair call: histogram slot of every stream it paired (-1: not part of it), for ht_camshift_debug_hist
+    int cs_pair_chunks = 0;
+
     // ingest (ht_ingest.hip): device staging of ht_draw_frames' host-resident source frames, grown on demand
     uint8_t *d_ingest_src = nullptr;
     size_t ingest_src_cap = 0;
@@ -480,6 +497,7 @@ void ht_capture_mark(ht_ctx *ctx, bool on);                 // ht_camshift.hip: 
 void ht_cs_hist_plan(uint32_t npix, int nstreams, uint32_t *chunk_px, uint32_t *nchunks);
 ht_status ht_cs_hist_launch(ht_ctx *ctx, const uint8_t *frames, size_t frame_stride, int n, uint32_t npix, uint32_t chunk_px, uint32_t nchunks, uint32_t *hist);
 void ht_backproject_free(ht_ctx *ctx);                      // ht_backproject.hip: its scratch (ht_destroy)
+void ht_cs_pairs_free(ht_ctx *ctx);                         // ht_cs_pairs.hip: pair table, staging and histogram scratch (ht_destroy)
 void ht_ingest_free(ht_ctx *ctx);                           // ht_ingest.hip: the host form's source staging (ht_destroy)
 ht_status ht_frames_own_reserve(ht_ctx *ctx, size_t need, const char *fn);  // ht_context.hip: the context's own frame buffer holds >= need bytes
 void ht_frames_bind_own(ht_ctx *ctx, int n);                // ht_context.hip: binds its first n frames (packed), as after ht_upload_frames

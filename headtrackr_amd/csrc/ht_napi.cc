@@ -1017,6 +1017,63 @@ napi_value CamshiftTrackBound(napi_env env, napi_callback_info info) {
     return trackobjs_result(env, out);
 }
 
+// Int32Array pairs[2n] = stream0, frame0, stream1, frame1, ... (ht_cs_pair); *n = pairs
+bool get_pairs(napi_env env, napi_value v, const ht_cs_pair **pairs, int32_t *n) {
+    napi_typedarray_type t;
+    size_t len;
+    void *p;
+    napi_value ab;
+    size_t off;
+    if (napi_get_typedarray_info(env, v, &t, &len, &p, &ab, &off) != napi_ok || t != napi_int32_array || len < 2 || (len & 1) || len > (size_t)1 << 24) return false;
+    *pairs = static_cast<const ht_cs_pair *>(p);
+    *n = (int32_t)(len / 2);
+    return true;
+}
+
+napi_value CamshiftInitPairs(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Locked L;
+    const ht_cs_pair *pairs = nullptr;
+    int32_t n = 0;
+    napi_typedarray_type t;
+    size_t len;
+    void *p;
+    napi_value ab;
+    size_t off;
+    if (too_few(env, argc, 3) || !lock_ctx(env, argv[0], &L)) return nullptr;
+    if (!get_pairs(env, argv[1], &pairs, &n) || napi_get_typedarray_info(env, argv[2], &t, &len, &p, &ab, &off) != napi_ok || t != napi_int32_array ||
+        len < (size_t)n * 4) {
+        napi_throw_type_error(env, nullptr, "camshiftInitPairs(ctx, Int32Array pairs[2n], Int32Array rects[4n])");
+        return nullptr;
+    }
+    ht_status st = ht_camshift_init_pairs(L.ctx, pairs, n, static_cast<const ht_cs_rect *>(p));
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_init_pairs");
+    return nullptr;
+}
+
+napi_value CamshiftTrackPairs(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Locked L;
+    const ht_cs_pair *pairs = nullptr;
+    int32_t n = 0, calc = 1;
+    bool fetch = true;
+    if (too_few(env, argc, 3) || !lock_ctx(env, argv[0], &L)) return nullptr;
+    if (!get_pairs(env, argv[1], &pairs, &n) || !get_i32(env, argv[2], &calc)) {
+        napi_throw_type_error(env, nullptr, "camshiftTrackPairs(ctx, Int32Array pairs[2n], calcAngles, fetch)");
+        return nullptr;
+    }
+    if (argc > 3) napi_get_value_bool(env, argv[3], &fetch);
+    std::vector<ht_cs_trackobj> out((size_t)n);
+    ht_status st = ht_camshift_track_pairs(L.ctx, pairs, n, calc, fetch ? out.data() : nullptr);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_track_pairs");
+    if (!fetch) return nullptr;
+    return trackobjs_result(env, out);
+}
+
 napi_value CamshiftTrackCollect(napi_env env, napi_callback_info info) {
     size_t argc = 2;
     napi_value argv[2];
@@ -1270,6 +1327,7 @@ napi_value Init(napi_env env, napi_value exports) {
                {"detectEnqueue", DetectEnqueue}, {"detectCollect", DetectCollect}, {"collectBest", CollectBest},
                {"detectWhitebalance", DetectWhitebalance}, {"whitebalanceBound", WhitebalanceBound},
                {"camshiftInitBound", CamshiftInitBound}, {"camshiftTrackBound", CamshiftTrackBound}, {"camshiftTrackCollect", CamshiftTrackCollect},
+               {"camshiftInitPairs", CamshiftInitPairs}, {"camshiftTrackPairs", CamshiftTrackPairs},
                {"camshiftTrackSequence", CamshiftTrackSequence}, {"camshiftSequenceCollect", CamshiftSequenceCollect},
                {"camshiftBackProject", CamshiftBackProject}, {"camshiftBackProjectDevice", CamshiftBackProjectDevice},
                {"drawFrames", DrawFrames},       {"drawFramesDevice", DrawFramesDevice},

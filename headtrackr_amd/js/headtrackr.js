@@ -12,6 +12,7 @@
  *                                                                            seq construction + grouping stay in JS
  *   ccv.array_group(seq,gfunc)                          ccv.js:34-107    (host, O(n^2) on a few dozen rects)
  *   camshift.Tracker / Histogram / Moments / Rectangle / TrackObj          camshift.js:49-378 -> ht_camshift_*
+ *   camshift.MultiTracker                               several trackers on one canvas, one device call per frame -> ht_camshift_*_pairs
  *   facetrackr.Tracker / TrackObj                       facetrackr.js:37-255  (state machine WB -> VJ -> CS)
  *   getWhitebalance(canvas)                             whitebalance.js:5-30 -> ht_whitebalance_batch
  * plus batch entry points that the single-frame browser API has no room for:
@@ -367,7 +368,7 @@ headtrackr.ccv.detect_objects_batch = function (frames, n, w, h, cascade, interv
 };
 
 /* ---- device-resident batches: the pipelined path -------------------------------------------------------------------------
- * new ccv.DeviceBatch(w, h, n, {cascade, interval, device, depth, sets}):
+ * new ccv.DeviceBatch(w, h, n, {cascade, interval, device, depth, sets, trackers}):
  *   `sets` frame sets of n RGBA frames each live in ONE device buffer (HBM); `depth` native contexts (own HIP streams, own pyramid
  *   arenas) take detect batches in turn so that `depth` batches are in flight while the host groups the previous one
  *   (ht_detect_enqueue + ht_detect_collect_best_requeue: the C2 / C4 loop of bench.py, from JavaScript).
@@ -391,7 +392,9 @@ headtrackr.ccv.detect_objects_batch = function (frames, n, w, h, cascade, interv
  *                                           contexts read the work set on streams of their own
  *     drawBound(sset, rect)                the same into context 0's own frame buffer, which becomes its bound frames: follow with the step
  *                                           functions at set = -1
- *     destroy() */
+ *     initPairs / trackPairs / trackPairsEnqueue / detectStepFinish(min_neighbors, {feeds})   trackers and frames paired freely (below);
+                                           opts.trackers = tracker slots to reserve (default n)
+     destroy() */
 headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
   opts = opts || {};
   const cascade = opts.cascade || headtrackr.cascade, interval = opts.interval === undefined ? 5 : opts.interval;
@@ -408,7 +411,9 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     ctxs.push(hnd);
   }
   const dev = A.deviceAlloc(ctxs[0], sets * setBytes);
+  const slots = Math.max(n, opts.trackers | 0); /* tracker slots reserved on first use: n, or opts.trackers when several trackers share a frame */
   let bound = -1, trackers = false;
+  const pendingTrack = []; /* streams of the outstanding enqueue-only track steps, oldest first (pair steps need not have n) */
   const bind = function (set) { if (bound !== set) { ctxs.forEach(function (c) { A.bindDevice(c, dev, set * setBytes, n, fbytes); }); bound = set; } };
   this.width = w; this.height = h; this.frames = n; this.depth = depth;
   this.upload = function (frames, set) {
@@ -446,7 +451,7 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
   };
   this.initTrackers = function (rects, set) { /* rects: Int32Array [x, y, width, height] per stream (camshift.js:198-211) */
     bind(set || 0);
-    if (!trackers) { A.camshiftReserve(ctxs[0], n); trackers = true; }
+    if (!trackers) { A.camshiftReserve(ctxs[0], slots); trackers = true; }
     A.camshiftInitBound(ctxs[0], n, 0, rects);
   };
   this.trackSequence = function (setList, calcAngles, outAll) {
@@ -475,15 +480,31 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     this.detectStepEnqueue(set);
     return this.detectStepFinish(min_neighbors);
   };
-  this.detectStepFinish = function (min_neighbors) {
+  this.detectStepFinish = function (min_neighbors, sel) {
     const r = A.collectBest(ctxs[0], min_neighbors === undefined ? 1 : min_neighbors, -1);
+    if (sel && sel.feeds) { /* feeds in different states: trackers only for the LISTED feeds that found a face (facetrackr.js:97) */
+      const found = [];
+      for (let i = 0; i < sel.feeds.length; i++) {
+        const f = sel.feeds[i];
+        if (!(f >= 0 && f < n)) throw new RangeError('DeviceBatch.detectStepFinish: feed ' + f + ' is not one of the ' + n + ' feeds');
+        if (r.best[6 * f + 5] > 0 && r.best[6 * f + 4] > -10) found.push(f);
+      }
+      const pr = new Int32Array(2 * found.length), rc = new Int32Array(4 * found.length);
+      found.forEach(function (f, i) {
+        pr[2 * i] = f; pr[2 * i + 1] = f; /* feed f's tracker is stream f, its frame is frame f of the batch */
+        for (let k = 0; k < 4; k++) rc[4 * i + k] = Math.floor(r.best[6 * f + k]);
+      });
+      if (found.length) { needPairs('detectStepFinish'); reserve(); A.camshiftInitPairs(ctxs[0], pr, rc); }
+      r.initialised = found; r.rects = rc;
+      return r;
+    }
     const rects = new Int32Array(4 * n);
     for (let f = 0; f < n; f++) {
       const ok = r.best[6 * f + 5] > 0 && r.best[6 * f + 4] > -10;
       const v = ok ? [r.best[6 * f], r.best[6 * f + 1], r.best[6 * f + 2], r.best[6 * f + 3]] : [w >> 2, h >> 2, w >> 1, h >> 1];
       for (let k = 0; k < 4; k++) rects[4 * f + k] = Math.floor(v[k]);
     }
-    if (!trackers) { A.camshiftReserve(ctxs[0], n); trackers = true; }
+    if (!trackers) { A.camshiftReserve(ctxs[0], slots); trackers = true; }
     A.camshiftInitBound(ctxs[0], n, 0, rects);
     r.rects = rects;
     return r;
@@ -499,8 +520,45 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
   this.trackEnqueue = function (set, calcAngles) {
     bind0(set === undefined ? 0 : set);
     A.camshiftTrackBound(ctxs[0], n, 0, calcAngles === false ? 0 : 1, false);
+    pendingTrack.push(n);
   };
-  this.trackCollect = function () { return A.camshiftTrackCollect(ctxs[0], n); };
+  this.trackCollect = function () { return A.camshiftTrackCollect(ctxs[0], pendingTrack.length ? pendingTrack.shift() : n); };
+  /* Trackers and frames paired freely (ht_camshift_init_pairs / ht_camshift_track_pairs): pairs = Int32Array [stream, frame, ...] — any of
+   * the opts.trackers slots (default n) in any order, each at most once per call, on any of the n frames of `set`, repeats allowed: several
+   * faces of one frame each get a tracker, and of K feeds in different states (main.js:229-244) exactly those that track are tracked.  The
+   * frame histogram is computed once per distinct frame.
+   *   initPairs(set, pairs, rects)             camshift.initTracker per pair, rects: Int32Array [x, y, width, height] per pair
+   *   trackPairs(set, pairs, calcAngles)       -> Float64Array(9 pairs), pair order
+   *   trackPairsEnqueue(set, pairs, calcAngles) enqueue only; trackCollect() returns the oldest outstanding step, pair or not
+   *   detectStepFinish(min_neighbors, {feeds}) best face of EVERY feed; trackers are initialised only for the listed feeds that found one
+   *                                            (confidence > -10, facetrackr.js:97): result.initialised lists them, no centre-half substitute */
+  const needPairs = function (what) {
+    if (typeof A.camshiftInitPairs !== 'function' || typeof A.camshiftTrackPairs !== 'function')
+      throw new Error('DeviceBatch.' + what + ': this headtrackr_hip.node has no camshiftInitPairs / camshiftTrackPairs (rebuild it)');
+  };
+  const reserve = function () { if (!trackers) { A.camshiftReserve(ctxs[0], slots); trackers = true; } };
+  const pairList = function (what, pairs) {
+    if (!(pairs instanceof Int32Array) || pairs.length < 2 || (pairs.length & 1)) throw new TypeError('DeviceBatch.' + what + ': pairs is an Int32Array [stream, frame, ...]');
+    return pairs;
+  };
+  this.initPairs = function (set, pairs, rects) {
+    needPairs('initPairs'); pairList('initPairs', pairs);
+    if (!(rects instanceof Int32Array) || rects.length < 2 * pairs.length) throw new TypeError('DeviceBatch.initPairs: rects is an Int32Array [x, y, width, height] per pair');
+    bind0(set === undefined ? 0 : set);
+    reserve();
+    A.camshiftInitPairs(ctxs[0], pairs, rects);
+  };
+  this.trackPairs = function (set, pairs, calcAngles) {
+    needPairs('trackPairs'); pairList('trackPairs', pairs);
+    bind0(set === undefined ? 0 : set);
+    return A.camshiftTrackPairs(ctxs[0], pairs, calcAngles === false ? 0 : 1, true);
+  };
+  this.trackPairsEnqueue = function (set, pairs, calcAngles) {
+    needPairs('trackPairsEnqueue'); pairList('trackPairsEnqueue', pairs);
+    bind0(set === undefined ? 0 : set);
+    A.camshiftTrackPairs(ctxs[0], pairs, calcAngles === false ? 0 : 1, false);
+    pendingTrack.push(pairs.length >> 1);
+  };
   this.backProjection = function (set, kind) {
     if (!trackers) throw new Error('DeviceBatch.backProjection: no trackers yet (initTrackers or detectStep first)');
     if (kind !== undefined && kind !== 'rgba8' && kind !== 'f64') throw new RangeError("DeviceBatch.backProjection: kind is 'rgba8' or 'f64'");
@@ -700,6 +758,61 @@ headtrackr.camshift.Tracker = function (params) { /* camshift.js:148-354 */
    * replaces a tracker on "redetecting" / stop(), so a long-running feed that loses its face keeps one slot. */
   let released = false;
   this.release = function () { if (!released) { released = true; csPool.free.push(slot); } };
+};
+
+/* not in the reference: M camshift trackers on ONE canvas — what a page does with one camshift.Tracker per detected face — with one
+ * upload and one device call per frame (ht_camshift_track_pairs, every pair on frame 0: the frame's histogram is computed once, not M
+ * times).  Results equal M camshift.Tracker instances on that canvas; the slots come from the same pool.
+ *   initTracker(canvas, rects)   rects: array of camshift.Rectangle (or {x, y, width, height}), one tracker each (camshift.js:198-211)
+ *   track(canvas)                one track() of every tracker (camshift.js:213-353)
+ *   getTrackObj(i) / getSearchWindow(i) / release() */
+headtrackr.camshift.MultiTracker = function (params) {
+  if (params === undefined) params = {};
+  if (params.calcAngles === undefined) params.calcAngles = true;
+  let slots = [], pairs = null, windows = [], objs = [];
+  const needPairs = function () {
+    if (typeof addon().camshiftInitPairs !== 'function' || typeof addon().camshiftTrackPairs !== 'function')
+      throw new Error('camshift.MultiTracker: this headtrackr_hip.node has no camshiftInitPairs / camshiftTrackPairs (rebuild it)');
+  };
+  this.count = function () { return slots.length; };
+  this.getSearchWindow = function (i) { return windows[i].clone(); };
+  this.getTrackObj = function (i) { return objs[i].clone(); };
+  this.release = function () { slots.forEach(function (s) { csPool.free.push(s); }); slots = []; pairs = null; windows = []; objs = []; };
+  this.initTracker = function (canvas, rects) {
+    needPairs();
+    if (!rects || !rects.length) throw new TypeError('camshift.MultiTracker.initTracker(canvas, rects): at least one rect');
+    this.release();
+    for (let i = 0; i < rects.length; i++) slots.push(csSlot());
+    pairs = new Int32Array(2 * rects.length);
+    const rc = new Int32Array(4 * rects.length);
+    rects.forEach(function (r, i) {
+      pairs[2 * i] = slots[i]; pairs[2 * i + 1] = 0;
+      rc[4 * i] = r.x; rc[4 * i + 1] = r.y; rc[4 * i + 2] = r.width; rc[4 * i + 3] = r.height;
+      windows.push(new headtrackr.camshift.Rectangle(r.x, r.y, r.width, r.height));
+      objs.push(new headtrackr.camshift.TrackObj());
+    });
+    const img = canvas.getContext('2d').getImageData(0, 0, canvas.width, canvas.height);
+    if (!(img.width > 0 && img.height > 0)) return;
+    try {
+      bindFrame(csPool.ctx, img, headtrackr.cascade, 5);
+      addon().camshiftInitPairs(csPool.ctx.handle, pairs, rc);
+    } finally { unbindFrames(); }
+  };
+  this.track = function (canvas) {
+    if (!pairs) throw new Error('camshift.MultiTracker.track: initTracker first');
+    const img = canvas.getContext('2d').getImageData(0, 0, canvas.width, canvas.height);
+    if (img.width === 0 || img.height === 0) return; /* camshift.js:219 */
+    let r;
+    try {
+      bindFrame(csPool.ctx, img, headtrackr.cascade, 5);
+      r = addon().camshiftTrackPairs(csPool.ctx.handle, pairs, params.calcAngles ? 1 : 0, true);
+    } finally { unbindFrames(); }
+    for (let i = 0; i < slots.length; i++) {
+      const o = objs[i], w = windows[i], b = 9 * i;
+      o.x = r[b]; o.y = r[b + 1]; o.width = r[b + 2]; o.height = r[b + 3]; o.angle = r[b + 4];
+      w.x = r[b + 5]; w.y = r[b + 6]; w.width = r[b + 7]; w.height = r[b + 8];
+    }
+  };
 };
 
 /* ---- facetrackr ------------------------------------------------------------------------------------------------------------ */

@@ -49,6 +49,7 @@ RECT_DTYPE = np.dtype(
     [("x", "<f8"), ("y", "<f8"), ("width", "<f8"), ("height", "<f8"), ("confidence", "<f8"), ("neighbors", "<i4"), ("reserved", "<i4")]
 )
 CS_RECT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("width", "<i4"), ("height", "<i4")])
+PAIR_DTYPE = np.dtype([("stream", "<i4"), ("frame", "<i4")])  # ht_cs_pair: tracker `stream` meets bound frame `frame`
 CS_TRACKOBJ_DTYPE = np.dtype(
     [("x", "<f8"), ("y", "<f8"), ("width", "<f8"), ("height", "<f8"), ("angle", "<f8"),
      ("sw_x", "<i4"), ("sw_y", "<i4"), ("sw_width", "<i4"), ("sw_height", "<i4")]
@@ -67,7 +68,7 @@ SYMBOLS = [
     "ht_windows_per_frame", "ht_pyramid_bytes_per_frame", "ht_upload_frames", "ht_upload_frames_async", "ht_swap_frames", "ht_bind_frames_device", "ht_frames_bound", "ht_frames_enqueued", "ht_host_alloc", "ht_host_free", "ht_device_alloc", "ht_device_free", "ht_device_upload", "ht_device_download", "ht_draw_frames_device", "ht_draw_frames", "ht_detect_enqueue",
     "ht_detect_collect", "ht_detect_batch", "ht_pyramid_readback", "ht_stage_counts", "ht_grayscale_batch",
     "ht_whitebalance_batch", "ht_detect_whitebalance", "ht_hits_to_rects", "ht_group_rects", "ht_best_faces", "ht_detect_collect_best", "ht_detect_collect_best_requeue", "ht_camshift_reserve", "ht_camshift_init_batch",
-    "ht_camshift_track_batch", "ht_camshift_track_collect", "ht_camshift_track_sequence", "ht_camshift_sequence_collect", "ht_camshift_stats", "ht_camshift_debug_hist", "ht_camshift_backproject", "ht_camshift_backproject_device", "ht_allgather_records", "ht_allgather_best_faces", "ht_device_count", "ht_profile", "ht_kernel_times", "ht_stream", "ht_graph_launches", "ht_synchronize",
+    "ht_camshift_track_batch", "ht_camshift_track_collect", "ht_camshift_init_pairs", "ht_camshift_track_pairs", "ht_camshift_track_sequence", "ht_camshift_sequence_collect", "ht_camshift_stats", "ht_camshift_debug_hist", "ht_camshift_backproject", "ht_camshift_backproject_device", "ht_allgather_records", "ht_allgather_best_faces", "ht_device_count", "ht_profile", "ht_kernel_times", "ht_stream", "ht_graph_launches", "ht_synchronize",
 ]
 
 _lib = None
@@ -157,6 +158,10 @@ def lib():
     L.ht_camshift_init_batch.argtypes = [vp, i32, i32, vp]
     L.ht_camshift_track_batch.restype = i32
     L.ht_camshift_track_batch.argtypes = [vp, i32, i32, i32, vp]
+    L.ht_camshift_init_pairs.restype = i32
+    L.ht_camshift_init_pairs.argtypes = [vp, vp, i32, vp]
+    L.ht_camshift_track_pairs.restype = i32
+    L.ht_camshift_track_pairs.argtypes = [vp, vp, i32, i32, vp]
     L.ht_detect_whitebalance.restype = i32
     L.ht_detect_whitebalance.argtypes = [vp, vp, i32]
     L.ht_camshift_track_sequence.restype = i32

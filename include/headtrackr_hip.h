@@ -72,6 +72,7 @@ typedef struct ht_config {
                              *   cs_barrier_budget=N  shader-clock cycles a cluster exchange may wait before the call fails with HT_ERR_STATE
                              *   cs_flags=0|1         enqueue-only track calls of the cluster path are completed by marks in the pinned slot (1) or an event
                              *   cs_sync_ring=0|1     a synchronous track call takes the enqueue-only route and collects at once (1) or copies back + synchronises (0)
+                             *   cs_pairs_force=1     ht_camshift_*_pairs calls whose pairs are (first + i, i) run the pair kernels too instead of the batch schedules
                              *   fp_sparse=0|1        tile kernel: sparse stages one lane per (window, feature) pair when <= 256 pairs are left (1)
                              *   graph_max_frames=N   batches up to N frames replay a captured hipGraph (256; 0 = never)
                              *   split=S, deep_bias=B, deep_v=2|4, deep_grid=N                    tile kernel -> deep kernel hand-off (grid kept >= 16 wavefronts)
@@ -110,6 +111,7 @@ typedef struct ht_plane_info {
 } ht_plane_info;
 
 typedef struct ht_cs_rect { int32_t x, y, width, height; } ht_cs_rect;
+typedef struct ht_cs_pair { int32_t stream, frame; } ht_cs_pair; /* tracker `stream` meets BOUND frame `frame` (ht_camshift_*_pairs) */
 
 /* camshift.Tracker's persistent per-stream state (camshift.js:153-160): lives on the device, one per stream. */
 typedef struct ht_cs_trackobj { /* camshift.TrackObj, camshift.js:362-378 (+ the search window, camshift.js:162-165) */
@@ -264,6 +266,21 @@ ht_status ht_camshift_track_batch(ht_ctx *ctx, int32_t first, int32_t n, int32_t
  * feed's track() first and collects afterwards (the reference's loop, main.js:168-180, is one feed; this is its K-feed form).
  * ht_camshift_reserve drops uncollected results. */
 ht_status ht_camshift_track_collect(ht_ctx *ctx, int32_t n, ht_cs_trackobj *out);
+/* The same two calls over an arbitrary list of (stream, frame) pairs: several trackers on one frame (one per face of a canvas, as the
+ * reference allows), or the tracking feeds of a host whose feeds are in different states (main.js:229-244).  Streams are any reserved
+ * slots in any order, each at most once per call; frames are any indices below ht_frames_bound(), repeats allowed.  The full-frame
+ * histogram (camshift.js:268) is computed once per DISTINCT frame of the call and shared by the streams paired with it.  All argument
+ * checks happen before anything is enqueued and a failed call changes no tracker state: HT_ERR_INVALID for a duplicate or unreserved
+ * stream, a frame that is not bound, n <= 0, n > reserved streams, NULL pairs / rects; HT_ERR_STATE without bound frames.
+ * initTracker (camshift.js:198-211) of pairs[i].stream on bound frame pairs[i].frame with rects[i]. */
+ht_status ht_camshift_init_pairs(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, const ht_cs_rect *rects);
+/* One track() (camshift.js:213-353) of pairs[i].stream on bound frame pairs[i].frame; out[n] in pair order.  out == NULL: enqueue only —
+ * the results go into the same ring of pinned slots as ht_camshift_track_batch's (pair steps and batch steps may be outstanding
+ * together, four in total, oldest first) and ht_camshift_track_collect(ctx, n, out) fetches them in pair order.  The results are the
+ * bits of ht_camshift_track_batch's few-stream schedule (one mean-shift workgroup per stream).  Pairs (first + i, i), i = 0 .. n - 1, ARE
+ * ht_camshift_track_batch(first, n) and take its schedules (option cs_pairs_force=1 sends them through the pair kernels).  Afterwards
+ * ht_camshift_debug_hist(stream, .., current) returns the histogram of the frame the stream was paired with. */
+ht_status ht_camshift_track_pairs(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, int32_t calc_angles, ht_cs_trackobj *out);
 /* ncalls successive track() calls (camshift.js:213-220 called once per video frame, main.js:168-180) for streams
  * [first, first+n) in ONE host call: call k uses the n device-resident frames at dev_frames[k] (frame_stride bytes apart;
  * same geometry as ht_set_geometry).  A stream's calls are sequentially dependent (its search window), so they are
