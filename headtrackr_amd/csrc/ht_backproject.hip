@@ -30,16 +30,9 @@ constexpr int BP_NT = 1024;   // threads of a k_bp_project workgroup: one chunk 
 constexpr int BP_UNROLL = 4;  // 16-byte loads of a thread in flight before the first lookup (k_cs_hist measured 4 as the optimum for this access pattern)
 constexpr int BP_LUT_NT = 512;
 
-// camshift.js:63-66 (px = R | G<<8 | B<<16 | A<<24): bin = (R>>4)<<8 | (G>>4)<<4 | (B>>4).  The body is ht_camshift.hip's, character for
-// character (tests/test_backproject_cpu.py compares the two texts; the reasoning lives there).
-__device__ __forceinline__ uint32_t cs_bin(uint32_t px) {
-    const uint32_t t = px & 0x00f0f0f0u;
-    return ((t << 24) | (t + (t << 12))) >> 20;  // v_and, v_mul_u32_u24 0x1001, v_lshl_or_b32, v_lshrrev
-}
-
-// a batch of predicated loads followed by cs_bin is laundered after the WHOLE batch, or every load is waited for on the spot
-// (ht_camshift.hip, CS_BATCH_LOADED)
-#define BP_BATCH_LOADED(v_) asm volatile("" : "+v"(v_))
+// cs_bin, CS_BATCH_LOADED and the workgroup sizes of the histogram pass — and, for ht_cs_pairs.hip at the end of this file, every device
+// helper of the camshift kernels
+#include "ht_cs_device.h"
 
 // LUTs of frame slot s from its chunk histograms and the model of stream first + s: grid (64, n) x 512 threads; a block owns 64 bins,
 // its 8 wavefronts each sum every 8th chunk (the summation of k_cs_lut, without that kernel's cluster exchange slots).
@@ -125,10 +118,10 @@ __global__ __launch_bounds__(BP_NT) void k_bp_project(const uint8_t *__restrict_
         }
 #pragma unroll
         for (int u = 0; u < BP_UNROLL; u++) {
-            BP_BATCH_LOADED(pv[u].x);
-            BP_BATCH_LOADED(pv[u].y);
-            BP_BATCH_LOADED(pv[u].z);
-            BP_BATCH_LOADED(pv[u].w);
+            CS_BATCH_LOADED(pv[u].x);
+            CS_BATCH_LOADED(pv[u].y);
+            CS_BATCH_LOADED(pv[u].z);
+            CS_BATCH_LOADED(pv[u].w);
         }
 #pragma unroll
         for (int u = 0; u < BP_UNROLL; u++) {

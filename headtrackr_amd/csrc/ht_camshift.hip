@@ -32,18 +32,22 @@
 
 namespace {
 
-// camshift.js:63-66 (px = R | G<<8 | B<<16 | A<<24): bin = (R>>4)<<8 | (G>>4)<<4 | (B>>4).  Four instructions instead of the eight of
-// the field-by-field form (the histogram pass of k_cs_track_fused spent 32 of its ~50 vector instructions per 16-byte load on its four
-// bins): with t = px & 0xf0f0f0 = r<<4 | g<<12 | b<<20 (r, g, b the 4-bit fields), t + (t << 12) puts g at bit 24 next to b at bit 20
-// (all fields of the sum are disjoint: no carries; b << 32 leaves the register), t << 24 puts r at bit 28, and the bin is bits 20-31.
-__device__ __forceinline__ uint32_t cs_bin(uint32_t px) {
-    const uint32_t t = px & 0x00f0f0f0u;
-    return ((t << 24) | (t + (t << 12))) >> 20;  // v_and, v_mul_u32_u24 0x1001, v_lshl_or_b32, v_lshrrev
-}
-
-// the device helpers this unit shares with the pair kernels (ht_cs_pairs.hip): CS_STAMP, CS_NT / HIST_NT / HIST_UNROLL / CS_REGION_CAP,
-// CS_BATCH_LOADED, toint32, hist_add_wave, Mom, the DPP wave sum, CsRegion, cs_cache_region, window_moments*, meanshift_body
+// the device helpers this unit shares with the pair kernels (ht_cs_pairs.hip) and the back-projection: cs_bin, CS_STAMP, CS_NT / HIST_NT /
+// HIST_UNROLL / INIT_NT / CS_REGION_CAP, CS_BATCH_LOADED, toint32, hist_add_wave, Mom, the DPP wave sum, CsRegion, cs_cache_region,
+// window_moments*, meanshift_body
 #include "ht_cs_device.h"
+
+// k_cs_init, k_cs_hist and k_cs_meanshift are ht_cs_kernels.inc with the look-ups of a batch: stream first + s works on bound frame s,
+// whose chunk histograms are slot s, and its rect is rects[s]
+#define CS_K(name) k_cs_##name
+typedef int CsLookup;  // `first`
+__device__ __forceinline__ int cs_stream_of(int first, int s) { return first + s; }
+__device__ __forceinline__ int cs_frame_of(int, int s) { return s; }
+__device__ __forceinline__ int cs_slot_of(int, int s) { return s; }
+#define CS_INIT_PARAMS const ht_cs_rect *__restrict__ rects, HtCsState *__restrict__ states, CsLookup lk
+#define CS_INIT_RECT(s_) rects[s_]
+#define CS_HIST_FRAMES_PARAM
+#define CS_HIST_FRAME(y_) (y_)
 
 // Partial histograms per stream: enough chunks to put ~256 workgroups of 1024 threads on the chip (a single 1080p stream gets 127,
 // eight of them 32 each, a batch of >= 32 streams 8 each), each chunk >= 16384 pixels and a multiple of 4 * HIST_NT.  Round 5, same box,
@@ -61,47 +65,8 @@ inline void hist_chunks(uint32_t npix, uint32_t max_chunks, uint32_t *chunk_px, 
     *nchunks = std::max<uint32_t>((npix + *chunk_px - 1) / *chunk_px, 1u);
 }
 
-// initTracker: one 1024-thread workgroup per stream; rows of the rect by wavefront, columns by lane (no per-pixel division),
-// 8 independent loads per lane in flight (a 360 x 360 rect of a 1080p feed took 174 us with the one-pixel-at-a-time loop)
-constexpr int INIT_NT = 1024;
-__global__ __launch_bounds__(INIT_NT) void k_cs_init(const uint8_t *__restrict__ frames, size_t frame_stride, int W, int H,
-                                                     const ht_cs_rect *__restrict__ rects, HtCsState *__restrict__ states, int first) {
-    __shared__ uint32_t h[4096];
-    const int s = blockIdx.x;
-    for (int i = threadIdx.x; i < 4096; i += INIT_NT) h[i] = 0;
-    __syncthreads();
-    const ht_cs_rect r = rects[s];
-    const uint32_t *img = reinterpret_cast<const uint32_t *>(frames + (size_t)s * frame_stride);
-    const int rw = max(r.width, 0), rh = max(r.height, 0);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    constexpr int NWV = INIT_NT / 64;
-    for (int j0 = wave; j0 - wave < rh; j0 += 8 * NWV) {      // same trip count for every wavefront's lanes (ballots inside)
-        for (int cb = 0; cb < rw; cb += 64) {
-            const int c = cb + lane;
-            uint32_t px[8];
-            bool in[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int y = r.y + j0 + u * NWV, x = r.x + c;
-                in[u] = c < rw && j0 + u * NWV < rh;                                   // inside the rect
-                const bool img_ok = in[u] && x >= 0 && x < W && y >= 0 && y < H;      // inside the canvas
-                px[u] = img_ok ? img[(size_t)y * W + x] : 0u;  // getImageData outside the canvas: transparent black -> bin 0 (camshift.js:206)
-            }
-#pragma unroll
-            for (int u = 0; u < 8; u++) CS_BATCH_LOADED(px[u]);
-#pragma unroll
-            for (int u = 0; u < 8; u++) hist_add_wave(h, cs_bin(px[u]), 1u, in[u]);
-        }
-    }
-    __syncthreads();
-    HtCsState &st = states[first + s];
-    for (int i = threadIdx.x; i < 4096; i += INIT_NT) st.model[i] = h[i];
-    if (threadIdx.x == 0) {
-        st.sw[0] = r.x, st.sw[1] = r.y, st.sw[2] = r.width, st.sw[3] = r.height;  // camshift.js:209
-        st.x = st.y = st.width = st.height = st.angle = 0.0;                         // camshift.js:210
-        st.win_px = st.calls = 0;
-    }
-}
+#define CS_KERNELS_PART 1  // k_cs_init
+#include "ht_cs_kernels.inc"
 
 // initTracker for a FEW streams with large rects (a live 1080p feed: 360 x 360 = 0.5 MB took the single workgroup above 54 us):
 // grid (G, streams), workgroup g takes rows g*4 + wavefront, + 4 G, ...; LDS histogram per workgroup, non-zero bins added to the
@@ -144,107 +109,8 @@ __global__ __launch_bounds__(256) void k_cs_init_rows(const uint8_t *__restrict_
     }
 }
 
-// full-frame histogram (camshift.js:268): grid (chunks, streams) -> hist[stream][chunk][4096] partial histograms.
-// 4 pixels per 16-byte load.  LDS atomics on one address serialise lane by lane, and flat image regions put whole
-// wavefronts into one bin (a flat 320x240 background cost 64 cycles per wave instruction: the kernel ran at a quarter of
-// HBM speed), so counts are merged before they reach LDS: the 4 pixels of a thread when they share a bin, and all lanes
-// that share the first active lane's bin through one ballot — one atomic for the whole wavefront on flat regions,
-// a few extra scalar instructions elsewhere.  Counts are integers: any order gives the same histogram.
-
-__global__ __launch_bounds__(HIST_NT) void k_cs_hist(const uint8_t *__restrict__ frames, size_t frame_stride, uint32_t npix,
-                                                     uint32_t chunk_px, uint32_t *__restrict__ hist) {
-    __shared__ uint32_t h[4096];
-    for (int i = threadIdx.x; i < 4096; i += HIST_NT) h[i] = 0;
-    __syncthreads();
-    const uint8_t *frame = frames + (size_t)blockIdx.y * frame_stride;
-    const uint32_t beg = blockIdx.x * chunk_px, end = min(beg + chunk_px, npix);  // chunk_px is a multiple of 4 * HIST_NT
-    const uint32_t nquad = (end - beg) / 4;
-    const uint4 *img4 = reinterpret_cast<const uint4 *>(frame + (size_t)beg * 4);
-    const uint32_t iters = chunk_px / (4 * HIST_NT);
-    // HIST_UNROLL loads of a thread in flight before the first bin is counted, written out: the wave-level merge below is convergent code,
-    // which keeps the optimiser from unrolling the loop itself (`#pragma unroll` was refused), and with ONE 16-byte load in flight per
-    // thread the pass was a chain of chunk_px / 1024 memory round trips (16 x ~1.3 us at 1080p = the kernel's whole duration)
-    for (uint32_t it0 = 0; it0 < iters; it0 += HIST_UNROLL) {
-        uint4 pv[HIST_UNROLL];
-        bool onv[HIST_UNROLL];
-#pragma unroll
-        for (int u = 0; u < HIST_UNROLL; u++) {
-            const uint32_t i = (it0 + (uint32_t)u) * HIST_NT + threadIdx.x;
-            onv[u] = it0 + (uint32_t)u < iters && i < nquad;
-            pv[u] = make_uint4(0u, 0u, 0u, 0u);
-            if (onv[u]) pv[u] = img4[i];
-        }
-#pragma unroll
-        for (int u = 0; u < HIST_UNROLL; u++) {
-            CS_BATCH_LOADED(pv[u].x);
-            CS_BATCH_LOADED(pv[u].y);
-            CS_BATCH_LOADED(pv[u].z);
-            CS_BATCH_LOADED(pv[u].w);
-        }
-#pragma unroll
-        for (int u = 0; u < HIST_UNROLL; u++) {
-            if (it0 + (uint32_t)u >= iters) break;  // workgroup-uniform
-            const uint4 p = pv[u];
-            const bool on = onv[u];
-            const uint32_t b0 = cs_bin(p.x), b1 = cs_bin(p.y), b2 = cs_bin(p.z), b3 = cs_bin(p.w);
-            const bool flat = (b0 == b1) && (b2 == b3) && (b0 == b2);
-            hist_add_wave(h, b0, flat ? 4u : 1u, on);
-            if (on && !flat) {
-                atomicAdd(&h[b1], 1u);
-                atomicAdd(&h[b2], 1u);
-                atomicAdd(&h[b3], 1u);
-            }
-        }
-    }
-    const uint32_t *img = reinterpret_cast<const uint32_t *>(frame);
-    for (uint32_t i = beg + nquad * 4 + threadIdx.x; i < end; i += HIST_NT) atomicAdd(&h[cs_bin(img[i])], 1u);  // < 4 pixels
-    __syncthreads();
-    // this chunk's partial histogram, written whole (no zeroing pass, no global atomics); k_cs_meanshift adds the chunks
-    uint32_t *out = hist + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4096;
-    for (int i = threadIdx.x; i < 4096; i += HIST_NT) out[i] = h[i];
-}
-
-
-__global__ __launch_bounds__(CS_NT) void k_cs_meanshift(const uint8_t *__restrict__ frames, size_t frame_stride, int W, int H,
-                                                        const uint32_t *__restrict__ hist, int nchunks, HtCsState *__restrict__ states,
-                                                        int first, int calc_angles, int max_it, int region_cap, ht_cs_trackobj *__restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t cs_dyn[];  // [region_cap] u16 bins of the cached search region
-    __shared__ double lut[4096];
-    __shared__ double red[6][CS_NT / 64];
-    __shared__ int s_sw[4];
-    const int s = blockIdx.x;
-    HtCsState &st = states[first + s];
-    const uint32_t *cur = hist + (size_t)s * nchunks * 4096;
-    const uint32_t *img = reinterpret_cast<const uint32_t *>(frames + (size_t)s * frame_stride);
-    {  // getWeights, camshift.js:314-330; the frame's histogram = sum of its chunk histograms (4 bins per 16-byte load)
-        const uint4 *cur4 = reinterpret_cast<const uint4 *>(cur);
-        const uint4 *model4 = reinterpret_cast<const uint4 *>(st.model);
-        for (int i4 = threadIdx.x; i4 < 1024; i4 += CS_NT) {
-            uint4 acc = make_uint4(0u, 0u, 0u, 0u);
-            for (int k = 0; k < nchunks; k++) {
-                const uint4 v = cur4[(size_t)k * 1024 + i4];
-                acc.x += v.x, acc.y += v.y, acc.z += v.z, acc.w += v.w;
-            }
-            const uint4 m = model4[i4];
-            const uint32_t chv[4] = {acc.x, acc.y, acc.z, acc.w}, mv[4] = {m.x, m.y, m.z, m.w};
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                double p = 0.0;
-                if (chv[q] != 0) {
-                    p = (double)mv[q] / (double)chv[q];
-                    p = p < 1.0 ? p : 1.0;
-                }
-                lut[i4 * 4 + q] = p;
-            }
-        }
-    }
-    if (threadIdx.x < 4) s_sw[threadIdx.x] = st.sw[threadIdx.x];
-    __syncthreads();
-    const CsRegion R = cs_cache_region<CS_NT>(img, W, H, s_sw, reinterpret_cast<uint16_t *>(cs_dyn), region_cap);
-    __syncthreads();
-    meanshift_body(W, H, s_sw, st, calc_angles, max_it, out ? out + s : nullptr, nullptr, true,
-                   [&](int x, int y, int w, int h) { return window_moments_any<true, CS_NT / 64>(img, W, lut, R, x, y, w, h, red); });
-}
+#define CS_KERNELS_PART 2  // k_cs_hist, k_cs_meanshift: behind k_cs_init_rows, the order the recorded code object has
+#include "ht_cs_kernels.inc"
 
 // One launch per track() call when there are enough streams to fill the chip by themselves: ONE 1024-thread workgroup per stream
 // does the full-frame histogram in LDS, turns it into the weight LUT in place (no partial histograms through HBM, no second
@@ -910,6 +776,25 @@ static ht_status launch_track(ht_ctx *c, const uint8_t *frames, size_t frame_str
     return HT_OK;
 }
 
+// The result ring of the enqueue-only track calls, for ht_camshift_track_batch and ht_camshift_track_pairs (`fn`, for the message).
+// A call without `out` is enqueue-only; a synchronous call with nothing outstanding goes the same way and collects at once (*via_ring).
+// *slot = the next free pinned slot on that route — refused when the ring does not hold n streams or is full —, nullptr on the copy-back
+// route.  ht_cs_ring_commit counts the slot as outstanding once its completion (a mark or an event) has been enqueued.
+ht_status ht_cs_ring_begin(ht_ctx *c, const char *fn, int32_t n, const ht_cs_trackobj *out, bool *via_ring, ht_ctx::HtCsSlot **slot) {
+    *slot = nullptr;
+    *via_ring = out && c->cs_sync_ring && c->cs_ring_count == 0 && n <= c->cs_ring_streams;
+    if (out && !*via_ring) return HT_OK;
+    if (n > c->cs_ring_streams) return ht_fail(c, HT_ERR_STATE, std::string(fn) + ": no result ring for this many streams (ht_camshift_reserve failed to allocate it)");
+    if (c->cs_ring_count == ht_ctx::HT_CS_RING)
+        return ht_fail(c, HT_ERR_STATE, std::string(fn) + ": too many enqueue-only calls outstanding (collect with ht_camshift_track_collect)");
+    *slot = &c->cs_ring[(c->cs_ring_head + c->cs_ring_count) % ht_ctx::HT_CS_RING];
+    return HT_OK;
+}
+void ht_cs_ring_commit(ht_ctx *c, ht_ctx::HtCsSlot *slot, int32_t n) {
+    slot->n = n;
+    c->cs_ring_count++;
+}
+
 extern "C" ht_status ht_camshift_track_batch(ht_ctx *c, int32_t first, int32_t n, int32_t calc_angles, ht_cs_trackobj *out) {
     HtRange range("ht_camshift_track_batch");
     if (!c) return HT_ERR_INVALID;
@@ -921,12 +806,12 @@ extern "C" ht_status ht_camshift_track_batch(ht_ctx *c, int32_t first, int32_t n
     // the track objects into a pinned slot and mark it, the host polls the marks — no device-to-host copies (two copy kernels: objects and
     // the error word) and no stream synchronisation.  Wall clock of a single-stream track() call, round 6 (tools/gpu_cs_wall.py):
     // 41.4 -> 28.9 us at 320x240 (event-marked slot), 38.7 -> 20.7 us at 640x480 and 41.0 -> 22.6 us at 1920x1080 (kernel-marked slot).
-    const bool via_ring = out && c->cs_sync_ring && c->cs_ring_count == 0 && n <= c->cs_ring_streams;
-    if (!out || via_ring) {  // enqueue only: results go straight to the next pinned slot, a mark or an event says they are complete
-        if (n > c->cs_ring_streams) return ht_fail(c, HT_ERR_STATE, "ht_camshift_track_batch: no result ring for this many streams (ht_camshift_reserve failed to allocate it)");
-        if (c->cs_ring_count == ht_ctx::HT_CS_RING)
-            return ht_fail(c, HT_ERR_STATE, "ht_camshift_track_batch: too many enqueue-only calls outstanding (collect with ht_camshift_track_collect)");
-        ht_ctx::HtCsSlot &sl = c->cs_ring[(c->cs_ring_head + c->cs_ring_count) % ht_ctx::HT_CS_RING];
+    bool via_ring = false;
+    ht_ctx::HtCsSlot *slot = nullptr;
+    ht_status rs = ht_cs_ring_begin(c, "ht_camshift_track_batch", n, out, &via_ring, &slot);
+    if (rs != HT_OK) return rs;
+    if (slot) {  // enqueue only: results go straight to the next pinned slot, a mark or an event says they are complete
+        ht_ctx::HtCsSlot &sl = *slot;
         bool flagged = false;
         uint32_t seq = 0;
         if (c->cs_flags && sl.h_flag) {
@@ -937,8 +822,7 @@ extern "C" ht_status ht_camshift_track_batch(ht_ctx *c, int32_t first, int32_t n
         if (st != HT_OK) return st;
         sl.seq = flagged ? seq : 0u;
         if (!flagged) HT_HIP(c, hipEventRecord(sl.ev, c->stream));
-        sl.n = n;
-        c->cs_ring_count++;
+        ht_cs_ring_commit(c, slot, n);
         return via_ring ? ht_camshift_track_collect(c, n, out) : HT_OK;
     }
     ht_status st = launch_track(c, c->d_frames, c->frame_stride, first, n, calc_angles, c->d_cs_out);

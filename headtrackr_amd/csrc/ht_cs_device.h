@@ -1,7 +1,18 @@
-// ht_cs_device.h — device helpers of the camshift kernels, shared by ht_camshift.hip and ht_cs_pairs.hip (compiled as part of
-// ht_backproject.hip).  Included INSIDE the including unit's anonymous namespace, after its cs_bin(): the bin function stays spelled out in
-// both units (tests/test_backproject_cpu.py compares the two texts, tests/test_oracle_golden.py proves the expression).  Everything here
-// was moved out of ht_camshift.hip character for character: the camshift code object of profiles/traffic.json must not change.
+// ht_cs_device.h — device helpers of the camshift kernels: the histogram bin (cs_bin), the workgroup sizes, the load-laundering macro, the
+// wave-merged histogram update, the window moments and the mean-shift loop.  Included ONCE per translation unit, INSIDE the unit's
+// anonymous namespace, ahead of its kernels: by ht_camshift.hip, and by ht_backproject.hip for its own kernels and for ht_cs_pairs.hip,
+// which it compiles.  Every helper has this one definition (tests/test_pairs_cpu.py counts them).  A change here changes the camshift
+// code object that profiles/traffic.json is tied to.
+
+// camshift.js:63-66 (px = R | G<<8 | B<<16 | A<<24): bin = (R>>4)<<8 | (G>>4)<<4 | (B>>4).  Four instructions instead of the eight of
+// the field-by-field form (the histogram pass of k_cs_track_fused spent 32 of its ~50 vector instructions per 16-byte load on its four
+// bins): with t = px & 0xf0f0f0 = r<<4 | g<<12 | b<<20 (r, g, b the 4-bit fields), t + (t << 12) puts g at bit 24 next to b at bit 20
+// (all fields of the sum are disjoint: no carries; b << 32 leaves the register), t << 24 puts r at bit 28, and the bin is bits 20-31.
+// tests/test_oracle_golden.py proves the expression against the reference formula on every RGB value.
+__device__ __forceinline__ uint32_t cs_bin(uint32_t px) {
+    const uint32_t t = px & 0x00f0f0f0u;
+    return ((t << 24) | (t + (t << 12))) >> 20;  // v_and, v_mul_u32_u24 0x1001, v_lshl_or_b32, v_lshrrev
+}
 
 #ifdef HT_CS_TIMELINE  // measurement build (tools/gpu_cs_timeline.py): shader-clock stamps of a workgroup's phases
 #define CS_STAMP(arr, i)                                                      \
@@ -17,6 +28,7 @@
 constexpr int CS_NT = 512;          // threads of the mean-shift workgroup
 constexpr int HIST_NT = 1024;
 constexpr int HIST_UNROLL = 4;  // 16-byte loads of a thread in flight in the histogram pass (k_cs_hist)
+constexpr int INIT_NT = 1024;   // threads of the one-workgroup-per-stream initTracker (k_cs_init)
 
 constexpr int CS_REGION_CAP = 40960;  // pixels of the cached search region: 80 KB of LDS next to the 32 KB LUT (which the 16 KB histogram overlays)
 
@@ -35,7 +47,7 @@ __device__ __forceinline__ int32_t toint32(double v) {  // ECMAScript ToInt32 (>
     return (int32_t)(uint32_t)m;
 }
 
-// wave-merged LDS histogram update (see k_cs_hist in ht_camshift.hip): the counts of all lanes that share the first active lane's bin
+// wave-merged LDS histogram update (see k_cs_hist in ht_cs_kernels.inc): the counts of all lanes that share the first active lane's bin
 // go out as one atomic.  Counts are integers: any order gives the same histogram.
 __device__ __forceinline__ void hist_add_wave(uint32_t *h, uint32_t bin, uint32_t count, bool active) {
     const unsigned long long act = __ballot(active);

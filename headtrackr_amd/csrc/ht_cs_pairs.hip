@@ -9,19 +9,17 @@
 //   k_csp_meanshift  one CS_NT-thread workgroup per pair: k_cs_meanshift with three look-ups (state, pixels, histogram slot)
 //   k_csp_init       one workgroup per pair: k_cs_init with the same look-ups
 //
-// Everything below the look-ups is ht_cs_device.h, i.e. the code k_cs_meanshift runs: same wavefront count, same summation order, same
-// bits as the few-stream schedule of ht_camshift_track_batch (options cs_fused_min=large, cs_cluster=0).
+// The three kernels are ht_cs_kernels.inc, the text ht_camshift.hip compiles its k_cs_* from; this unit supplies the look-ups through
+// the call's device table (CspEntry).  Same wavefront count, same summation order, same bits as the few-stream schedule of
+// ht_camshift_track_batch (options cs_fused_min=large, cs_cluster=0).
 //
 // Compiled as part of ht_backproject.hip (included at its end, like ht_ingest.hip): the library keeps ONE code object besides the three
-// that profiles/traffic.json fingerprints.  No kernel name here carries one of the fingerprint's markers.
+// that profiles/traffic.json fingerprints.  No kernel name here carries one of the fingerprint's markers.  ht_backproject.hip has
+// included ht_cs_device.h (cs_bin, the workgroup sizes, the device helpers) in front of its own kernels: this file sees it from there.
 #include <cstring>
 #include <vector>
 
 namespace {
-
-#include "ht_cs_device.h"  // after ht_backproject.hip's cs_bin
-
-constexpr int CSP_INIT_NT = 1024;  // k_cs_init's workgroup
 
 struct CspEntry {
     int32_t stream, frame;  // the pair
@@ -31,142 +29,16 @@ struct CspEntry {
 };
 static_assert(sizeof(CspEntry) == 32, "CspEntry");
 
-// k_cs_hist over the frames frame_list[0 .. gridDim.y) names: four 16-byte loads per thread in flight, counts merged per thread and per
-// wavefront before they reach LDS, the chunk's histogram written whole into hist[blockIdx.y][blockIdx.x][4096]
-__global__ __launch_bounds__(HIST_NT) void k_csp_hist(const uint8_t *__restrict__ frames, size_t frame_stride, uint32_t npix, uint32_t chunk_px,
-                                                      const int32_t *__restrict__ frame_list, uint32_t *__restrict__ hist) {
-    __shared__ uint32_t h[4096];
-    for (int i = threadIdx.x; i < 4096; i += HIST_NT) h[i] = 0;
-    __syncthreads();
-    const uint8_t *frame = frames + (size_t)frame_list[blockIdx.y] * frame_stride;
-    const uint32_t beg = blockIdx.x * chunk_px, end = min(beg + chunk_px, npix);  // chunk_px is a multiple of 4 * HIST_NT; beg < npix
-    const uint32_t nquad = (end - beg) / 4;
-    const uint4 *img4 = reinterpret_cast<const uint4 *>(frame + (size_t)beg * 4);
-    const uint32_t iters = chunk_px / (4 * HIST_NT);
-    for (uint32_t it0 = 0; it0 < iters; it0 += HIST_UNROLL) {
-        uint4 pv[HIST_UNROLL];
-        bool onv[HIST_UNROLL];
-#pragma unroll
-        for (int u = 0; u < HIST_UNROLL; u++) {
-            const uint32_t i = (it0 + (uint32_t)u) * HIST_NT + threadIdx.x;
-            onv[u] = it0 + (uint32_t)u < iters && i < nquad;
-            pv[u] = make_uint4(0u, 0u, 0u, 0u);
-            if (onv[u]) pv[u] = img4[i];
-        }
-#pragma unroll
-        for (int u = 0; u < HIST_UNROLL; u++) {
-            CS_BATCH_LOADED(pv[u].x);
-            CS_BATCH_LOADED(pv[u].y);
-            CS_BATCH_LOADED(pv[u].z);
-            CS_BATCH_LOADED(pv[u].w);
-        }
-#pragma unroll
-        for (int u = 0; u < HIST_UNROLL; u++) {
-            if (it0 + (uint32_t)u >= iters) break;  // workgroup-uniform
-            const uint4 p = pv[u];
-            const bool on = onv[u];
-            const uint32_t b0 = cs_bin(p.x), b1 = cs_bin(p.y), b2 = cs_bin(p.z), b3 = cs_bin(p.w);
-            const bool flat = (b0 == b1) && (b2 == b3) && (b0 == b2);
-            hist_add_wave(h, b0, flat ? 4u : 1u, on);
-            if (on && !flat) {
-                atomicAdd(&h[b1], 1u);
-                atomicAdd(&h[b2], 1u);
-                atomicAdd(&h[b3], 1u);
-            }
-        }
-    }
-    const uint32_t *img = reinterpret_cast<const uint32_t *>(frame);
-    for (uint32_t i = beg + nquad * 4 + threadIdx.x; i < end; i += HIST_NT) atomicAdd(&h[cs_bin(img[i])], 1u);  // < 4 pixels
-    __syncthreads();
-    uint32_t *out = hist + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4096;
-    for (int i = threadIdx.x; i < 4096; i += HIST_NT) out[i] = h[i];
-}
-
-// track() of pair blockIdx.x: the state is states[pair.stream], the pixels are frame pair.frame, the frame's histogram is the sum of the
-// chunk histograms of slot pair.slot; the track object goes to out[blockIdx.x] (pair order)
-__global__ __launch_bounds__(CS_NT) void k_csp_meanshift(const uint8_t *__restrict__ frames, size_t frame_stride, int W, int H,
-                                                         const uint32_t *__restrict__ hist, int nchunks, HtCsState *__restrict__ states,
-                                                         const CspEntry *__restrict__ entries, int calc_angles, int max_it, int region_cap,
-                                                         ht_cs_trackobj *__restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t cs_dyn[];  // [region_cap] u16 bins of the cached search region
-    __shared__ double lut[4096];
-    __shared__ double red[6][CS_NT / 64];
-    __shared__ int s_sw[4];
-    const int s = blockIdx.x;
-    const int e_stream = entries[s].stream, e_frame = entries[s].frame, e_slot = entries[s].slot;
-    HtCsState &st = states[e_stream];
-    const uint32_t *cur = hist + (size_t)e_slot * nchunks * 4096;
-    const uint32_t *img = reinterpret_cast<const uint32_t *>(frames + (size_t)e_frame * frame_stride);
-    {  // getWeights, camshift.js:314-330; the frame's histogram = sum of its chunk histograms (4 bins per 16-byte load)
-        const uint4 *cur4 = reinterpret_cast<const uint4 *>(cur);
-        const uint4 *model4 = reinterpret_cast<const uint4 *>(st.model);
-        for (int i4 = threadIdx.x; i4 < 1024; i4 += CS_NT) {
-            uint4 acc = make_uint4(0u, 0u, 0u, 0u);
-            for (int k = 0; k < nchunks; k++) {
-                const uint4 v = cur4[(size_t)k * 1024 + i4];
-                acc.x += v.x, acc.y += v.y, acc.z += v.z, acc.w += v.w;
-            }
-            const uint4 m = model4[i4];
-            const uint32_t chv[4] = {acc.x, acc.y, acc.z, acc.w}, mv[4] = {m.x, m.y, m.z, m.w};
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                double p = 0.0;
-                if (chv[q] != 0) {
-                    p = (double)mv[q] / (double)chv[q];
-                    p = p < 1.0 ? p : 1.0;
-                }
-                lut[i4 * 4 + q] = p;
-            }
-        }
-    }
-    if (threadIdx.x < 4) s_sw[threadIdx.x] = st.sw[threadIdx.x];
-    __syncthreads();
-    const CsRegion R = cs_cache_region<CS_NT>(img, W, H, s_sw, reinterpret_cast<uint16_t *>(cs_dyn), region_cap);
-    __syncthreads();
-    meanshift_body(W, H, s_sw, st, calc_angles, max_it, out ? out + s : nullptr, nullptr, true,
-                   [&](int x, int y, int w, int h) { return window_moments_any<true, CS_NT / 64>(img, W, lut, R, x, y, w, h, red); });
-}
-
-// initTracker of pair blockIdx.x (k_cs_init: rows of the rect by wavefront, columns by lane, 8 independent loads per lane in flight)
-__global__ __launch_bounds__(CSP_INIT_NT) void k_csp_init(const uint8_t *__restrict__ frames, size_t frame_stride, int W, int H,
-                                                          const CspEntry *__restrict__ entries, HtCsState *__restrict__ states) {
-    __shared__ uint32_t h[4096];
-    const int s = blockIdx.x;
-    for (int i = threadIdx.x; i < 4096; i += CSP_INIT_NT) h[i] = 0;
-    __syncthreads();
-    const ht_cs_rect r = entries[s].rect;
-    const int e_stream = entries[s].stream, e_frame = entries[s].frame;
-    const uint32_t *img = reinterpret_cast<const uint32_t *>(frames + (size_t)e_frame * frame_stride);
-    const int rw = max(r.width, 0), rh = max(r.height, 0);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    constexpr int NWV = CSP_INIT_NT / 64;
-    for (int j0 = wave; j0 - wave < rh; j0 += 8 * NWV) {  // same trip count for every wavefront's lanes (ballots inside)
-        for (int cb = 0; cb < rw; cb += 64) {
-            const int c = cb + lane;
-            uint32_t px[8];
-            bool in[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int y = r.y + j0 + u * NWV, x = r.x + c;
-                in[u] = c < rw && j0 + u * NWV < rh;                               // inside the rect
-                const bool img_ok = in[u] && x >= 0 && x < W && y >= 0 && y < H;  // inside the canvas
-                px[u] = img_ok ? img[(size_t)y * W + x] : 0u;  // getImageData outside the canvas: transparent black -> bin 0 (camshift.js:206)
-            }
-#pragma unroll
-            for (int u = 0; u < 8; u++) CS_BATCH_LOADED(px[u]);
-#pragma unroll
-            for (int u = 0; u < 8; u++) hist_add_wave(h, cs_bin(px[u]), 1u, in[u]);
-        }
-    }
-    __syncthreads();
-    HtCsState &st = states[e_stream];
-    for (int i = threadIdx.x; i < 4096; i += CSP_INIT_NT) st.model[i] = h[i];
-    if (threadIdx.x == 0) {
-        st.sw[0] = r.x, st.sw[1] = r.y, st.sw[2] = r.width, st.sw[3] = r.height;  // camshift.js:209
-        st.x = st.y = st.width = st.height = st.angle = 0.0;                         // camshift.js:210
-        st.win_px = st.calls = 0;
-    }
-}
+#define CS_K(name) k_csp_##name
+typedef const CspEntry *__restrict__ CsLookup;  // the call's table: workgroup s is pair s
+__device__ __forceinline__ int cs_stream_of(const CspEntry *e, int s) { return e[s].stream; }
+__device__ __forceinline__ int cs_frame_of(const CspEntry *e, int s) { return e[s].frame; }
+__device__ __forceinline__ int cs_slot_of(const CspEntry *e, int s) { return e[s].slot; }
+#define CS_INIT_PARAMS CsLookup lk, HtCsState *__restrict__ states
+#define CS_INIT_RECT(s_) lk[s_].rect
+#define CS_HIST_FRAMES_PARAM const int32_t *__restrict__ frame_list,  // the call's distinct frames, one per grid row
+#define CS_HIST_FRAME(y_) frame_list[y_]
+#include "ht_cs_kernels.inc"
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
 
@@ -301,7 +173,7 @@ extern "C" ht_status ht_camshift_init_pairs(ht_ctx *c, const ht_cs_pair *pairs, 
     st = csp_upload(c, "ht_camshift_init_pairs", plan, &d_entries, &d_flist);
     if (st != HT_OK) return st;
     HtProfScope ps(c, "csp_init");
-    hipLaunchKernelGGL(k_csp_init, dim3(n), dim3(CSP_INIT_NT), 0, c->stream, c->d_frames, c->frame_stride, c->W, c->H, d_entries, c->d_cs);
+    hipLaunchKernelGGL(k_csp_init, dim3(n), dim3(INIT_NT), 0, c->stream, c->d_frames, c->frame_stride, c->W, c->H, d_entries, c->d_cs);
     HT_HIP(c, hipGetLastError());
     return HT_OK;
 }
@@ -315,19 +187,16 @@ extern "C" ht_status ht_camshift_track_pairs(ht_ctx *c, const ht_cs_pair *pairs,
     if (plan.identity && !c->cs_pairs_force) return ht_camshift_track_batch(c, plan.first, n, calc_angles, out);  // all three schedules, unchanged
     if (c->W == 0 || c->H == 0) return HT_OK;  // camshift.js:219
     HT_HIP(c, hipSetDevice(c->device));
-    // like ht_camshift_track_batch: a synchronous call with nothing outstanding takes the enqueue-only route and collects at once
-    const bool via_ring = out && c->cs_sync_ring && c->cs_ring_count == 0 && n <= c->cs_ring_streams;
-    if (!out || via_ring) {
-        if (n > c->cs_ring_streams) return ht_fail(c, HT_ERR_STATE, "ht_camshift_track_pairs: no result ring for this many streams (ht_camshift_reserve failed to allocate it)");
-        if (c->cs_ring_count == ht_ctx::HT_CS_RING)
-            return ht_fail(c, HT_ERR_STATE, "ht_camshift_track_pairs: too many enqueue-only calls outstanding (collect with ht_camshift_track_collect)");
-        ht_ctx::HtCsSlot &sl = c->cs_ring[(c->cs_ring_head + c->cs_ring_count) % ht_ctx::HT_CS_RING];
-        st = csp_launch_track(c, plan, calc_angles, sl.h_out);
+    bool via_ring = false;
+    ht_ctx::HtCsSlot *slot = nullptr;
+    st = ht_cs_ring_begin(c, "ht_camshift_track_pairs", n, out, &via_ring, &slot);
+    if (st != HT_OK) return st;
+    if (slot) {
+        st = csp_launch_track(c, plan, calc_angles, slot->h_out);
         if (st != HT_OK) return st;
-        sl.seq = 0u;  // completed by the event
-        HT_HIP(c, hipEventRecord(sl.ev, c->stream));
-        sl.n = n;
-        c->cs_ring_count++;
+        slot->seq = 0u;  // completed by the event
+        HT_HIP(c, hipEventRecord(slot->ev, c->stream));
+        ht_cs_ring_commit(c, slot, n);
         return via_ring ? ht_camshift_track_collect(c, n, out) : HT_OK;
     }
     st = csp_launch_track(c, plan, calc_angles, c->d_cs_out);

@@ -496,6 +496,11 @@ void ht_capture_mark(ht_ctx *ctx, bool on);                 // ht_camshift.hip: 
 // hist[n][nchunks][4096] (for ht_backproject.hip, which must not carry a copy of the kernel)
 void ht_cs_hist_plan(uint32_t npix, int nstreams, uint32_t *chunk_px, uint32_t *nchunks);
 ht_status ht_cs_hist_launch(ht_ctx *ctx, const uint8_t *frames, size_t frame_stride, int n, uint32_t npix, uint32_t chunk_px, uint32_t nchunks, uint32_t *hist);
+// ht_camshift.hip: the result ring of the enqueue-only track calls (batch and pair form).  begin: *slot = the next free pinned slot when
+// the call is enqueue-only or a synchronous call that goes through the ring (*via_ring), nullptr when it copies back; commit: the slot
+// is outstanding
+ht_status ht_cs_ring_begin(ht_ctx *ctx, const char *fn, int32_t n, const ht_cs_trackobj *out, bool *via_ring, ht_ctx::HtCsSlot **slot);
+void ht_cs_ring_commit(ht_ctx *ctx, ht_ctx::HtCsSlot *slot, int32_t n);
 void ht_backproject_free(ht_ctx *ctx);                      // ht_backproject.hip: its scratch (ht_destroy)
 void ht_cs_pairs_free(ht_ctx *ctx);                         // ht_cs_pairs.hip: pair table, staging and histogram scratch (ht_destroy)
 void ht_ingest_free(ht_ctx *ctx);                           // ht_ingest.hip: the host form's source staging (ht_destroy)

@@ -104,18 +104,23 @@ def _gfx950_code_objects(lib):
     return out
 
 
-def _cs_bin_body(path):
-    text = open(path).read()
-    m = re.search(r"__device__ __forceinline__ uint32_t cs_bin\(uint32_t px\) \{\n(.*?)\n\}\n", text, flags=re.S)
-    assert m, path
-    return m.group(1)
-
-
 def test_bin_function_is_the_camshift_units_text():
-    """tests/test_oracle_golden.py proves ht_camshift.hip's four-instruction cs_bin against the reference formula exhaustively; the new
-    unit's copy is the same characters, so the proof covers it"""
-    a, b = _cs_bin_body(os.path.join(CSRC, "ht_camshift.hip")), _cs_bin_body(os.path.join(CSRC, "ht_backproject.hip"))
-    assert a == b and "0x00f0f0f0u" in a
+    """tests/test_oracle_golden.py proves the four-instruction cs_bin against the reference formula exhaustively.  There is exactly ONE
+    definition — in ht_cs_device.h, which this unit and ht_camshift.hip include — so the proof covers every kernel that bins a pixel: no
+    file of csrc/ defines cs_bin or a load-laundering macro of its own"""
+    sig = "__device__ __forceinline__ uint32_t cs_bin(uint32_t px) {"
+    texts = {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".inc", ".hip", ".cc"))}
+    assert sum(t.count(sig) for t in texts.values()) == 1 and texts["ht_cs_device.h"].count(sig) == 1
+    m = re.search(re.escape(sig) + r"\n(.*?)\n\}\n", texts["ht_cs_device.h"], flags=re.S)
+    assert m and "0x00f0f0f0u" in m.group(1)
+    for f, t in texts.items():
+        defs = re.findall(r"\bcs_bin\s*\([^;{)]*\)\s*\{", t)  # any definition, whatever its qualifiers
+        macros = re.findall(r"#\s*define\s+(\w*_BATCH_LOADED)\b", t)
+        if f == "ht_cs_device.h":
+            assert len(defs) == 1 and macros == ["CS_BATCH_LOADED"], (defs, macros)
+        else:
+            assert not defs and not macros, (f, defs, macros)
+    assert "CS_BATCH_LOADED(" in texts["ht_backproject.hip"] and "cs_bin(" in texts["ht_backproject.hip"]  # and the unit uses them
 
 
 def test_new_kernels_fit_their_budgets():

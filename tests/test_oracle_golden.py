@@ -105,14 +105,15 @@ def check_camshift_case(case):
 
 
 def test_four_instruction_histogram_bin_equals_the_reference_formula_exhaustively():
-    """ht_camshift.hip's cs_bin computes camshift.Histogram's bin (camshift.js:63-66: 256 * (R >> 4) + 16 * (G >> 4) + (B >> 4)) from the
-    packed pixel R | G << 8 | B << 16 | A << 24 as ((t << 24) | (t + (t << 12))) >> 20 with t = px & 0xf0f0f0, in 32-bit arithmetic; the
-    code object multiplies by 0x1001 with v_mul_u32_u24 (t is a 24-bit value).  Every RGB value, alpha 0 / 0x5a / 0xff, against the
-    reference formula — and the source must still hold the expression this test restates."""
+    """cs_bin (ht_cs_device.h: the one definition every camshift and back-projection kernel compiles) computes camshift.Histogram's bin
+    (camshift.js:63-66: 256 * (R >> 4) + 16 * (G >> 4) + (B >> 4)) from the packed pixel R | G << 8 | B << 16 | A << 24 as
+    ((t << 24) | (t + (t << 12))) >> 20 with t = px & 0xf0f0f0, in 32-bit arithmetic; the code object multiplies by 0x1001 with
+    v_mul_u32_u24 (t is a 24-bit value).  Every RGB value, alpha 0 / 0x5a / 0xff, against the reference formula — and the source must
+    still hold the expression this test restates."""
     import os
     import re
 
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "headtrackr_amd", "csrc", "ht_camshift.hip")).read()
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "headtrackr_amd", "csrc", "ht_cs_device.h")).read()
     body = re.search(r"uint32_t cs_bin\(uint32_t px\) \{(.*?)\n\}", src, re.S).group(1)
     assert "px & 0x00f0f0f0u" in body and "((t << 24) | (t + (t << 12))) >> 20" in body
     rgb = np.arange(1 << 24, dtype=np.uint32)

@@ -244,17 +244,40 @@ def test_pair_kernels_live_in_the_fourth_code_object_within_their_budgets():
     assert "ht_cs_pairs.hip" not in build.HIP_SOURCES
 
 
+def _included(text):
+    return re.findall(r'^\s*#\s*include\s+"([^"]+)"', text, flags=re.M)
+
+
+def _times_seen(unit, header, texts):
+    """how often the translation unit `unit` sees `header`, directly or through the files it includes"""
+    return sum(1 if inc == header else _times_seen(inc, header, texts) for inc in _included(texts[unit]) if inc in texts)
+
+
 def test_shared_helpers_have_one_definition():
-    """the device helpers moved into ht_cs_device.h; ht_camshift.hip and ht_cs_pairs.hip include it and define none of them again"""
-    hdr = open(os.path.join(CSRC, "ht_cs_device.h")).read()
-    units = [open(os.path.join(CSRC, f)).read() for f in ("ht_camshift.hip", "ht_cs_pairs.hip")]
+    """the device helpers live in ht_cs_device.h and the init / histogram / mean-shift kernels in ht_cs_kernels.inc; ht_camshift.hip and
+    ht_cs_pairs.hip define none of them again, and each translation unit sees the header exactly once"""
+    texts = {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".inc", ".hip", ".cc"))}
+    hdr = texts["ht_cs_device.h"]
+    units = [texts[f] for f in ("ht_camshift.hip", "ht_cs_pairs.hip")]
     for sig in ("void hist_add_wave(", "int32_t toint32(", "struct Mom {", "double wave_sum_f64(", "struct CsRegion {", "CsRegion cs_cache_region(",
-                "Mom window_moments(", "Mom window_moments_any(", "void meanshift_body(", "#define CS_BATCH_LOADED"):
+                "Mom window_moments(", "Mom window_moments_any(", "void meanshift_body(", "#define CS_BATCH_LOADED", "uint32_t cs_bin(uint32_t px) {"):
         assert hdr.count(sig) == 1, sig
+        assert sum(t.count(sig) for t in texts.values()) == 1, sig
         for u in units:
             assert sig not in u, sig
-    for u in units:
-        assert '#include "ht_cs_device.h"' in u
+    # the three kernel bodies: one __global__ definition each in all of csrc/, in the shared file, under the name the unit gives it
+    kern = re.compile(r"__global__[^;{]*?\b(k_csp?_(?:hist|meanshift|init)|CS_K\((?:hist|meanshift|init)\))\s*\(")
+    found = {f: kern.findall(t) for f, t in texts.items()}
+    assert sorted(found.pop("ht_cs_kernels.inc")) == ["CS_K(hist)", "CS_K(init)", "CS_K(meanshift)"]
+    assert not any(found.values()), found
+    for f in ("ht_camshift.hip", "ht_cs_pairs.hip"):
+        assert "ht_cs_kernels.inc" in _included(texts[f]) and re.search(r"#define CS_K\(name\) k_csp?_##name\n", texts[f]), f
+    # each translation unit sees the header exactly once, directly or through the file it is included by
+    assert "ht_cs_pairs.hip" in _included(texts["ht_backproject.hip"]) and "ht_cs_pairs.hip" not in build.HIP_SOURCES
+    for tu in build.HIP_SOURCES:
+        uses = any(n in texts[tu] or any(n in texts[i] for i in _included(texts[tu]) if i in texts) for n in ("cs_bin(", "CS_BATCH_LOADED("))
+        assert _times_seen(tu, "ht_cs_device.h", texts) == (1 if uses else 0), tu
+    assert _times_seen("ht_camshift.hip", "ht_cs_device.h", texts) == _times_seen("ht_backproject.hip", "ht_cs_device.h", texts) == 1
 
 
 # ---- the JavaScript layer on the mock -------------------------------------------------------------------------------------------------------
