@@ -15,6 +15,7 @@
 
 #include "ht_internal.h"
 #include "ht_hostpost.h"
+#include "ht_geometry_plan.h"
 
 static thread_local std::string g_create_err;
 
@@ -455,10 +456,10 @@ static void free_geometry(ht_ctx *c) {
     if (c->d_tail_taps) (void)hipFree(c->d_tail_taps), c->d_tail_taps = nullptr;
     if (c->d_tail_taps_fast) (void)hipFree(c->d_tail_taps_fast), c->d_tail_taps_fast = nullptr;
     if (c->d_tail_tapref) (void)hipFree(c->d_tail_tapref), c->d_tail_tapref = nullptr;
-    c->tail_first_gen = 0;
-    c->h_gens.clear();
-    c->gen_blocks.clear();
-    c->h_scales.clear();
+    c->plan.tail_first_gen = 0;
+    c->plan.gens.clear();
+    c->plan.gen_blocks.clear();
+    c->plan.scales.clear();
 }
 
 extern "C" void ht_destroy(ht_ctx *c) {
@@ -542,287 +543,52 @@ extern "C" void ht_destroy(ht_ctx *c) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// geometry, ccv.js:110-147
+// geometry, ccv.js:110-147: planned on the host by ht_plan_geometry (ht_geometry_plan.h), uploaded here
 
-
-static inline uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
-
-// rs_tap (ht_pyramid.hip) on the host: the same binary64 operations in the same order (this file is compiled with
-// -ffp-contract=off like the kernels, so nothing is fused)
-static HtTap ht_host_tap(int i, double r, int s, int origin) {
-    double f = ((double)i + 0.5) * r;
-    f = f + (-0.5);
-    f = f < 0.0 ? 0.0 : f;
-    const double fmax = (double)(s - 1);
-    f = f > fmax ? fmax : f;
-    const double af = std::floor(f);
-    HtTap tp;
-    tp.a = origin + (int)af;
-    tp.b = origin + std::min((int)af + 1, s - 1);
-    tp.t = f - af;
-    tp.u = 1.0 - tp.t;
-    return tp;
+// one table of the plan on the device
+template <typename T>
+static ht_status upload_table(ht_ctx *c, T *&dst, const std::vector<T> &src) {
+    if (src.empty()) return HT_OK;
+    HT_HIP(c, hipMalloc(&dst, src.size() * sizeof(T)));
+    HT_HIP(c, hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    return HT_OK;
 }
 
 // Builds every table / allocation of one geometry.  On any failure the caller (ht_set_geometry) frees what was built and
 // leaves the context without a geometry, so a retry (e.g. with a smaller max_batch after HT_ERR_NOMEM) starts clean.
 static ht_status set_geometry_impl(ht_ctx *c, int32_t width, int32_t height, int32_t max_batch, const int32_t *level_dims, int n, int upto) {
-    const int next = c->next;
     c->W = width;
     c->H = height;
     c->max_batch = max_batch;
     c->nlevels = n;
     c->upto = upto;
 
-    uint64_t off = 0;
-    c->pyr_bytes = 0;
-    for (int i = 0; i < n; i++) {
-        HtDevLevel &L = c->h_levels[i];
-        if (level_dims) {  // validated by ht_set_geometry
-            L.w = level_dims[2 * i];
-            L.h = level_dims[2 * i + 1];
-        } else if (i == 0) {
-            L.w = width;
-            L.h = height;
-        } else if (i <= c->interval) {  // ccv.js:119-120
-            L.w = (int)std::floor((double)width / ht_scale_pow(c->interval, i));
-            L.h = (int)std::floor((double)height / ht_scale_pow(c->interval, i));
-        } else {  // ccv.js:126-127
-            L.w = c->h_levels[i - next].w / 2;
-            L.h = c->h_levels[i - next].h / 2;
-        }
-        L.stride = (int)align_up((uint64_t)L.w, 4);
-        for (int s = 0; s < 4; s++) {
-            if (s == 0 || i >= 2 * next) {  // ccv.js:131
-                if (off > 0xfffffff0ull) return ht_fail(c, HT_ERR_INVALID, "ht_set_geometry: frame too large");
-                L.off[s] = (uint32_t)off;
-                off = align_up(off + (uint64_t)L.stride * L.h, 256);
-                c->pyr_bytes += (uint64_t)L.w * L.h;
-            } else {
-                L.off[s] = 0xffffffffu;
-            }
-        }
-    }
-    c->arena_stride = align_up(off + 256, 256);
+    HtPlanInputs in;
+    in.interval = c->interval, in.next = c->next, in.cw = c->cw, in.ch = c->ch;
+    in.rs_rpt = c->rs_rpt, in.rs_nofast = c->rs_nofast, in.rs_nosort = c->rs_nosort, in.rs_notail = c->rs_notail;
+    in.rs_tailcap = c->rs_tailcap, in.rs_tailcap_forced = c->rs_tailcap_forced;
+    in.tail_table = c->tail_table, in.tail_table_forced = c->tail_table_forced;
+    in.early_scan = c->early_scan, in.aux_stream = c->aux_stream != nullptr;
+    in.queue_capacity_cfg = c->queue_capacity_cfg;
+    HtGeometryPlan &P = c->plan;
+    std::string why;
+    ht_status st = ht_plan_geometry(in, width, height, max_batch, level_dims, n, upto, &P, &why);
+    if (st != HT_OK) return ht_fail(c, st, why);
 
-    // resample jobs by dependency generation (generation 0 = the gray plane itself)
-    std::vector<int> gen(n, 0);
-    int ngen = 1;
-    for (int i = 1; i < n; i++) {
-        gen[i] = (i <= c->interval) ? 1 : gen[i - next] + 1;
-        ngen = std::max(ngen, gen[i] + 1);
-    }
-    c->h_gens.assign(ngen, {});
-    auto add_job = [&](int g, int src, int dst, int slot, int sx, int sy, int sw, int sh, int dw, int dh) {
-        const HtDevLevel &S = c->h_levels[src], &D = c->h_levels[dst];
-        if (D.w <= 0 || D.h <= 0) return;
-        HtResampleJob j;
-        std::memset(&j, 0, sizeof(j));
-        j.src_off = S.off[0];
-        j.dst_off = D.off[slot];
-        j.src_stride = S.stride;
-        j.dst_stride = D.stride;
-        j.sx = sx, j.sy = sy, j.sw = sw, j.sh = sh;
-        j.dw = dw, j.dh = dh;
-        j.cw = D.w, j.ch = D.h;
-        if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0) {  // nothing is drawn: the canvas stays transparent black
-            j.dw = j.dh = 0;
-            j.sw = j.sh = 1;
-            j.rx = j.ry = 1;
-        } else {
-            j.rx = (double)sw / (double)dw;
-            j.ry = (double)sh / (double)dh;
-        }
-        c->h_gens[g].push_back(j);
-    };
-    for (int i = 1; i < n; i++) {
-        const HtDevLevel &D = c->h_levels[i];
-        if (i <= c->interval) {  // ccv.js:121
-            add_job(gen[i], 0, i, 0, 0, 0, c->h_levels[0].w, c->h_levels[0].h, D.w, D.h);
-        } else {  // ccv.js:128
-            const HtDevLevel &S = c->h_levels[i - next];
-            add_job(gen[i], i - next, i, 0, 0, 0, S.w, S.h, D.w, D.h);
-            if (i >= 2 * next) {  // ccv.js:135,140,145
-                add_job(gen[i], i - next, i, 1, 1, 0, S.w - 1, S.h, D.w - 2, D.h);
-                add_job(gen[i], i - next, i, 2, 0, 1, S.w, S.h - 1, D.w, D.h - 2);
-                add_job(gen[i], i - next, i, 3, 1, 1, S.w - 1, S.h - 1, D.w - 2, D.h - 2);
-            }
-        }
-    }
-    c->d_gen_blocks.assign(ngen, nullptr);
-    c->gen_blocks.assign(ngen, 0);
-    for (int g = 1; g < ngen; g++) {
-        // k_resample tile records: 64 columns x np passes of 16 rows.  np is bounded by the LDS source window (the rows
-        // a tile touches: ~16 np ry + 3 <= HT_RS_SRC_ROWS; the kernel falls back to HBM taps if a tile still does not fit)
-        // and by rs_rpt; a canvas of P = ceil(ch / 16) passes is then cut into ceil(P / np) tiles of near-equal pass counts.
-        std::vector<HtResampleJob> tiles;
-        for (auto &j : c->h_gens[g]) {
-            int npmax = 1;
-            for (int t = 2; t <= std::min(c->rs_rpt, HT_RS_MAX_PASSES); t++)
-                if ((int)std::ceil(16.0 * t * j.ry) + 3 <= HT_RS_SRC_ROWS) npmax = t;
-            const int passes = (j.ch + 15) / 16, nby = (passes + npmax - 1) / npmax, nbx = (j.cw + 63) / 64;
-            int pass0 = 0;
-            for (int y = 0; y < nby; y++) {
-                const int np = passes / nby + (y < passes % nby ? 1 : 0);
-                for (int x = 0; x < nbx; x++) {
-                    HtResampleJob t = j;
-                    t.bx = (uint16_t)x, t.pass0 = (uint16_t)pass0, t.np = (uint16_t)np;
-                    // bit 0: exact 2:1 in both directions (2x2 box mean, see the BOX rows of k_resample); option rs_nofast keeps
-                    // every pixel on the declared binary64 sequence (A/B and cross-check)
-                    t.pad = c->rs_nofast ? 2 : (uint16_t)((j.dw > 0 && j.sw == 2 * j.dw && j.sh == 2 * j.dh) ? 1 : 0);
-                    const int X0 = 64 * x, Y0 = 16 * pass0, ncols = std::min(64, j.dw - X0), nrows = std::min(16 * np, j.dh - Y0);
-                    if (ncols > 0 && nrows > 0) {  // the source extent k_resample stages into LDS (same expressions as in the kernel)
-                        t.ex_xa = ht_host_tap(X0, j.rx, j.sw, j.sx).a & ~15;
-                        t.ex_ya = ht_host_tap(Y0, j.ry, j.sh, j.sy).a;
-                        t.ex_sw16 = (ht_host_tap(X0 + ncols - 1, j.rx, j.sw, j.sx).b - t.ex_xa) / 16 + 1;
-                        t.ex_sh = ht_host_tap(Y0 + nrows - 1, j.ry, j.sh, j.sy).b - t.ex_ya + 1;
-                        // k_resample_bands: the source rows of each wavefront's quarter of the tile (rows beyond the drawn ones read the
-                        // last drawn row's taps, as in the kernel)
-                        bool fit = t.ex_sw16 * 16 <= 160;
-                        for (int w = 0; w < 4; w++) {
-                            const int r0 = std::min(4 * np * w, nrows - 1), r1 = std::min(4 * np * (w + 1) - 1, nrows - 1);
-                            const int bya = ht_host_tap(Y0 + r0, j.ry, j.sh, j.sy).a - t.ex_ya;
-                            const int bsh = ht_host_tap(Y0 + r1, j.ry, j.sh, j.sy).b - (t.ex_ya + bya) + 1;
-                            if (bya < 0 || bya > 255 || bsh < 1 || bsh > HT_RSB_ROWS) fit = false;
-                            t.band_ya4 |= (uint32_t)(bya & 0xff) << (8 * w), t.band_sh4 |= (uint32_t)(bsh & 0xff) << (8 * w);
-                        }
-                        if (fit) t.pad |= 4;
-                    }
-                    tiles.push_back(t);
-                }
-                pass0 += np;
-            }
-        }
-        // launch order = source order: tiles of different drawImage calls that read the same rows of the same source
-        // plane (levels 1..6 all read level 0; the four variants of a level read the same parent) run back to back on
-        // an XCD, so the source band is fetched from HBM once and then served by that XCD's L2
-        if (!c->rs_nosort)
-            std::stable_sort(tiles.begin(), tiles.end(), [](const HtResampleJob &a, const HtResampleJob &b) {
-                if (a.src_off != b.src_off) return a.src_off < b.src_off;
-                const int ya = (int)(16.0 * a.pass0 * a.ry), yb = (int)(16.0 * b.pass0 * b.ry);
-                if (ya / 32 != yb / 32) return ya < yb;
-                return a.bx < b.bx;
-            });
-        c->gen_blocks[g] = (uint32_t)tiles.size();
-        if (tiles.empty()) continue;
-        HT_HIP(c, hipMalloc(&c->d_gen_blocks[g], tiles.size() * sizeof(HtResampleJob)));
-        HT_HIP(c, hipMemcpy(c->d_gen_blocks[g], tiles.data(), tiles.size() * sizeof(HtResampleJob), hipMemcpyHostToDevice));
-    }
-
+    c->d_gen_blocks.assign(P.gens.size(), nullptr);
+    for (size_t g = 1; g < P.gens.size(); g++)
+        if ((st = upload_table(c, c->d_gen_blocks[g], P.gen_tiles[g])) != HT_OK) return st;
     HT_HIP(c, hipMalloc(&c->d_levels, sizeof(HtDevLevel) * HT_MAX_LEVELS));
-    HT_HIP(c, hipMemcpy(c->d_levels, c->h_levels, sizeof(HtDevLevel) * n, hipMemcpyHostToDevice));
-    if (hipMalloc(&c->d_arena, c->arena_stride * (uint64_t)max_batch) != hipSuccess)
+    HT_HIP(c, hipMemcpy(c->d_levels, P.levels, sizeof(HtDevLevel) * n, hipMemcpyHostToDevice));
+    if (hipMalloc(&c->d_arena, P.arena_stride * (uint64_t)max_batch) != hipSuccess)
         return ht_fail(c, HT_ERR_NOMEM, "ht_set_geometry: hipMalloc(pyramid arena) failed");
-    HT_HIP(c, hipMemset(c->d_arena, 0, c->arena_stride * (uint64_t)max_batch));
-
-    // tail plan: from the first generation g0 on which every generation has <= HT_TAIL_MAX_JOBS jobs and all of them
-    // together <= tail_cap destination pixels per frame, one workgroup per frame does the rest of the pyramid in one launch
-    // (k_resample_tail) instead of one nearly empty launch per generation.
-    constexpr int HT_SMALL_BATCH = 48;
-    // Small batches (a live feed's frame, the 8 feeds of a streaming step) are latency chains, not throughput: the tail kernel is ONE
-    // workgroup per frame walking its generations behind barriers — 21 us for 17 k pixels of a single 320x240 frame, the longest kernel
-    // of the call —, while a k_resample_bands launch of the same generation is 4.5 us on the otherwise idle chip.  rocprofv3 kernel
-    // trace of single-frame calls (tools/gpu_one_frame_trace.sh, round 6): cap 32 768 -> 4 000 pixels takes 74.1 -> 63.5 us off the
-    // device span at 320x240 (generation 4 as a launch, generations 5 - 7 in the tail) and 92.9 -> 79.3 us at 1920x1080 (no tail at all);
-    // batches that fill the chip keep the large cap (C2: cap 4 000 costs +3 % on the pyramid, no tail at all +19 %).  Where it ends, pipelined
-    // (three batches of 320x240 in flight / two of 1280x720, small plan against large): 24 frames +11 %, 32 +10.6 %, 48 +9.5 %, 64 +-0 %, 128 +-0 %;
-    // 720p: 16 frames +2 %, 32 +3 %.
-    const uint64_t tail_cap = c->rs_tailcap_forced ? c->rs_tailcap : (max_batch <= HT_SMALL_BATCH ? 4000u : c->rs_tailcap);
-    // which tail kernel: measured (3 batches in flight), the table-driven binary32 tail (68 VGPRs, 35 KB LDS) is worth +4-5 % at
-    // 128 x 720p but costs 3 % at 256 x 320x240, where its grid puts a 1024-thread workgroup on EVERY CU and its footprint keeps
-    // the other batches' kernels from sharing them; the round-1 binary64 tail (41 VGPRs) is kept for batches that cover the chip.
-    // Larger caps (generation 3 of C2 = 54 k pixels in the tail) lose with either kernel.
-    // ... and for a handful of frames: 7.6 us against the table form's 10.3 for generations 5 - 7 of a single 320x240 frame (the same trace)
-    if (!c->tail_table_forced) c->tail_table = (max_batch <= 128 && max_batch > HT_SMALL_BATCH) ? 1 : 0;
-    c->tail_first_gen = 0;
-    if (c->d_tail_jobs) (void)hipFree(c->d_tail_jobs), c->d_tail_jobs = nullptr;
-    if (c->d_tail_prefix) (void)hipFree(c->d_tail_prefix), c->d_tail_prefix = nullptr;
-    if (!c->rs_notail) {
-        int g0 = ngen;
-        uint64_t px = 0;
-        for (int g = ngen - 1; g >= 1; g--) {
-            uint64_t gp = 0;
-            for (auto &j : c->h_gens[g]) gp += (uint64_t)j.cw * j.ch;
-            if (c->h_gens[g].size() > (size_t)HT_TAIL_MAX_JOBS || px + gp > tail_cap) break;
-            px += gp;
-            g0 = g;
-        }
-        if (ngen - g0 >= 2 && ngen - g0 <= HT_TAIL_MAX_GENS) {
-            std::vector<HtResampleJob> tj;
-            std::vector<uint32_t> pref;
-            HtTailGens &T = c->h_tail;
-            std::memset(&T, 0, sizeof(T));
-            T.ngen = ngen - g0;
-            for (int g = g0; g < ngen; g++) {
-                T.job_begin[g - g0] = (int32_t)tj.size();
-                uint32_t groups = 0;
-                for (auto &j : c->h_gens[g]) {
-                    tj.push_back(j);
-                    pref.push_back(groups);
-                    groups += (uint32_t)((j.cw + 3) / 4) * (uint32_t)j.ch;
-                }
-                T.groups[g - g0] = groups;
-            }
-            T.job_begin[T.ngen] = (int32_t)tj.size();
-            if (!tj.empty()) {
-                HT_HIP(c, hipMalloc(&c->d_tail_jobs, tj.size() * sizeof(HtResampleJob)));
-                HT_HIP(c, hipMemcpy(c->d_tail_jobs, tj.data(), tj.size() * sizeof(HtResampleJob), hipMemcpyHostToDevice));
-                HT_HIP(c, hipMalloc(&c->d_tail_prefix, pref.size() * sizeof(uint32_t)));
-                HT_HIP(c, hipMemcpy(c->d_tail_prefix, pref.data(), pref.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-                // tap tables: the geometry is the same for every frame, so the taps are computed once here
-                std::vector<HtTap> taps;
-                std::vector<HtTapFast> fast;
-                std::vector<HtTailTapRef> refs;
-                const bool nofast = c->rs_nofast;
-                size_t jidx = 0;
-                for (auto &j : tj) {
-                    for (int g = 0; g <= T.ngen; g++)
-                        if ((size_t)T.job_begin[g] == jidx) T.tap_begin[g] = (uint32_t)taps.size();
-                    jidx++;
-                    HtTailTapRef r;
-                    r.col = (uint32_t)taps.size();
-                    const int ncol = std::max(j.dw, 1), nrow = std::max(j.dh, 1);
-                    for (int i = 0; i < ncol + 3; i++) taps.push_back(ht_host_tap(std::min(i, ncol - 1), j.rx, j.sw, j.sx));
-                    r.row = (uint32_t)taps.size();
-                    for (int i = 0; i < nrow; i++) taps.push_back(ht_host_tap(i, j.ry, j.sh, j.sy));
-                    r.mode = nofast ? 2u : ((j.dw > 0 && j.sw == 2 * j.dw && j.sh == 2 * j.dh) ? 1u : 0u);
-                    r.pad = 0;
-                    refs.push_back(r);
-                }
-                T.tap_begin[T.ngen] = (uint32_t)taps.size();
-                fast.resize(taps.size());
-                for (size_t i = 0; i < taps.size(); i++) fast[i].a = taps[i].a, fast[i].tf = (float)taps[i].t;
-                HT_HIP(c, hipMalloc(&c->d_tail_taps, taps.size() * sizeof(HtTap)));
-                HT_HIP(c, hipMemcpy(c->d_tail_taps, taps.data(), taps.size() * sizeof(HtTap), hipMemcpyHostToDevice));
-                HT_HIP(c, hipMalloc(&c->d_tail_taps_fast, fast.size() * sizeof(HtTapFast)));
-                HT_HIP(c, hipMemcpy(c->d_tail_taps_fast, fast.data(), fast.size() * sizeof(HtTapFast), hipMemcpyHostToDevice));
-                HT_HIP(c, hipMalloc(&c->d_tail_tapref, refs.size() * sizeof(HtTailTapRef)));
-                HT_HIP(c, hipMemcpy(c->d_tail_tapref, refs.data(), refs.size() * sizeof(HtTailTapRef), hipMemcpyHostToDevice));
-                c->tail_first_gen = g0;
-            }
-        }
-    }
-
-    ht_status st = ht_scan_plan_tiles(c);
-    if (st != HT_OK) return st;
-    // early scan plan: scale i needs levels i, i + next, i + 2 next; the leading scales whose last plane is finished after
-    // generation 2 (interval 5: scale 0 = ~30 % of the windows) can start while generations 3.. are still being built
-    c->early_gen = 0;
-    c->early_tiles = 0;
-    if (c->early_scan && c->aux_stream && ngen > 3 && (c->tail_first_gen == 0 || c->tail_first_gen > 2)) {
-        uint32_t tiles = 0;
-        for (auto &S : c->h_scales) {
-            if (gen[S.l2] > 2) break;
-            tiles += (uint32_t)(S.ntx * S.nty);
-        }
-        if (tiles > 0 && tiles < c->tiles_per_frame) c->early_gen = 2, c->early_tiles = tiles;
-    }
-
-    // survivor queue between the tile kernel and the deep kernel: 1/8 of all windows unless configured
-    uint64_t qc = c->queue_capacity_cfg ? c->queue_capacity_cfg : std::max<uint64_t>(1u << 16, c->windows_per_frame * (uint64_t)max_batch / 8);
-    qc = std::min<uint64_t>(qc, 1ull << 28);
-    c->queue_capacity = (uint32_t)qc;
-    if (hipMalloc(&c->d_queue, (size_t)qc * sizeof(HtQueueEntry) + HT_DEEP_CTR_BYTES) != hipSuccess)  // + the deep kernel's work counters
+    HT_HIP(c, hipMemset(c->d_arena, 0, P.arena_stride * (uint64_t)max_batch));
+    if ((st = upload_table(c, c->d_tail_jobs, P.tail_jobs)) != HT_OK || (st = upload_table(c, c->d_tail_prefix, P.tail_prefix)) != HT_OK ||
+        (st = upload_table(c, c->d_tail_taps, P.tail_taps)) != HT_OK || (st = upload_table(c, c->d_tail_taps_fast, P.tail_taps_fast)) != HT_OK ||
+        (st = upload_table(c, c->d_tail_tapref, P.tail_tapref)) != HT_OK || (st = upload_table(c, c->d_tile_recs, P.tile_recs)) != HT_OK ||
+        (st = upload_table(c, c->d_scales, P.scales)) != HT_OK)
+        return st;
+    if (hipMalloc(&c->d_queue, (size_t)P.queue_capacity * sizeof(HtQueueEntry) + HT_DEEP_CTR_BYTES) != hipSuccess)  // + the deep kernel's work counters
         return ht_fail(c, HT_ERR_NOMEM, "ht_set_geometry: hipMalloc(survivor queue) failed");
     return HT_OK;
 }
@@ -863,12 +629,12 @@ extern "C" ht_status ht_set_geometry(ht_ctx *c, int32_t width, int32_t height, i
 }
 
 extern "C" int32_t ht_num_levels(const ht_ctx *c) { return c ? c->nlevels : 0; }
-extern "C" uint64_t ht_windows_per_frame(const ht_ctx *c) { return c ? c->windows_per_frame : 0; }
-extern "C" uint64_t ht_pyramid_bytes_per_frame(const ht_ctx *c) { return c ? c->pyr_bytes : 0; }
+extern "C" uint64_t ht_windows_per_frame(const ht_ctx *c) { return c ? c->plan.windows_per_frame : 0; }
+extern "C" uint64_t ht_pyramid_bytes_per_frame(const ht_ctx *c) { return c ? c->plan.pyr_bytes : 0; }
 
 extern "C" ht_status ht_plane(const ht_ctx *c, int32_t level, int32_t slot, ht_plane_info *out) {
     if (!c || !out || level < 0 || level >= c->nlevels || slot < 0 || slot > 3) return HT_ERR_INVALID;
-    const HtDevLevel &L = c->h_levels[level];
+    const HtDevLevel &L = c->plan.levels[level];
     out->width = L.w;
     out->height = L.h;
     out->stride = L.stride;
@@ -1298,13 +1064,13 @@ extern "C" ht_status ht_pyramid_readback(ht_ctx *c, int32_t frame, int32_t level
     if (!c || !out) return HT_ERR_INVALID;
     if (frame < 0 || frame >= c->max_batch || level < 0 || level >= c->nlevels || slot < 0 || slot > 3)
         return ht_fail(c, HT_ERR_INVALID, "ht_pyramid_readback: index out of range");
-    const HtDevLevel &L = c->h_levels[level];
+    const HtDevLevel &L = c->plan.levels[level];
     if (L.off[slot] == 0xffffffffu) return ht_fail(c, HT_ERR_INVALID, "ht_pyramid_readback: plane does not exist");
     if (cap < (size_t)L.w * L.h) return ht_fail(c, HT_ERR_CAPACITY, "ht_pyramid_readback: buffer too small");
     if (L.w == 0 || L.h == 0) return HT_OK;
     HT_HIP(c, hipSetDevice(c->device));
     HT_HIP(c, hipStreamSynchronize(c->stream));
-    HT_HIP(c, hipMemcpy2D(out, L.w, c->d_arena + (uint64_t)frame * c->arena_stride + L.off[slot], L.stride, L.w, L.h, hipMemcpyDeviceToHost));
+    HT_HIP(c, hipMemcpy2D(out, L.w, c->d_arena + (uint64_t)frame * c->plan.arena_stride + L.off[slot], L.stride, L.w, L.h, hipMemcpyDeviceToHost));
     return HT_OK;
 }
 

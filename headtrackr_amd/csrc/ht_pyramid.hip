@@ -253,7 +253,7 @@ __device__ unsigned long long g_rs_timeline[1 << 16][8];
 #define RS_WSTAMP(i)
 #endif
 // One workgroup = one tile record x one group of K consecutive frames.  A tile is 64 columns x (16 * np) rows of one
-// drawImage call, np <= RPT passes chosen per tile by the host (ht_context.hip) so that (a) a level's rows are split
+// drawImage call, np <= RPT passes chosen per tile by the host (ht_geometry_plan.h) so that (a) a level's rows are split
 // evenly — 214 rows are 4 + 4 + 3 + 3 passes, not 4 x 4 with the last tile a third empty — and (b) the source rows the
 // tile touches fit the fixed HT_RS_SRC_ROWS-row LDS window (np = 4 at ratio 1.12, 2 at ratio 2).
 //
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(256, RS_WPS) void k_resample(const HtResampleJob *_
     int xa = 0, ya = 0, sw16 = 1, sh = 1;
     bool in_lds = false;
     if (drawn) {
-        if (J.ex_sw16 > 0) {  // from the host (ht_context.hip)
+        if (J.ex_sw16 > 0) {  // from the host (ht_geometry_plan.h)
             xa = J.ex_xa, ya = J.ex_ya, sw16 = J.ex_sw16, sh = J.ex_sh;
         } else {
             xa = rs_tap(X0, J.rx, J.sw, J.sx).a & ~15;
@@ -589,7 +589,7 @@ __global__ __launch_bounds__(256, RS_WPS) void k_resample(const HtResampleJob *_
 // M0 = the band's LDS address; lanes outside the band are masked off) — no staging registers, no ds_write — and nobody else ever reads it:
 // the frame loop has NO workgroup barrier, a wavefront only waits for its own loads (s_waitcnt vmcnt) while the CU's other wavefronts
 // compute.  16 KB of bands + 3 KB of tap tables per workgroup and <= 64 VGPRs: 8 workgroups per CU (k_resample: 7 by registers).
-// The host fills in each tile record's band extents (ht_context.hip, the binary64 operations of rs_tap); a tile whose bands do not fit takes
+// The host fills in each tile record's band extents (ht_geometry_plan.h, the binary64 operations of rs_tap); a tile whose bands do not fit takes
 // the HBM-tap path exactly like k_resample's.
 constexpr int RSB_WPS = 8;
 constexpr int RSB_BAND = 4096;  // LDS bytes per wavefront = four 1 KB LDS-DMA instructions = 25.6 rows of RS_SP bytes
@@ -849,7 +849,7 @@ constexpr int TAIL_SMALL_WPS = 8;  // waves per SIMD the small-footprint tail le
 // used to spend ~135 binary64 instructions per group of 4 pixels on re-deriving taps and on the lerps.
 // LDS_TAPS = false (round 5, option rs_tailtable=2): the compact taps stay in global memory (a few KB per geometry, L1 / L2 resident) and
 // the register allocator leaves room for WPS waves per SIMD — the small-footprint form for batches that cover the chip, where the
-// 35 KB / 68-VGPR form keeps the other batches' kernels off every CU (see the tail plan in ht_context.hip).
+// 35 KB / 68-VGPR form keeps the other batches' kernels off every CU (see the tail plan in ht_geometry_plan.h).
 template <bool LDS_TAPS, int WPS>
 __global__ __launch_bounds__(TAIL_NT, WPS) void k_resample_tail(const HtResampleJob *__restrict__ jobs, const uint32_t *__restrict__ prefix,
                                                           const HtTailTapRef *__restrict__ tapref, const HtTapFast *__restrict__ tfast,
@@ -1066,7 +1066,7 @@ __global__ __launch_bounds__(256) void k_channel_sums(const uint8_t *__restrict_
 
 ht_status ht_launch_pyramid(ht_ctx *c, uint32_t flags) {
     const bool gray_in_r = (flags & HT_INPUT_GRAY_IN_R) != 0;
-    const HtDevLevel &L0 = c->h_levels[0];
+    const HtDevLevel &L0 = c->plan.levels[0];
     {
         HtProfScope ps(c, "gray");
         if ((c->W & 3) == 0) {
@@ -1075,7 +1075,7 @@ ht_status ht_launch_pyramid(ht_ctx *c, uint32_t flags) {
             dim3 grid((bpf * (uint32_t)c->nframes + 7u) & ~7u);
             unsigned long long *wb = c->wb_fused ? reinterpret_cast<unsigned long long *>(c->d_scratch) : nullptr;
 #define HT_GRAY_LAUNCH(G, W_)                                                                                                          \
-    hipLaunchKernelGGL((k_gray_linear<G, W_>), grid, dim3(256), 0, c->stream, c->d_frames, c->frame_stride, c->d_arena, c->arena_stride, \
+    hipLaunchKernelGGL((k_gray_linear<G, W_>), grid, dim3(256), 0, c->stream, c->d_frames, c->frame_stride, c->d_arena, c->plan.arena_stride, \
                        L0.off[0], ngroups, bpf, (uint32_t)c->nframes, wb)
             if (gray_in_r) {
                 if (wb) HT_GRAY_LAUNCH(true, true);
@@ -1089,17 +1089,17 @@ ht_status ht_launch_pyramid(ht_ctx *c, uint32_t flags) {
             dim3 grid((L0.stride / 4 + 63) / 64, (c->H + 3) / 4, c->nframes);
             if (gray_in_r)
                 hipLaunchKernelGGL(k_gray_rows<true>, grid, dim3(64, 4), 0, c->stream, c->d_frames, c->frame_stride, c->d_arena,
-                                   c->arena_stride, L0.off[0], c->W, c->H, L0.stride);
+                                   c->plan.arena_stride, L0.off[0], c->W, c->H, L0.stride);
             else
                 hipLaunchKernelGGL(k_gray_rows<false>, grid, dim3(64, 4), 0, c->stream, c->d_frames, c->frame_stride, c->d_arena,
-                                   c->arena_stride, L0.off[0], c->W, c->H, L0.stride);
+                                   c->plan.arena_stride, L0.off[0], c->W, c->H, L0.stride);
         }
         HT_HIP(c, hipGetLastError());
     }
-    const size_t regular_end = c->tail_first_gen > 0 ? (size_t)c->tail_first_gen : c->h_gens.size();
+    const size_t regular_end = c->plan.tail_first_gen > 0 ? (size_t)c->plan.tail_first_gen : c->plan.gens.size();
     const int dbg_maxgen = c->rs_maxgen;  // 1 << 30 unless a -DHT_DEBUG_KNOBS build was told otherwise (results stale: what do the later generations cost the wall clock?)
     for (size_t g = 1; g < regular_end; g++) {
-        if (c->gen_blocks[g] == 0 || (int)g > dbg_maxgen) continue;
+        if (c->plan.gen_blocks[g] == 0 || (int)g > dbg_maxgen) continue;
         char gname[24];
         std::snprintf(gname, sizeof(gname), "resample_g%d", (int)g);
         HtProfScope ps(c, c->rs_gennames ? gname : "resample");  // option rs_gennames: device time per pyramid generation
@@ -1107,35 +1107,35 @@ ht_status ht_launch_pyramid(ht_ctx *c, uint32_t flags) {
         // straddle the 8 XCD shares of the batch when the batch is a multiple of 8 * K
         uint32_t K = 1;
         const uint32_t kmax = (uint32_t)((!c->rs_group_forced && (int64_t)c->W * c->H >= 400000) ? std::min(c->rs_group, 4) : c->rs_group);
-        while (K * 2 <= kmax && (uint64_t)c->gen_blocks[g] * ((uint32_t)c->nframes / (K * 2)) >= (uint64_t)c->rs_min_wgs &&
+        while (K * 2 <= kmax && (uint64_t)c->plan.gen_blocks[g] * ((uint32_t)c->nframes / (K * 2)) >= (uint64_t)c->rs_min_wgs &&
                (uint32_t)c->nframes % (K * 2 * 8) == 0)
             K *= 2;
         if (c->dbg_rs_k > 0) K = (uint32_t)std::min(c->dbg_rs_k, std::max(1, c->nframes));  // option rs_k: measurement knob
         const uint32_t ngroups = ((uint32_t)c->nframes + K - 1) / K;
-        const dim3 rgrid((c->gen_blocks[g] * ngroups + 7u) & ~7u);
+        const dim3 rgrid((c->plan.gen_blocks[g] * ngroups + 7u) & ~7u);
         if (c->rs_bands)
-            hipLaunchKernelGGL(k_resample_bands<HT_RS_MAX_PASSES>, rgrid, dim3(256), 0, c->stream, c->d_gen_blocks[g], c->d_arena, c->arena_stride,
-                               c->gen_blocks[g], ngroups, (uint32_t)c->nframes, K);
+            hipLaunchKernelGGL(k_resample_bands<HT_RS_MAX_PASSES>, rgrid, dim3(256), 0, c->stream, c->d_gen_blocks[g], c->d_arena, c->plan.arena_stride,
+                               c->plan.gen_blocks[g], ngroups, (uint32_t)c->nframes, K);
         else
-            hipLaunchKernelGGL(k_resample<HT_RS_MAX_PASSES>, rgrid, dim3(256), 0, c->stream, c->d_gen_blocks[g], c->d_arena, c->arena_stride,
-                               c->gen_blocks[g], ngroups, (uint32_t)c->nframes, K);
+            hipLaunchKernelGGL(k_resample<HT_RS_MAX_PASSES>, rgrid, dim3(256), 0, c->stream, c->d_gen_blocks[g], c->d_arena, c->plan.arena_stride,
+                               c->plan.gen_blocks[g], ngroups, (uint32_t)c->nframes, K);
         HT_HIP(c, hipGetLastError());
-        if ((int)g == c->early_gen && c->early_gen > 0) {  // the early scales' planes are complete: their scan starts on the second stream
+        if ((int)g == c->plan.early_gen && c->plan.early_gen > 0) {  // the early scales' planes are complete: their scan starts on the second stream
             ht_status st = ht_launch_scan_early(c, flags);
             if (st != HT_OK) return st;
         }
     }
-    if (c->tail_first_gen > 0 && c->tail_first_gen <= dbg_maxgen) {
+    if (c->plan.tail_first_gen > 0 && c->plan.tail_first_gen <= dbg_maxgen) {
         HtProfScope ps(c, c->rs_gennames ? "resample_tail" : "resample");
-        if (c->tail_table == 2)
+        if (c->plan.tail_table == 2)
             hipLaunchKernelGGL((k_resample_tail<false, TAIL_SMALL_WPS>), dim3(((uint32_t)c->nframes + 7u) & ~7u), dim3(TAIL_NT), 0, c->stream, c->d_tail_jobs,
-                               c->d_tail_prefix, c->d_tail_tapref, c->d_tail_taps_fast, c->d_tail_taps, c->h_tail, c->d_arena, c->arena_stride, (uint32_t)c->nframes);
-        else if (c->tail_table)
+                               c->d_tail_prefix, c->d_tail_tapref, c->d_tail_taps_fast, c->d_tail_taps, c->plan.tail, c->d_arena, c->plan.arena_stride, (uint32_t)c->nframes);
+        else if (c->plan.tail_table)
             hipLaunchKernelGGL((k_resample_tail<true, 4>), dim3(((uint32_t)c->nframes + 7u) & ~7u), dim3(TAIL_NT), 0, c->stream, c->d_tail_jobs, c->d_tail_prefix,
-                               c->d_tail_tapref, c->d_tail_taps_fast, c->d_tail_taps, c->h_tail, c->d_arena, c->arena_stride, (uint32_t)c->nframes);
+                               c->d_tail_tapref, c->d_tail_taps_fast, c->d_tail_taps, c->plan.tail, c->d_arena, c->plan.arena_stride, (uint32_t)c->nframes);
         else
             hipLaunchKernelGGL(k_resample_tail_f64, dim3(((uint32_t)c->nframes + 7u) & ~7u), dim3(TAILF_NT), 0, c->stream, c->d_tail_jobs, c->d_tail_prefix,
-                               c->h_tail, c->d_arena, c->arena_stride, (uint32_t)c->nframes);
+                               c->plan.tail, c->d_arena, c->plan.arena_stride, (uint32_t)c->nframes);
         HT_HIP(c, hipGetLastError());
     }
     return HT_OK;

@@ -1,5 +1,5 @@
 // ht_resample_tap.h — the tap of the declared resampler (oracle/canvas_shim.js) on the device, shared by the translation units that
-// evaluate it: the pyramid (ht_pyramid.hip) and the video -> canvas draw (ht_ingest.hip).  The host form is ht_host_tap (ht_context.hip):
+// evaluate it: the pyramid (ht_pyramid.hip) and the video -> canvas draw (ht_ingest.hip).  The host form is ht_host_tap (ht_geometry_plan.h):
 // the same binary64 operations in the same order.
 #pragma once
 

@@ -34,8 +34,8 @@
 namespace {
 
 // tile geometry (window = 24x24, see ht_scan_tile_tables for the check)
-constexpr int TXH = 64;                 // tile width  in half-window steps X'
-constexpr int TYH = 32;                 // tile height in half-window steps Y'
+constexpr int TXH = HT_SCAN_TXH;        // tile width  in half-window steps X' (ht_plan_types.h: the planner cuts the scales by it)
+constexpr int TYH = HT_SCAN_TYH;        // tile height in half-window steps Y'
 constexpr int NT = 256;                 // threads per workgroup (256: 4 waves/SIMD at <=128 VGPRs; 512: 8 waves/SIMD at <=64)
 // waves per SIMD the register allocator must leave room for: 6 workgroups per CU (80 VGPRs, no spills; 26.4 KB of LDS each now that the
 // survivor queue lives in the unused tails of the plane-1/2 rows).  Measured: 4 -> 5 workgroups -15 %, 5 -> 6 another -7 % (C2) / -6 % (C4)
@@ -1340,72 +1340,6 @@ bool ht_scan_is_builtin_cascade(const uint8_t *blob, size_t len) {
     return h == HT_GEN_CASCADE_FNV;
 }
 
-ht_status ht_scan_plan_tiles(ht_ctx *c) {
-    c->h_scales.clear();
-    c->windows_per_frame = 0;
-    uint32_t tiles = 0;
-    for (int i = 0; i < c->upto; i++) {  // ccv.js:154
-        HtScanScale S;
-        std::memset(&S, 0, sizeof(S));
-        S.l0 = i;
-        S.l1 = i + c->next;
-        S.l2 = i + 2 * c->next;
-        S.qw = c->h_levels[S.l2].w - (int)(c->cw / 4);  // ccv.js:155
-        S.qh = c->h_levels[S.l2].h - (int)(c->ch / 4);  // ccv.js:156
-        if (S.qw <= 0 || S.qh <= 0) continue;
-        S.ntx = (2 * S.qw + TXH - 1) / TXH;
-        S.tw2 = (2 * S.qw + S.ntx - 1) / S.ntx;
-        S.tw2 = (S.tw2 + 7) & ~7;  // multiple of 8 half-steps: tile rows start on 16 / 8 / 4-byte boundaries of the three planes' rows
-        S.nty = (2 * S.qh + TYH - 1) / TYH;
-        S.th2 = (2 * S.qh + S.nty - 1) / S.nty;
-        S.th2 += S.th2 & 1;
-        S.ntx = (2 * S.qw + S.tw2 - 1) / S.tw2;
-        S.nty = (2 * S.qh + S.th2 - 1) / S.th2;
-        S.tile_begin = tiles;
-        S.div_magic = ((1u << 20) + (uint32_t)S.tw2 - 1) / (uint32_t)S.tw2;
-        if (c->windows_per_frame + 4ull * S.qw * S.qh > 0xffffffffull) return ht_fail(c, HT_ERR_INVALID, "frame too large");
-        S.win_begin = (uint32_t)c->windows_per_frame;
-        tiles += (uint32_t)(S.ntx * S.nty);
-        c->windows_per_frame += 4ull * (uint64_t)S.qw * (uint64_t)S.qh;
-        c->h_scales.push_back(S);
-    }
-    c->tiles_per_frame = tiles;
-    if (!c->h_scales.empty()) {
-        std::vector<HtTileRec> recs;
-        for (const HtScanScale &S : c->h_scales) {
-            const HtDevLevel &A = c->h_levels[S.l0], &B = c->h_levels[S.l1], &Cq = c->h_levels[S.l2];
-            if (A.stride > 0xffff || A.h > 0xffff) return ht_fail(c, HT_ERR_INVALID, "frame too large");
-            for (int y = 0; y < S.nty; y++)
-                for (int x = 0; x < S.ntx; x++) {
-                    HtTileRec r;
-                    std::memset(&r, 0, sizeof(r));
-                    const int X0 = x * S.tw2, Y0 = y * S.th2;
-                    r.off0 = A.off[0], r.off1 = B.off[0];
-                    for (int q = 0; q < 4; q++) r.off2[q] = Cq.off[q];
-                    r.sh0 = (uint32_t)A.stride | (uint32_t)A.h << 16;
-                    r.sh1 = (uint32_t)B.stride | (uint32_t)B.h << 16;
-                    r.sh2 = (uint32_t)Cq.stride | (uint32_t)Cq.h << 16;
-                    r.origin = (uint32_t)X0 | (uint32_t)Y0 << 16;
-                    r.size = (uint32_t)std::min(S.tw2, 2 * S.qw - X0) | (uint32_t)std::min(S.th2, 2 * S.qh - Y0) << 16;
-                    r.tw2_l0 = (uint32_t)S.tw2 | (uint32_t)S.l0 << 16;
-                    r.div_magic = S.div_magic;
-                    {  // n / (4 * th) == (n * magic) >> 24 for every pair index n of the tile (n <= 1024, 4 * th <= 128: error term n * 127 < 2^24 / 128); checked anyway
-                        const uint32_t th = r.size >> 16, d = 4u * th;
-                        r.strip_magic = ((1u << 24) + d - 1u) / d;
-                        for (uint32_t n = 0; n < (uint32_t)(S.tw2 / 2) * th; n++)
-                            if (((n * r.strip_magic) >> 24) != n / d) return ht_fail(c, HT_ERR_INVALID, "tile plan: strip_magic is not exact");
-                    }
-                    recs.push_back(r);
-                }
-        }
-        HT_HIP(c, hipMalloc(&c->d_tile_recs, recs.size() * sizeof(HtTileRec)));
-        HT_HIP(c, hipMemcpy(c->d_tile_recs, recs.data(), recs.size() * sizeof(HtTileRec), hipMemcpyHostToDevice));
-        HT_HIP(c, hipMalloc(&c->d_scales, c->h_scales.size() * sizeof(HtScanScale)));
-        HT_HIP(c, hipMemcpy(c->d_scales, c->h_scales.data(), c->h_scales.size() * sizeof(HtScanScale), hipMemcpyHostToDevice));
-    }
-    return HT_OK;
-}
-
 // tile kernel over tiles [first, first + count) of every frame's tile list, on `stream`
 static ht_status launch_tiles(ht_ctx *c, uint32_t flags, hipStream_t stream, uint32_t first, uint32_t count) {
     unsigned long long *stats = (flags & HT_SCAN_STATS) ? c->d_stats : nullptr;
@@ -1419,13 +1353,13 @@ static ht_status launch_tiles(ht_ctx *c, uint32_t flags, hipStream_t stream, uin
     const int stop_stage = c->dbg_stop_stage, force_exact = c->dbg_force_exact;
     HtProfScope ps(c, "scan_tiles", stream);
     if (gen)
-        hipLaunchKernelGGL(k_scan_tiles<true>, dim3((total + 7u) & ~7u), dim3(NT), 0, stream, c->d_arena, c->arena_stride,
+        hipLaunchKernelGGL(k_scan_tiles<true>, dim3((total + 7u) & ~7u), dim3(NT), 0, stream, c->d_arena, c->plan.arena_stride,
                            c->d_tile_recs + first, c->d_tile_feats, c->fp_sparse ? c->d_fp_feats : nullptr, c->d_stages, (int)c->nstages, split, c->deep_bias, stop_stage, force_exact, count, total,
-                           c->d_queue, c->queue_capacity, c->d_hits, c->hit_capacity, c->d_counters, stats);
+                           c->d_queue, c->plan.queue_capacity, c->d_hits, c->hit_capacity, c->d_counters, stats);
     else
-        hipLaunchKernelGGL(k_scan_tiles<false>, dim3((total + 7u) & ~7u), dim3(NT), 0, stream, c->d_arena, c->arena_stride,
+        hipLaunchKernelGGL(k_scan_tiles<false>, dim3((total + 7u) & ~7u), dim3(NT), 0, stream, c->d_arena, c->plan.arena_stride,
                            c->d_tile_recs + first, c->d_tile_feats, c->fp_sparse ? c->d_fp_feats : nullptr, c->d_stages, (int)c->nstages, split, c->deep_bias, stop_stage, force_exact, count, total,
-                           c->d_queue, c->queue_capacity, c->d_hits, c->hit_capacity, c->d_counters, stats);
+                           c->d_queue, c->plan.queue_capacity, c->d_hits, c->hit_capacity, c->d_counters, stats);
     HT_HIP(c, hipGetLastError());
     return HT_OK;
 }
@@ -1433,10 +1367,10 @@ static ht_status launch_tiles(ht_ctx *c, uint32_t flags, hipStream_t stream, uin
 // Called by ht_launch_pyramid right after the generation that completes the early scales' planes: their tiles are scanned on the
 // second stream while the main stream builds the remaining small generations (which are latency-, not throughput-bound).
 ht_status ht_launch_scan_early(ht_ctx *c, uint32_t flags) {
-    if (c->early_tiles == 0 || !c->aux_stream || (flags & HT_SCAN_SIMPLE) || c->cw != 24 || c->ch != 24) return HT_OK;
+    if (c->plan.early_tiles == 0 || !c->aux_stream || (flags & HT_SCAN_SIMPLE) || c->cw != 24 || c->ch != 24) return HT_OK;
     HT_HIP(c, hipEventRecord(c->ev_early_ready, c->stream));
     HT_HIP(c, hipStreamWaitEvent(c->aux_stream, c->ev_early_ready, 0));
-    ht_status st = launch_tiles(c, flags, c->aux_stream, 0, c->early_tiles);
+    ht_status st = launch_tiles(c, flags, c->aux_stream, 0, c->plan.early_tiles);
     if (st != HT_OK) return st;
     HT_HIP(c, hipEventRecord(c->ev_early_done, c->aux_stream));
     c->early_launched = true;
@@ -1444,15 +1378,15 @@ ht_status ht_launch_scan_early(ht_ctx *c, uint32_t flags) {
 }
 
 ht_status ht_launch_scan(ht_ctx *c, uint32_t flags) {
-    if (c->h_scales.empty() || c->tiles_per_frame == 0) return HT_OK;  // image too small for any window
-    const int nscales = (int)c->h_scales.size();
+    if (c->plan.scales.empty() || c->plan.tiles_per_frame == 0) return HT_OK;  // image too small for any window
+    const int nscales = (int)c->plan.scales.size();
     unsigned long long *stats = (flags & HT_SCAN_STATS) ? c->d_stats : nullptr;
     const bool tile_ok = (c->cw == 24 && c->ch == 24);
     if ((flags & HT_SCAN_SIMPLE) || !tile_ok) {
         HtProfScope ps(c, "scan_simple");
-        dim3 grid((uint32_t)((c->windows_per_frame + 255) / 256), c->nframes);
-        hipLaunchKernelGGL(k_scan_simple, grid, dim3(256), 0, c->stream, c->d_arena, c->arena_stride, c->d_levels, c->next, c->d_scales,
-                           nscales, (uint32_t)c->windows_per_frame, c->d_deep_feats, c->d_stages, (int)c->nstages, c->d_hits,
+        dim3 grid((uint32_t)((c->plan.windows_per_frame + 255) / 256), c->nframes);
+        hipLaunchKernelGGL(k_scan_simple, grid, dim3(256), 0, c->stream, c->d_arena, c->plan.arena_stride, c->d_levels, c->next, c->d_scales,
+                           nscales, (uint32_t)c->plan.windows_per_frame, c->d_deep_feats, c->d_stages, (int)c->nstages, c->d_hits,
                            c->hit_capacity, c->d_counters, stats);
         HT_HIP(c, hipGetLastError());
         return HT_OK;
@@ -1460,8 +1394,8 @@ ht_status ht_launch_scan(ht_ctx *c, uint32_t flags) {
     const int split = (flags & HT_SCAN_NO_SPLIT) ? (int)c->nstages : (int)std::min<uint32_t>(c->split_stage, c->nstages);
     const int force_exact = c->dbg_force_exact;
     {
-        const uint32_t first = c->early_launched ? c->early_tiles : 0u;
-        ht_status st = launch_tiles(c, flags, c->stream, first, c->tiles_per_frame - first);
+        const uint32_t first = c->early_launched ? c->plan.early_tiles : 0u;
+        ht_status st = launch_tiles(c, flags, c->stream, first, c->plan.tiles_per_frame - first);
         if (st != HT_OK) return st;
         if (c->early_launched) HT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_early_done, 0));  // the deep kernel needs every tile's survivors
     }
@@ -1483,12 +1417,12 @@ ht_status ht_launch_scan(ht_ctx *c, uint32_t flags) {
             // every one of the HT_DEEP_CTRS work counters needs a wavefront that draws from it (entry nwaves + 16 k + c is only ever
             // handed out by counter c): a grid below 16 wavefronts (option deep_grid=1) would silently skip queue entries
             const uint32_t deep_grid = std::max<uint32_t>((uint32_t)c->deep_grid, (HT_DEEP_CTRS + DEEPL_WAVES - 1) / DEEPL_WAVES);
-            hipLaunchKernelGGL(k_scan_deep_lds, dim3(deep_grid), dim3(64 * DEEPL_WAVES), lds, c->stream, c->d_arena, c->arena_stride, c->d_levels, c->next,
-                               c->d_packed_feats, c->packed_count, c->packed_first, c->d_stages, (int)c->nstages, force_exact, c->d_queue, c->queue_capacity,
+            hipLaunchKernelGGL(k_scan_deep_lds, dim3(deep_grid), dim3(64 * DEEPL_WAVES), lds, c->stream, c->d_arena, c->plan.arena_stride, c->d_levels, c->next,
+                               c->d_packed_feats, c->packed_count, c->packed_first, c->d_stages, (int)c->nstages, force_exact, c->d_queue, c->plan.queue_capacity,
                                c->d_hits, c->hit_capacity, c->d_counters, stats);
         } else
-        hipLaunchKernelGGL(k_scan_deep, dim3(2048), dim3(64 * DEEP_WAVES), 0, c->stream, c->d_arena, c->arena_stride, c->d_levels, c->next,
-                           c->d_patch_feats, c->d_stages, (int)c->nstages, c->decimal_alphas ? (force_exact ? 2 : 1) : 0, c->d_queue, c->queue_capacity, c->d_hits,
+        hipLaunchKernelGGL(k_scan_deep, dim3(2048), dim3(64 * DEEP_WAVES), 0, c->stream, c->d_arena, c->plan.arena_stride, c->d_levels, c->next,
+                           c->d_patch_feats, c->d_stages, (int)c->nstages, c->decimal_alphas ? (force_exact ? 2 : 1) : 0, c->d_queue, c->plan.queue_capacity, c->d_hits,
                            c->hit_capacity, c->d_counters, stats);
         HT_HIP(c, hipGetLastError());
     }

@@ -4,7 +4,7 @@
 Levels >= upto and all 81 variant canvases are never a plane 0: they exist only as plane 1 / plane 2 of some scale.  k_scan_tiles holds
 a scale's plane-0 tile in LDS, so its plane-1 cells (level i + 6 = resample of level i) and the four plane-2 variants (level i + 12 =
 resample of level i + 6 shifted by (dx, dy)) could be built during staging and the pyramid would stop building them.  This script
-counts, with the library's own geometry and tile plan (ht_context.hip set_geometry_impl, ht_scan.hip ht_scan_plan_tiles restated), the
+counts, with the library's own geometry and tile plan (ht_geometry_plan.h ht_plan_geometry restated), the
 pixels either side and prices them with the measured instruction figures of the round (PMC, wave instructions):
 
   * pyramid pixels that would no longer be built (variants + levels that are never a plane 0), at k_resample_bands' measured VALU
