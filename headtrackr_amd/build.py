@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libheadtrackr_hip.so")
 ADDON = os.path.join(HERE, "js", "headtrackr_hip.node")
 
-HIP_SOURCES = ["ht_context.hip", "ht_pyramid.hip", "ht_scan.hip", "ht_camshift.hip", "ht_backproject.hip"]
+HIP_SOURCES = ["ht_context.hip", "ht_pyramid.hip", "ht_scan.hip", "ht_camshift.hip", "ht_backproject.hip", "ht_allgather.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HIP_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",

@@ -135,21 +135,6 @@ __global__ __launch_bounds__(BP_NT) void k_bp_project(const uint8_t *__restrict_
     for (uint32_t i = beg + nquad * 4 + threadIdx.x; i < end; i += BP_NT) dst[i] = lut[cs_bin(img[i])];  // < 4 pixels
 }
 
-// scratch of this unit, grown on demand (a reallocation waits for the work in flight first, like every reallocation of the library)
-template <typename T>
-ht_status bp_grow(ht_ctx *c, T **p, size_t *cap, size_t need, const char *what) {
-    if (*cap >= need) return HT_OK;
-    HT_HIP(c, hipStreamSynchronize(c->stream));
-    if (*p) (void)hipFree(*p);
-    *p = nullptr, *cap = 0;
-    if (hipMalloc(reinterpret_cast<void **>(p), need * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        return ht_fail(c, HT_ERR_NOMEM, std::string("ht_camshift_backproject: hipMalloc failed (") + what + ")");
-    }
-    *cap = need;
-    return HT_OK;
-}
-
 size_t bp_elem(int32_t kind) { return kind == HT_BP_F64 ? sizeof(double) : sizeof(uint32_t); }
 
 // the checks both entry points share; *frame_bytes = bytes of one output frame, *stride = the effective output stride
@@ -170,9 +155,10 @@ ht_status bp_enqueue(ht_ctx *c, int32_t first, int32_t n, int32_t kind, void *d_
     if (npix == 0) return HT_OK;
     uint32_t chunk_px = 0, nchunks = 0;
     ht_cs_hist_plan(npix, n, &chunk_px, &nchunks);
-    ht_status st = bp_grow(c, &c->d_bp_hist, &c->bp_hist_cap, (size_t)n * nchunks * 4096, "chunk histograms");
-    if (st == HT_OK) st = bp_grow(c, &c->d_bp_lut_w, &c->bp_lut_w_cap, (size_t)n * 4096, "weight LUTs");
-    if (st == HT_OK) st = bp_grow(c, &c->d_bp_lut_px, &c->bp_lut_px_cap, (size_t)n * 4096, "pixel LUTs");
+    // scratch of this unit, grown on demand
+    ht_status st = ht_grow_device(c, &c->d_bp_hist, &c->bp_hist_cap, (size_t)n * nchunks * 4096, "ht_camshift_backproject: hipMalloc failed (chunk histograms)");
+    if (st == HT_OK) st = ht_grow_device(c, &c->d_bp_lut_w, &c->bp_lut_w_cap, (size_t)n * 4096, "ht_camshift_backproject: hipMalloc failed (weight LUTs)");
+    if (st == HT_OK) st = ht_grow_device(c, &c->d_bp_lut_px, &c->bp_lut_px_cap, (size_t)n * 4096, "ht_camshift_backproject: hipMalloc failed (pixel LUTs)");
     if (st != HT_OK) return st;
     {
         HtProfScope ps(c, "cs_bp_hist");
@@ -217,7 +203,7 @@ extern "C" ht_status ht_camshift_backproject(ht_ctx *c, int32_t first, int32_t n
     if (st != HT_OK) return st;
     if (frame_bytes == 0) return HT_OK;
     HT_HIP(c, hipSetDevice(c->device));
-    st = bp_grow(c, &c->d_bp_out, &c->bp_out_cap, (size_t)n * frame_bytes, "output staging");
+    st = ht_grow_device(c, &c->d_bp_out, &c->bp_out_cap, (size_t)n * frame_bytes, "ht_camshift_backproject: hipMalloc failed (output staging)");
     if (st != HT_OK) return st;
     st = bp_enqueue(c, first, n, kind, c->d_bp_out, frame_bytes);  // packed on the device; the caller's stride is applied by the copy
     if (st != HT_OK) return st;

@@ -25,9 +25,6 @@
 #include <string>
 #include <vector>
 
-#include <dlfcn.h>
-#include <rccl/rccl.h>  // types only: librccl.so is opened lazily (dlopen) the first time ht_allgather_records runs
-
 #include "ht_internal.h"
 
 namespace {
@@ -49,21 +46,7 @@ __device__ __forceinline__ int cs_slot_of(int, int s) { return s; }
 #define CS_HIST_FRAMES_PARAM
 #define CS_HIST_FRAME(y_) (y_)
 
-// Partial histograms per stream: enough chunks to put ~256 workgroups of 1024 threads on the chip (a single 1080p stream gets 127,
-// eight of them 32 each, a batch of >= 32 streams 8 each), each chunk >= 16384 pixels and a multiple of 4 * HIST_NT.  Round 5, same box,
-// the C5 track step of 8 / 1 feeds (tools/gpu_cs_step.py): 256 threads x ~1024 workgroups 39.1 / 27.8 us, 512 x 512: 36.5 / 24.6,
-// 1024 x 512: 36.4 / 24.2, 1024 x 256: 35.8 / 24.0 (a quarter of the chunk histograms to write and to sum), 8 loads in flight per
-// thread instead of 4: 39.4 / 26.8.
-constexpr int HIST_MAXCHUNKS = 128;
-constexpr int HIST_TARGET_WGS = 256;  // workgroups of a k_cs_hist launch, all streams together
-inline uint32_t hist_max_chunks(int nstreams) { return (uint32_t)std::min(HIST_MAXCHUNKS, std::max(8, HIST_TARGET_WGS / std::max(nstreams, 1))); }
-inline void hist_chunks(uint32_t npix, uint32_t max_chunks, uint32_t *chunk_px, uint32_t *nchunks) {
-    uint32_t n = std::min<uint32_t>((npix + 16383u) / 16384u, max_chunks);
-    n = std::max<uint32_t>(n, 1u);
-    const uint32_t q = 4u * HIST_NT;
-    *chunk_px = std::max<uint32_t>(((npix + n - 1) / n + q - 1) / q * q, q);
-    *nchunks = std::max<uint32_t>((npix + *chunk_px - 1) / *chunk_px, 1u);
-}
+// (the chunk plan of the histogram pass — HIST_MAXCHUNKS, hist_max_chunks, hist_chunks — and every workgroup size: ht_cs_schedule.h)
 
 #define CS_KERNELS_PART 1  // k_cs_init
 #include "ht_cs_kernels.inc"
@@ -116,16 +99,7 @@ __global__ __launch_bounds__(256) void k_cs_init_rows(const uint8_t *__restrict_
 // does the full-frame histogram in LDS, turns it into the weight LUT in place (no partial histograms through HBM, no second
 // launch) and runs the mean-shift loop.  Per stream and call the only memory traffic left is the frame itself (4*W*H, then the
 // window passes from L2), the model histogram (16 KB) and the state.
-constexpr int FUSED_NT = 1024;
-// The 1024-thread form owns its CU: 112 KB of LDS and 16 wavefronts x 122 VGPRs leave no room for anything else, so the track launches
-// of several contexts (and the detect kernels of their next batches) run strictly one after the other although a call is a bandwidth
-// phase (the frame streams through the histogram) followed by a latency phase (<= 10 dependent moment passes from LDS).  The
-// 512-thread form (round 5) is half of it — 8 wavefronts, <= 128 VGPRs, a 44 KB region: 77 KB of LDS — so TWO workgroups share a CU,
-// normally at different phases of their calls, or a workgroup shares it with another batch's detect kernels.  Its wavefronts play the
-// 16 of the large form in window_moments, so both forms return the same bits.  Chosen per launch (fused_threads below): more streams
-// than CUs, or more than one context of the device on this path.
-constexpr int FUSED_NT_SMALL = 512;
-constexpr int CS_REGION_CAP_SMALL = 22528;  // 44 KB: a 118 x 118 search window + 16 px of margin, or 150 x 150 without
+// FUSED_NT threads, or FUSED_NT_SMALL with a CS_REGION_CAP_SMALL region: two forms with the same bits, chosen per launch (ht_cs_schedule.h).
 
 // Up to CS_SEQ_MAX successive track() calls of every stream in ONE launch (ht_camshift_track_sequence): the frame batches of the calls
 // travel as kernel arguments, a workgroup walks its stream's calls in order.  The calls of a stream depend on each other through its
@@ -308,7 +282,7 @@ __global__ __launch_bounds__(NT, 4) void k_cs_track_fused(const CsFusedArgs args
 // counter, read the partials = three dependent L2 round trips, ~3 us per pass).  No agent-scope fences: every payload word is an
 // sc1 store on one side and an sc1 load on the other.  Every workgroup sums the G partials in the same order, so all of them take
 // identical mean-shift decisions; workgroup 0 writes the state.  The grid (streams x G <= 256 workgroups) is always co-resident: the spin cannot starve a workgroup that has not started.
-constexpr int CL_NT = 512, CL_MAXG = 32, CL_SLOTS = 12;  // <= 11 moment passes per call (camshift.js:284-306)
+// (CL_NT threads, <= CL_MAXG workgroups per stream, CL_SLOTS exchange slots: ht_cs_schedule.h)
 // "not written yet" mark of an exchange entry: a NaN no moment sum can be (the sums are finite and >= 0)
 constexpr unsigned long long CL_UNWRITTEN = 0xFFF8C0DEC0DE0001ull;
 
@@ -495,9 +469,8 @@ ClusterGate &cluster_gate() {
     return g;
 }
 
-}  // namespace
-// ht_destroy: the context stops counting as a user of its device's cluster gate (its stream has been synchronised)
-void ht_cluster_gate_forget(const ht_ctx *c) {
+// ht_camshift_free: the context stops counting as a user of its device's cluster gate (its stream has been synchronised)
+void cluster_gate_forget(const ht_ctx *c) {
     ClusterGate &gate = cluster_gate();
     std::lock_guard<std::mutex> lk(gate.mu);
     auto it = gate.dev.find(c->device);
@@ -511,6 +484,7 @@ void ht_cluster_gate_forget(const ht_ctx *c) {
         it->second.multi = false;
     }
 }
+}  // namespace
 // ht_detect_enqueue around its graph capture.  Setting the flag takes the gate's lock, and fused_threads() holds that lock across its
 // queries: a query of this context's stream either completed before the capture began or sees the flag and is skipped.
 void ht_capture_mark(ht_ctx *c, bool on) {
@@ -533,8 +507,7 @@ ht_status cs_check_err(ht_ctx *c, const char *where) {
 }
 }  // namespace
 
-// the histogram pass for callers outside this unit (ht_backproject.hip): host code only, the kernel stays here
-void ht_cs_hist_plan(uint32_t npix, int nstreams, uint32_t *chunk_px, uint32_t *nchunks) { hist_chunks(npix, hist_max_chunks(nstreams), chunk_px, nchunks); }
+// the histogram pass, also for callers outside this unit (ht_backproject.hip): host code only, the kernel stays here
 ht_status ht_cs_hist_launch(ht_ctx *c, const uint8_t *frames, size_t frame_stride, int n, uint32_t npix, uint32_t chunk_px, uint32_t nchunks, uint32_t *hist) {
     hipLaunchKernelGGL(k_cs_hist, dim3(nchunks, n), dim3(HIST_NT), 0, c->stream, frames, frame_stride, npix, chunk_px, hist);
     HT_HIP(c, hipGetLastError());
@@ -547,23 +520,19 @@ extern "C" ht_status ht_camshift_reserve(ht_ctx *c, int32_t nstreams) {
     if (c->cs_streams >= nstreams) return HT_OK;
     HT_HIP(c, hipStreamSynchronize(c->stream));
     // every new buffer first; the context only changes once all of them exist (a failed reservation keeps the old trackers usable)
-    const int ncl = std::min(nstreams, 64);  // the cluster path is only taken for <= 64 streams per call
+    const HtCsReserveSizes sz = ht_cs_reserve_sizes(nstreams);
     HtCsState *ns = nullptr;
     uint32_t *nhist = nullptr, *nerr = c->d_cs_err, *herr = c->h_cs_err;
     ht_cs_trackobj *nout = nullptr;
     double *nlut = nullptr, *nparts = nullptr;
-    bool ok = hipMalloc(&ns, sizeof(HtCsState) * (size_t)nstreams) == hipSuccess &&
-              hipMalloc(&nhist, sizeof(uint32_t) * 4096 * hist_max_chunks(nstreams) * (size_t)nstreams) == hipSuccess &&
-              hipMalloc(&nout, sizeof(ht_cs_trackobj) * (size_t)nstreams) == hipSuccess &&
-              // cluster mean-shift (few large streams): per stream a LUT and CL_SLOTS x CL_MAXG partial-sum slots
-              hipMalloc(&nlut, sizeof(double) * 4096 * (size_t)ncl) == hipSuccess &&
-              hipMalloc(&nparts, sizeof(double) * CL_SLOTS * CL_MAXG * 6 * (size_t)ncl) == hipSuccess;
-    if (ok && !nerr) ok = hipMalloc(&nerr, sizeof(uint32_t)) == hipSuccess && hipMemset(nerr, 0, sizeof(uint32_t)) == hipSuccess;
+    bool ok = hipMalloc(&ns, sz.states) == hipSuccess && hipMalloc(&nhist, sz.hist) == hipSuccess && hipMalloc(&nout, sz.out) == hipSuccess &&
+              hipMalloc(&nlut, sz.lut) == hipSuccess && hipMalloc(&nparts, sz.parts) == hipSuccess;
+    if (ok && !nerr) ok = hipMalloc(&nerr, sz.err_word) == hipSuccess && hipMemset(nerr, 0, sz.err_word) == hipSuccess;
     if (ok && !herr) {
-        ok = hipHostMalloc(reinterpret_cast<void **>(&herr), sizeof(uint32_t), hipHostMallocDefault) == hipSuccess;
+        ok = hipHostMalloc(reinterpret_cast<void **>(&herr), sz.err_word, hipHostMallocDefault) == hipSuccess;
         if (ok) *herr = 0;
     }
-    if (ok) ok = hipMemset(ns, 0, sizeof(HtCsState) * (size_t)nstreams) == hipSuccess;
+    if (ok) ok = hipMemset(ns, 0, sz.states) == hipSuccess;
     if (ok && c->d_cs)  // keep existing trackers
         ok = hipMemcpy(ns, c->d_cs, sizeof(HtCsState) * (size_t)c->cs_streams, hipMemcpyDeviceToDevice) == hipSuccess;
     if (!ok) {
@@ -590,28 +559,48 @@ extern "C" ht_status ht_camshift_reserve(ht_ctx *c, int32_t nstreams) {
     // result ring of the enqueue-only track calls (the stream was synchronised above: no slot is in use; uncollected results are dropped)
     c->cs_ring_head = c->cs_ring_count = 0;
     if (!c->h_cs_err_direct) {
-        if (hipHostMalloc(reinterpret_cast<void **>(&c->h_cs_err_direct), sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+        if (hipHostMalloc(reinterpret_cast<void **>(&c->h_cs_err_direct), sz.err_word, hipHostMallocDefault) != hipSuccess)
             return ht_fail(c, HT_ERR_NOMEM, "ht_camshift_reserve: hipHostMalloc failed");
         *c->h_cs_err_direct = 0;
     }
     for (auto &sl : c->cs_ring) {
         if (sl.h_out) (void)hipHostFree(sl.h_out);
         sl.h_out = nullptr;
-        if (hipHostMalloc(reinterpret_cast<void **>(&sl.h_out), sizeof(ht_cs_trackobj) * (size_t)nstreams, hipHostMallocDefault) != hipSuccess) {
+        if (hipHostMalloc(reinterpret_cast<void **>(&sl.h_out), sz.ring_out, hipHostMallocDefault) != hipSuccess) {
             c->cs_ring_streams = 0;
             return ht_fail(c, HT_ERR_NOMEM, "ht_camshift_reserve: hipHostMalloc failed");
         }
         if (!sl.ev && hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming) != hipSuccess) return ht_fail(c, HT_ERR_HIP, "ht_camshift_reserve: hipEventCreate failed");
         if (sl.h_flag) (void)hipHostFree(sl.h_flag);
         sl.h_flag = nullptr, sl.seq = 0;
-        if (hipHostMalloc(reinterpret_cast<void **>(&sl.h_flag), sizeof(uint32_t) * (size_t)nstreams, hipHostMallocDefault) != hipSuccess) {
+        if (hipHostMalloc(reinterpret_cast<void **>(&sl.h_flag), sz.ring_flags, hipHostMallocDefault) != hipSuccess) {
             c->cs_ring_streams = 0;
             return ht_fail(c, HT_ERR_NOMEM, "ht_camshift_reserve: hipHostMalloc failed");
         }
-        std::memset(sl.h_flag, 0, sizeof(uint32_t) * (size_t)nstreams);
+        std::memset(sl.h_flag, 0, sz.ring_flags);
     }
     c->cs_ring_streams = nstreams;
     return HT_OK;
+}
+
+void ht_camshift_free(ht_ctx *c) {  // ht_destroy (the stream has been synchronised)
+    if (c->d_cs_err) (void)hipFree(c->d_cs_err);
+    if (c->h_cs_err) (void)hipHostFree(c->h_cs_err);
+    if (c->h_cs_err_direct) (void)hipHostFree(c->h_cs_err_direct);
+    for (auto &sl : c->cs_ring) {
+        if (sl.h_out) (void)hipHostFree(sl.h_out);
+        if (sl.h_flag) (void)hipHostFree(sl.h_flag);
+        if (sl.ev) (void)hipEventDestroy(sl.ev);
+    }
+    cluster_gate_forget(c);
+    if (c->h_cs_rects) (void)hipHostFree(c->h_cs_rects);
+    if (c->ev_cs_rects) (void)hipEventDestroy(c->ev_cs_rects);
+    if (c->d_cs) (void)hipFree(c->d_cs);
+    if (c->d_cs_hist) (void)hipFree(c->d_cs_hist);
+    if (c->d_cs_out) (void)hipFree(c->d_cs_out);
+    if (c->d_cs_seq_out) (void)hipFree(c->d_cs_seq_out);
+    if (c->d_cs_lut) (void)hipFree(c->d_cs_lut);
+    if (c->d_cs_parts) (void)hipFree(c->d_cs_parts);
 }
 
 extern "C" ht_status ht_camshift_init_batch(ht_ctx *c, int32_t first, int32_t n, const ht_cs_rect *rects) {
@@ -642,13 +631,12 @@ extern "C" ht_status ht_camshift_init_batch(ht_ctx *c, int32_t first, int32_t n,
     HT_HIP(c, hipEventRecord(c->ev_cs_rects, c->stream));
     {
         HtProfScope ps(c, "cs_init");
-        // few streams with tall rects: rows spread over G workgroups per stream (one workgroup per stream would leave the chip idle)
         int max_rh = 0;
         for (int i = 0; i < n; i++) max_rh = std::max(max_rh, rects[i].height);
-        const int G = std::min(std::min(32, std::max(1, c->num_cus * 2 / std::max(n, 1))), (max_rh + 15) / 16);
-        if (n < 64 && G >= 2) {
+        const HtCsInitPlan ip = ht_cs_plan_init(n, max_rh, c->num_cus);
+        if (ip.rows) {
             HT_HIP(c, hipMemset2DAsync(c->d_cs[first].model, sizeof(HtCsState), 0, sizeof(uint32_t) * 4096, (size_t)n, c->stream));
-            hipLaunchKernelGGL(k_cs_init_rows, dim3(G, n), dim3(256), 0, c->stream, c->d_frames, c->frame_stride, c->W, c->H, d_rects, c->d_cs, first);
+            hipLaunchKernelGGL(k_cs_init_rows, dim3(ip.G, n), dim3(CS_INIT_ROWS_NT), 0, c->stream, c->d_frames, c->frame_stride, c->W, c->H, d_rects, c->d_cs, first);
         } else {
             hipLaunchKernelGGL(k_cs_init, dim3(n), dim3(INIT_NT), 0, c->stream, c->d_frames, c->frame_stride, c->W, c->H, d_rects, c->d_cs, first);
         }
@@ -657,15 +645,11 @@ extern "C" ht_status ht_camshift_init_batch(ht_ctx *c, int32_t first, int32_t n,
     return HT_OK;
 }
 
-// Threads per workgroup of k_cs_track_fused for a launch of n streams: option cs_fused_nt, else the small form when the launch has
-// more workgroups than the device has CUs (all of them resident at once, two per CU) or when ANOTHER live context of the device that
-// uses this path has work in flight right now (hipStreamQuery on its stream: no packet, ~1 us) — its track launch, or the detect
-// kernels of its next batch, then share the CUs with this launch instead of queueing behind it —, else the large form (one stream per
-// CU with the whole CU to itself: the lowest latency, and the right choice whenever nothing else wants the chip: measured on C3 with
-// TWO steps in flight, where a context's track launch never meets the other's, the small form costs 18 %).  Both forms return the
-// same bits.
+// Threads per workgroup of k_cs_track_fused for a launch of n streams (ht_cs_fused_form): this is the part of the choice that needs the
+// device — does ANOTHER live context of the device that uses this path have work in flight right now (hipStreamQuery on its stream: no
+// packet, ~1 us)?
 static int fused_threads(ht_ctx *c, int n) {
-    if (c->cs_fused_nt == FUSED_NT || c->cs_fused_nt == FUSED_NT_SMALL) return c->cs_fused_nt;
+    if (ht_cs_fused_form_forced(c->cs_fused_nt)) return c->cs_fused_nt;
     bool other_busy = false;
     {
         ClusterGate &gate = cluster_gate();
@@ -683,65 +667,75 @@ static int fused_threads(ht_ctx *c, int n) {
         }
         (void)hipGetLastError();  // hipErrorNotReady is an answer, not an error: keep it out of the launch checks that follow
     }
-    return (n > c->num_cus || other_busy) ? FUSED_NT_SMALL : FUSED_NT;
+    return ht_cs_fused_form(c->cs_fused_nt, n, c->num_cus, other_busy);
 }
 
-// one track() call of streams [first, first + n) on frames[0..n): histogram pass + mean-shift, results to d_out[0..n)
+// the schedule of a track() call of n streams with this context's geometry, reservation and options (ht_cs_schedule.h)
+static HtCsTrackPlan plan_track(ht_ctx *c, int n) {
+    HtCsTrackIn in;
+    in.n = n, in.cs_streams = c->cs_streams, in.W = c->W, in.H = c->H, in.num_cus = c->num_cus;
+    in.cs_fused_min_streams = c->cs_fused_min_streams, in.cs_cluster = c->cs_cluster, in.cs_cluster_min_px = c->cs_cluster_min_px;
+    in.dbg_cs_iters = c->dbg_cs_iters, in.cs_region_cap = c->cs_region_cap;
+    if (ht_cs_takes_fused(n, c->cs_fused_min_streams)) in.fused_nt = fused_threads(c, n);
+    return ht_cs_plan_track(in);
+}
+
+// k_cs_track_fused as the plan says: ncalls successive track() calls of streams [first, first + n), call k on frames[k]; the track
+// objects of call k go to d_out + k * out_call_stride (stride 0: the last call's remain).  `seq`: the instantiation whose workgroups walk
+// a list of calls (ht_camshift_track_sequence); a single track() call launches the other one, which ignores everything but frames[0].
+static ht_status launch_fused(ht_ctx *c, const HtCsTrackPlan &p, bool seq, const void *const *frames, int ncalls, size_t frame_stride, int32_t first,
+                              int32_t n, int32_t calc_angles, ht_cs_trackobj *d_out, uint32_t out_call_stride) {
+    const bool small = p.form == HT_CS_FUSED_512;
+    const dim3 grid(p.fused.grid_x), block(p.fused.block);
+    HtProfScope ps(c, p.fused.timer);
+    c->cs_fused_launches[small ? 1 : 0]++;
+    CsFusedArgs ka;
+    std::memset(&ka, 0, sizeof(ka));
+    for (int k = 0; k < ncalls; k++) ka.flist.p[k] = static_cast<const uint8_t *>(frames[k]);
+    ka.ncalls = ncalls, ka.W = c->W, ka.H = c->H, ka.npix = p.npix, ka.frame_stride = frame_stride, ka.states = c->d_cs, ka.first = first;
+    ka.calc_angles = calc_angles, ka.max_it = c->dbg_cs_iters, ka.region_cap = p.region_cap, ka.out = d_out, ka.out_call_stride = out_call_stride;
+    ka.dbg_hist = c->cs_keep_hist ? c->d_cs_hist : nullptr;
+    // (the instantiations are emitted in the order they are named here: the recorded camshift code object has this one)
+    if (!seq && !small) hipLaunchKernelGGL((k_cs_track_fused<false, FUSED_NT>), grid, block, p.fused.lds, c->stream, ka);
+    else if (!seq) hipLaunchKernelGGL((k_cs_track_fused<false, FUSED_NT_SMALL>), grid, block, p.fused.lds, c->stream, ka);
+    else if (!small) hipLaunchKernelGGL((k_cs_track_fused<true, FUSED_NT>), grid, block, p.fused.lds, c->stream, ka);
+    else hipLaunchKernelGGL((k_cs_track_fused<true, FUSED_NT_SMALL>), grid, block, p.fused.lds, c->stream, ka);
+    HT_HIP(c, hipGetLastError());
+    c->cs_last_first = first, c->cs_last_n = n, c->cs_last_chunks = c->cs_keep_hist ? 1 : 0;
+    c->cs_last_hist = c->d_cs_hist;
+    return HT_OK;
+}
+
+// one track() call of streams [first, first + n) on frames[0..n): plan, then launch what the plan says; results to d_out[0..n)
 // done_flags (pinned, n words) / done_seq: completion marks for an enqueue-only call — written by the cluster kernel if that path is
 // taken (*flags_used = true), otherwise the caller records its event.
 static ht_status launch_track(ht_ctx *c, const uint8_t *frames, size_t frame_stride, int32_t first, int32_t n, int32_t calc_angles,
                               ht_cs_trackobj *d_out, uint32_t *done_flags = nullptr, uint32_t done_seq = 0u, bool *flags_used = nullptr) {
-    const uint32_t npix = (uint32_t)((size_t)c->W * c->H);
     if (!c->cs_attr_set) {  // the cached search region needs more than the default 64 KB of LDS per workgroup (per context = per device)
         HT_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_cs_track_fused<false, FUSED_NT>), hipFuncAttributeMaxDynamicSharedMemorySize, CS_REGION_CAP * 2));
         HT_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_cs_meanshift), hipFuncAttributeMaxDynamicSharedMemorySize, CS_REGION_CAP * 2));
         c->cs_attr_set = true;
     }
-    // enough streams to keep (most of) the 256 CUs busy with one workgroup each: the fused single-launch kernel; fewer streams
-    // (a handful of large feeds): chunk histograms from every CU, then one mean-shift workgroup per stream
-    if (n >= c->cs_fused_min_streams) {
-        const bool small = fused_threads(c, n) == FUSED_NT_SMALL;
-        HtProfScope ps(c, small ? "cs_track_512" : "cs_track");  // the timer's name tells the form
-        c->cs_fused_launches[small ? 1 : 0]++;
-        CsFusedArgs ka;
-        std::memset(&ka, 0, sizeof(ka));
-        ka.flist.p[0] = frames;
-        ka.ncalls = 1, ka.W = c->W, ka.H = c->H, ka.npix = npix, ka.frame_stride = frame_stride, ka.states = c->d_cs, ka.first = first;
-        ka.calc_angles = calc_angles, ka.max_it = c->dbg_cs_iters, ka.region_cap = c->cs_region_cap, ka.out = d_out, ka.out_call_stride = 0u;
-        ka.dbg_hist = c->cs_keep_hist ? c->d_cs_hist : nullptr;
-        if (small) {
-            ka.region_cap = std::min(ka.region_cap, CS_REGION_CAP_SMALL);
-            hipLaunchKernelGGL((k_cs_track_fused<false, FUSED_NT_SMALL>), dim3(n), dim3(FUSED_NT_SMALL), (size_t)CS_REGION_CAP_SMALL * 2, c->stream, ka);
-        } else {
-            hipLaunchKernelGGL((k_cs_track_fused<false, FUSED_NT>), dim3(n), dim3(FUSED_NT), (size_t)CS_REGION_CAP * 2, c->stream, ka);
-        }
-        HT_HIP(c, hipGetLastError());
-        c->cs_last_first = first, c->cs_last_n = n, c->cs_last_chunks = c->cs_keep_hist ? 1 : 0;
-        c->cs_last_hist = c->d_cs_hist;
-        return HT_OK;
+    const HtCsTrackPlan p = plan_track(c, n);
+    if (p.form == HT_CS_FUSED_1024 || p.form == HT_CS_FUSED_512) {
+        const void *frame_list[1] = {frames};
+        return launch_fused(c, p, false, frame_list, 1, frame_stride, first, n, calc_angles, d_out, 0u);
     }
-    uint32_t chunk_px, nchunks;
-    hist_chunks(npix, hist_max_chunks(c->cs_streams), &chunk_px, &nchunks);  // buffer sized for cs_streams x that many chunks
-    // a few large frames: G workgroups per stream share every moment pass (k_cs_meanshift_cluster); otherwise one workgroup per stream
-    // cluster size: the grid never exceeds one workgroup per CU of THIS device, so it is co-resident whatever else is resident
-    // (a CU has room for four of these workgroups); fewer than 4 workgroups per stream are not worth the barriers
-    const int G = std::min(CL_MAXG, c->num_cus / std::max(n, 1));
-    const bool cluster = c->cs_cluster && n <= 64 && G >= 4 && npix >= c->cs_cluster_min_px && c->dbg_cs_iters > 0;
     uint32_t *hist = c->d_cs_hist;
     double *lut = c->d_cs_lut;
     {
-        HtProfScope ps(c, "cs_hist");
-        hipLaunchKernelGGL(k_cs_hist, dim3(nchunks, n), dim3(HIST_NT), 0, c->stream, frames, frame_stride, npix, chunk_px, hist);
-        HT_HIP(c, hipGetLastError());
+        HtProfScope ps(c, p.hist.timer);
+        ht_status st = ht_cs_hist_launch(c, frames, frame_stride, n, p.npix, p.chunk_px, p.nchunks, hist);
+        if (st != HT_OK) return st;
     }
-    if (cluster) {
-        HtProfScope ps(c, "cs_lut");
-        hipLaunchKernelGGL(k_cs_lut, dim3(64, n), dim3(512), 0, c->stream, hist, (int)nchunks, c->d_cs, first, lut,
-                           reinterpret_cast<unsigned long long *>(c->d_cs_parts));
-        HT_HIP(c, hipGetLastError());
-    }
-    if (cluster) {
-        HtProfScope ps(c, "cs_meanshift");
+    if (p.form == HT_CS_CLUSTER) {
+        {
+            HtProfScope ps(c, p.lut.timer);
+            hipLaunchKernelGGL(k_cs_lut, dim3(p.lut.grid_x, p.lut.grid_y), dim3(p.lut.block), 0, c->stream, hist, (int)p.nchunks, c->d_cs, first, lut,
+                               reinterpret_cast<unsigned long long *>(c->d_cs_parts));
+            HT_HIP(c, hipGetLastError());
+        }
+        HtProfScope ps(c, p.meanshift.timer);
         if (flags_used) *flags_used = done_flags != nullptr;
         ClusterGate &gate = cluster_gate();
         std::lock_guard<std::mutex> lk(gate.mu);
@@ -760,19 +754,19 @@ static ht_status launch_track(ht_ctx *c, const uint8_t *frames, size_t frame_str
             if (!gd.last) HT_HIP(c, hipEventCreateWithFlags(&gd.last, hipEventDisableTiming));
             else HT_HIP(c, hipStreamWaitEvent(c->stream, gd.last, 0));  // the previous cluster grid on this device (any context) has drained
         }
-        hipLaunchKernelGGL(k_cs_meanshift_cluster, dim3(n * G), dim3(CL_NT), 0, c->stream, frames, frame_stride, c->W, c->H, lut, c->d_cs, first,
-                           calc_angles, c->dbg_cs_iters, G, c->d_cs_parts, c->d_cs_err, c->h_cs_err_direct, (long long)c->cs_barrier_budget, d_out,
-                           done_flags, done_seq);
+        hipLaunchKernelGGL(k_cs_meanshift_cluster, dim3(p.meanshift.grid_x), dim3(p.meanshift.block), p.meanshift.lds, c->stream, frames, frame_stride, c->W,
+                           c->H, lut, c->d_cs, first, calc_angles, c->dbg_cs_iters, p.G, c->d_cs_parts, c->d_cs_err, c->h_cs_err_direct,
+                           (long long)c->cs_barrier_budget, d_out, done_flags, done_seq);
         HT_HIP(c, hipGetLastError());
         if (gd.multi) HT_HIP(c, hipEventRecord(gd.last, c->stream));
     } else {
-        HtProfScope ps(c, "cs_meanshift");
-        hipLaunchKernelGGL(k_cs_meanshift, dim3(n), dim3(CS_NT), (size_t)CS_REGION_CAP * 2, c->stream, frames, frame_stride, c->W, c->H, hist, (int)nchunks,
-                           c->d_cs, first, calc_angles, c->dbg_cs_iters, c->cs_region_cap, d_out);
+        HtProfScope ps(c, p.meanshift.timer);
+        hipLaunchKernelGGL(k_cs_meanshift, dim3(p.meanshift.grid_x), dim3(p.meanshift.block), p.meanshift.lds, c->stream, frames, frame_stride, c->W, c->H, hist,
+                           (int)p.nchunks, c->d_cs, first, calc_angles, c->dbg_cs_iters, p.region_cap, d_out);
         HT_HIP(c, hipGetLastError());
     }
     c->cs_last_hist = hist;
-    c->cs_last_first = first, c->cs_last_n = n, c->cs_last_chunks = (int)nchunks;
+    c->cs_last_first = first, c->cs_last_n = n, c->cs_last_chunks = (int)p.nchunks;
     return HT_OK;
 }
 
@@ -793,6 +787,20 @@ ht_status ht_cs_ring_begin(ht_ctx *c, const char *fn, int32_t n, const ht_cs_tra
 void ht_cs_ring_commit(ht_ctx *c, ht_ctx::HtCsSlot *slot, int32_t n) {
     slot->n = n;
     c->cs_ring_count++;
+}
+
+// the oldest outstanding call leaves the ring
+static void cs_ring_pop(ht_ctx *c) {
+    c->cs_ring_head = (c->cs_ring_head + 1) % ht_ctx::HT_CS_RING;
+    c->cs_ring_count--;
+}
+
+// the copy-back route of a result read-back: `count` track objects and the error word, then the stream is synchronised and the word checked
+static ht_status cs_read_back(ht_ctx *c, const char *fn, ht_cs_trackobj *out, const ht_cs_trackobj *d_src, size_t count) {
+    HT_HIP(c, hipMemcpyAsync(out, d_src, sizeof(ht_cs_trackobj) * count, hipMemcpyDeviceToHost, c->stream));
+    HT_HIP(c, hipMemcpyAsync(c->h_cs_err, c->d_cs_err, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HT_HIP(c, hipStreamSynchronize(c->stream));
+    return cs_check_err(c, fn);
 }
 
 extern "C" ht_status ht_camshift_track_batch(ht_ctx *c, int32_t first, int32_t n, int32_t calc_angles, ht_cs_trackobj *out) {
@@ -827,13 +835,7 @@ extern "C" ht_status ht_camshift_track_batch(ht_ctx *c, int32_t first, int32_t n
     }
     ht_status st = launch_track(c, c->d_frames, c->frame_stride, first, n, calc_angles, c->d_cs_out);
     if (st != HT_OK) return st;
-    if (out) {
-        HT_HIP(c, hipMemcpyAsync(out, c->d_cs_out, sizeof(ht_cs_trackobj) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-        HT_HIP(c, hipMemcpyAsync(c->h_cs_err, c->d_cs_err, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HT_HIP(c, hipStreamSynchronize(c->stream));
-        return cs_check_err(c, "ht_camshift_track_batch");
-    }
-    return HT_OK;
+    return out ? cs_read_back(c, "ht_camshift_track_batch", out, c->d_cs_out, (size_t)n) : HT_OK;
 }
 
 extern "C" ht_status ht_camshift_track_collect(ht_ctx *c, int32_t n, ht_cs_trackobj *out) {
@@ -866,8 +868,7 @@ extern "C" ht_status ht_camshift_track_collect(ht_ctx *c, int32_t n, ht_cs_track
         HT_HIP(c, hipEventSynchronize(sl.ev));  // the OLDEST outstanding call; later ones keep running
     }
     std::memcpy(out, sl.h_out, sizeof(ht_cs_trackobj) * (size_t)n);
-    c->cs_ring_head = (c->cs_ring_head + 1) % ht_ctx::HT_CS_RING;
-    c->cs_ring_count--;
+    cs_ring_pop(c);
     return cs_check_err(c, "ht_camshift_track_collect");
 }
 
@@ -883,45 +884,22 @@ extern "C" ht_status ht_camshift_track_sequence(ht_ctx *c, int32_t first, int32_
         if (!dev_frames[k] || ((uintptr_t)dev_frames[k] & 3)) return ht_fail(c, HT_ERR_INVALID, "ht_camshift_track_sequence: bad frame pointer");
     HT_HIP(c, hipSetDevice(c->device));
     const size_t need = (size_t)n * (size_t)(out_all ? ncalls : 1);
-    if (c->cs_seq_cap < need) {
-        HT_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->d_cs_seq_out) (void)hipFree(c->d_cs_seq_out);
-        c->d_cs_seq_out = nullptr;
-        c->cs_seq_cap = 0;
-        if (hipMalloc(&c->d_cs_seq_out, need * sizeof(ht_cs_trackobj)) != hipSuccess) return ht_fail(c, HT_ERR_NOMEM, "ht_camshift_track_sequence: hipMalloc failed");
-        c->cs_seq_cap = need;
-    }
+    ht_status gs = ht_grow_device(c, &c->d_cs_seq_out, &c->cs_seq_cap, need, "ht_camshift_track_sequence: hipMalloc failed");
+    if (gs != HT_OK) return gs;
     // the calls of one stream are sequentially dependent (search window, camshift.js:257-258), the streams are not: 2 launches
     // per call on the context's stream, no host round trip in between
-    if (n >= c->cs_fused_min_streams && c->cs_seq_fused) {
+    if (ht_cs_takes_fused(n, c->cs_fused_min_streams) && c->cs_seq_fused) {
         // one launch per CS_SEQ_MAX calls: every workgroup walks its stream's calls on its own (see k_cs_track_fused)
         if (!c->cs_seq_attr_set) {
             HT_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_cs_track_fused<true, FUSED_NT>), hipFuncAttributeMaxDynamicSharedMemorySize, CS_REGION_CAP * 2));
             c->cs_seq_attr_set = true;
         }
-        const uint32_t npix = (uint32_t)((size_t)c->W * c->H);
-        const bool small = fused_threads(c, n) == FUSED_NT_SMALL;
+        const HtCsTrackPlan p = plan_track(c, n);  // the form is chosen once for the whole sequence
         for (int k0 = 0; k0 < ncalls; k0 += CS_SEQ_MAX) {
-            const int kc = std::min(CS_SEQ_MAX, ncalls - k0);
-            CsFusedArgs ka;
-            std::memset(&ka, 0, sizeof(ka));
-            for (int k = 0; k < kc; k++) ka.flist.p[k] = static_cast<const uint8_t *>(dev_frames[k0 + k]);
-            ka.ncalls = kc, ka.W = c->W, ka.H = c->H, ka.npix = npix, ka.frame_stride = frame_stride, ka.states = c->d_cs, ka.first = first;
-            ka.calc_angles = calc_angles, ka.max_it = c->dbg_cs_iters, ka.region_cap = c->cs_region_cap;
-            ka.out = c->d_cs_seq_out + (out_all ? (size_t)k0 * n : 0), ka.out_call_stride = out_all ? (uint32_t)n : 0u;
-            ka.dbg_hist = c->cs_keep_hist ? c->d_cs_hist : nullptr;
-            HtProfScope ps(c, small ? "cs_track_512" : "cs_track");
-            c->cs_fused_launches[small ? 1 : 0]++;
-            if (small) {
-                ka.region_cap = std::min(ka.region_cap, CS_REGION_CAP_SMALL);
-                hipLaunchKernelGGL((k_cs_track_fused<true, FUSED_NT_SMALL>), dim3(n), dim3(FUSED_NT_SMALL), (size_t)CS_REGION_CAP_SMALL * 2, c->stream, ka);
-            } else {
-                hipLaunchKernelGGL((k_cs_track_fused<true, FUSED_NT>), dim3(n), dim3(FUSED_NT), (size_t)CS_REGION_CAP * 2, c->stream, ka);
-            }
-            HT_HIP(c, hipGetLastError());
+            ht_status st = launch_fused(c, p, true, dev_frames + k0, std::min(CS_SEQ_MAX, ncalls - k0), frame_stride, first, n, calc_angles,
+                                        c->d_cs_seq_out + (out_all ? (size_t)k0 * n : 0), out_all ? (uint32_t)n : 0u);
+            if (st != HT_OK) return st;
         }
-        c->cs_last_first = first, c->cs_last_n = n, c->cs_last_chunks = c->cs_keep_hist ? 1 : 0;
-        c->cs_last_hist = c->d_cs_hist;
     } else {
         for (int k = 0; k < ncalls; k++) {
             ht_cs_trackobj *d_out = c->d_cs_seq_out + (out_all ? (size_t)k * n : 0);
@@ -930,12 +908,7 @@ extern "C" ht_status ht_camshift_track_sequence(ht_ctx *c, int32_t first, int32_
         }
     }
     c->cs_seq_pending_n = 0;
-    if (out) {
-        HT_HIP(c, hipMemcpyAsync(out, c->d_cs_seq_out, need * sizeof(ht_cs_trackobj), hipMemcpyDeviceToHost, c->stream));
-        HT_HIP(c, hipMemcpyAsync(c->h_cs_err, c->d_cs_err, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HT_HIP(c, hipStreamSynchronize(c->stream));
-        return cs_check_err(c, "ht_camshift_track_sequence");
-    }
+    if (out) return cs_read_back(c, "ht_camshift_track_sequence", out, c->d_cs_seq_out, need);
     c->cs_seq_pending_n = n, c->cs_seq_pending_calls = ncalls, c->cs_seq_pending_all = out_all ? 1 : 0;  // what ht_camshift_sequence_collect may fetch
     return HT_OK;
 }
@@ -948,11 +921,9 @@ extern "C" ht_status ht_camshift_sequence_collect(ht_ctx *c, int32_t n, int32_t 
     if (!c->d_cs_seq_out || c->cs_seq_cap < need || c->cs_seq_pending_n != n || c->cs_seq_pending_calls != ncalls || c->cs_seq_pending_all != (out_all ? 1 : 0))
         return ht_fail(c, HT_ERR_STATE, "ht_camshift_sequence_collect: no enqueue-only sequence with this n / ncalls / out_all is pending");
     HT_HIP(c, hipSetDevice(c->device));
-    HT_HIP(c, hipMemcpyAsync(out, c->d_cs_seq_out, need * sizeof(ht_cs_trackobj), hipMemcpyDeviceToHost, c->stream));
-    HT_HIP(c, hipMemcpyAsync(c->h_cs_err, c->d_cs_err, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HT_HIP(c, hipStreamSynchronize(c->stream));
-    c->cs_seq_pending_n = 0;
-    return cs_check_err(c, "ht_camshift_sequence_collect");
+    const ht_status st = cs_read_back(c, "ht_camshift_sequence_collect", out, c->d_cs_seq_out, need);
+    if (st != HT_ERR_HIP) c->cs_seq_pending_n = 0;  // fetched, whatever the error word says; a failed copy leaves the sequence pending
+    return st;
 }
 
 extern "C" ht_status ht_camshift_stats(ht_ctx *c, int32_t first, int32_t n, uint64_t *window_pixels, uint64_t *calls, int32_t reset) {
@@ -969,6 +940,18 @@ extern "C" ht_status ht_camshift_stats(ht_ctx *c, int32_t first, int32_t n, uint
     return HT_OK;
 }
 
+// current[4096] = the sum of the nchunks chunk histograms at d_hist (either layout: a stream's slot of d_cs_hist or a frame's of d_csp_hist)
+static ht_status cs_sum_chunks(ht_ctx *c, const uint32_t *d_hist, int nchunks, uint32_t *current) {
+    std::vector<uint32_t> part((size_t)nchunks * 4096);
+    HT_HIP(c, hipMemcpy(part.data(), d_hist, part.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int b = 0; b < 4096; b++) {
+        uint32_t v = 0;
+        for (int k = 0; k < nchunks; k++) v += part[(size_t)k * 4096 + b];
+        current[b] = v;
+    }
+    return HT_OK;
+}
+
 extern "C" ht_status ht_camshift_debug_hist(ht_ctx *c, int32_t stream, uint32_t *model, uint32_t *current) {
     if (!c || stream < 0 || stream >= c->cs_streams) return HT_ERR_INVALID;
     HT_HIP(c, hipSetDevice(c->device));
@@ -978,141 +961,11 @@ extern "C" ht_status ht_camshift_debug_hist(ht_ctx *c, int32_t stream, uint32_t 
         if (c->d_csp_hist && c->cs_last_hist == c->d_csp_hist) {  // the last track call was a pair call: the stream's frame has a slot of its own
             const int slot = stream < (int)c->cs_pair_slot.size() ? c->cs_pair_slot[stream] : -1;
             if (slot < 0 || c->cs_pair_chunks <= 0) return ht_fail(c, HT_ERR_STATE, "ht_camshift_debug_hist: the stream was not part of the last track call");
-            std::vector<uint32_t> part((size_t)c->cs_pair_chunks * 4096);
-            HT_HIP(c, hipMemcpy(part.data(), c->d_csp_hist + (size_t)slot * c->cs_pair_chunks * 4096, part.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            for (int b = 0; b < 4096; b++) {
-                uint32_t v = 0;
-                for (int k = 0; k < c->cs_pair_chunks; k++) v += part[(size_t)k * 4096 + b];
-                current[b] = v;
-            }
-            return HT_OK;
+            return cs_sum_chunks(c, c->d_csp_hist + (size_t)slot * c->cs_pair_chunks * 4096, c->cs_pair_chunks, current);
         }
         if (stream < c->cs_last_first || stream >= c->cs_last_first + c->cs_last_n || c->cs_last_chunks <= 0 || !c->cs_last_hist)
             return ht_fail(c, HT_ERR_STATE, "ht_camshift_debug_hist: the stream was not part of the last track call");
-        std::vector<uint32_t> part((size_t)c->cs_last_chunks * 4096);
-        HT_HIP(c, hipMemcpy(part.data(), c->cs_last_hist + (size_t)(stream - c->cs_last_first) * c->cs_last_chunks * 4096, part.size() * sizeof(uint32_t),
-                            hipMemcpyDeviceToHost));
-        for (int b = 0; b < 4096; b++) {
-            uint32_t v = 0;
-            for (int k = 0; k < c->cs_last_chunks; k++) v += part[(size_t)k * 4096 + b];
-            current[b] = v;
-        }
-    }
-    return HT_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// multi-GPU: in-place all-gather of fixed-size records over RCCL (xGMI), single-process form for the Node host.
-// (bench.py / torch.distributed use one process per GPU and call RCCL through torch instead.)
-
-namespace {
-struct CommSet {
-    std::vector<int> devs;
-    std::vector<ncclComm_t> comms;
-};
-std::map<std::vector<int>, CommSet> g_comms;
-
-struct Rccl {
-    void *h = nullptr;
-    ncclResult_t (*CommInitAll)(ncclComm_t *, int, const int *) = nullptr;
-    ncclResult_t (*GroupStart)() = nullptr;
-    ncclResult_t (*GroupEnd)() = nullptr;
-    ncclResult_t (*AllGather)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-    const char *(*GetErrorString)(ncclResult_t) = nullptr;
-    bool ok = false;
-};
-Rccl &rccl() {
-    static Rccl r;
-    if (r.h) return r;
-    r.h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-    if (!r.h) r.h = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!r.h) r.h = dlopen("/opt/rocm/lib/librccl.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!r.h) return r;
-    r.CommInitAll = reinterpret_cast<decltype(r.CommInitAll)>(dlsym(r.h, "ncclCommInitAll"));
-    r.GroupStart = reinterpret_cast<decltype(r.GroupStart)>(dlsym(r.h, "ncclGroupStart"));
-    r.GroupEnd = reinterpret_cast<decltype(r.GroupEnd)>(dlsym(r.h, "ncclGroupEnd"));
-    r.AllGather = reinterpret_cast<decltype(r.AllGather)>(dlsym(r.h, "ncclAllGather"));
-    r.GetErrorString = reinterpret_cast<decltype(r.GetErrorString)>(dlsym(r.h, "ncclGetErrorString"));
-    r.ok = r.CommInitAll && r.GroupStart && r.GroupEnd && r.AllGather && r.GetErrorString;
-    return r;
-}
-}  // namespace
-
-extern "C" ht_status ht_allgather_records(ht_ctx *const *ctxs, int32_t nranks, void *const *records_dev, size_t bytes_per_rank) {
-    if (!ctxs || !records_dev || nranks <= 0 || bytes_per_rank == 0) return HT_ERR_INVALID;
-    if (nranks == 1 && ctxs[0] && !ctxs[0]->force_rccl) return HT_OK;  // (option force_rccl runs RCCL with one rank: dlopen + ncclCommInitAll + ncclAllGather on a 1-GPU box)
-    std::vector<int> devs(nranks);
-    for (int i = 0; i < nranks; i++) {
-        if (!ctxs[i] || !records_dev[i]) return HT_ERR_INVALID;
-        devs[i] = ctxs[i]->device;
-    }
-    Rccl &R = rccl();
-    if (!R.ok) return ht_fail(ctxs[0], HT_ERR_HIP, "ht_allgather_records: librccl.so could not be loaded");
-    auto it = g_comms.find(devs);
-    if (it == g_comms.end()) {
-        CommSet cs;
-        cs.devs = devs;
-        cs.comms.resize(nranks);
-        if (R.CommInitAll(cs.comms.data(), nranks, devs.data()) != ncclSuccess)
-            return ht_fail(ctxs[0], HT_ERR_HIP, "ht_allgather_records: ncclCommInitAll failed");
-        it = g_comms.emplace(devs, cs).first;
-    }
-    ncclResult_t r = R.GroupStart();
-    for (int i = 0; i < nranks && r == ncclSuccess; i++) {
-        char *buf = static_cast<char *>(records_dev[i]);
-        r = R.AllGather(buf + (size_t)i * bytes_per_rank, buf, bytes_per_rank, ncclChar, it->second.comms[i], ctxs[i]->stream);
-    }
-    if (r == ncclSuccess) r = R.GroupEnd();
-    if (r != ncclSuccess) return ht_fail(ctxs[0], HT_ERR_HIP, std::string("ht_allgather_records: ") + R.GetErrorString(r));
-    for (int i = 0; i < nranks; i++) {
-        HT_HIP(ctxs[i], hipSetDevice(ctxs[i]->device));
-        HT_HIP(ctxs[i], hipStreamSynchronize(ctxs[i]->stream));
-    }
-    return HT_OK;
-}
-
-extern "C" int32_t ht_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    return n;
-}
-
-// Single-process multi-GPU exchange of the per-frame bounding boxes: rank i's ht_best_faces output goes into slot i of a
-// device buffer on ITS GPU, one ncclAllGather per rank over xGMI, then every rank's gathered table is read back and compared —
-// all ranks must hold the same table — and the table is returned.
-extern "C" ht_status ht_allgather_best_faces(ht_ctx *const *ctxs, int32_t nranks, const ht_rect *const *best, int32_t frames_per_rank, ht_rect *gathered) {
-    if (!ctxs || !best || !gathered || nranks <= 0 || frames_per_rank <= 0) return HT_ERR_INVALID;
-    const size_t per = sizeof(ht_rect) * (size_t)frames_per_rank, total = per * (size_t)nranks;
-    std::vector<void *> bufs(nranks, nullptr);
-    for (int i = 0; i < nranks; i++) {
-        ht_ctx *c = ctxs[i];
-        if (!c || !best[i]) return HT_ERR_INVALID;
-        HT_HIP(c, hipSetDevice(c->device));
-        if (c->d_gather_bytes < total) {
-            HT_HIP(c, hipStreamSynchronize(c->stream));
-            if (c->d_gather) (void)hipFree(c->d_gather);
-            c->d_gather = nullptr;
-            c->d_gather_bytes = 0;
-            if (hipMalloc(&c->d_gather, total) != hipSuccess) return ht_fail(c, HT_ERR_NOMEM, "ht_allgather_best_faces: hipMalloc failed");
-            c->d_gather_bytes = total;
-        }
-        HT_HIP(c, hipMemsetAsync(c->d_gather, 0, total, c->stream));
-        HT_HIP(c, hipMemcpyAsync(static_cast<char *>(c->d_gather) + (size_t)i * per, best[i], per, hipMemcpyHostToDevice, c->stream));
-        HT_HIP(c, hipStreamSynchronize(c->stream));  // best[i] is the caller's pageable memory
-        bufs[i] = c->d_gather;
-    }
-    ht_status st = ht_allgather_records(ctxs, nranks, bufs.data(), per);
-    if (st != HT_OK) return st;
-    std::vector<char> other(total);
-    for (int i = 0; i < nranks; i++) {
-        ht_ctx *c = ctxs[i];
-        HT_HIP(c, hipSetDevice(c->device));
-        HT_HIP(c, hipMemcpy(i == 0 ? reinterpret_cast<char *>(gathered) : other.data(), c->d_gather, total, hipMemcpyDeviceToHost));
-        if (i > 0 && std::memcmp(other.data(), gathered, total) != 0)
-            return ht_fail(ctxs[0], HT_ERR_HIP, "ht_allgather_best_faces: rank " + std::to_string(i) + " holds a different table than rank 0 after the all-gather");
+        return cs_sum_chunks(c, c->cs_last_hist + (size_t)(stream - c->cs_last_first) * c->cs_last_chunks * 4096, c->cs_last_chunks, current);
     }
     return HT_OK;
 }

@@ -507,23 +507,7 @@ extern "C" void ht_destroy(ht_ctx *c) {
     if (c->h_pinned) (void)hipHostFree(c->h_pinned);
     if (c->d_scratch) (void)hipFree(c->d_scratch);
     if (c->h_wb_pinned) (void)hipHostFree(c->h_wb_pinned);
-    if (c->d_cs_err) (void)hipFree(c->d_cs_err);
-    if (c->h_cs_err) (void)hipHostFree(c->h_cs_err);
-    if (c->h_cs_err_direct) (void)hipHostFree(c->h_cs_err_direct);
-    for (auto &sl : c->cs_ring) {
-        if (sl.h_out) (void)hipHostFree(sl.h_out);
-        if (sl.h_flag) (void)hipHostFree(sl.h_flag);
-        if (sl.ev) (void)hipEventDestroy(sl.ev);
-    }
-    ht_cluster_gate_forget(c);
-    if (c->h_cs_rects) (void)hipHostFree(c->h_cs_rects);
-    if (c->ev_cs_rects) (void)hipEventDestroy(c->ev_cs_rects);
-    if (c->d_cs) (void)hipFree(c->d_cs);
-    if (c->d_cs_hist) (void)hipFree(c->d_cs_hist);
-    if (c->d_cs_out) (void)hipFree(c->d_cs_out);
-    if (c->d_cs_seq_out) (void)hipFree(c->d_cs_seq_out);
-    if (c->d_cs_lut) (void)hipFree(c->d_cs_lut);
-    if (c->d_cs_parts) (void)hipFree(c->d_cs_parts);
+    ht_camshift_free(c);
     ht_backproject_free(c);
     ht_ingest_free(c);
     ht_cs_pairs_free(c);

@@ -25,12 +25,8 @@ __device__ __forceinline__ uint32_t cs_bin(uint32_t px) {
 #define CS_STAMP(arr, i)
 #endif
 
-constexpr int CS_NT = 512;          // threads of the mean-shift workgroup
-constexpr int HIST_NT = 1024;
+// (the workgroup sizes CS_NT / HIST_NT / INIT_NT and CS_REGION_CAP: ht_cs_schedule.h, where the host plans its launches with them)
 constexpr int HIST_UNROLL = 4;  // 16-byte loads of a thread in flight in the histogram pass (k_cs_hist)
-constexpr int INIT_NT = 1024;   // threads of the one-workgroup-per-stream initTracker (k_cs_init)
-
-constexpr int CS_REGION_CAP = 40960;  // pixels of the cached search region: 80 KB of LDS next to the 32 KB LUT (which the 16 KB histogram overlays)
 
 // A batch of PREDICATED loads (`v = ok ? p[i] : 0`) followed by cs_bin: the optimiser folds the bin's first instruction (`& 0xf0f0f0`, which maps
 // the 0 of the not-taken side to 0) into the load's own block, where it has to wait for the load on the spot — every load of the batch

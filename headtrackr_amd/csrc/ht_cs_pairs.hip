@@ -124,17 +124,10 @@ ht_status csp_launch_track(ht_ctx *c, const CspPlan &plan, int32_t calc_angles, 
     uint32_t chunk_px = 0, nchunks = 0;
     ht_cs_hist_plan(npix, nd, &chunk_px, &nchunks);
     const size_t need = (size_t)nd * nchunks * 4096;
-    if (c->csp_hist_cap < need) {
-        HT_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->d_csp_hist) (void)hipFree(c->d_csp_hist);
-        c->d_csp_hist = nullptr, c->csp_hist_cap = 0;
-        if (c->cs_last_hist && c->cs_last_hist != c->d_cs_hist) c->cs_last_hist = nullptr, c->cs_last_n = 0;  // pointed into the old scratch
-        if (hipMalloc(reinterpret_cast<void **>(&c->d_csp_hist), need * sizeof(uint32_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            return ht_fail(c, HT_ERR_NOMEM, std::string(fn) + ": hipMalloc failed (chunk histograms)");
-        }
-        c->csp_hist_cap = need;
-    }
+    // the scratch is about to be replaced: what ht_camshift_debug_hist would read must not point into the old one, also when the allocation fails
+    if (c->csp_hist_cap < need && c->cs_last_hist && c->cs_last_hist != c->d_cs_hist) c->cs_last_hist = nullptr, c->cs_last_n = 0;
+    ht_status gs = ht_grow_device(c, &c->d_csp_hist, &c->csp_hist_cap, need, "ht_camshift_track_pairs: hipMalloc failed (chunk histograms)");
+    if (gs != HT_OK) return gs;
     const CspEntry *d_entries = nullptr;
     const int32_t *d_flist = nullptr;
     ht_status st = csp_upload(c, fn, plan, &d_entries, &d_flist);

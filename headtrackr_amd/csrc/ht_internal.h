@@ -119,14 +119,9 @@ struct HtCounters {
     uint32_t pad;
 };
 
-// camshift per-stream device state (camshift.js:153-160)
-struct alignas(16) HtCsState {
-    uint32_t model[4096];  // _modelHist
-    int32_t sw[4];         // _searchWindow
-    double x, y, width, height, angle;  // _trackObj
-    unsigned long long win_px;          // measurement: pixels visited by the window moment passes since the last reset
-    unsigned long long calls;           // measurement: track() calls since the last reset
-};
+// The camshift launch constants, the per-stream device state (HtCsState) and the host-side schedule of the camshift calls live in a header
+// without HIP as well, shared with the CPU suite's harness.
+#include "ht_cs_schedule.h"
 
 // A captured detect sequence (memsets + gray + pyramid generations + scan kernels: ~10 dependent launches) replayed with one
 // hipGraphLaunch.  Keyed by everything the kernels' arguments depend on besides the geometry (which owns the cache).
@@ -320,7 +315,7 @@ struct ht_ctx {
     int num_cus = 256;                 // hipDeviceProp_t::multiProcessorCount: sizes the cluster of k_cs_meanshift_cluster
     uint32_t cs_fused_launches[2] = {0, 0};  // k_cs_track_fused launches in the 1024- / 512-thread form since the last ht_kernel_times(reset): reported there as
                                             // the pseudo-timers cs_fused_launches_1024 / _512 (ms = 0), profiling on or off
-    int cs_fused_nt = 0;             // option cs_fused_nt=512|1024: threads per workgroup of k_cs_track_fused (0: chosen per launch, ht_camshift.hip fused_threads)
+    int cs_fused_nt = 0;             // option cs_fused_nt=512|1024: threads per workgroup of k_cs_track_fused (0: chosen per launch, ht_cs_fused_form)
     int cs_fused_min_streams = 192;  // >= this many streams per call: k_cs_track_fused (option cs_fused_min)
     bool cs_seq_attr_set = false;
     bool cs_seq_fused = true;      // option cs_seq_fused=0: ht_camshift_track_sequence launches one kernel per call (A/B)
@@ -362,7 +357,7 @@ struct ht_ctx {
 
     std::vector<std::pair<void *, size_t>> user_allocs;  // ht_device_alloc buffers still alive (pointer, bytes): freed by ht_destroy at the latest
 
-    // multi-GPU exchange buffer (ht_allgather_best_faces)
+    // multi-GPU exchange buffer (ht_allgather.hip: ht_allgather_best_faces)
     void *d_gather = nullptr;
     size_t d_gather_bytes = 0;
 
@@ -388,6 +383,23 @@ ht_status ht_fail(ht_ctx *ctx, ht_status st, const std::string &msg);
             return ht_fail((ctx), HT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));           \
     } while (0)
 
+// Device scratch grown on demand: *p holds >= need elements afterwards.  A reallocation waits for the work in flight first, like every
+// reallocation of the library: synchronise, free, zero the capacity, allocate.  `message`: the HT_ERR_NOMEM text of a failed allocation
+// (the buffer is then gone: *p == nullptr, *cap == 0).
+template <typename T>
+ht_status ht_grow_device(ht_ctx *c, T **p, size_t *cap, size_t need, const char *message) {
+    if (*cap >= need) return HT_OK;
+    HT_HIP(c, hipStreamSynchronize(c->stream));
+    if (*p) (void)hipFree(*p);
+    *p = nullptr, *cap = 0;
+    if (hipMalloc(reinterpret_cast<void **>(p), need * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        return ht_fail(c, HT_ERR_NOMEM, message);
+    }
+    *cap = need;
+    return HT_OK;
+}
+
 // profiling scope: records a start/stop event pair around kernel launches when ctx->profiling
 struct HtProfScope {
     ht_ctx *ctx;
@@ -399,17 +411,16 @@ struct HtProfScope {
 };
 
 // implemented in the .hip files ---------------------------------------------------------------------------
-void ht_cluster_gate_forget(const ht_ctx *ctx);             // ht_camshift.hip
 void ht_capture_mark(ht_ctx *ctx, bool on);                 // ht_camshift.hip: ctx->capturing, ordered against fused_threads' stream queries
-// ht_camshift.hip: the chunk plan of the full-frame histogram pass for a call of nstreams frames, and k_cs_hist on n frames into
-// hist[n][nchunks][4096] (for ht_backproject.hip, which must not carry a copy of the kernel)
-void ht_cs_hist_plan(uint32_t npix, int nstreams, uint32_t *chunk_px, uint32_t *nchunks);
+// ht_camshift.hip: k_cs_hist on n frames into hist[n][nchunks][4096], chunk plan from ht_cs_hist_plan (ht_cs_schedule.h) — for
+// ht_backproject.hip, which must not carry a copy of the kernel
 ht_status ht_cs_hist_launch(ht_ctx *ctx, const uint8_t *frames, size_t frame_stride, int n, uint32_t npix, uint32_t chunk_px, uint32_t nchunks, uint32_t *hist);
 // ht_camshift.hip: the result ring of the enqueue-only track calls (batch and pair form).  begin: *slot = the next free pinned slot when
 // the call is enqueue-only or a synchronous call that goes through the ring (*via_ring), nullptr when it copies back; commit: the slot
 // is outstanding
 ht_status ht_cs_ring_begin(ht_ctx *ctx, const char *fn, int32_t n, const ht_cs_trackobj *out, bool *via_ring, ht_ctx::HtCsSlot **slot);
 void ht_cs_ring_commit(ht_ctx *ctx, ht_ctx::HtCsSlot *slot, int32_t n);
+void ht_camshift_free(ht_ctx *ctx);                         // ht_camshift.hip: tracker state, scratch, result ring, the cluster gate's entry (ht_destroy)
 void ht_backproject_free(ht_ctx *ctx);                      // ht_backproject.hip: its scratch (ht_destroy)
 void ht_cs_pairs_free(ht_ctx *ctx);                         // ht_cs_pairs.hip: pair table, staging and histogram scratch (ht_destroy)
 void ht_ingest_free(ht_ctx *ctx);                           // ht_ingest.hip: the host form's source staging (ht_destroy)

@@ -230,6 +230,19 @@ def range_batch(seqs, first, n, k):
 
 
 @functools.lru_cache(maxsize=None)
+def default_path_streams(w, h, steps=3, distinct=8):
+    """E: the trackers of a default-options call at a small frame size: `distinct` different sequences (position, size, colour, rotation, walk),
+    stream s of a call takes sequence s % distinct — neighbouring streams differ, and the oracle runs `distinct` times whatever the call's size"""
+    out = []
+    for k in range(distinct):
+        a, b = w // 6 + k % 3, h // 8 + k % 2
+        moves = [((k + j) % 3 - 1, (2 * k + j) % 3 - 1) for j in range(steps)]
+        out.append(blob_seq(f"default-{w}x{h}-{k}", w, h, w // 2 - 6 + 2 * (k % 4), h // 2 - 4 + k // 2, a, b, moves, 5200 + 11 * k + w, rot=ROTS[k % 5],
+                            color=COLORS[k % 4]))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
 def growing():
     """A: the reservation grows between two track calls (1 -> 40 streams); at 1920x1080 that changes the chunking from 127 to 8 chunks"""
     mv = [(3, 1), (-2, 2), (4, -1), (2, 2)]

@@ -24,6 +24,14 @@ def _rt():
     return _hip
 
 
+def multiprocessor_count(device: int = 0) -> int:
+    """compute units of the device (hipDeviceAttributeMultiprocessorCount): what the library sizes its camshift clusters with"""
+    n = C.c_int(0)
+    if _rt().hipDeviceGetAttribute(C.byref(n), 63, device) != 0 or not 0 < n.value <= 4096:
+        raise RuntimeError("hipDeviceGetAttribute(hipDeviceAttributeMultiprocessorCount) failed")
+    return n.value
+
+
 class DeviceArray:
     def __init__(self, host: np.ndarray):
         host = np.ascontiguousarray(host)

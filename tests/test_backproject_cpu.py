@@ -71,10 +71,12 @@ def test_recorded_code_objects_are_unchanged_and_the_new_unit_is_its_own():
         assert k in names, (k, names)
         for marker in fingerprint.UNITS.values():
             assert marker.decode() not in k
-    # one code object per translation unit with device code (ht_context.hip has none): the three recorded ones and ONE more, which
-    # holds the new kernels and none of the markers
+    # one code object per translation unit with device code (ht_context.hip and ht_allgather.hip have none): the three recorded ones and
+    # ONE more, which holds the new kernels and none of the markers
     objs = _gfx950_code_objects(build.LIB)
-    assert len(objs) == len(build.HIP_SOURCES) - 1 == 4
+    with_device_code = [s for s in build.HIP_SOURCES if "__global__" in open(os.path.join(CSRC, s)).read()]
+    assert len(objs) == len(with_device_code) == 4, (len(objs), with_device_code)
+    assert sorted(set(build.HIP_SOURCES) - set(with_device_code)) == ["ht_allgather.hip", "ht_context.hip"]
     mine = [o for o in objs if b"k_bp_project" in o]
     assert len(mine) == 1 and b"k_bp_lut" in mine[0]
     for marker in fingerprint.UNITS.values():

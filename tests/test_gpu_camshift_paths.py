@@ -6,18 +6,21 @@ the CPU oracle through the C ABI:
   B  the LDS search-region cache of the mean-shift kernels: windows that leave it in the middle of a call, its capacity and margin
      boundaries (option cs_region), margins clamped by the frame, the two ways the single-launch kernel fills it, the two capacities;
   C  the two initTracker kernels at rect sizes next to their lane / row quanta;
-  D  the chunk histograms at pixel counts next to the chunking quanta.
+  D  the chunk histograms at pixel counts next to the chunking quanta;
+  E  the schedule a call takes with DEFAULT options (parts A - D force one): both sides of every threshold of the decision table of
+     headtrackr_amd/csrc/ht_cs_schedule.h, told apart by the profiling timers the call leaves behind.
 
 Inputs, and the CPU proof that they reach these states and that the reference is unambiguous on them: tests/cs_cases.py,
-tests/test_cs_cases_cpu.py.  Every track() call is checked with check() and is in an assert_all_exact(): the oracle's integers, no tie
+tests/test_cs_cases_cpu.py.  Every track() call is checked with check() and, in parts A - D, is in an assert_all_exact(): the oracle's integers, no tie
 class.  The module's calls are in the tally of camshift_parity.json (tests/test_gpu_camshift.py writes it), with sub-totals "paths" and
 "paths/<schedule>"."""
 import numpy as np
 import pytest
 
 import cs_cases as cc
+import cs_schedule
 from headtrackr_amd.api import Context, HtError
-from hipmem import DeviceArray
+from hipmem import DeviceArray, multiprocessor_count
 from test_gpu_camshift import SCHEDULES, assert_all_exact, check
 
 pytestmark = pytest.mark.gpu
@@ -357,3 +360,113 @@ def test_chunk_histogram_edges(sched):
                         assert np.array_equal(cur, want), (w, h, family, n, reserved, s, np.flatnonzero(cur != want)[:8])
     finally:
         c.close()
+
+
+# ---- E: the default decision table ----------------------------------------------------------------------------------------------------------
+
+CS_TIMERS = ("cs_track", "cs_track_512", "cs_hist", "cs_lut", "cs_meanshift", "cs_fused_launches_1024", "cs_fused_launches_512")
+# (streams, W, H, the case on the other side of the threshold this one guards): 10 240 / 9 216 pixels around cs_cluster_min_px, 64 / 65
+# streams around the cluster form's stream limit (and, with 256 CUs, its 4 workgroups per stream), 191 / 192 around cs_fused_min, 192 / 257
+# around one workgroup per CU
+DEFAULT_CASES = {"n1-128x80": (1, 128, 80, "n1-96x96"), "n1-96x96": (1, 96, 96, "n1-128x80"), "n64-128x80": (64, 128, 80, "n65-128x80"),
+                 "n65-128x80": (65, 128, 80, "n64-128x80"), "n191-64x64": (191, 64, 64, "n192-64x64"), "n192-64x64": (192, 64, 64, "n191-64x64"),
+                 "n257-64x64": (257, 64, 64, "n192-64x64")}
+ON_256_CUS = {"n1-128x80": "CLUSTER", "n1-96x96": "PER_STREAM", "n64-128x80": "CLUSTER", "n65-128x80": "PER_STREAM", "n191-64x64": "PER_STREAM",
+              "n192-64x64": "FUSED_1024", "n257-64x64": "FUSED_512"}
+
+
+def _default_plan(name, cus):
+    n, w, h, _other = DEFAULT_CASES[name]
+    return cs_schedule.track_plan(n, w, h, num_cus=cus)
+
+
+def _expected_timers(plan, calls):
+    want = {t: calls for t in plan["timers"]}
+    if plan["form"].startswith("FUSED"):
+        want["cs_fused_launches_" + plan["form"][6:]] = calls
+    return want
+
+
+def _default_batches(w, h, n, steps):
+    seqs = cc.default_path_streams(w, h)
+    per = [seqs[s % len(seqs)] for s in range(n)]
+    return per, [np.stack([q.frames[k] for q in per]) for k in range(steps + 1)]
+
+
+def test_default_table_on_256_compute_units():
+    """the table the cases below are computed from, at the CU count of the device this library is written for (no device needed)"""
+    assert {name: _default_plan(name, 256)["form"] for name in DEFAULT_CASES} == ON_256_CUS
+
+
+@pytest.mark.parametrize("name", list(DEFAULT_CASES))
+def test_default_options_take_the_schedule_of_the_table(name):
+    """default options, profiling on: one init + two track() calls, every track object against the oracle, then the timers the two calls
+    left behind say which kernels ran: the form the decision table gives for this device's CU count, and nothing of another form.  The
+    process's other contexts are idle, so no other context is busy on the fused path."""
+    n, w, h, other = DEFAULT_CASES[name]
+    cus = multiprocessor_count()
+    plan = _default_plan(name, cus)
+    if plan["form"] == _default_plan(other, cus)["form"]:
+        pytest.skip(f"with {cus} compute units {name} and {other} take the same schedule ({plan['form']}): no threshold between them")
+    per, batches = _default_batches(w, h, n, 2)
+    c = Context()
+    try:
+        c.profile(True)
+        c.set_geometry(w, h, n)
+        c.camshift_reserve(n)
+        c.upload(batches[0])
+        c.camshift_init([q.rect for q in per])
+        c.synchronize()
+        c.kernel_times(reset=True)
+        stats = []
+        for k in (1, 2):
+            c.upload(batches[k])
+            got = c.camshift_track(n, calc_angles=True)
+            for s, q in enumerate(per):
+                sw, to = _expected(q)[k - 1]
+                check(got[s], sw, to, stats, where=(name, "default", s, k), tally=_tally("default"))
+        assert len(stats) == 2 * n
+        c.synchronize()
+        times = c.kernel_times()
+        got_timers = {t: times[t]["launches"] for t in CS_TIMERS if t in times}
+        assert got_timers == _expected_timers(plan, 2), (name, cus, plan["form"], got_timers)
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("fetch", ["all", "last"])
+def test_fused_track_sequence_equals_single_calls(fetch):
+    """ht_camshift_track_sequence on the fused path with default options (192 streams, 3 calls in ONE launch whose workgroups walk their
+    stream's calls) returns the bytes of three single track() calls from the same initial state, for every call's objects and for the
+    last call's only; the single calls are checked against the oracle"""
+    n, w, h, steps = 192, 64, 64, 3
+    form = cs_schedule.track_plan(n, w, h, num_cus=multiprocessor_count())["form"]
+    per, batches = _default_batches(w, h, n, steps)
+    dev = [DeviceArray(b) for b in batches]
+    c = Context()
+    try:
+        c.set_geometry(w, h, n)
+        c.camshift_reserve(n)
+        rects = [q.rect for q in per]
+        c.bind_device(dev[0].ptr, n)
+        c.camshift_init(rects)
+        single, stats = [], []
+        for k in range(1, steps + 1):
+            c.bind_device(dev[k].ptr, n)
+            got = c.camshift_track(n, calc_angles=True)
+            for s, q in enumerate(per):
+                sw, to = _expected(q)[k - 1]
+                check(got[s], sw, to, stats, where=("sequence-default", s, k), tally=_tally("default"))
+            single.append(got.tobytes())
+        c.bind_device(dev[0].ptr, n)
+        c.camshift_init(rects)  # the same initial state again
+        c.kernel_times(reset=True)
+        got = c.camshift_track_sequence([d.ptr for d in dev[1:]], n, calc_angles=True, fetch=fetch)
+        assert got.tobytes() == (b"".join(single) if fetch == "all" else single[-1])
+        times = c.kernel_times()
+        assert times["cs_fused_launches_" + form[6:]]["launches"] == 1 and form.startswith("FUSED"), (form, times)
+    finally:
+        c.synchronize()
+        c.close()
+        for d in dev:
+            d.free()
