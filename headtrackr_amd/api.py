@@ -365,6 +365,24 @@ class Context:
         element size): enqueued on the context's stream, no copy, no wait."""
         self._check(self._lib.ht_camshift_backproject_device(self._h, first, n, int(self._BP_KINDS.get(kind, kind)), dev_ptr, stride))
 
+    def camshift_backproject_pairs(self, pairs, kind: str = "rgba8") -> np.ndarray:
+        """Back-projection of bound frame pairs[i][1] through the model of stream pairs[i][0], in pair order: "rgba8" -> uint8
+        [n, H, W, 4], "f64" -> float64 [n, H, W].  Any reserved streams, frames may repeat: the frame's histogram is computed once and
+        the trackers of one frame share one pass over its pixels."""
+        p = self._pairs(pairs)
+        n = len(p)
+        k = self._BP_KINDS.get(kind, kind)
+        shape = (n, self.height, self.width) if k == native.HT_BP_F64 else (n, self.height, self.width, 4)
+        out = np.zeros(shape if n > 0 else (0,), dtype=np.float64 if k == native.HT_BP_F64 else np.uint8)
+        self._check(self._lib.ht_camshift_backproject_pairs(self._h, p.ctypes.data, n, int(k), out.ctypes.data, 0))
+        return out
+
+    def camshift_backproject_pairs_device(self, dev_ptr: int, pairs, kind: str = "rgba8", stride: int = 0):
+        """The same into device memory at dev_ptr (outputs `stride` bytes apart, 0 = packed): enqueued on the context's stream, no copy,
+        no wait."""
+        p = self._pairs(pairs)
+        self._check(self._lib.ht_camshift_backproject_pairs_device(self._h, p.ctypes.data, len(p), int(self._BP_KINDS.get(kind, kind)), dev_ptr, stride))
+
     # -- measurement --------------------------------------------------------------------------------------------
     def profile(self, on: bool = True):
         self._check(self._lib.ht_profile(self._h, int(on)))

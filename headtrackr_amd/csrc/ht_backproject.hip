@@ -149,16 +149,33 @@ ht_status bp_check(ht_ctx *c, const char *fn, int32_t first, int32_t n, int32_t 
     return HT_OK;
 }
 
+// scratch of this unit, grown on demand, for both forms of the call (batch and pairs): the chunk histograms of `frames` frames and
+// `luts` LUTs of either kind
+ht_status bp_scratch(ht_ctx *c, size_t frames, uint32_t nchunks, size_t luts) {
+    ht_status st = ht_grow_device(c, &c->d_bp_hist, &c->bp_hist_cap, frames * nchunks * 4096, "ht_camshift_backproject: hipMalloc failed (chunk histograms)");
+    if (st == HT_OK) st = ht_grow_device(c, &c->d_bp_lut_w, &c->bp_lut_w_cap, luts * 4096, "ht_camshift_backproject: hipMalloc failed (weight LUTs)");
+    if (st == HT_OK) st = ht_grow_device(c, &c->d_bp_lut_px, &c->bp_lut_px_cap, luts * 4096, "ht_camshift_backproject: hipMalloc failed (pixel LUTs)");
+    return st;
+}
+
+// the host forms' result on the device (packed), then to the caller with the caller's stride; waits
+ht_status bp_staging(ht_ctx *c, size_t bytes) {
+    return ht_grow_device(c, &c->d_bp_out, &c->bp_out_cap, bytes, "ht_camshift_backproject: hipMalloc failed (output staging)");
+}
+ht_status bp_copy_out(ht_ctx *c, void *out_host, size_t stride, size_t frame_bytes, int32_t n) {
+    if (stride == frame_bytes) HT_HIP(c, hipMemcpyAsync(out_host, c->d_bp_out, (size_t)n * frame_bytes, hipMemcpyDeviceToHost, c->stream));
+    else HT_HIP(c, hipMemcpy2DAsync(out_host, stride, c->d_bp_out, frame_bytes, frame_bytes, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HT_HIP(c, hipStreamSynchronize(c->stream));
+    return HT_OK;
+}
+
 // the three launches; d_out: device memory, n frames `stride` bytes apart
 ht_status bp_enqueue(ht_ctx *c, int32_t first, int32_t n, int32_t kind, void *d_out, size_t stride) {
     const uint32_t npix = (uint32_t)((size_t)c->W * c->H);
     if (npix == 0) return HT_OK;
     uint32_t chunk_px = 0, nchunks = 0;
     ht_cs_hist_plan(npix, n, &chunk_px, &nchunks);
-    // scratch of this unit, grown on demand
-    ht_status st = ht_grow_device(c, &c->d_bp_hist, &c->bp_hist_cap, (size_t)n * nchunks * 4096, "ht_camshift_backproject: hipMalloc failed (chunk histograms)");
-    if (st == HT_OK) st = ht_grow_device(c, &c->d_bp_lut_w, &c->bp_lut_w_cap, (size_t)n * 4096, "ht_camshift_backproject: hipMalloc failed (weight LUTs)");
-    if (st == HT_OK) st = ht_grow_device(c, &c->d_bp_lut_px, &c->bp_lut_px_cap, (size_t)n * 4096, "ht_camshift_backproject: hipMalloc failed (pixel LUTs)");
+    ht_status st = bp_scratch(c, (size_t)n, nchunks, (size_t)n);
     if (st != HT_OK) return st;
     {
         HtProfScope ps(c, "cs_bp_hist");
@@ -203,14 +220,11 @@ extern "C" ht_status ht_camshift_backproject(ht_ctx *c, int32_t first, int32_t n
     if (st != HT_OK) return st;
     if (frame_bytes == 0) return HT_OK;
     HT_HIP(c, hipSetDevice(c->device));
-    st = ht_grow_device(c, &c->d_bp_out, &c->bp_out_cap, (size_t)n * frame_bytes, "ht_camshift_backproject: hipMalloc failed (output staging)");
+    st = bp_staging(c, (size_t)n * frame_bytes);
     if (st != HT_OK) return st;
     st = bp_enqueue(c, first, n, kind, c->d_bp_out, frame_bytes);  // packed on the device; the caller's stride is applied by the copy
     if (st != HT_OK) return st;
-    if (stride == frame_bytes) HT_HIP(c, hipMemcpyAsync(out_host, c->d_bp_out, (size_t)n * frame_bytes, hipMemcpyDeviceToHost, c->stream));
-    else HT_HIP(c, hipMemcpy2DAsync(out_host, stride, c->d_bp_out, frame_bytes, frame_bytes, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HT_HIP(c, hipStreamSynchronize(c->stream));
-    return HT_OK;
+    return bp_copy_out(c, out_host, stride, frame_bytes, n);
 }
 
 void ht_backproject_free(ht_ctx *c) {  // ht_destroy (the stream has been synchronised)
@@ -229,3 +243,7 @@ void ht_backproject_free(ht_ctx *c) {  // ht_destroy (the stream has been synchr
 // So are the pair forms of the camshift calls (ht_camshift_init_pairs / ht_camshift_track_pairs, k_csp_*): new kernels must not enter the
 // fingerprinted camshift object, and the library keeps four code objects.
 #include "ht_cs_pairs.hip"
+
+// And the back-projection over pairs (ht_camshift_backproject_pairs / _device, k_bpp_*), behind the pair unit whose plan, table upload and
+// histogram kernel it uses.
+#include "ht_bp_pairs.hip"

@@ -77,11 +77,13 @@ ht_status csp_plan(ht_ctx *c, const char *fn, const ht_cs_pair *pairs, int32_t n
 
 // the call's table -> device (entries, then the distinct frames): staged in a pinned buffer, copied on the context's stream in front of
 // the kernels that read it.  HT_CSP_STAGE staging buffers take turns, so a call practically never waits for an earlier call's copy.
-ht_status csp_upload(ht_ctx *c, const char *fn, const CspPlan &plan, const CspEntry **d_entries, const int32_t **d_frames) {
-    const size_t n = plan.entries.size(), words = n * (sizeof(CspEntry) / 4) + plan.frames.size();
+// ht_bp_pairs.hip sends its group records along (`extra`, extra_words 32-bit words behind the frame list; at most 8 per pair).
+ht_status csp_upload(ht_ctx *c, const char *fn, const CspPlan &plan, const CspEntry **d_entries, const int32_t **d_frames, const void *extra = nullptr,
+                     size_t extra_words = 0, const int32_t **d_extra = nullptr) {
+    const size_t n = plan.entries.size(), base_words = n * (sizeof(CspEntry) / 4) + plan.frames.size(), words = base_words + extra_words;
     if (c->csp_tab_cap < words || c->h_csp_tab_cap < words) {
         HT_HIP(c, hipStreamSynchronize(c->stream));
-        const size_t cap = std::max(words, (size_t)c->cs_streams * (sizeof(CspEntry) / 4 + 1));
+        const size_t cap = std::max(words, (size_t)c->cs_streams * (2 * sizeof(CspEntry) / 4 + 1));  // entry + frame + group record per stream
         if (c->d_csp_tab) (void)hipFree(c->d_csp_tab);
         c->d_csp_tab = nullptr, c->csp_tab_cap = 0;
         for (auto &h : c->h_csp_tab) {
@@ -105,10 +107,12 @@ ht_status csp_upload(ht_ctx *c, const char *fn, const CspPlan &plan, const CspEn
     HT_HIP(c, hipEventSynchronize(c->ev_csp_tab[k]));  // never recorded: returns at once
     std::memcpy(c->h_csp_tab[k], plan.entries.data(), n * sizeof(CspEntry));
     std::memcpy(c->h_csp_tab[k] + n * (sizeof(CspEntry) / 4), plan.frames.data(), plan.frames.size() * 4);
+    if (extra_words) std::memcpy(c->h_csp_tab[k] + base_words, extra, extra_words * 4);
     HT_HIP(c, hipMemcpyAsync(c->d_csp_tab, c->h_csp_tab[k], words * 4, hipMemcpyHostToDevice, c->stream));
     HT_HIP(c, hipEventRecord(c->ev_csp_tab[k], c->stream));
     *d_entries = reinterpret_cast<const CspEntry *>(c->d_csp_tab);
     *d_frames = c->d_csp_tab + n * (sizeof(CspEntry) / 4);
+    if (d_extra) *d_extra = c->d_csp_tab + base_words;
     return HT_OK;
 }
 

@@ -33,6 +33,8 @@
 //   camshiftSequenceCollect(ctx, n, ncalls, outAll) -> Float64Array
 //   camshiftBackProject(ctx, n, first, kind) -> Uint8Array(4 n w h) (BP_RGBA8) | Float64Array(n w h) (BP_F64): back-projection of the bound frames
 //   camshiftBackProjectDevice(ctx, n, first, kind, dev, byteOffset, stride)   the same into a deviceAlloc() buffer, enqueue only
+//   camshiftBackProjectPairs(ctx, Int32Array pairs, kind) -> Uint8Array(4 n w h) | Float64Array(n w h): bound frame pairs[2i + 1] through stream pairs[2i]
+//   camshiftBackProjectPairsDevice(ctx, Int32Array pairs, kind, dev, byteOffset, stride)   the same into a deviceAlloc() buffer, enqueue only
 //   drawFrames(ctx, Uint8Array rgba, n, sw, sh, Int32Array rect[4] | null)   ht_draw_frames: the loop's video -> canvas drawImage (main.js:170) of n host
 //        frames of sw x sh onto the context's geometry, on the device; the result becomes the bound frames
 //   drawFramesDevice(ctx, srcDev, srcOffset, n, sw, sh, pitch, stride, rect | null, dstDev | null, dstOffset, dstStride, wait)   ht_draw_frames_device between
@@ -1209,6 +1211,69 @@ napi_value CamshiftBackProjectDevice(napi_env env, napi_callback_info info) {
     return nullptr;
 }
 
+// camshiftBackProjectPairs(ctx, Int32Array pairs[2n], kind) -> Uint8Array(n*w*h*4) | Float64Array(n*w*h): ht_camshift_backproject_pairs — output i is
+// bound frame pairs[2i + 1] through the model of stream pairs[2i]
+napi_value CamshiftBackProjectPairs(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Locked L;
+    const ht_cs_pair *pairs = nullptr;
+    int32_t n = 0, kind = 0;
+    if (too_few(env, argc, 3) || !lock_ctx(env, argv[0], &L)) return nullptr;
+    if (!get_pairs(env, argv[1], &pairs, &n) || !get_i32(env, argv[2], &kind) || (kind != HT_BP_RGBA8 && kind != HT_BP_F64)) {
+        napi_throw_type_error(env, nullptr, "camshiftBackProjectPairs(ctx, Int32Array pairs[2n], kind = BP_RGBA8 | BP_F64)");
+        return nullptr;
+    }
+    ht_plane_info pl;  // level 0 of the pyramid is the frame itself
+    if (ht_plane(L.ctx, 0, 0, &pl) != HT_OK || pl.width <= 0 || pl.height <= 0) {
+        napi_throw_error(env, nullptr, "camshiftBackProjectPairs: no geometry (setGeometry first)");
+        return nullptr;
+    }
+    const size_t elem = kind == HT_BP_F64 ? 8 : 4, count = (size_t)n * (size_t)pl.width * (size_t)pl.height;
+    napi_value ab, ta;
+    void *p = nullptr;
+    NAPI_OK(napi_create_arraybuffer(env, count * elem, &p, &ab));
+    // the stride is passed explicitly: the library refuses one that is smaller than ITS frame, so the buffer can never be too small
+    ht_status st = ht_camshift_backproject_pairs(L.ctx, pairs, n, kind, p, (size_t)pl.width * (size_t)pl.height * elem);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_backproject_pairs");
+    if (kind == HT_BP_F64) NAPI_OK(napi_create_typedarray(env, napi_float64_array, count, ab, 0, &ta));
+    else NAPI_OK(napi_create_typedarray(env, napi_uint8_array, count * 4, ab, 0, &ta));
+    return ta;
+}
+
+// camshiftBackProjectPairsDevice(ctx, Int32Array pairs[2n], kind, dev, byteOffset, stride): the same into a deviceAlloc() buffer, enqueue only
+napi_value CamshiftBackProjectPairsDevice(napi_env env, napi_callback_info info) {
+    size_t argc = 6;
+    napi_value argv[6];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Locked L;
+    DevBuf *d = nullptr;
+    const ht_cs_pair *pairs = nullptr;
+    int32_t n = 0, kind = 0;
+    size_t off = 0, stride = 0;
+    if (too_few(env, argc, 6) || !lock_ctx(env, argv[0], &L)) return nullptr;
+    if (!get_pairs(env, argv[1], &pairs, &n) || !get_i32(env, argv[2], &kind) || (kind != HT_BP_RGBA8 && kind != HT_BP_F64)) {
+        napi_throw_type_error(env, nullptr, "camshiftBackProjectPairsDevice(ctx, Int32Array pairs[2n], kind = BP_RGBA8 | BP_F64, dev, byteOffset, stride)");
+        return nullptr;
+    }
+    if (!get_devbuf(env, argv[3], &d)) return nullptr;
+    ht_plane_info pl;
+    if (ht_plane(L.ctx, 0, 0, &pl) != HT_OK || pl.width <= 0 || pl.height <= 0) {
+        napi_throw_error(env, nullptr, "camshiftBackProjectPairsDevice: no geometry (setGeometry first)");
+        return nullptr;
+    }
+    const size_t frame = (size_t)pl.width * (size_t)pl.height * (kind == HT_BP_F64 ? 8 : 4);
+    if (!get_offset(env, argv[4], &off) || !get_offset(env, argv[5], &stride) || (stride != 0 && stride < frame) ||
+        off + (size_t)(n - 1) * (stride ? stride : frame) + frame > d->bytes) {
+        napi_throw_range_error(env, nullptr, "camshiftBackProjectPairsDevice(ctx, pairs, kind, dev, byteOffset, stride): outside the device buffer");
+        return nullptr;
+    }
+    ht_status st = ht_camshift_backproject_pairs_device(L.ctx, pairs, n, kind, static_cast<char *>(d->ptr) + off, stride ? stride : frame);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_backproject_pairs_device");
+    return nullptr;
+}
+
 // rect argument of the draw calls: null / undefined (the whole source frame) or an Int32Array [x, y, width, height]
 bool get_rect(napi_env env, napi_value v, ht_cs_rect *r, const ht_cs_rect **out) {
     napi_valuetype vt;
@@ -1330,6 +1395,7 @@ napi_value Init(napi_env env, napi_value exports) {
                {"camshiftInitPairs", CamshiftInitPairs}, {"camshiftTrackPairs", CamshiftTrackPairs},
                {"camshiftTrackSequence", CamshiftTrackSequence}, {"camshiftSequenceCollect", CamshiftSequenceCollect},
                {"camshiftBackProject", CamshiftBackProject}, {"camshiftBackProjectDevice", CamshiftBackProjectDevice},
+               {"camshiftBackProjectPairs", CamshiftBackProjectPairs}, {"camshiftBackProjectPairsDevice", CamshiftBackProjectPairsDevice},
                {"drawFrames", DrawFrames},       {"drawFramesDevice", DrawFramesDevice},
                {"framesBound", FramesBound},     {"framesEnqueued", FramesEnqueued}, {"graphLaunches", GraphLaunches}};
     for (auto &f : fns) {

@@ -12,7 +12,8 @@
  *                                                                            seq construction + grouping stay in JS
  *   ccv.array_group(seq,gfunc)                          ccv.js:34-107    (host, O(n^2) on a few dozen rects)
  *   camshift.Tracker / Histogram / Moments / Rectangle / TrackObj          camshift.js:49-378 -> ht_camshift_*
- *   camshift.MultiTracker                               several trackers on one canvas, one device call per frame -> ht_camshift_*_pairs
+ *   camshift.MultiTracker                               several trackers on one canvas, one device call per frame -> ht_camshift_*_pairs;
+ *                                                       getBackProjectionImg(i) / getBackProjectionImgs() / getPdf(i) -> ht_camshift_backproject_pairs
  *   facetrackr.Tracker / TrackObj                       facetrackr.js:37-255  (state machine WB -> VJ -> CS)
  *   getWhitebalance(canvas)                             whitebalance.js:5-30 -> ht_whitebalance_batch
  * plus batch entry points that the single-frame browser API has no room for:
@@ -392,6 +393,7 @@ headtrackr.ccv.detect_objects_batch = function (frames, n, w, h, cascade, interv
  *                                           contexts read the work set on streams of their own
  *     drawBound(sset, rect)                the same into context 0's own frame buffer, which becomes its bound frames: follow with the step
  *                                           functions at set = -1
+ *     backProjectionPairs(set, pairs, kind) -> the same per (tracker, frame) pair, pair order: ht_camshift_backproject_pairs
  *     initPairs / trackPairs / trackPairsEnqueue / detectStepFinish(min_neighbors, {feeds})   trackers and frames paired freely (below);
                                            opts.trackers = tracker slots to reserve (default n)
      destroy() */
@@ -565,6 +567,17 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     bind0(set === undefined ? 0 : set);
     return A.camshiftBackProject(ctxs[0], n, 0, kind === 'f64' ? A.BP_F64 : A.BP_RGBA8);
   };
+  /* output i: frame pairs[2i + 1] of `set` through the model of tracker pairs[2i] (ht_camshift_backproject_pairs) — the trackers of one
+   * frame share its histogram and one pass over its pixels; the result is laid out like backProjection's, in pair order */
+  this.backProjectionPairs = function (set, pairs, kind) {
+    if (typeof A.camshiftBackProjectPairs !== 'function')
+      throw new Error('DeviceBatch.backProjectionPairs: this headtrackr_hip.node has no camshiftBackProjectPairs (rebuild it)');
+    pairList('backProjectionPairs', pairs);
+    if (!trackers) throw new Error('DeviceBatch.backProjectionPairs: no trackers yet (initPairs, initTrackers or detectStep first)');
+    if (kind !== undefined && kind !== 'rgba8' && kind !== 'f64') throw new RangeError("DeviceBatch.backProjectionPairs: kind is 'rgba8' or 'f64'");
+    bind0(set === undefined ? 0 : set);
+    return A.camshiftBackProjectPairs(ctxs[0], pairs, kind === 'f64' ? A.BP_F64 : A.BP_RGBA8);
+  };
   const source = opts.source || null;
   const ssetBytes = source ? n * source.width * source.height * 4 : 0;
   const sdev = source ? A.deviceAlloc(ctxs[0], Math.max(1, source.sets || 1) * ssetBytes) : null;
@@ -660,6 +673,45 @@ function csSlot() {
 }
 headtrackr.camshift._pool = csPool; /* exposed for tests */
 
+/* getPdf() on the host (camshift.js:198-211, 314-353): `last` through the model of rect `mr` on `mframe` (both ImageData) */
+function hostPdf(last, mframe, mr) {
+  const w = last.width, h = last.height, d = last.data;
+  const mw = mframe.width, mh = mframe.height, md = mframe.data;
+  const model = new Uint32Array(4096);
+  for (let y = mr.y; y < mr.y + mr.height; y++) {
+    for (let x = mr.x; x < mr.x + mr.width; x++) {
+      if (x >= 0 && x < mw && y >= 0 && y < mh) {
+        const p = (y * mw + x) * 4;
+        model[256 * (md[p] >> 4) + 16 * (md[p + 1] >> 4) + (md[p + 2] >> 4)]++;
+      } else model[0]++;
+    }
+  }
+  const cur = new headtrackr.camshift.Histogram(d);
+  const weights = new Float64Array(4096);
+  for (let i = 0; i < 4096; i++) weights[i] = cur.getBin(i) !== 0 ? Math.min(model[i] / cur.getBin(i), 1) : 0;
+  const data = [];
+  for (let x = 0; x < w; x++) {
+    const col = [];
+    for (let y = 0; y < h; y++) {
+      const p = (y * w + x) * 4;
+      col.push(weights[256 * (d[p] >> 4) + 16 * (d[p + 1] >> 4) + (d[p + 2] >> 4)]);
+    }
+    data[x] = col;
+  }
+  return data;
+}
+/* getBackProjectionImg() from a pdf (camshift.js:177-196) */
+function pdfToImg(ctx2d, pdf, w, h) {
+  const img = ctx2d.createImageData(w, h), out = img.data;
+  for (let x = 0; x < w; x++) {
+    for (let y = 0; y < h; y++) {
+      const v = Math.floor(255 * pdf[x][y]), p = (y * w + x) * 4;
+      out[p] = v; out[p + 1] = v; out[p + 2] = v; out[p + 3] = 255;
+    }
+  }
+  return img;
+}
+
 headtrackr.camshift.Tracker = function (params) { /* camshift.js:148-354 */
   if (params === undefined) params = {};
   if (params.calcAngles === undefined) params.calcAngles = true;
@@ -703,30 +755,7 @@ headtrackr.camshift.Tracker = function (params) { /* camshift.js:148-354 */
    * whatever the source —, so it is rebuilt here from the last frame; getBackProjectionImg's bytes come from the device (below) */
   this.getPdf = function () {
     if (!lastFrame || !modelFrame) return undefined;
-    const w = lastFrame.width, h = lastFrame.height, d = lastFrame.data;
-    const mr = modelRect, mw = modelFrame.width, mh = modelFrame.height, md = modelFrame.data;
-    const model = new Uint32Array(4096);
-    for (let y = mr.y; y < mr.y + mr.height; y++) {
-      for (let x = mr.x; x < mr.x + mr.width; x++) {
-        if (x >= 0 && x < mw && y >= 0 && y < mh) {
-          const p = (y * mw + x) * 4;
-          model[256 * (md[p] >> 4) + 16 * (md[p + 1] >> 4) + (md[p + 2] >> 4)]++;
-        } else model[0]++;
-      }
-    }
-    const cur = new headtrackr.camshift.Histogram(d);
-    const weights = new Float64Array(4096);
-    for (let i = 0; i < 4096; i++) weights[i] = cur.getBin(i) !== 0 ? Math.min(model[i] / cur.getBin(i), 1) : 0;
-    const data = [];
-    for (let x = 0; x < w; x++) {
-      const col = [];
-      for (let y = 0; y < h; y++) {
-        const p = (y * w + x) * 4;
-        col.push(weights[256 * (d[p] >> 4) + 16 * (d[p + 1] >> 4) + (d[p + 2] >> 4)]);
-      }
-      data[x] = col;
-    }
-    return data;
+    return hostPdf(lastFrame, modelFrame, modelRect);
   };
 
   this.getBackProjectionImg = function () {
@@ -742,16 +771,7 @@ headtrackr.camshift.Tracker = function (params) { /* camshift.js:148-354 */
         return img;
       } finally { if (mine) unbindFrames(); }
     }
-    const pdf = this.getPdf();
-    const w = lastFrame.width, h = lastFrame.height;
-    const img = canvasCtx.createImageData(w, h), out = img.data;
-    for (let x = 0; x < w; x++) {
-      for (let y = 0; y < h; y++) {
-        const v = Math.floor(255 * pdf[x][y]), p = (y * w + x) * 4;
-        out[p] = v; out[p + 1] = v; out[p + 2] = v; out[p + 3] = 255;
-      }
-    }
-    return img;
+    return pdfToImg(canvasCtx, this.getPdf(), lastFrame.width, lastFrame.height);
   };
 
   /* not in the reference: returns the device slot (idempotent).  facetrackr.Tracker.release() calls it when the facade
@@ -765,11 +785,17 @@ headtrackr.camshift.Tracker = function (params) { /* camshift.js:148-354 */
  * times).  Results equal M camshift.Tracker instances on that canvas; the slots come from the same pool.
  *   initTracker(canvas, rects)   rects: array of camshift.Rectangle (or {x, y, width, height}), one tracker each (camshift.js:198-211)
  *   track(canvas)                one track() of every tracker (camshift.js:213-353)
- *   getTrackObj(i) / getSearchWindow(i) / release() */
+ *   getTrackObj(i) / getSearchWindow(i) / release()
+ *   getBackProjectionImg(i)      ImageData: the last tracked canvas through tracker i's model (camshift.js:177-196)
+ *   getBackProjectionImgs()      all of them, in ONE device call (ht_camshift_backproject_pairs: the canvas is read once per 4 trackers)
+ *   getPdf(i)                    the reference's [x][y] arrays (camshift.js:172-175), rebuilt from the device's binary64 output
+ * The getters re-bind the last canvas and unbind it afterwards, like camshift.Tracker.getBackProjectionImg; with an addon that lacks
+ * camshiftBackProjectPairs they run the host loop, with the same result.  Before the first track() they return undefined. */
 headtrackr.camshift.MultiTracker = function (params) {
   if (params === undefined) params = {};
   if (params.calcAngles === undefined) params.calcAngles = true;
   let slots = [], pairs = null, windows = [], objs = [];
+  let lastFrame = null, modelFrame = null, modelRects = [], canvasCtx = null;
   const needPairs = function () {
     if (typeof addon().camshiftInitPairs !== 'function' || typeof addon().camshiftTrackPairs !== 'function')
       throw new Error('camshift.MultiTracker: this headtrackr_hip.node has no camshiftInitPairs / camshiftTrackPairs (rebuild it)');
@@ -777,7 +803,50 @@ headtrackr.camshift.MultiTracker = function (params) {
   this.count = function () { return slots.length; };
   this.getSearchWindow = function (i) { return windows[i].clone(); };
   this.getTrackObj = function (i) { return objs[i].clone(); };
-  this.release = function () { slots.forEach(function (s) { csPool.free.push(s); }); slots = []; pairs = null; windows = []; objs = []; };
+  this.release = function () {
+    slots.forEach(function (s) { csPool.free.push(s); });
+    slots = []; pairs = null; windows = []; objs = []; lastFrame = null; modelFrame = null; modelRects = []; canvasCtx = null;
+  };
+  /* the bytes of the device call for trackers [first, first + m): Uint8Array(4 m w h) or Float64Array(m w h) */
+  const deviceBp = function (first, m, kind) {
+    try {
+      bindFrame(csPool.ctx, lastFrame, headtrackr.cascade, 5);
+      return addon().camshiftBackProjectPairs(csPool.ctx.handle, pairs.subarray(2 * first, 2 * (first + m)), kind);
+    } finally { unbindFrames(); }
+  };
+  const onDevice = function () { return typeof addon().camshiftBackProjectPairs === 'function' && modelFrame.width > 0 && modelFrame.height > 0; };
+  const imgsOf = function (first, m) {
+    if (!lastFrame || !modelFrame) return undefined;
+    const w = lastFrame.width, h = lastFrame.height, out = [];
+    if (onDevice()) {
+      const bytes = deviceBp(first, m, addon().BP_RGBA8);
+      for (let i = 0; i < m; i++) {
+        const img = canvasCtx.createImageData(w, h);
+        img.data.set(bytes.subarray(4 * w * h * i, 4 * w * h * (i + 1)));
+        out.push(img);
+      }
+    } else {
+      for (let i = first; i < first + m; i++) out.push(pdfToImg(canvasCtx, hostPdf(lastFrame, modelFrame, modelRects[i]), w, h));
+    }
+    return out;
+  };
+  const tracker = function (what, i) {
+    if (!(i >= 0 && i < slots.length && Math.floor(i) === i)) throw new RangeError('camshift.MultiTracker.' + what + '(i): i is 0 .. count() - 1');
+  };
+  this.getBackProjectionImg = function (i) { tracker('getBackProjectionImg', i); const r = imgsOf(i, 1); return r && r[0]; };
+  this.getBackProjectionImgs = function () { return imgsOf(0, slots.length); };
+  this.getPdf = function (i) {
+    tracker('getPdf', i);
+    if (!lastFrame || !modelFrame) return undefined;
+    if (!onDevice()) return hostPdf(lastFrame, modelFrame, modelRects[i]);
+    const w = lastFrame.width, h = lastFrame.height, v = deviceBp(i, 1, addon().BP_F64), data = [];
+    for (let x = 0; x < w; x++) {
+      const col = [];
+      for (let y = 0; y < h; y++) col.push(v[y * w + x]);
+      data[x] = col;
+    }
+    return data;
+  };
   this.initTracker = function (canvas, rects) {
     needPairs();
     if (!rects || !rects.length) throw new TypeError('camshift.MultiTracker.initTracker(canvas, rects): at least one rect');
@@ -789,9 +858,12 @@ headtrackr.camshift.MultiTracker = function (params) {
       pairs[2 * i] = slots[i]; pairs[2 * i + 1] = 0;
       rc[4 * i] = r.x; rc[4 * i + 1] = r.y; rc[4 * i + 2] = r.width; rc[4 * i + 3] = r.height;
       windows.push(new headtrackr.camshift.Rectangle(r.x, r.y, r.width, r.height));
+      modelRects.push(new headtrackr.camshift.Rectangle(r.x, r.y, r.width, r.height));
       objs.push(new headtrackr.camshift.TrackObj());
     });
-    const img = canvas.getContext('2d').getImageData(0, 0, canvas.width, canvas.height);
+    canvasCtx = canvas.getContext('2d');
+    const img = canvasCtx.getImageData(0, 0, canvas.width, canvas.height);
+    modelFrame = img;
     if (!(img.width > 0 && img.height > 0)) return;
     try {
       bindFrame(csPool.ctx, img, headtrackr.cascade, 5);
@@ -802,6 +874,7 @@ headtrackr.camshift.MultiTracker = function (params) {
     if (!pairs) throw new Error('camshift.MultiTracker.track: initTracker first');
     const img = canvas.getContext('2d').getImageData(0, 0, canvas.width, canvas.height);
     if (img.width === 0 || img.height === 0) return; /* camshift.js:219 */
+    lastFrame = img;
     let r;
     try {
       bindFrame(csPool.ctx, img, headtrackr.cascade, 5);

@@ -311,6 +311,16 @@ ht_status ht_camshift_backproject(ht_ctx *ctx, int32_t first, int32_t n, int32_t
 /* The same into device memory (pointer and stride multiples of the element size: 4 bytes for HT_BP_RGBA8, 8 for HT_BP_F64): enqueued on the
  * ctx stream behind the outstanding track steps, never copies or waits. */
 ht_status ht_camshift_backproject_device(ht_ctx *ctx, int32_t first, int32_t n, int32_t kind, void *out_dev, size_t out_stride);
+/* The same two calls over an arbitrary list of (stream, frame) pairs: output i is bound frame pairs[i].frame through the model of stream
+ * pairs[i].stream (every tracker of one canvas, or the tracking feeds of a host whose feeds are in different states).  kind, stride,
+ * alignment and blocking / enqueue-only behaviour as above; the pair list obeys the rules of ht_camshift_track_pairs, and every check
+ * happens before anything is enqueued.  The frame histogram is computed once per DISTINCT frame, and pairs that share a frame share one
+ * pass over its pixels (groups of 4 for HT_BP_RGBA8, of 2 for HT_BP_F64).  Pairs (first + i, i) ARE the batch call above (option
+ * cs_pairs_force=1 sends them through the pair kernels).  Uses the back-projection's own scratch: it may sit between enqueue-only pair or
+ * batch track steps and changes nothing they or ht_camshift_stats / ht_camshift_debug_hist read.  The bytes are those of the batch call
+ * on replicated frames. */
+ht_status ht_camshift_backproject_pairs(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, int32_t kind, void *out_host, size_t out_stride);
+ht_status ht_camshift_backproject_pairs_device(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, int32_t kind, void *out_dev, size_t out_stride);
 
 /* ---- multi-GPU: fixed-size result records, all-gathered over RCCL/xGMI ------------------------------------ */
 
