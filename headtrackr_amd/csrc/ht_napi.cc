@@ -1,9 +1,10 @@
 // ht_napi.cc — thin N-API (raw node_api.h, no node-addon-api) shim over the C ABI in include/headtrackr_hip.h.
 // It contains no algorithm: argument unpacking, one C-ABI call, result packing.  The JavaScript facade
 // (headtrackr_amd/js/headtrackr.js) builds the reference's API (headtrackr.ccv / camshift / facetrackr) on top of it.
+// This comment is the one list of the JavaScript signatures; the usage strings in the error messages repeat them.
 //
-//   createContext({device, interval, cascade:<Buffer HTCB>, hitCapacity, queueCapacity}) -> ctx (external)
-//   destroy(ctx)
+//   createContext({device, interval, cascade:<Buffer HTCB>, hitCapacity, queueCapacity, options}) -> ctx (external)
+//   destroy(ctx)                                          exitNow(code): destroys every live context and leaves with _exit
 //   setGeometry(ctx, w, h, maxBatch, Int32Array levelDims | null)
 //   detect(ctx, Uint8Array rgba, n, w, h, flags)        -> {frame,x,y,scale,q,sum, counts}   (sync; the drop-in path)
 //   detectAsync(ctx, rgba, n, w, h, flags)              -> Promise of the same              (napi_create_async_work)
@@ -18,23 +19,26 @@
 //        -> Float64Array(6 * nranks * framesPerRank): every rank's best-face rects after the RCCL all-gather (ht_allgather_best_faces)
 //
 // The pipelined path (what the throughput numbers are made of; every C-ABI export has a JS name):
-//   hostAlloc(bytes) -> Uint8Array over PINNED host memory (ht_host_alloc)         deviceAlloc(ctx, bytes) -> device buffer (external)
-//   deviceUpload(ctx, dev, byteOffset, Uint8Array)      deviceFree(ctx, dev)
+//   hostAlloc(bytes) -> Uint8Array over PINNED host memory (ht_host_alloc)         hostFree(Uint8Array returned by hostAlloc)
+//   deviceAlloc(ctx, bytes) -> device buffer (external)    deviceFree(ctx, dev)
+//   deviceUpload(ctx, dev, byteOffset, Uint8Array)
 //   deviceDownload(ctx, dev, byteOffset, Uint8Array)    ht_device_download: fills the array from the buffer, behind the enqueued work; waits
 //   upload(ctx, rgba, n, w, h)            ht_upload_frames: bind host frames once, then any number of *Bound calls on them
-//   bindDevice(ctx, dev, byteOffset, n)   ht_bind_frames_device
+//   bindDevice(ctx, dev, byteOffset, n, frameStride)     ht_bind_frames_device
 //   uploadAsync(ctx, rgba, n) / swapFrames(ctx)          double-buffered ingest (rgba should come from hostAlloc)
 //   detectEnqueue(ctx, flags)             ht_detect_enqueue           detectCollect(ctx) -> hits object (ht_detect_collect)
 //   collectBest(ctx, minNeighbors, requeueFlags = -1) -> {best: Float64Array(6 n), hits}   ht_detect_collect_best(_requeue)
 //   detectWhitebalance(ctx, n) -> Float64Array(n)        whitebalanceBound(ctx, n) -> Float64Array(n)
-//   camshiftInitBound(ctx, n, first, Int32Array rects)   camshiftTrackBound(ctx, n, first, calcAngles, fetch = true) -> Float64Array(9n) | undefined
+//   camshiftInitBound(ctx, n, first, Int32Array rects[4n])   camshiftTrackBound(ctx, n, first, calcAngles, fetch = true) -> Float64Array(9n) | undefined
 //   camshiftTrackCollect(ctx, n) -> Float64Array(9n)
-//   camshiftTrackSequence(ctx, first, n, calcAngles, dev, Float64Array byteOffsets[ncalls], frameStride, outAll, fetch) -> Float64Array | undefined
+//   camshiftInitPairs(ctx, Int32Array pairs[2n], Int32Array rects[4n])   pairs = stream0, frame0, stream1, frame1, ... (ht_cs_pair)
+//   camshiftTrackPairs(ctx, Int32Array pairs[2n], calcAngles, fetch = true) -> Float64Array(9n) | undefined
+//   camshiftTrackSequence(ctx, first, n, calcAngles, dev, Float64Array byteOffsets, frameStride, outAll, fetch) -> Float64Array | undefined
 //   camshiftSequenceCollect(ctx, n, ncalls, outAll) -> Float64Array
 //   camshiftBackProject(ctx, n, first, kind) -> Uint8Array(4 n w h) (BP_RGBA8) | Float64Array(n w h) (BP_F64): back-projection of the bound frames
 //   camshiftBackProjectDevice(ctx, n, first, kind, dev, byteOffset, stride)   the same into a deviceAlloc() buffer, enqueue only
-//   camshiftBackProjectPairs(ctx, Int32Array pairs, kind) -> Uint8Array(4 n w h) | Float64Array(n w h): bound frame pairs[2i + 1] through stream pairs[2i]
-//   camshiftBackProjectPairsDevice(ctx, Int32Array pairs, kind, dev, byteOffset, stride)   the same into a deviceAlloc() buffer, enqueue only
+//   camshiftBackProjectPairs(ctx, Int32Array pairs[2n], kind) -> Uint8Array(4 n w h) | Float64Array(n w h): bound frame pairs[2i + 1] through stream pairs[2i]
+//   camshiftBackProjectPairsDevice(ctx, Int32Array pairs[2n], kind, dev, byteOffset, stride)   the same into a deviceAlloc() buffer, enqueue only
 //   drawFrames(ctx, Uint8Array rgba, n, sw, sh, Int32Array rect[4] | null)   ht_draw_frames: the loop's video -> canvas drawImage (main.js:170) of n host
 //        frames of sw x sh onto the context's geometry, on the device; the result becomes the bound frames
 //   drawFramesDevice(ctx, srcDev, srcOffset, n, sw, sh, pitch, stride, rect | null, dstDev | null, dstOffset, dstStride, wait)   ht_draw_frames_device between
@@ -69,6 +73,15 @@ napi_value throw_ht(napi_env env, ht_ctx *ctx, ht_status st, const char *where) 
     napi_throw_error(env, nullptr, msg.c_str());
     return nullptr;
 }
+// throw and return nullptr — "no result" for an entry point, `false` for a helper that returns bool
+napi_value type_error(napi_env env, const char *msg) {
+    napi_throw_type_error(env, nullptr, msg);
+    return nullptr;
+}
+napi_value range_error(napi_env env, const char *msg) {
+    napi_throw_range_error(env, nullptr, msg);
+    return nullptr;
+}
 
 // What the JS side holds (a napi external): the context plus the lock that serialises every use of it.  An ht_ctx is not
 // thread-safe (include/headtrackr_hip.h) but detectAsync() runs on a libuv pool thread while the JS thread may call any
@@ -83,6 +96,13 @@ struct Slot {
     std::recursive_mutex mu;
     napi_env env = nullptr;  // the environment (main thread or a worker_threads Worker) that created the context: its cleanup hook destroys it
 };
+// a device buffer: freed explicitly (deviceFree) or, at the latest, with the context it was allocated on
+struct DevBuf {
+    uint32_t tag = DEVBUF_TAG;
+    Slot *slot = nullptr;  // Slots are never freed (a few bytes per context): a JS handle may outlive destroy()
+    void *ptr = nullptr;
+    size_t bytes = 0;
+};
 
 bool get_slot(napi_env env, napi_value v, Slot **out) {
     void *p = nullptr;
@@ -91,6 +111,16 @@ bool get_slot(napi_env env, napi_value v, Slot **out) {
         return false;
     }
     *out = static_cast<Slot *>(p);
+    return true;
+}
+bool get_devbuf(napi_env env, napi_value v, DevBuf **out) {
+    void *p = nullptr;
+    if (napi_get_value_external(env, v, &p) != napi_ok || !p || static_cast<DevBuf *>(p)->tag != DEVBUF_TAG || !static_cast<DevBuf *>(p)->ptr ||
+        !static_cast<DevBuf *>(p)->slot->ctx) {
+        napi_throw_type_error(env, nullptr, "expected a live device buffer (deviceAlloc) of a live context");
+        return false;
+    }
+    *out = static_cast<DevBuf *>(p);
     return true;
 }
 
@@ -121,30 +151,109 @@ bool too_few(napi_env env, size_t argc, size_t need) {
 
 bool get_i32(napi_env env, napi_value v, int32_t *out) { return napi_get_value_int32(env, v, out) == napi_ok; }
 
+// a typed array's element type, length and storage; get(.., want, min): of that type with at least min elements
+struct View {
+    napi_typedarray_type type;
+    size_t len = 0, off = 0;
+    void *p = nullptr;
+    napi_value ab;
+    bool get(napi_env env, napi_value v) { return napi_get_typedarray_info(env, v, &type, &len, &p, &ab, &off) == napi_ok; }
+    bool get(napi_env env, napi_value v, napi_typedarray_type want, size_t min) { return get(env, v) && type == want && len >= min; }
+    template <class T>
+    const T *as() const { return static_cast<const T *>(p); }
+};
+
 // Uint8Array / Uint8ClampedArray / Buffer -> pointer + length
 bool get_bytes(napi_env env, napi_value v, uint8_t **data, size_t *len) {
     bool is_ta = false;
     if (napi_is_typedarray(env, v, &is_ta) == napi_ok && is_ta) {
-        napi_typedarray_type t;
-        size_t n;
-        void *p;
-        napi_value ab;
-        size_t off;
-        if (napi_get_typedarray_info(env, v, &t, &n, &p, &ab, &off) != napi_ok) return false;
-        if (t != napi_uint8_array && t != napi_uint8_clamped_array && t != napi_int8_array) return false;
-        *data = static_cast<uint8_t *>(p);
-        *len = n;
+        View a;
+        if (!a.get(env, v) || (a.type != napi_uint8_array && a.type != napi_uint8_clamped_array && a.type != napi_int8_array)) return false;
+        *data = static_cast<uint8_t *>(a.p);
+        *len = a.len;
         return true;
     }
     bool is_buf = false;
-    if (napi_is_buffer(env, v, &is_buf) == napi_ok && is_buf) {
-        void *p;
-        if (napi_get_buffer_info(env, v, &p, len) != napi_ok) return false;
-        *data = static_cast<uint8_t *>(p);
-        return true;
-    }
-    return false;
+    void *p;
+    if (napi_is_buffer(env, v, &is_buf) != napi_ok || !is_buf || napi_get_buffer_info(env, v, &p, len) != napi_ok) return false;
+    *data = static_cast<uint8_t *>(p);
+    return true;
 }
+
+// byte offsets and strides arrive as doubles: 0 .. 2.5e11 (more than any device has), checked BEFORE the conversion to size_t
+bool to_offset(double d, size_t *out) {
+    if (!(d >= 0) || d > 2.5e11) return false;
+    *out = (size_t)d;
+    return true;
+}
+bool get_offset(napi_env env, napi_value v, size_t *out) {
+    double d = 0;
+    return napi_get_value_double(env, v, &d) == napi_ok && to_offset(d, out);
+}
+
+// Int32Array pairs[2n] = stream0, frame0, stream1, frame1, ... (ht_cs_pair); *n = pairs
+bool get_pairs(napi_env env, napi_value v, const ht_cs_pair **pairs, int32_t *n) {
+    View a;
+    if (!a.get(env, v, napi_int32_array, 2) || (a.len & 1) || a.len > (size_t)1 << 24) return false;
+    *pairs = a.as<ht_cs_pair>();
+    *n = (int32_t)(a.len / 2);
+    return true;
+}
+
+// rect argument of the draw calls: null / undefined (the whole source frame) or an Int32Array [x, y, width, height]
+bool get_rect(napi_env env, napi_value v, ht_cs_rect *r, const ht_cs_rect **out) {
+    napi_valuetype vt;
+    *out = nullptr;
+    if (napi_typeof(env, v, &vt) == napi_ok && (vt == napi_null || vt == napi_undefined)) return true;
+    View a;
+    if (!a.get(env, v, napi_int32_array, 4)) return false;
+    memcpy(r, a.p, sizeof(*r));
+    *out = r;
+    return true;
+}
+
+// n frames, `stride` bytes apart and `frame` bytes each, from byte `off` of a buffer of `bytes`: off + (n - 1) stride + frame <= bytes.
+// Every range an entry point hands to the library together with a DevBuf's pointer goes through here (the library cannot know the sizes
+// of the buffers the handles stand for).  No product can wrap: a factor is first bounded by a division through the size it has to fit into.
+bool frames_fit(size_t off, size_t n, size_t stride, size_t frame, size_t bytes) {
+    if (off > bytes || frame > bytes - off) return false;
+    return n == 1 || stride <= (bytes - off - frame) / (n - 1);
+}
+
+// One entry point's arguments: napi_get_cb_info once for the `max` arguments of its signature (13 = the longest, drawFramesDevice; those
+// of them that the caller left out read as undefined; argv[max] and beyond are never read), the arity check, and typed getters by argument
+// index.  Lives on the stack of the entry point: this is the Node host's per-frame path.
+struct Args {
+    napi_env env;
+    size_t argc;  // in: max; out: what the caller passed, which may be more
+    napi_value argv[13];
+    bool ok;
+    Args(napi_env e, napi_callback_info info, size_t max) : env(e), argc(max) { ok = napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) == napi_ok; }
+    bool arity(size_t need) const {
+        if (!ok) napi_throw_error(env, nullptr, "N-API call failed: napi_get_cb_info");
+        return ok && !too_few(env, argc, need);
+    }
+    // the usual opening: at least `need` arguments, the first of them a live context, locked from here on
+    bool ctx(size_t need, Locked *L) const { return arity(need) && lock_ctx(env, argv[0], L); }
+    bool i32(size_t i, int32_t *out) const { return get_i32(env, argv[i], out); }
+    bool offset(size_t i, size_t *out) const { return get_offset(env, argv[i], out); }
+    bool bytes(size_t i, uint8_t **data, size_t *len) const { return get_bytes(env, argv[i], data, len); }
+    // optional trailing arguments: absent or of another type, the default stays
+    void opt_i32(size_t i, int32_t *out) const {
+        if (argc > i) get_i32(env, argv[i], out);
+    }
+    void opt_bool(size_t i, bool *out) const {
+        if (argc > i) napi_get_value_bool(env, argv[i], out);
+    }
+    bool i32s(size_t i, size_t min, View *a) const { return a->get(env, argv[i], napi_int32_array, min); }
+    bool f64s(size_t i, size_t min, View *a) const { return a->get(env, argv[i], napi_float64_array, min); }
+    bool devbuf(size_t i, DevBuf **out) const { return get_devbuf(env, argv[i], out); }
+    bool devbuf_or_null(size_t i, DevBuf **out) const {  // null / undefined: *out stays nullptr
+        napi_valuetype vt;
+        if (napi_typeof(env, argv[i], &vt) != napi_ok) return false;
+        return vt == napi_null || vt == napi_undefined || get_devbuf(env, argv[i], out);
+    }
+};
 
 // Every live Slot, so that the environment's cleanup hook can destroy the contexts while the HIP runtime is still up: finalizers
 // of externals may run during environment teardown or not at all, and a context destroyed after the runtime's own static
@@ -169,44 +278,76 @@ void env_cleanup(void *arg) {
 std::mutex g_host_mu;
 std::vector<std::pair<void *, size_t>> g_host_allocs;
 
+// ---- result packing ---------------------------------------------------------------------------------------------
+
+// a new Float64Array(n); *data = its storage, for the caller to fill (results are written in place, not copied)
+napi_value f64_result(napi_env env, size_t n, double **data) {
+    napi_value ab, ta;
+    void *p = nullptr;
+    NAPI_OK(napi_create_arraybuffer(env, n * 8, &p, &ab));
+    NAPI_OK(napi_create_typedarray(env, napi_float64_array, n, ab, 0, &ta));
+    *data = static_cast<double *>(p);
+    return ta;
+}
+
+// 9 numbers per stream: x, y, width, height, angle, then the search window
+napi_value trackobjs_result(napi_env env, const std::vector<ht_cs_trackobj> &out) {
+    double *d = nullptr;
+    napi_value ta = f64_result(env, out.size() * 9, &d);
+    for (size_t i = 0; ta && i < out.size(); i++) {
+        const ht_cs_trackobj &o = out[i];
+        double *r = d + 9 * i;
+        r[0] = o.x, r[1] = o.y, r[2] = o.width, r[3] = o.height, r[4] = o.angle;
+        r[5] = o.sw_x, r[6] = o.sw_y, r[7] = o.sw_width, r[8] = o.sw_height;
+    }
+    return ta;
+}
+
+// the 6-number rect layout of the JS side: x, y, width, height, confidence, neighbors
+napi_value rect6_result(napi_env env, const ht_rect *r, size_t n) {
+    double *d = nullptr;
+    napi_value ta = f64_result(env, n * 6, &d);
+    for (size_t k = 0; ta && k < n; k++) {
+        double *o = d + 6 * k;
+        o[0] = r[k].x, o[1] = r[k].y, o[2] = r[k].width, o[3] = r[k].height, o[4] = r[k].confidence, o[5] = r[k].neighbors;
+    }
+    return ta;
+}
+ht_rect rect6_unpack(const double *d) { return ht_rect{d[0], d[1], d[2], d[3], d[4], (int32_t)d[5], 0}; }
+
 // NO finalizers on the handles this addon hands to JavaScript.  Node 12 runs finalizers that are still pending while it tears the
 // environment down, through N-API's own phantom-callback wrapper, and that wrapper crashes inside libnode (SIGSEGV at exit in
 // GlobalHandles::InvokeSecondPassPhantomCallbacks -> libnode, seen in one of two runs of tests/js/bench_host.js whatever the callback
 // did).  Native resources are therefore released explicitly — destroy(ctx), deviceFree(ctx, buf), hostFree(arr) — and, for whatever is
 // still alive at exit, by the environment's cleanup hook (env_cleanup), which is an ordinary callback, not a finalizer.  A handle that
 // is dropped without destroy() keeps its GPU memory until the process exits.
+
+// the optional properties of createContext's argument; an int32 one that is absent or not a number leaves *out alone
+bool get_prop(napi_env env, napi_value obj, const char *name, napi_value *v) {
+    bool has;
+    return napi_has_named_property(env, obj, name, &has) == napi_ok && has && napi_get_named_property(env, obj, name, v) == napi_ok;
+}
+template <class T>
+void prop_i32(napi_env env, napi_value obj, const char *name, T *out) {
+    napi_value v;
+    int32_t i;
+    if (get_prop(env, obj, name, &v) && get_i32(env, v, &i)) *out = (T)i;
+}
+
 napi_value CreateContext(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Args a(env, info, 1);
+    if (!a.arity(0)) return nullptr;
+    napi_value arg = a.argv[0], v;
     ht_config cfg;
     std::memset(&cfg, 0, sizeof(cfg));
     cfg.struct_size = sizeof(cfg);
     cfg.interval = 5;
-    napi_value v;
-    bool has;
-    int32_t i;
-    uint8_t *blob = nullptr;
-    size_t blob_len = 0;
-    if (napi_has_named_property(env, argv[0], "device", &has) == napi_ok && has) {
-        NAPI_OK(napi_get_named_property(env, argv[0], "device", &v));
-        if (get_i32(env, v, &i)) cfg.device = i;
-    }
-    if (napi_has_named_property(env, argv[0], "interval", &has) == napi_ok && has) {
-        NAPI_OK(napi_get_named_property(env, argv[0], "interval", &v));
-        if (get_i32(env, v, &i)) cfg.interval = i;
-    }
-    if (napi_has_named_property(env, argv[0], "hitCapacity", &has) == napi_ok && has) {
-        NAPI_OK(napi_get_named_property(env, argv[0], "hitCapacity", &v));
-        if (get_i32(env, v, &i)) cfg.hit_capacity = (uint32_t)i;
-    }
-    if (napi_has_named_property(env, argv[0], "queueCapacity", &has) == napi_ok && has) {
-        NAPI_OK(napi_get_named_property(env, argv[0], "queueCapacity", &v));
-        if (get_i32(env, v, &i)) cfg.queue_capacity = (uint32_t)i;
-    }
+    prop_i32(env, arg, "device", &cfg.device);
+    prop_i32(env, arg, "interval", &cfg.interval);
+    prop_i32(env, arg, "hitCapacity", &cfg.hit_capacity);
+    prop_i32(env, arg, "queueCapacity", &cfg.queue_capacity);
     std::string options;  // ht_config.options: "key=value,..." schedule selectors (tests, A/B runs)
-    if (napi_has_named_property(env, argv[0], "options", &has) == napi_ok && has) {
-        NAPI_OK(napi_get_named_property(env, argv[0], "options", &v));
+    if (get_prop(env, arg, "options", &v)) {
         size_t len = 0;
         if (napi_get_value_string_utf8(env, v, nullptr, 0, &len) == napi_ok) {
             options.resize(len + 1);
@@ -215,11 +356,10 @@ napi_value CreateContext(napi_env env, napi_callback_info info) {
             cfg.options = options.c_str();
         }
     }
-    NAPI_OK(napi_get_named_property(env, argv[0], "cascade", &v));
-    if (!get_bytes(env, v, &blob, &blob_len)) {
-        napi_throw_type_error(env, nullptr, "createContext: `cascade` must be a Buffer/Uint8Array holding an HTCB blob");
-        return nullptr;
-    }
+    uint8_t *blob = nullptr;
+    size_t blob_len = 0;
+    NAPI_OK(napi_get_named_property(env, arg, "cascade", &v));
+    if (!get_bytes(env, v, &blob, &blob_len)) return type_error(env, "createContext: `cascade` must be a Buffer/Uint8Array holding an HTCB blob");
     ht_ctx *ctx = nullptr;
     ht_status st = ht_create(&cfg, blob, blob_len, &ctx);
     if (st != HT_OK) return throw_ht(env, nullptr, st, "ht_create");
@@ -231,16 +371,14 @@ napi_value CreateContext(napi_env env, napi_callback_info info) {
         g_slots.push_back(slot);
     }
     napi_value ext;
-    NAPI_OK(napi_create_external(env, slot, nullptr, nullptr, &ext));  // no finalizer, see release_slot
+    NAPI_OK(napi_create_external(env, slot, nullptr, nullptr, &ext));  // no finalizer, see above
     return ext;
 }
 
-napi_value Destroy(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+napi_value Destroy(napi_env env, napi_callback_info info) {  // idempotent; anything but a context is ignored
+    Args a(env, info, 1);
     void *p = nullptr;
-    if (argc >= 1 && napi_get_value_external(env, argv[0], &p) == napi_ok && p && static_cast<Slot *>(p)->tag == SLOT_TAG) {
+    if (a.ok && a.argc >= 1 && napi_get_value_external(env, a.argv[0], &p) == napi_ok && p && static_cast<Slot *>(p)->tag == SLOT_TAG) {
         Slot *slot = static_cast<Slot *>(p);
         std::lock_guard<std::recursive_mutex> lk(slot->mu);  // waits for an asynchronous job in flight on this context
         if (slot->ctx) ht_destroy(slot->ctx);
@@ -250,36 +388,17 @@ napi_value Destroy(napi_env env, napi_callback_info info) {
 }
 
 napi_value SetGeometry(napi_env env, napi_callback_info info) {
-    size_t argc = 5;
-    napi_value argv[5];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Args a(env, info, 5);
     Locked L;
-    if (!lock_ctx(env, argv[0], &L)) return nullptr;
-    ht_ctx *ctx = L.ctx;
     int32_t w, h, nb;
-    if (!get_i32(env, argv[1], &w) || !get_i32(env, argv[2], &h) || !get_i32(env, argv[3], &nb)) {
-        napi_throw_type_error(env, nullptr, "setGeometry(ctx, w, h, maxBatch, levelDims)");
-        return nullptr;
-    }
-    const int32_t *dims = nullptr;
-    int32_t nlev = 0;
+    if (!a.ctx(0, &L)) return nullptr;
+    if (!a.i32(1, &w) || !a.i32(2, &h) || !a.i32(3, &nb)) return type_error(env, "setGeometry(ctx, w, h, maxBatch, levelDims)");
+    View dims;  // anything but a typed array (null, undefined): the library computes the level sizes
     bool is_ta = false;
-    if (argc > 4 && napi_is_typedarray(env, argv[4], &is_ta) == napi_ok && is_ta) {
-        napi_typedarray_type t;
-        size_t n;
-        void *p;
-        napi_value ab;
-        size_t off;
-        NAPI_OK(napi_get_typedarray_info(env, argv[4], &t, &n, &p, &ab, &off));
-        if (t != napi_int32_array || (n & 1)) {
-            napi_throw_type_error(env, nullptr, "levelDims must be an Int32Array [w0,h0,w1,h1,...]");
-            return nullptr;
-        }
-        dims = static_cast<const int32_t *>(p);
-        nlev = (int32_t)(n / 2);
-    }
-    ht_status st = ht_set_geometry(ctx, w, h, nb, dims, nlev);
-    if (st != HT_OK) return throw_ht(env, ctx, st, "ht_set_geometry");
+    if (napi_is_typedarray(env, a.argv[4], &is_ta) == napi_ok && is_ta && (!a.i32s(4, 0, &dims) || (dims.len & 1)))
+        return type_error(env, "levelDims must be an Int32Array [w0,h0,w1,h1,...]");
+    ht_status st = ht_set_geometry(L.ctx, w, h, nb, dims.as<int32_t>(), (int32_t)(dims.len / 2));
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_set_geometry");
     return nullptr;
 }
 
@@ -322,32 +441,35 @@ void run_detect(DetectJob *j) {
     }
     if (j->st != HT_OK) j->err = ht_last_error(ctx);
 }
+std::string detect_error(const DetectJob &j) { return "ht_detect_batch: status " + std::to_string(j.st) + ": " + j.err; }
 
+// the typed array whose elements are T
+template <class T> constexpr napi_typedarray_type array_type_of();
+template <> constexpr napi_typedarray_type array_type_of<uint8_t>() { return napi_uint8_array; }
+template <> constexpr napi_typedarray_type array_type_of<uint16_t>() { return napi_uint16_array; }
+template <> constexpr napi_typedarray_type array_type_of<uint32_t>() { return napi_uint32_array; }
+template <> constexpr napi_typedarray_type array_type_of<double>() { return napi_float64_array; }
+
+// obj[name] = the first n elements' member M as a typed array of M's own type
+template <class S, class T>
+bool set_column(napi_env env, napi_value obj, const char *name, const S *rows, size_t n, T S::*M) {
+    napi_value ab, ta;
+    void *p = nullptr;
+    if (napi_create_arraybuffer(env, n * sizeof(T), &p, &ab) != napi_ok) return false;
+    for (size_t i = 0; i < n; i++) static_cast<T *>(p)[i] = rows[i].*M;
+    return napi_create_typedarray(env, array_type_of<T>(), n, ab, 0, &ta) == napi_ok && napi_set_named_property(env, obj, name, ta) == napi_ok;
+}
+
+// the hits as one typed array per ht_hit member + counts per frame
 napi_value pack_hits(napi_env env, const DetectJob &j) {
     napi_value obj;
     NAPI_OK(napi_create_object(env, &obj));
+    const ht_hit *h = j.hits.data();
     const size_t n = j.total;
-    struct Col {
-        const char *name;
-        napi_typedarray_type type;
-        size_t esz;
-    } cols[] = {{"frame", napi_uint32_array, 4}, {"x", napi_uint16_array, 2}, {"y", napi_uint16_array, 2},
-                {"scale", napi_uint8_array, 1},  {"q", napi_uint8_array, 1},   {"sum", napi_float64_array, 8}};
-    for (const Col &c : cols) {
-        napi_value ab, ta;
-        void *p = nullptr;
-        NAPI_OK(napi_create_arraybuffer(env, n * c.esz, &p, &ab));
-        for (size_t i = 0; i < n; i++) {
-            const ht_hit &h = j.hits[i];
-            if (c.name[0] == 'f') static_cast<uint32_t *>(p)[i] = h.frame;
-            else if (c.name[0] == 'x') static_cast<uint16_t *>(p)[i] = h.x;
-            else if (c.name[0] == 'y') static_cast<uint16_t *>(p)[i] = h.y;
-            else if (c.name[0] == 's' && c.name[1] == 'c') static_cast<uint8_t *>(p)[i] = h.scale;
-            else if (c.name[0] == 'q') static_cast<uint8_t *>(p)[i] = h.q;
-            else static_cast<double *>(p)[i] = h.sum;
-        }
-        NAPI_OK(napi_create_typedarray(env, c.type, n, ab, 0, &ta));
-        NAPI_OK(napi_set_named_property(env, obj, c.name, ta));
+    if (!set_column(env, obj, "frame", h, n, &ht_hit::frame) || !set_column(env, obj, "x", h, n, &ht_hit::x) || !set_column(env, obj, "y", h, n, &ht_hit::y) ||
+        !set_column(env, obj, "scale", h, n, &ht_hit::scale) || !set_column(env, obj, "q", h, n, &ht_hit::q) || !set_column(env, obj, "sum", h, n, &ht_hit::sum)) {
+        napi_throw_error(env, nullptr, "N-API call failed: pack_hits");
+        return nullptr;
     }
     napi_value ab, ta;
     void *p = nullptr;
@@ -358,37 +480,26 @@ napi_value pack_hits(napi_env env, const DetectJob &j) {
     return obj;
 }
 
-bool parse_detect_args(napi_env env, napi_callback_info info, DetectJob *j, napi_value *rgba_val, napi_value *ctx_val = nullptr) {
-    size_t argc = 6;
-    napi_value argv[6];
-    if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 5) {
-        napi_throw_type_error(env, nullptr, "detect(ctx, rgba, n, w, h, flags)");
-        return false;
-    }
-    if (!get_slot(env, argv[0], &j->slot)) return false;
-    if (ctx_val) *ctx_val = argv[0];
+bool parse_detect_args(const Args &a, DetectJob *j) {
+    napi_env env = a.env;
+    if (!a.ok || a.argc < 5) return type_error(env, "detect(ctx, rgba, n, w, h, flags)");
+    if (!get_slot(env, a.argv[0], &j->slot)) return false;
     size_t len = 0;
     int32_t fl = 0;
-    if (!get_bytes(env, argv[1], &j->rgba, &len) || !get_i32(env, argv[2], &j->n) || !get_i32(env, argv[3], &j->w) || !get_i32(env, argv[4], &j->h)) {
-        napi_throw_type_error(env, nullptr, "detect(ctx, rgba, n, w, h, flags): bad argument");
-        return false;
-    }
-    if (argc > 5) get_i32(env, argv[5], &fl);
+    if (!a.bytes(1, &j->rgba, &len) || !a.i32(2, &j->n) || !a.i32(3, &j->w) || !a.i32(4, &j->h)) return type_error(env, "detect(ctx, rgba, n, w, h, flags): bad argument");
+    a.opt_i32(5, &fl);
     j->flags = (uint32_t)fl;
-    if (j->n <= 0 || j->w <= 0 || j->h <= 0 || len < (size_t)j->n * j->w * j->h * 4) {
-        napi_throw_range_error(env, nullptr, "detect: rgba buffer smaller than n*w*h*4");
-        return false;
-    }
-    if (rgba_val) *rgba_val = argv[1];
+    if (j->n <= 0 || j->w <= 0 || j->h <= 0 || len < (size_t)j->n * j->w * j->h * 4) return range_error(env, "detect: rgba buffer smaller than n*w*h*4");
     return true;
 }
 
 napi_value Detect(napi_env env, napi_callback_info info) {
+    Args a(env, info, 6);
     DetectJob j;
-    if (!parse_detect_args(env, info, &j, nullptr)) return nullptr;
+    if (!parse_detect_args(a, &j)) return nullptr;
     run_detect(&j);
     if (j.st != HT_OK) {
-        napi_throw_error(env, nullptr, ("ht_detect_batch: status " + std::to_string(j.st) + ": " + j.err).c_str());
+        napi_throw_error(env, nullptr, detect_error(j).c_str());
         return nullptr;
     }
     return pack_hits(env, j);
@@ -403,8 +514,7 @@ void detect_complete(napi_env env, napi_status, void *data) {
         napi_resolve_deferred(env, j->deferred, v);
     } else {
         napi_value msg, err;
-        std::string m = "ht_detect_batch: status " + std::to_string(j->st) + ": " + j->err;
-        napi_create_string_utf8(env, m.c_str(), NAPI_AUTO_LENGTH, &msg);
+        napi_create_string_utf8(env, detect_error(*j).c_str(), NAPI_AUTO_LENGTH, &msg);
         napi_create_error(env, nullptr, msg, &err);
         napi_reject_deferred(env, j->deferred, err);
     }
@@ -415,23 +525,23 @@ void detect_complete(napi_env env, napi_status, void *data) {
 }
 
 napi_value DetectAsync(napi_env env, napi_callback_info info) {
+    Args a(env, info, 6);
     DetectJob *j = new DetectJob();
-    napi_value rgba_val, ctx_val;
-    if (!parse_detect_args(env, info, j, &rgba_val, &ctx_val)) {
+    if (!parse_detect_args(a, j)) {
         delete j;
         return nullptr;
     }
     napi_value promise, name;
     NAPI_OK(napi_create_promise(env, &j->deferred, &promise));
-    NAPI_OK(napi_create_reference(env, rgba_val, 1, &j->rgba_ref));  // keep the frame buffer alive while the GPU works
-    NAPI_OK(napi_create_reference(env, ctx_val, 1, &j->ctx_ref));
+    NAPI_OK(napi_create_reference(env, a.argv[1], 1, &j->rgba_ref));  // keep the frame buffer alive while the GPU works
+    NAPI_OK(napi_create_reference(env, a.argv[0], 1, &j->ctx_ref));
     NAPI_OK(napi_create_string_utf8(env, "headtrackr_hip.detect", NAPI_AUTO_LENGTH, &name));
     NAPI_OK(napi_create_async_work(env, nullptr, name, detect_execute, detect_complete, j, &j->work));
     NAPI_OK(napi_queue_async_work(env, j->work));
     return promise;
 }
 
-// ---- grayscale / whitebalance -------------------------------------------------------------------------------------
+// ---- host frames: grayscale / whitebalance / camshift / upload / drawFrames ---------------------------------------------
 
 struct FrameArgs {
     Locked L;  // the context stays locked for the lifetime of the argument block = the whole entry point
@@ -440,15 +550,14 @@ struct FrameArgs {
     int32_t n, w, h;
 };
 
-bool parse_frames(napi_env env, napi_value *argv, FrameArgs *a) {
+// (ctx, rgba, n, w, h, ...) of an entry point that needs `need` arguments
+bool parse_frames(const Args &a, size_t need, FrameArgs *f) {
     size_t len = 0;
-    if (!lock_ctx(env, argv[0], &a->L)) return false;
-    a->ctx = a->L.ctx;
-    if (!get_bytes(env, argv[1], &a->rgba, &len) || !get_i32(env, argv[2], &a->n) || !get_i32(env, argv[3], &a->w) || !get_i32(env, argv[4], &a->h) ||
-        a->n <= 0 || a->w <= 0 || a->h <= 0 || len < (size_t)a->n * a->w * a->h * 4) {
-        napi_throw_type_error(env, nullptr, "expected (ctx, Uint8Array rgba, n, w, h, ...) with rgba.length >= n*w*h*4");
-        return false;
-    }
+    if (!a.ctx(need, &f->L)) return false;
+    f->ctx = f->L.ctx;
+    if (!a.bytes(1, &f->rgba, &len) || !a.i32(2, &f->n) || !a.i32(3, &f->w) || !a.i32(4, &f->h) || f->n <= 0 || f->w <= 0 || f->h <= 0 ||
+        len < (size_t)f->n * f->w * f->h * 4)
+        return type_error(a.env, "expected (ctx, Uint8Array rgba, n, w, h, ...) with rgba.length >= n*w*h*4");
     return true;
 }
 
@@ -459,120 +568,304 @@ ht_status bind_host_frames(const FrameArgs &a) {
 }
 
 napi_value Grayscale(napi_env env, napi_callback_info info) {
-    size_t argc = 5;
-    napi_value argv[5];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    FrameArgs a;
-    if (too_few(env, argc, 5) || !parse_frames(env, argv, &a)) return nullptr;
-    ht_status st = ht_grayscale_batch(a.ctx, a.rgba, a.n, a.w, a.h, (size_t)a.w * a.h * 4);
-    if (st != HT_OK) return throw_ht(env, a.ctx, st, "ht_grayscale_batch");
+    Args a(env, info, 5);
+    FrameArgs f;
+    if (!parse_frames(a, 5, &f)) return nullptr;
+    ht_status st = ht_grayscale_batch(f.ctx, f.rgba, f.n, f.w, f.h, (size_t)f.w * f.h * 4);
+    if (st != HT_OK) return throw_ht(env, f.ctx, st, "ht_grayscale_batch");
     return nullptr;
 }
 
-napi_value Whitebalance(napi_env env, napi_callback_info info) {
-    size_t argc = 5;
-    napi_value argv[5];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    FrameArgs a;
-    if (too_few(env, argc, 5) || !parse_frames(env, argv, &a)) return nullptr;
-    ht_status st = bind_host_frames(a);
-    if (st != HT_OK) return throw_ht(env, a.ctx, st, "ht_upload_frames");
-    napi_value ab, ta;
-    void *p = nullptr;
-    NAPI_OK(napi_create_arraybuffer(env, (size_t)a.n * 8, &p, &ab));
-    st = ht_whitebalance_batch(a.ctx, static_cast<double *>(p), a.n);
-    if (st != HT_OK) return throw_ht(env, a.ctx, st, "ht_whitebalance_batch");
-    NAPI_OK(napi_create_typedarray(env, napi_float64_array, (size_t)a.n, ab, 0, &ta));
+// getWhitebalance of the first n bound frames, or (fused) of the batch enqueued with DETECT_WHITEBALANCE
+napi_value wb_result(napi_env env, ht_ctx *ctx, int32_t n, bool fused) {
+    double *out = nullptr;
+    napi_value ta = f64_result(env, (size_t)n, &out);
+    if (!ta) return nullptr;
+    ht_status st = fused ? ht_detect_whitebalance(ctx, out, n) : ht_whitebalance_batch(ctx, out, n);
+    if (st != HT_OK) return throw_ht(env, ctx, st, fused ? "ht_detect_whitebalance" : "ht_whitebalance_batch");
     return ta;
+}
+
+napi_value Whitebalance(napi_env env, napi_callback_info info) {
+    Args a(env, info, 5);
+    FrameArgs f;
+    if (!parse_frames(a, 5, &f)) return nullptr;
+    ht_status st = bind_host_frames(f);
+    if (st != HT_OK) return throw_ht(env, f.ctx, st, "ht_upload_frames");
+    return wb_result(env, f.ctx, f.n, false);
+}
+
+napi_value wb_common(napi_env env, napi_callback_info info, bool fused) {
+    Args a(env, info, 2);
+    Locked L;
+    int32_t n = 0;
+    if (!a.ctx(2, &L)) return nullptr;
+    if (!a.i32(1, &n) || n <= 0) return type_error(env, "(ctx, n)");
+    return wb_result(env, L.ctx, n, fused);
+}
+napi_value DetectWhitebalance(napi_env env, napi_callback_info info) { return wb_common(env, info, true); }
+napi_value WhitebalanceBound(napi_env env, napi_callback_info info) { return wb_common(env, info, false); }
+
+napi_value Upload(napi_env env, napi_callback_info info) {
+    Args a(env, info, 5);
+    FrameArgs f;
+    if (!parse_frames(a, 5, &f)) return nullptr;
+    ht_status st = bind_host_frames(f);
+    if (st != HT_OK) return throw_ht(env, f.ctx, st, "ht_upload_frames");
+    return nullptr;
+}
+
+napi_value DrawFrames(napi_env env, napi_callback_info info) {
+    Args a(env, info, 6);
+    FrameArgs f;
+    ht_cs_rect r;
+    const ht_cs_rect *rp = nullptr;
+    if (!parse_frames(a, 5, &f)) return nullptr;
+    if (!get_rect(env, a.argv[5], &r, &rp)) return type_error(env, "drawFrames(ctx, Uint8Array rgba, n, sw, sh, Int32Array rect[4] | null)");
+    ht_status st = ht_draw_frames(f.ctx, f.rgba, f.n, f.w, f.h, 0, rp);
+    if (st != HT_OK) return throw_ht(env, f.ctx, st, "ht_draw_frames");
+    return nullptr;
 }
 
 // ---- camshift ---------------------------------------------------------------------------------------------------
 
 napi_value CamshiftReserve(napi_env env, napi_callback_info info) {
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Args a(env, info, 2);
     Locked L;
     int32_t n;
-    if (!lock_ctx(env, argv[0], &L)) return nullptr;
-    ht_ctx *ctx = L.ctx;
-    if (!get_i32(env, argv[1], &n)) {
-        napi_throw_type_error(env, nullptr, "camshiftReserve(ctx, nstreams)");
-        return nullptr;
-    }
-    ht_status st = ht_camshift_reserve(ctx, n);
-    if (st != HT_OK) return throw_ht(env, ctx, st, "ht_camshift_reserve");
+    if (!a.ctx(0, &L)) return nullptr;
+    if (!a.i32(1, &n)) return type_error(env, "camshiftReserve(ctx, nstreams)");
+    ht_status st = ht_camshift_reserve(L.ctx, n);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_reserve");
     return nullptr;
 }
 
 napi_value CamshiftInit(napi_env env, napi_callback_info info) {
-    size_t argc = 7;
-    napi_value argv[7];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    FrameArgs a;
-    if (too_few(env, argc, 7) || !parse_frames(env, argv, &a)) return nullptr;
+    Args a(env, info, 7);
+    FrameArgs f;
     int32_t first;
-    napi_typedarray_type t;
-    size_t n;
-    void *p;
-    napi_value ab;
-    size_t off;
-    if (!get_i32(env, argv[5], &first) || napi_get_typedarray_info(env, argv[6], &t, &n, &p, &ab, &off) != napi_ok || t != napi_int32_array ||
-        n < (size_t)a.n * 4) {
-        napi_throw_type_error(env, nullptr, "camshiftInit(ctx, rgba, n, w, h, first, Int32Array rects[4n])");
-        return nullptr;
-    }
-    ht_status st = bind_host_frames(a);
-    if (st != HT_OK) return throw_ht(env, a.ctx, st, "ht_upload_frames");
-    st = ht_camshift_init_batch(a.ctx, first, a.n, static_cast<const ht_cs_rect *>(p));
-    if (st != HT_OK) return throw_ht(env, a.ctx, st, "ht_camshift_init_batch");
+    View rects;
+    if (!parse_frames(a, 7, &f)) return nullptr;
+    if (!a.i32(5, &first) || !a.i32s(6, (size_t)f.n * 4, &rects)) return type_error(env, "camshiftInit(ctx, rgba, n, w, h, first, Int32Array rects[4n])");
+    ht_status st = bind_host_frames(f);
+    if (st != HT_OK) return throw_ht(env, f.ctx, st, "ht_upload_frames");
+    st = ht_camshift_init_batch(f.ctx, first, f.n, rects.as<ht_cs_rect>());
+    if (st != HT_OK) return throw_ht(env, f.ctx, st, "ht_camshift_init_batch");
     return nullptr;
 }
 
 napi_value CamshiftTrack(napi_env env, napi_callback_info info) {
-    size_t argc = 7;
-    napi_value argv[7];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    FrameArgs a;
-    if (too_few(env, argc, 7) || !parse_frames(env, argv, &a)) return nullptr;
+    Args a(env, info, 7);
+    FrameArgs f;
     int32_t first, calc;
-    if (!get_i32(env, argv[5], &first) || !get_i32(env, argv[6], &calc)) {
-        napi_throw_type_error(env, nullptr, "camshiftTrack(ctx, rgba, n, w, h, first, calcAngles)");
-        return nullptr;
+    if (!parse_frames(a, 7, &f)) return nullptr;
+    if (!a.i32(5, &first) || !a.i32(6, &calc)) return type_error(env, "camshiftTrack(ctx, rgba, n, w, h, first, calcAngles)");
+    ht_status st = bind_host_frames(f);
+    if (st != HT_OK) return throw_ht(env, f.ctx, st, "ht_upload_frames");
+    std::vector<ht_cs_trackobj> out((size_t)f.n);
+    st = ht_camshift_track_batch(f.ctx, first, f.n, calc, out.data());
+    if (st != HT_OK) return throw_ht(env, f.ctx, st, "ht_camshift_track_batch");
+    return trackobjs_result(env, out);
+}
+
+napi_value CamshiftInitBound(napi_env env, napi_callback_info info) {
+    Args a(env, info, 4);
+    Locked L;
+    int32_t n = 0, first = 0;
+    View rects;
+    if (!a.ctx(4, &L)) return nullptr;
+    if (!a.i32(1, &n) || !a.i32(2, &first) || n <= 0 || !a.i32s(3, (size_t)n * 4, &rects)) return type_error(env, "camshiftInitBound(ctx, n, first, Int32Array rects[4n])");
+    ht_status st = ht_camshift_init_batch(L.ctx, first, n, rects.as<ht_cs_rect>());
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_init_batch");
+    return nullptr;
+}
+
+napi_value CamshiftTrackBound(napi_env env, napi_callback_info info) {
+    Args a(env, info, 5);
+    Locked L;
+    int32_t n = 0, first = 0, calc = 1;
+    bool fetch = true;
+    if (!a.ctx(4, &L)) return nullptr;
+    if (!a.i32(1, &n) || !a.i32(2, &first) || !a.i32(3, &calc) || n <= 0) return type_error(env, "camshiftTrackBound(ctx, n, first, calcAngles, fetch)");
+    a.opt_bool(4, &fetch);
+    std::vector<ht_cs_trackobj> out((size_t)n);
+    ht_status st = ht_camshift_track_batch(L.ctx, first, n, calc, fetch ? out.data() : nullptr);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_track_batch");
+    return fetch ? trackobjs_result(env, out) : nullptr;
+}
+
+napi_value CamshiftInitPairs(napi_env env, napi_callback_info info) {
+    Args a(env, info, 3);
+    Locked L;
+    const ht_cs_pair *pairs = nullptr;
+    int32_t n = 0;
+    View rects;
+    if (!a.ctx(3, &L)) return nullptr;
+    if (!get_pairs(env, a.argv[1], &pairs, &n) || !a.i32s(2, (size_t)n * 4, &rects)) return type_error(env, "camshiftInitPairs(ctx, Int32Array pairs[2n], Int32Array rects[4n])");
+    ht_status st = ht_camshift_init_pairs(L.ctx, pairs, n, rects.as<ht_cs_rect>());
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_init_pairs");
+    return nullptr;
+}
+
+napi_value CamshiftTrackPairs(napi_env env, napi_callback_info info) {
+    Args a(env, info, 4);
+    Locked L;
+    const ht_cs_pair *pairs = nullptr;
+    int32_t n = 0, calc = 1;
+    bool fetch = true;
+    if (!a.ctx(3, &L)) return nullptr;
+    if (!get_pairs(env, a.argv[1], &pairs, &n) || !a.i32(2, &calc)) return type_error(env, "camshiftTrackPairs(ctx, Int32Array pairs[2n], calcAngles, fetch)");
+    a.opt_bool(3, &fetch);
+    std::vector<ht_cs_trackobj> out((size_t)n);
+    ht_status st = ht_camshift_track_pairs(L.ctx, pairs, n, calc, fetch ? out.data() : nullptr);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_track_pairs");
+    return fetch ? trackobjs_result(env, out) : nullptr;
+}
+
+napi_value CamshiftTrackCollect(napi_env env, napi_callback_info info) {
+    Args a(env, info, 2);
+    Locked L;
+    int32_t n = 0;
+    if (!a.ctx(2, &L)) return nullptr;
+    if (!a.i32(1, &n) || n <= 0) return type_error(env, "camshiftTrackCollect(ctx, n)");
+    std::vector<ht_cs_trackobj> out((size_t)n);
+    ht_status st = ht_camshift_track_collect(L.ctx, n, out.data());
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_track_collect");
+    return trackobjs_result(env, out);
+}
+
+napi_value CamshiftTrackSequence(napi_env env, napi_callback_info info) {
+    Args a(env, info, 9);
+    Locked L;
+    DevBuf *d = nullptr;
+    int32_t first = 0, n = 0, calc = 1;
+    size_t stride = 0;
+    bool out_all = false, fetch = true;
+    View offs;
+    if (!a.ctx(7, &L)) return nullptr;
+    if (!a.i32(1, &first) || !a.i32(2, &n) || !a.i32(3, &calc) || !a.devbuf(4, &d)) return nullptr;
+    if (!a.f64s(5, 1, &offs) || offs.len > 100000 || !a.offset(6, &stride) || n <= 0)
+        return type_error(env, "camshiftTrackSequence(ctx, first, n, calcAngles, dev, Float64Array byteOffsets, frameStride, outAll, fetch)");
+    a.opt_bool(7, &out_all);
+    a.opt_bool(8, &fetch);
+    const size_t ncalls = offs.len;
+    std::vector<const void *> ptrs(ncalls);
+    for (size_t k = 0; k < ncalls; k++) {
+        size_t o = 0;
+        if (!to_offset(offs.as<double>()[k], &o) || !frames_fit(o, (size_t)n, stride, stride, d->bytes))
+            return range_error(env, "camshiftTrackSequence: a call's frames lie outside the device buffer");
+        ptrs[k] = static_cast<const char *>(d->ptr) + o;
     }
-    ht_status st = bind_host_frames(a);
-    if (st != HT_OK) return throw_ht(env, a.ctx, st, "ht_upload_frames");
-    std::vector<ht_cs_trackobj> out((size_t)a.n);
-    st = ht_camshift_track_batch(a.ctx, first, a.n, calc, out.data());
-    if (st != HT_OK) return throw_ht(env, a.ctx, st, "ht_camshift_track_batch");
+    std::vector<ht_cs_trackobj> out(fetch ? (size_t)n * (out_all ? ncalls : 1) : 0);
+    ht_status st = ht_camshift_track_sequence(L.ctx, first, n, calc, ptrs.data(), (int32_t)ncalls, stride, fetch ? out.data() : nullptr, out_all ? 1 : 0);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_track_sequence");
+    return fetch ? trackobjs_result(env, out) : nullptr;
+}
+
+napi_value CamshiftSequenceCollect(napi_env env, napi_callback_info info) {
+    Args a(env, info, 4);
+    Locked L;
+    int32_t n = 0, ncalls = 0;
+    bool out_all = false;
+    if (!a.ctx(3, &L)) return nullptr;
+    if (!a.i32(1, &n) || !a.i32(2, &ncalls) || n <= 0 || ncalls <= 0) return type_error(env, "camshiftSequenceCollect(ctx, n, ncalls, outAll)");
+    a.opt_bool(3, &out_all);
+    std::vector<ht_cs_trackobj> out((size_t)n * (out_all ? (size_t)ncalls : 1));
+    ht_status st = ht_camshift_sequence_collect(L.ctx, n, ncalls, out_all ? 1 : 0, out.data());
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_sequence_collect");
+    return trackobjs_result(env, out);
+}
+
+// bytes of one frame of the context's geometry at `elem` bytes per pixel (level 0 of the pyramid is the frame itself); 0, with `who`'s
+// exception pending, when the context has no geometry yet
+size_t frame_bytes(napi_env env, ht_ctx *ctx, size_t elem, const char *who) {
+    ht_plane_info pl;
+    if (ht_plane(ctx, 0, 0, &pl) == HT_OK && pl.width > 0 && pl.height > 0) return (size_t)pl.width * (size_t)pl.height * elem;  // <= 16384 * 16384 * 8
+    napi_throw_error(env, nullptr, (std::string(who) + ": no geometry (setGeometry first)").c_str());
+    return 0;
+}
+
+// The four back-projection exports are two functions, host and device, over two forms of saying which (stream, frame) pairs:
+// the batch form (n, first) — streams [first, first + n) on bound frames [0, n) — or a pair list.
+struct BpForm {
+    bool pairs;
+    const char *name, *where, *usage, *range;
+};
+const BpForm BP_HOST[2] = {{false, "camshiftBackProject", "ht_camshift_backproject", "camshiftBackProject(ctx, n, first, kind = BP_RGBA8 | BP_F64)", nullptr},
+                           {true, "camshiftBackProjectPairs", "ht_camshift_backproject_pairs", "camshiftBackProjectPairs(ctx, Int32Array pairs[2n], kind = BP_RGBA8 | BP_F64)", nullptr}};
+const BpForm BP_DEVICE[2] = {
+    {false, "camshiftBackProjectDevice", "ht_camshift_backproject_device", "camshiftBackProjectDevice(ctx, n, first, kind = BP_RGBA8 | BP_F64, dev, byteOffset, stride)",
+     "camshiftBackProjectDevice(ctx, n, first, kind, dev, byteOffset, stride): outside the device buffer"},
+    {true, "camshiftBackProjectPairsDevice", "ht_camshift_backproject_pairs_device",
+     "camshiftBackProjectPairsDevice(ctx, Int32Array pairs[2n], kind = BP_RGBA8 | BP_F64, dev, byteOffset, stride)",
+     "camshiftBackProjectPairsDevice(ctx, pairs, kind, dev, byteOffset, stride): outside the device buffer"}};
+
+struct BpCall {
+    Locked L;
+    const ht_cs_pair *pairs = nullptr;
+    int32_t n = 0, first = 0, kind = 0;
+    size_t rest = 0;  // index of the first argument after `kind`
+};
+// (ctx, n, first | pairs, kind, `more` further arguments): the context, the form's arguments and a valid kind
+bool bp_begin(const Args &a, const BpForm &f, size_t more, BpCall *c) {
+    c->rest = f.pairs ? 3 : 4;
+    if (!a.ctx(c->rest + more, &c->L)) return false;
+    const bool which = f.pairs ? get_pairs(a.env, a.argv[1], &c->pairs, &c->n) : a.i32(1, &c->n) && a.i32(2, &c->first);
+    if (!which || !a.i32(c->rest - 1, &c->kind) || c->n <= 0 || (c->kind != HT_BP_RGBA8 && c->kind != HT_BP_F64)) return type_error(a.env, f.usage);
+    return true;
+}
+
+napi_value bp_host(napi_env env, napi_callback_info info, const BpForm &f) {
+    Args a(env, info, f.pairs ? 3 : 4);
+    BpCall c;
+    if (!bp_begin(a, f, 0, &c)) return nullptr;
+    const size_t elem = c.kind == HT_BP_F64 ? 8 : 4, frame = frame_bytes(env, c.L.ctx, elem, f.name);
+    if (!frame) return nullptr;
     napi_value ab, ta;
     void *p = nullptr;
-    NAPI_OK(napi_create_arraybuffer(env, (size_t)a.n * 9 * 8, &p, &ab));
-    double *d = static_cast<double *>(p);
-    for (int i = 0; i < a.n; i++) {
-        const ht_cs_trackobj &o = out[i];
-        double *r = d + 9 * i;
-        r[0] = o.x, r[1] = o.y, r[2] = o.width, r[3] = o.height, r[4] = o.angle;
-        r[5] = o.sw_x, r[6] = o.sw_y, r[7] = o.sw_width, r[8] = o.sw_height;
-    }
-    NAPI_OK(napi_create_typedarray(env, napi_float64_array, (size_t)a.n * 9, ab, 0, &ta));
+    NAPI_OK(napi_create_arraybuffer(env, (size_t)c.n * frame, &p, &ab));
+    // the stride is passed explicitly: the library refuses one that is smaller than ITS frame, so the buffer can never be too small
+    ht_status st = f.pairs ? ht_camshift_backproject_pairs(c.L.ctx, c.pairs, c.n, c.kind, p, frame) : ht_camshift_backproject(c.L.ctx, c.first, c.n, c.kind, p, frame);
+    if (st != HT_OK) return throw_ht(env, c.L.ctx, st, f.where);
+    if (c.kind == HT_BP_F64) NAPI_OK(napi_create_typedarray(env, napi_float64_array, (size_t)c.n * frame / 8, ab, 0, &ta));
+    else NAPI_OK(napi_create_typedarray(env, napi_uint8_array, (size_t)c.n * frame, ab, 0, &ta));
     return ta;
 }
 
+napi_value bp_device(napi_env env, napi_callback_info info, const BpForm &f) {
+    Args a(env, info, f.pairs ? 6 : 7);
+    BpCall c;
+    DevBuf *d = nullptr;
+    size_t off = 0, stride = 0;
+    if (!bp_begin(a, f, 3, &c) || !a.devbuf(c.rest, &d)) return nullptr;
+    const size_t frame = frame_bytes(env, c.L.ctx, c.kind == HT_BP_F64 ? 8 : 4, f.name);
+    if (!frame) return nullptr;
+    if (!a.offset(c.rest + 1, &off) || !a.offset(c.rest + 2, &stride) || (stride != 0 && stride < frame)) return range_error(env, f.range);
+    if (!stride) stride = frame;  // 0 = packed
+    if (!frames_fit(off, (size_t)c.n, stride, frame, d->bytes)) return range_error(env, f.range);
+    void *out = static_cast<char *>(d->ptr) + off;
+    ht_status st = f.pairs ? ht_camshift_backproject_pairs_device(c.L.ctx, c.pairs, c.n, c.kind, out, stride) : ht_camshift_backproject_device(c.L.ctx, c.first, c.n, c.kind, out, stride);
+    if (st != HT_OK) return throw_ht(env, c.L.ctx, st, f.where);
+    return nullptr;
+}
+napi_value CamshiftBackProject(napi_env env, napi_callback_info info) { return bp_host(env, info, BP_HOST[0]); }
+napi_value CamshiftBackProjectPairs(napi_env env, napi_callback_info info) { return bp_host(env, info, BP_HOST[1]); }
+napi_value CamshiftBackProjectDevice(napi_env env, napi_callback_info info) { return bp_device(env, info, BP_DEVICE[0]); }
+napi_value CamshiftBackProjectPairsDevice(napi_env env, napi_callback_info info) { return bp_device(env, info, BP_DEVICE[1]); }
+
+// ---- info / multi-GPU ----------------------------------------------------------------------------------------------
+
 napi_value Info(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Args a(env, info, 1);
     Locked L;
-    if (!lock_ctx(env, argv[0], &L)) return nullptr;
-    ht_ctx *ctx = L.ctx;
+    if (!a.ctx(0, &L)) return nullptr;
     napi_value obj, v;
     NAPI_OK(napi_create_object(env, &obj));
-    NAPI_OK(napi_create_int32(env, ht_num_levels(ctx), &v));
+    NAPI_OK(napi_create_int32(env, ht_num_levels(L.ctx), &v));
     NAPI_OK(napi_set_named_property(env, obj, "levels", v));
-    NAPI_OK(napi_create_double(env, (double)ht_windows_per_frame(ctx), &v));
+    NAPI_OK(napi_create_double(env, (double)ht_windows_per_frame(L.ctx), &v));
     NAPI_OK(napi_set_named_property(env, obj, "windowsPerFrame", v));
-    NAPI_OK(napi_create_double(env, (double)ht_pyramid_bytes_per_frame(ctx), &v));
+    NAPI_OK(napi_create_double(env, (double)ht_pyramid_bytes_per_frame(L.ctx), &v));
     NAPI_OK(napi_set_named_property(env, obj, "pyramidBytesPerFrame", v));
     return obj;
 }
@@ -584,16 +877,12 @@ napi_value DeviceCount(napi_env env, napi_callback_info) {
 }
 
 napi_value AllgatherBest(napi_env env, napi_callback_info info) {
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Args a(env, info, 3);
     uint32_t nctx = 0, nbest = 0;
     int32_t per = 0;
-    if (argc < 3 || napi_get_array_length(env, argv[0], &nctx) != napi_ok || napi_get_array_length(env, argv[1], &nbest) != napi_ok || nctx == 0 ||
-        nctx != nbest || !get_i32(env, argv[2], &per) || per <= 0) {
-        napi_throw_type_error(env, nullptr, "allgatherBest([ctx...], [Float64Array...], framesPerRank)");
-        return nullptr;
-    }
+    if (!a.ok || a.argc < 3 || napi_get_array_length(env, a.argv[0], &nctx) != napi_ok || napi_get_array_length(env, a.argv[1], &nbest) != napi_ok || nctx == 0 ||
+        nctx != nbest || !a.i32(2, &per) || per <= 0)
+        return type_error(env, "allgatherBest([ctx...], [Float64Array...], framesPerRank)");
     std::vector<Locked> locks(nctx);  // every rank's context stays locked for the exchange (slots are distinct: no lock-order issue
                                       // as long as callers pass the contexts in the same order, which headtrackr.js does)
     std::vector<ht_ctx *> ctxs(nctx);
@@ -601,8 +890,8 @@ napi_value AllgatherBest(napi_env env, napi_callback_info info) {
     std::vector<const ht_rect *> ptrs(nctx);
     for (uint32_t i = 0; i < nctx; i++) {
         napi_value cv, bv;
-        NAPI_OK(napi_get_element(env, argv[0], i, &cv));
-        NAPI_OK(napi_get_element(env, argv[1], i, &bv));
+        NAPI_OK(napi_get_element(env, a.argv[0], i, &cv));
+        NAPI_OK(napi_get_element(env, a.argv[1], i, &bv));
         Slot *slot = nullptr;
         if (!get_slot(env, cv, &slot)) return nullptr;
         for (uint32_t k = 0; k < i; k++)
@@ -612,50 +901,23 @@ napi_value AllgatherBest(napi_env env, napi_callback_info info) {
             }
         if (!lock_ctx(env, cv, &locks[i])) return nullptr;
         ctxs[i] = locks[i].ctx;
-        napi_typedarray_type t;
-        size_t n;
-        void *p;
-        napi_value ab;
-        size_t off;
-        if (napi_get_typedarray_info(env, bv, &t, &n, &p, &ab, &off) != napi_ok || t != napi_float64_array || n < (size_t)per * 6) {
-            napi_throw_type_error(env, nullptr, "allgatherBest: every rank needs a Float64Array of 6 * framesPerRank numbers");
-            return nullptr;
-        }
-        const double *d = static_cast<const double *>(p);
-        for (int f = 0; f < per; f++) {
-            ht_rect &r = rects[i][(size_t)f];
-            r.x = d[6 * f], r.y = d[6 * f + 1], r.width = d[6 * f + 2], r.height = d[6 * f + 3], r.confidence = d[6 * f + 4];
-            r.neighbors = (int32_t)d[6 * f + 5];
-            r.reserved = 0;
-        }
+        View best;
+        if (!best.get(env, bv, napi_float64_array, (size_t)per * 6)) return type_error(env, "allgatherBest: every rank needs a Float64Array of 6 * framesPerRank numbers");
+        for (int f = 0; f < per; f++) rects[i][(size_t)f] = rect6_unpack(best.as<double>() + 6 * f);
         ptrs[i] = rects[i].data();
     }
     std::vector<ht_rect> out((size_t)nctx * per);
     ht_status st = ht_allgather_best_faces(ctxs.data(), (int32_t)nctx, ptrs.data(), per, out.data());
     if (st != HT_OK) return throw_ht(env, ctxs[0], st, "ht_allgather_best_faces");
-    napi_value ab, ta;
-    void *p = nullptr;
-    NAPI_OK(napi_create_arraybuffer(env, out.size() * 6 * 8, &p, &ab));
-    double *d = static_cast<double *>(p);
-    for (size_t k = 0; k < out.size(); k++) {
-        d[6 * k] = out[k].x, d[6 * k + 1] = out[k].y, d[6 * k + 2] = out[k].width, d[6 * k + 3] = out[k].height, d[6 * k + 4] = out[k].confidence;
-        d[6 * k + 5] = out[k].neighbors;
-    }
-    NAPI_OK(napi_create_typedarray(env, napi_float64_array, out.size() * 6, ab, 0, &ta));
-    return ta;
+    return rect6_result(env, out.data(), out.size());
 }
 
 // ---- pipelined path ------------------------------------------------------------------------------------------------------------
 
 napi_value HostAlloc(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Args a(env, info, 1);
     double bytes = 0;
-    if (argc < 1 || napi_get_value_double(env, argv[0], &bytes) != napi_ok || !(bytes >= 1) || bytes > 1e12) {
-        napi_throw_type_error(env, nullptr, "hostAlloc(bytes)");
-        return nullptr;
-    }
+    if (!a.ok || a.argc < 1 || napi_get_value_double(env, a.argv[0], &bytes) != napi_ok || !(bytes >= 1) || bytes > 1e12) return type_error(env, "hostAlloc(bytes)");
     void *p = nullptr;
     ht_status st = ht_host_alloc((size_t)bytes, &p);
     if (st != HT_OK) return throw_ht(env, nullptr, st, "ht_host_alloc");
@@ -673,53 +935,27 @@ napi_value HostAlloc(napi_env env, napi_callback_info info) {
     return ta;
 }
 
-// a device buffer: freed explicitly (deviceFree) or, at the latest, when the JS handle is collected — through the context it was
-// allocated on, which the handle keeps alive
-struct DevBuf {
-    uint32_t tag = DEVBUF_TAG;
-    Slot *slot = nullptr;  // Slots are never freed (a few bytes per context): a JS handle may outlive destroy()
-    void *ptr = nullptr;
-    size_t bytes = 0;
-};
-bool get_devbuf(napi_env env, napi_value v, DevBuf **out) {
-    void *p = nullptr;
-    if (napi_get_value_external(env, v, &p) != napi_ok || !p || static_cast<DevBuf *>(p)->tag != DEVBUF_TAG || !static_cast<DevBuf *>(p)->ptr ||
-        !static_cast<DevBuf *>(p)->slot->ctx) {
-        napi_throw_type_error(env, nullptr, "expected a live device buffer (deviceAlloc) of a live context");
-        return false;
-    }
-    *out = static_cast<DevBuf *>(p);
-    return true;
-}
-
-// hostFree(Uint8Array from hostAlloc): releases the pinned memory; the array must not be used afterwards
+// releases the pinned memory; the array must not be used afterwards
 napi_value HostFree(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    napi_typedarray_type t;
-    size_t len = 0, off = 0;
-    void *p = nullptr;
-    napi_value ab;
+    Args a(env, info, 1);
+    View v;
     bool is_ta = false;
-    if (argc < 1 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta || napi_get_typedarray_info(env, argv[0], &t, &len, &p, &ab, &off) != napi_ok || !p) {
-        napi_throw_type_error(env, nullptr, "hostFree(Uint8Array returned by hostAlloc)");
-        return nullptr;
-    }
+    if (!a.ok || a.argc < 1 || napi_is_typedarray(env, a.argv[0], &is_ta) != napi_ok || !is_ta || !v.get(env, a.argv[0]) || !v.p)
+        return type_error(env, "hostFree(Uint8Array returned by hostAlloc)");
     {
         std::lock_guard<std::mutex> lk(g_host_mu);
         auto it = g_host_allocs.end();
-        if (off == 0)
+        if (v.off == 0)
             for (auto i = g_host_allocs.begin(); i != g_host_allocs.end(); ++i)
-                if (i->first == p && i->second == len) it = i;
+                if (i->first == v.p && i->second == v.len) it = i;
         if (it == g_host_allocs.end()) {  // a subarray / second view / foreign array / already freed: nothing is released
             napi_throw_error(env, nullptr, "hostFree: not a live hostAlloc() array (pass the array hostAlloc returned, whole, once)");
             return nullptr;
         }
         g_host_allocs.erase(it);
     }
-    ht_host_free(p);
-    (void)napi_detach_arraybuffer(env, ab);  // every view now has length 0: no use-after-free from JavaScript
+    ht_host_free(v.p);
+    (void)napi_detach_arraybuffer(env, v.ab);  // every view now has length 0: no use-after-free from JavaScript
     return nullptr;
 }
 
@@ -727,10 +963,9 @@ napi_value HostFree(napi_env env, napi_callback_info info) {
 // no static destructors, no environment teardown.  For hosts that are done: a Node 12 process that used HIP from libuv pool threads
 // (detectAsync) has been seen to crash with SIGSEGV inside the runtime's own exit path after a complete, correct run.
 napi_value ExitNow(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
+    Args a(env, info, 1);
     int32_t code = 0;
-    if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) == napi_ok && argc > 0) get_i32(env, argv[0], &code);
+    if (a.ok) a.opt_i32(0, &code);
     env_cleanup(nullptr);
     fflush(stdout);
     fflush(stderr);
@@ -739,23 +974,18 @@ napi_value ExitNow(napi_env env, napi_callback_info info) {
 }
 
 napi_value DeviceAlloc(napi_env env, napi_callback_info info) {
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Args a(env, info, 2);
     Locked L;
     double bytes = 0;
-    if (too_few(env, argc, 2) || !lock_ctx(env, argv[0], &L)) return nullptr;
-    if (napi_get_value_double(env, argv[1], &bytes) != napi_ok || !(bytes >= 1) || bytes > 2.5e11) {
-        napi_throw_type_error(env, nullptr, "deviceAlloc(ctx, bytes)");
-        return nullptr;
-    }
+    if (!a.ctx(2, &L)) return nullptr;
+    if (napi_get_value_double(env, a.argv[1], &bytes) != napi_ok || !(bytes >= 1) || bytes > 2.5e11) return type_error(env, "deviceAlloc(ctx, bytes)");
     DevBuf *d = new DevBuf();
     ht_status st = ht_device_alloc(L.ctx, (size_t)bytes, &d->ptr);
     if (st != HT_OK) {
         delete d;
         return throw_ht(env, L.ctx, st, "ht_device_alloc");
     }
-    get_slot(env, argv[0], &d->slot);
+    get_slot(env, a.argv[0], &d->slot);
     d->bytes = (size_t)bytes;
     napi_value ext;
     NAPI_OK(napi_create_external(env, d, nullptr, nullptr, &ext));  // no finalizer: freed by deviceFree or with its context
@@ -763,138 +993,85 @@ napi_value DeviceAlloc(napi_env env, napi_callback_info info) {
 }
 
 napi_value DeviceFree(napi_env env, napi_callback_info info) {
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Args a(env, info, 2);
     Locked L;
     DevBuf *d = nullptr;
-    if (too_few(env, argc, 2) || !lock_ctx(env, argv[0], &L) || !get_devbuf(env, argv[1], &d)) return nullptr;
+    if (!a.ctx(2, &L) || !a.devbuf(1, &d)) return nullptr;
     ht_status st = ht_device_free(L.ctx, d->ptr);
     if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_device_free");  // e.g. the wrong context, or still bound elsewhere: the handle stays valid
     d->ptr = nullptr;
     return nullptr;
 }
 
-bool get_offset(napi_env env, napi_value v, size_t *out) {
-    double d = 0;
-    if (napi_get_value_double(env, v, &d) != napi_ok || !(d >= 0) || d > 2.5e11) return false;
-    *out = (size_t)d;
-    return true;
-}
-
-napi_value DeviceUpload(napi_env env, napi_callback_info info) {
-    size_t argc = 4;
-    napi_value argv[4];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+// deviceUpload / deviceDownload(ctx, dev, byteOffset, Uint8Array): the array's bytes to / from byteOffset of the buffer
+napi_value device_copy(napi_env env, napi_callback_info info, bool up) {
+    Args a(env, info, 4);
     Locked L;
     DevBuf *d = nullptr;
-    uint8_t *src = nullptr;
+    uint8_t *host = nullptr;
     size_t len = 0, off = 0;
-    if (too_few(env, argc, 4) || !lock_ctx(env, argv[0], &L) || !get_devbuf(env, argv[1], &d)) return nullptr;
-    if (!get_offset(env, argv[2], &off) || !get_bytes(env, argv[3], &src, &len) || off + len > d->bytes) {
-        napi_throw_range_error(env, nullptr, "deviceUpload(ctx, dev, byteOffset, Uint8Array): outside the device buffer");
-        return nullptr;
-    }
-    ht_status st = ht_device_upload(L.ctx, static_cast<char *>(d->ptr) + off, src, len);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_device_upload");
+    if (!a.ctx(4, &L) || !a.devbuf(1, &d)) return nullptr;
+    if (!a.offset(2, &off) || !a.bytes(3, &host, &len) || !frames_fit(off, 1, 0, len, d->bytes))
+        return range_error(env, up ? "deviceUpload(ctx, dev, byteOffset, Uint8Array): outside the device buffer" : "deviceDownload(ctx, dev, byteOffset, Uint8Array): outside the device buffer");
+    char *dev = static_cast<char *>(d->ptr) + off;
+    ht_status st = up ? ht_device_upload(L.ctx, dev, host, len) : ht_device_download(L.ctx, host, dev, len);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, up ? "ht_device_upload" : "ht_device_download");
     return nullptr;
 }
-
-napi_value DeviceDownload(napi_env env, napi_callback_info info) {
-    size_t argc = 4;
-    napi_value argv[4];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    Locked L;
-    DevBuf *d = nullptr;
-    uint8_t *dst = nullptr;
-    size_t len = 0, off = 0;
-    if (too_few(env, argc, 4) || !lock_ctx(env, argv[0], &L) || !get_devbuf(env, argv[1], &d)) return nullptr;
-    if (!get_offset(env, argv[2], &off) || !get_bytes(env, argv[3], &dst, &len) || off > d->bytes || len > d->bytes - off) {
-        napi_throw_range_error(env, nullptr, "deviceDownload(ctx, dev, byteOffset, Uint8Array): outside the device buffer");
-        return nullptr;
-    }
-    ht_status st = ht_device_download(L.ctx, dst, static_cast<char *>(d->ptr) + off, len);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_device_download");
-    return nullptr;
-}
-
-napi_value Upload(napi_env env, napi_callback_info info) {
-    size_t argc = 5;
-    napi_value argv[5];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    FrameArgs a;
-    if (too_few(env, argc, 5) || !parse_frames(env, argv, &a)) return nullptr;
-    ht_status st = bind_host_frames(a);
-    if (st != HT_OK) return throw_ht(env, a.ctx, st, "ht_upload_frames");
-    return nullptr;
-}
+napi_value DeviceUpload(napi_env env, napi_callback_info info) { return device_copy(env, info, true); }
+napi_value DeviceDownload(napi_env env, napi_callback_info info) { return device_copy(env, info, false); }
 
 napi_value BindDevice(napi_env env, napi_callback_info info) {
-    size_t argc = 5;
-    napi_value argv[5];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Args a(env, info, 5);
     Locked L;
     DevBuf *d = nullptr;
     size_t off = 0, stride = 0;
     int32_t n = 0;
-    if (too_few(env, argc, 5) || !lock_ctx(env, argv[0], &L) || !get_devbuf(env, argv[1], &d)) return nullptr;
-    if (!get_offset(env, argv[2], &off) || !get_i32(env, argv[3], &n) || !get_offset(env, argv[4], &stride) || n <= 0 || off + (size_t)n * stride > d->bytes) {
-        napi_throw_range_error(env, nullptr, "bindDevice(ctx, dev, byteOffset, n, frameStride): outside the device buffer");
-        return nullptr;
-    }
+    if (!a.ctx(5, &L) || !a.devbuf(1, &d)) return nullptr;
+    if (!a.offset(2, &off) || !a.i32(3, &n) || !a.offset(4, &stride) || n <= 0 || !frames_fit(off, (size_t)n, stride, stride, d->bytes))
+        return range_error(env, "bindDevice(ctx, dev, byteOffset, n, frameStride): outside the device buffer");
     ht_status st = ht_bind_frames_device(L.ctx, static_cast<char *>(d->ptr) + off, n, stride);
     if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_bind_frames_device");
     return nullptr;
 }
 
 napi_value UploadAsync(napi_env env, napi_callback_info info) {
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Args a(env, info, 3);
     Locked L;
     uint8_t *src = nullptr;
     size_t len = 0;
     int32_t n = 0;
-    if (too_few(env, argc, 3) || !lock_ctx(env, argv[0], &L)) return nullptr;
-    if (!get_bytes(env, argv[1], &src, &len) || !get_i32(env, argv[2], &n) || n <= 0 || len % (size_t)n) {
-        napi_throw_type_error(env, nullptr, "uploadAsync(ctx, Uint8Array rgba (n frames, ideally from hostAlloc), n)");
-        return nullptr;
-    }
+    if (!a.ctx(3, &L)) return nullptr;
+    if (!a.bytes(1, &src, &len) || !a.i32(2, &n) || n <= 0 || len % (size_t)n) return type_error(env, "uploadAsync(ctx, Uint8Array rgba (n frames, ideally from hostAlloc), n)");
     ht_status st = ht_upload_frames_async(L.ctx, src, n, len / (size_t)n);  // rgba must stay untouched until swapFrames
     if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_upload_frames_async");
     return nullptr;
 }
 
 napi_value SwapFrames(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Args a(env, info, 1);
     Locked L;
-    if (too_few(env, argc, 1) || !lock_ctx(env, argv[0], &L)) return nullptr;
+    if (!a.ctx(1, &L)) return nullptr;
     ht_status st = ht_swap_frames(L.ctx);
     if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_swap_frames");
     return nullptr;
 }
 
 napi_value DetectEnqueue(napi_env env, napi_callback_info info) {
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Args a(env, info, 2);
     Locked L;
     int32_t fl = 0;
-    if (too_few(env, argc, 1) || !lock_ctx(env, argv[0], &L)) return nullptr;
-    if (argc > 1) get_i32(env, argv[1], &fl);
+    if (!a.ctx(1, &L)) return nullptr;
+    a.opt_i32(1, &fl);
     ht_status st = ht_detect_enqueue(L.ctx, (uint32_t)fl);
     if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_detect_enqueue");
     return nullptr;
 }
 
 napi_value DetectCollect(napi_env env, napi_callback_info info) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Args a(env, info, 1);
     Locked L;
-    if (too_few(env, argc, 1) || !lock_ctx(env, argv[0], &L)) return nullptr;
+    if (!a.ctx(1, &L)) return nullptr;
     DetectJob j;
     j.n = ht_frames_enqueued(L.ctx);  // the batch in flight, not whatever is bound by now
     j.hits.resize(1u << 16);
@@ -909,410 +1086,29 @@ napi_value DetectCollect(napi_env env, napi_callback_info info) {
 }
 
 napi_value CollectBest(napi_env env, napi_callback_info info) {
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Args a(env, info, 3);
     Locked L;
     int32_t mn = 1, rq = -1;
-    if (too_few(env, argc, 1) || !lock_ctx(env, argv[0], &L)) return nullptr;
-    if (argc > 1) get_i32(env, argv[1], &mn);
-    if (argc > 2) get_i32(env, argv[2], &rq);
+    if (!a.ctx(1, &L)) return nullptr;
+    a.opt_i32(1, &mn);
+    a.opt_i32(2, &rq);
     const int32_t n = ht_frames_enqueued(L.ctx);
     std::vector<ht_rect> best((size_t)(n > 0 ? n : 1));
     uint32_t total = 0;
     ht_status st = rq >= 0 ? ht_detect_collect_best_requeue(L.ctx, mn, best.data(), &total, (uint32_t)rq) : ht_detect_collect_best(L.ctx, mn, best.data(), &total);
     if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_detect_collect_best");
-    napi_value obj, ab, ta, v;
-    void *p = nullptr;
+    napi_value obj, v, ta = rect6_result(env, best.data(), (size_t)(n > 0 ? n : 0));
+    if (!ta) return nullptr;
     NAPI_OK(napi_create_object(env, &obj));
-    NAPI_OK(napi_create_arraybuffer(env, (size_t)n * 6 * 8, &p, &ab));
-    double *d = static_cast<double *>(p);
-    for (int i = 0; i < n; i++) {
-        const ht_rect &r = best[(size_t)i];
-        d[6 * i] = r.x, d[6 * i + 1] = r.y, d[6 * i + 2] = r.width, d[6 * i + 3] = r.height, d[6 * i + 4] = r.confidence, d[6 * i + 5] = r.neighbors;
-    }
-    NAPI_OK(napi_create_typedarray(env, napi_float64_array, (size_t)n * 6, ab, 0, &ta));
     NAPI_OK(napi_set_named_property(env, obj, "best", ta));
     NAPI_OK(napi_create_uint32(env, total, &v));
     NAPI_OK(napi_set_named_property(env, obj, "hits", v));
     return obj;
 }
 
-napi_value f64_result(napi_env env, const double *src, size_t n) {
-    napi_value ab, ta;
-    void *p = nullptr;
-    NAPI_OK(napi_create_arraybuffer(env, n * 8, &p, &ab));
-    if (n) std::memcpy(p, src, n * 8);
-    NAPI_OK(napi_create_typedarray(env, napi_float64_array, n, ab, 0, &ta));
-    return ta;
-}
-
-napi_value wb_common(napi_env env, napi_callback_info info, bool fused) {
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    Locked L;
-    int32_t n = 0;
-    if (too_few(env, argc, 2) || !lock_ctx(env, argv[0], &L)) return nullptr;
-    if (!get_i32(env, argv[1], &n) || n <= 0) {
-        napi_throw_type_error(env, nullptr, "(ctx, n)");
-        return nullptr;
-    }
-    std::vector<double> out((size_t)n);
-    ht_status st = fused ? ht_detect_whitebalance(L.ctx, out.data(), n) : ht_whitebalance_batch(L.ctx, out.data(), n);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, fused ? "ht_detect_whitebalance" : "ht_whitebalance_batch");
-    return f64_result(env, out.data(), out.size());
-}
-napi_value DetectWhitebalance(napi_env env, napi_callback_info info) { return wb_common(env, info, true); }
-napi_value WhitebalanceBound(napi_env env, napi_callback_info info) { return wb_common(env, info, false); }
-
-napi_value trackobjs_result(napi_env env, const std::vector<ht_cs_trackobj> &out) {
-    std::vector<double> d(out.size() * 9);
-    for (size_t i = 0; i < out.size(); i++) {
-        const ht_cs_trackobj &o = out[i];
-        double *r = d.data() + 9 * i;
-        r[0] = o.x, r[1] = o.y, r[2] = o.width, r[3] = o.height, r[4] = o.angle;
-        r[5] = o.sw_x, r[6] = o.sw_y, r[7] = o.sw_width, r[8] = o.sw_height;
-    }
-    return f64_result(env, d.data(), d.size());
-}
-
-napi_value CamshiftInitBound(napi_env env, napi_callback_info info) {
-    size_t argc = 4;
-    napi_value argv[4];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    Locked L;
-    int32_t n = 0, first = 0;
-    napi_typedarray_type t;
-    size_t len;
-    void *p;
-    napi_value ab;
-    size_t off;
-    if (too_few(env, argc, 4) || !lock_ctx(env, argv[0], &L)) return nullptr;
-    if (!get_i32(env, argv[1], &n) || !get_i32(env, argv[2], &first) || n <= 0 || napi_get_typedarray_info(env, argv[3], &t, &len, &p, &ab, &off) != napi_ok ||
-        t != napi_int32_array || len < (size_t)n * 4) {
-        napi_throw_type_error(env, nullptr, "camshiftInitBound(ctx, n, first, Int32Array rects[4n])");
-        return nullptr;
-    }
-    ht_status st = ht_camshift_init_batch(L.ctx, first, n, static_cast<const ht_cs_rect *>(p));
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_init_batch");
-    return nullptr;
-}
-
-napi_value CamshiftTrackBound(napi_env env, napi_callback_info info) {
-    size_t argc = 5;
-    napi_value argv[5];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    Locked L;
-    int32_t n = 0, first = 0, calc = 1;
-    bool fetch = true;
-    if (too_few(env, argc, 4) || !lock_ctx(env, argv[0], &L)) return nullptr;
-    if (!get_i32(env, argv[1], &n) || !get_i32(env, argv[2], &first) || !get_i32(env, argv[3], &calc) || n <= 0) {
-        napi_throw_type_error(env, nullptr, "camshiftTrackBound(ctx, n, first, calcAngles, fetch)");
-        return nullptr;
-    }
-    if (argc > 4) napi_get_value_bool(env, argv[4], &fetch);
-    std::vector<ht_cs_trackobj> out((size_t)n);
-    ht_status st = ht_camshift_track_batch(L.ctx, first, n, calc, fetch ? out.data() : nullptr);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_track_batch");
-    if (!fetch) return nullptr;
-    return trackobjs_result(env, out);
-}
-
-// Int32Array pairs[2n] = stream0, frame0, stream1, frame1, ... (ht_cs_pair); *n = pairs
-bool get_pairs(napi_env env, napi_value v, const ht_cs_pair **pairs, int32_t *n) {
-    napi_typedarray_type t;
-    size_t len;
-    void *p;
-    napi_value ab;
-    size_t off;
-    if (napi_get_typedarray_info(env, v, &t, &len, &p, &ab, &off) != napi_ok || t != napi_int32_array || len < 2 || (len & 1) || len > (size_t)1 << 24) return false;
-    *pairs = static_cast<const ht_cs_pair *>(p);
-    *n = (int32_t)(len / 2);
-    return true;
-}
-
-napi_value CamshiftInitPairs(napi_env env, napi_callback_info info) {
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    Locked L;
-    const ht_cs_pair *pairs = nullptr;
-    int32_t n = 0;
-    napi_typedarray_type t;
-    size_t len;
-    void *p;
-    napi_value ab;
-    size_t off;
-    if (too_few(env, argc, 3) || !lock_ctx(env, argv[0], &L)) return nullptr;
-    if (!get_pairs(env, argv[1], &pairs, &n) || napi_get_typedarray_info(env, argv[2], &t, &len, &p, &ab, &off) != napi_ok || t != napi_int32_array ||
-        len < (size_t)n * 4) {
-        napi_throw_type_error(env, nullptr, "camshiftInitPairs(ctx, Int32Array pairs[2n], Int32Array rects[4n])");
-        return nullptr;
-    }
-    ht_status st = ht_camshift_init_pairs(L.ctx, pairs, n, static_cast<const ht_cs_rect *>(p));
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_init_pairs");
-    return nullptr;
-}
-
-napi_value CamshiftTrackPairs(napi_env env, napi_callback_info info) {
-    size_t argc = 4;
-    napi_value argv[4];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    Locked L;
-    const ht_cs_pair *pairs = nullptr;
-    int32_t n = 0, calc = 1;
-    bool fetch = true;
-    if (too_few(env, argc, 3) || !lock_ctx(env, argv[0], &L)) return nullptr;
-    if (!get_pairs(env, argv[1], &pairs, &n) || !get_i32(env, argv[2], &calc)) {
-        napi_throw_type_error(env, nullptr, "camshiftTrackPairs(ctx, Int32Array pairs[2n], calcAngles, fetch)");
-        return nullptr;
-    }
-    if (argc > 3) napi_get_value_bool(env, argv[3], &fetch);
-    std::vector<ht_cs_trackobj> out((size_t)n);
-    ht_status st = ht_camshift_track_pairs(L.ctx, pairs, n, calc, fetch ? out.data() : nullptr);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_track_pairs");
-    if (!fetch) return nullptr;
-    return trackobjs_result(env, out);
-}
-
-napi_value CamshiftTrackCollect(napi_env env, napi_callback_info info) {
-    size_t argc = 2;
-    napi_value argv[2];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    Locked L;
-    int32_t n = 0;
-    if (too_few(env, argc, 2) || !lock_ctx(env, argv[0], &L)) return nullptr;
-    if (!get_i32(env, argv[1], &n) || n <= 0) {
-        napi_throw_type_error(env, nullptr, "camshiftTrackCollect(ctx, n)");
-        return nullptr;
-    }
-    std::vector<ht_cs_trackobj> out((size_t)n);
-    ht_status st = ht_camshift_track_collect(L.ctx, n, out.data());
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_track_collect");
-    return trackobjs_result(env, out);
-}
-
-napi_value CamshiftTrackSequence(napi_env env, napi_callback_info info) {
-    size_t argc = 9;
-    napi_value argv[9];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    Locked L;
-    DevBuf *d = nullptr;
-    int32_t first = 0, n = 0, calc = 1;
-    size_t stride = 0;
-    bool out_all = false, fetch = true;
-    napi_typedarray_type t;
-    size_t ncalls;
-    void *p;
-    napi_value ab;
-    size_t off;
-    if (too_few(env, argc, 7) || !lock_ctx(env, argv[0], &L)) return nullptr;
-    if (!get_i32(env, argv[1], &first) || !get_i32(env, argv[2], &n) || !get_i32(env, argv[3], &calc) || !get_devbuf(env, argv[4], &d)) return nullptr;
-    if (napi_get_typedarray_info(env, argv[5], &t, &ncalls, &p, &ab, &off) != napi_ok || t != napi_float64_array || ncalls == 0 || ncalls > 100000 ||
-        !get_offset(env, argv[6], &stride) || n <= 0) {
-        napi_throw_type_error(env, nullptr, "camshiftTrackSequence(ctx, first, n, calcAngles, dev, Float64Array byteOffsets, frameStride, outAll, fetch)");
-        return nullptr;
-    }
-    if (argc > 7) napi_get_value_bool(env, argv[7], &out_all);
-    if (argc > 8) napi_get_value_bool(env, argv[8], &fetch);
-    std::vector<const void *> ptrs(ncalls);
-    for (size_t k = 0; k < ncalls; k++) {
-        const double o = static_cast<const double *>(p)[k];
-        if (!(o >= 0) || (size_t)o + (size_t)n * stride > d->bytes) {
-            napi_throw_range_error(env, nullptr, "camshiftTrackSequence: a call's frames lie outside the device buffer");
-            return nullptr;
-        }
-        ptrs[k] = static_cast<const char *>(d->ptr) + (size_t)o;
-    }
-    std::vector<ht_cs_trackobj> out(fetch ? (size_t)n * (out_all ? ncalls : 1) : 0);
-    ht_status st = ht_camshift_track_sequence(L.ctx, first, n, calc, ptrs.data(), (int32_t)ncalls, stride, fetch ? out.data() : nullptr, out_all ? 1 : 0);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_track_sequence");
-    if (!fetch) return nullptr;
-    return trackobjs_result(env, out);
-}
-
-napi_value CamshiftSequenceCollect(napi_env env, napi_callback_info info) {
-    size_t argc = 4;
-    napi_value argv[4];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    Locked L;
-    int32_t n = 0, ncalls = 0;
-    bool out_all = false;
-    if (too_few(env, argc, 3) || !lock_ctx(env, argv[0], &L)) return nullptr;
-    if (!get_i32(env, argv[1], &n) || !get_i32(env, argv[2], &ncalls) || n <= 0 || ncalls <= 0) {
-        napi_throw_type_error(env, nullptr, "camshiftSequenceCollect(ctx, n, ncalls, outAll)");
-        return nullptr;
-    }
-    if (argc > 3) napi_get_value_bool(env, argv[3], &out_all);
-    std::vector<ht_cs_trackobj> out((size_t)n * (out_all ? (size_t)ncalls : 1));
-    ht_status st = ht_camshift_sequence_collect(L.ctx, n, ncalls, out_all ? 1 : 0, out.data());
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_sequence_collect");
-    return trackobjs_result(env, out);
-}
-
-// camshiftBackProject(ctx, n, first, kind) -> Uint8Array(n*w*h*4) | Float64Array(n*w*h): ht_camshift_backproject of the bound frames
-napi_value CamshiftBackProject(napi_env env, napi_callback_info info) {
-    size_t argc = 4;
-    napi_value argv[4];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    Locked L;
-    int32_t n = 0, first = 0, kind = 0;
-    if (too_few(env, argc, 4) || !lock_ctx(env, argv[0], &L)) return nullptr;
-    if (!get_i32(env, argv[1], &n) || !get_i32(env, argv[2], &first) || !get_i32(env, argv[3], &kind) || n <= 0 || (kind != HT_BP_RGBA8 && kind != HT_BP_F64)) {
-        napi_throw_type_error(env, nullptr, "camshiftBackProject(ctx, n, first, kind = BP_RGBA8 | BP_F64)");
-        return nullptr;
-    }
-    ht_plane_info pl;  // level 0 of the pyramid is the frame itself
-    if (ht_plane(L.ctx, 0, 0, &pl) != HT_OK || pl.width <= 0 || pl.height <= 0) {
-        napi_throw_error(env, nullptr, "camshiftBackProject: no geometry (setGeometry first)");
-        return nullptr;
-    }
-    const size_t elem = kind == HT_BP_F64 ? 8 : 4, count = (size_t)n * (size_t)pl.width * (size_t)pl.height;
-    napi_value ab, ta;
-    void *p = nullptr;
-    NAPI_OK(napi_create_arraybuffer(env, count * elem, &p, &ab));
-    // the stride is passed explicitly: the library refuses one that is smaller than ITS frame, so the buffer can never be too small
-    ht_status st = ht_camshift_backproject(L.ctx, first, n, kind, p, (size_t)pl.width * (size_t)pl.height * elem);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_backproject");
-    if (kind == HT_BP_F64) NAPI_OK(napi_create_typedarray(env, napi_float64_array, count, ab, 0, &ta));
-    else NAPI_OK(napi_create_typedarray(env, napi_uint8_array, count * 4, ab, 0, &ta));
-    return ta;
-}
-
-// camshiftBackProjectDevice(ctx, n, first, kind, dev, byteOffset, stride): the same into a deviceAlloc() buffer, enqueue only
-napi_value CamshiftBackProjectDevice(napi_env env, napi_callback_info info) {
-    size_t argc = 7;
-    napi_value argv[7];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    Locked L;
-    DevBuf *d = nullptr;
-    int32_t n = 0, first = 0, kind = 0;
-    size_t off = 0, stride = 0;
-    if (too_few(env, argc, 7) || !lock_ctx(env, argv[0], &L)) return nullptr;
-    if (!get_i32(env, argv[1], &n) || !get_i32(env, argv[2], &first) || !get_i32(env, argv[3], &kind) || n <= 0 || (kind != HT_BP_RGBA8 && kind != HT_BP_F64)) {
-        napi_throw_type_error(env, nullptr, "camshiftBackProjectDevice(ctx, n, first, kind = BP_RGBA8 | BP_F64, dev, byteOffset, stride)");
-        return nullptr;
-    }
-    if (!get_devbuf(env, argv[4], &d)) return nullptr;
-    ht_plane_info pl;
-    if (ht_plane(L.ctx, 0, 0, &pl) != HT_OK || pl.width <= 0 || pl.height <= 0) {
-        napi_throw_error(env, nullptr, "camshiftBackProjectDevice: no geometry (setGeometry first)");
-        return nullptr;
-    }
-    const size_t frame = (size_t)pl.width * (size_t)pl.height * (kind == HT_BP_F64 ? 8 : 4);
-    if (!get_offset(env, argv[5], &off) || !get_offset(env, argv[6], &stride) || (stride != 0 && stride < frame) ||
-        off + (size_t)(n - 1) * (stride ? stride : frame) + frame > d->bytes) {
-        napi_throw_range_error(env, nullptr, "camshiftBackProjectDevice(ctx, n, first, kind, dev, byteOffset, stride): outside the device buffer");
-        return nullptr;
-    }
-    ht_status st = ht_camshift_backproject_device(L.ctx, first, n, kind, static_cast<char *>(d->ptr) + off, stride ? stride : frame);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_backproject_device");
-    return nullptr;
-}
-
-// camshiftBackProjectPairs(ctx, Int32Array pairs[2n], kind) -> Uint8Array(n*w*h*4) | Float64Array(n*w*h): ht_camshift_backproject_pairs — output i is
-// bound frame pairs[2i + 1] through the model of stream pairs[2i]
-napi_value CamshiftBackProjectPairs(napi_env env, napi_callback_info info) {
-    size_t argc = 3;
-    napi_value argv[3];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    Locked L;
-    const ht_cs_pair *pairs = nullptr;
-    int32_t n = 0, kind = 0;
-    if (too_few(env, argc, 3) || !lock_ctx(env, argv[0], &L)) return nullptr;
-    if (!get_pairs(env, argv[1], &pairs, &n) || !get_i32(env, argv[2], &kind) || (kind != HT_BP_RGBA8 && kind != HT_BP_F64)) {
-        napi_throw_type_error(env, nullptr, "camshiftBackProjectPairs(ctx, Int32Array pairs[2n], kind = BP_RGBA8 | BP_F64)");
-        return nullptr;
-    }
-    ht_plane_info pl;  // level 0 of the pyramid is the frame itself
-    if (ht_plane(L.ctx, 0, 0, &pl) != HT_OK || pl.width <= 0 || pl.height <= 0) {
-        napi_throw_error(env, nullptr, "camshiftBackProjectPairs: no geometry (setGeometry first)");
-        return nullptr;
-    }
-    const size_t elem = kind == HT_BP_F64 ? 8 : 4, count = (size_t)n * (size_t)pl.width * (size_t)pl.height;
-    napi_value ab, ta;
-    void *p = nullptr;
-    NAPI_OK(napi_create_arraybuffer(env, count * elem, &p, &ab));
-    // the stride is passed explicitly: the library refuses one that is smaller than ITS frame, so the buffer can never be too small
-    ht_status st = ht_camshift_backproject_pairs(L.ctx, pairs, n, kind, p, (size_t)pl.width * (size_t)pl.height * elem);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_backproject_pairs");
-    if (kind == HT_BP_F64) NAPI_OK(napi_create_typedarray(env, napi_float64_array, count, ab, 0, &ta));
-    else NAPI_OK(napi_create_typedarray(env, napi_uint8_array, count * 4, ab, 0, &ta));
-    return ta;
-}
-
-// camshiftBackProjectPairsDevice(ctx, Int32Array pairs[2n], kind, dev, byteOffset, stride): the same into a deviceAlloc() buffer, enqueue only
-napi_value CamshiftBackProjectPairsDevice(napi_env env, napi_callback_info info) {
-    size_t argc = 6;
-    napi_value argv[6];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    Locked L;
-    DevBuf *d = nullptr;
-    const ht_cs_pair *pairs = nullptr;
-    int32_t n = 0, kind = 0;
-    size_t off = 0, stride = 0;
-    if (too_few(env, argc, 6) || !lock_ctx(env, argv[0], &L)) return nullptr;
-    if (!get_pairs(env, argv[1], &pairs, &n) || !get_i32(env, argv[2], &kind) || (kind != HT_BP_RGBA8 && kind != HT_BP_F64)) {
-        napi_throw_type_error(env, nullptr, "camshiftBackProjectPairsDevice(ctx, Int32Array pairs[2n], kind = BP_RGBA8 | BP_F64, dev, byteOffset, stride)");
-        return nullptr;
-    }
-    if (!get_devbuf(env, argv[3], &d)) return nullptr;
-    ht_plane_info pl;
-    if (ht_plane(L.ctx, 0, 0, &pl) != HT_OK || pl.width <= 0 || pl.height <= 0) {
-        napi_throw_error(env, nullptr, "camshiftBackProjectPairsDevice: no geometry (setGeometry first)");
-        return nullptr;
-    }
-    const size_t frame = (size_t)pl.width * (size_t)pl.height * (kind == HT_BP_F64 ? 8 : 4);
-    if (!get_offset(env, argv[4], &off) || !get_offset(env, argv[5], &stride) || (stride != 0 && stride < frame) ||
-        off + (size_t)(n - 1) * (stride ? stride : frame) + frame > d->bytes) {
-        napi_throw_range_error(env, nullptr, "camshiftBackProjectPairsDevice(ctx, pairs, kind, dev, byteOffset, stride): outside the device buffer");
-        return nullptr;
-    }
-    ht_status st = ht_camshift_backproject_pairs_device(L.ctx, pairs, n, kind, static_cast<char *>(d->ptr) + off, stride ? stride : frame);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_backproject_pairs_device");
-    return nullptr;
-}
-
-// rect argument of the draw calls: null / undefined (the whole source frame) or an Int32Array [x, y, width, height]
-bool get_rect(napi_env env, napi_value v, ht_cs_rect *r, const ht_cs_rect **out) {
-    napi_valuetype vt;
-    *out = nullptr;
-    if (napi_typeof(env, v, &vt) == napi_ok && (vt == napi_null || vt == napi_undefined)) return true;
-    napi_typedarray_type t;
-    size_t len, off;
-    void *p;
-    napi_value ab;
-    if (napi_get_typedarray_info(env, v, &t, &len, &p, &ab, &off) != napi_ok || t != napi_int32_array || len < 4) return false;
-    memcpy(r, p, sizeof(*r));
-    *out = r;
-    return true;
-}
-
-// drawFrames(ctx, rgba, n, sw, sh, rect | null): ht_draw_frames — n host frames of sw x sh drawn onto the context's geometry and bound
-napi_value DrawFrames(napi_env env, napi_callback_info info) {
-    size_t argc = 6;
-    napi_value argv[6];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    FrameArgs a;
-    ht_cs_rect r;
-    const ht_cs_rect *rp = nullptr;
-    if (too_few(env, argc, 5) || !parse_frames(env, argv, &a)) return nullptr;
-    if (argc > 5 && !get_rect(env, argv[5], &r, &rp)) {
-        napi_throw_type_error(env, nullptr, "drawFrames(ctx, Uint8Array rgba, n, sw, sh, Int32Array rect[4] | null)");
-        return nullptr;
-    }
-    ht_status st = ht_draw_frames(a.ctx, a.rgba, a.n, a.w, a.h, 0, rp);
-    if (st != HT_OK) return throw_ht(env, a.ctx, st, "ht_draw_frames");
-    return nullptr;
-}
-
-// drawFramesDevice(ctx, srcDev, srcOffset, n, sw, sh, pitch, stride, rect | null, dstDev | null, dstOffset, dstStride, wait): ht_draw_frames_device
 napi_value DrawFramesDevice(napi_env env, napi_callback_info info) {
-    size_t argc = 13;
-    napi_value argv[13];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
     static const char *usage = "drawFramesDevice(ctx, srcDev, srcOffset, n, sw, sh, pitch, stride, rect | null, dstDev | null, dstOffset, dstStride, wait)";
+    Args a(env, info, 13);
     Locked L;
     DevBuf *src = nullptr, *dst = nullptr;
     int32_t n = 0, sw = 0, sh = 0;
@@ -1320,41 +1116,22 @@ napi_value DrawFramesDevice(napi_env env, napi_callback_info info) {
     ht_cs_rect r;
     const ht_cs_rect *rp = nullptr;
     bool wait = false;
-    if (too_few(env, argc, 12) || !lock_ctx(env, argv[0], &L) || !get_devbuf(env, argv[1], &src)) return nullptr;
-    napi_valuetype vt;
-    if (napi_typeof(env, argv[9], &vt) != napi_ok) return nullptr;
-    if (vt != napi_null && vt != napi_undefined && !get_devbuf(env, argv[9], &dst)) return nullptr;
-    if (!get_offset(env, argv[2], &soff) || !get_i32(env, argv[3], &n) || !get_i32(env, argv[4], &sw) || !get_i32(env, argv[5], &sh) || !get_offset(env, argv[6], &pitch) ||
-        !get_offset(env, argv[7], &stride) || !get_rect(env, argv[8], &r, &rp) || !get_offset(env, argv[10], &doff) || !get_offset(env, argv[11], &dstride) || n <= 0 ||
-        sw <= 0 || sh <= 0) {
-        napi_throw_type_error(env, nullptr, usage);
-        return nullptr;
-    }
-    if (argc > 12) napi_get_value_bool(env, argv[12], &wait);
-    // the ranges must lie inside the buffers the handles stand for (the library cannot know their sizes); what it checks itself — strides smaller
-    // than a frame, alignment, overlap — is left to it
-    // no product below can wrap: a factor is first bounded by a division through the buffer size it has to fit into
-    const auto frames_fit = [](size_t off, size_t n, size_t stride, size_t frame, size_t bytes) {  // off + (n - 1) stride + frame <= bytes
-        if (off > bytes || frame > bytes - off) return false;
-        return n == 1 || stride <= (bytes - off - frame) / (n - 1);
-    };
+    if (!a.ctx(12, &L) || !a.devbuf(1, &src) || !a.devbuf_or_null(9, &dst)) return nullptr;
+    if (!a.offset(2, &soff) || !a.i32(3, &n) || !a.i32(4, &sw) || !a.i32(5, &sh) || !a.offset(6, &pitch) || !a.offset(7, &stride) || !get_rect(env, a.argv[8], &r, &rp) ||
+        !a.offset(10, &doff) || !a.offset(11, &dstride) || n <= 0 || sw <= 0 || sh <= 0)
+        return type_error(env, usage);
+    a.opt_bool(12, &wait);
+    // what the library checks itself — strides smaller than a frame, alignment, overlap — is left to it
     const size_t p = pitch ? pitch : (size_t)sw * 4;
     bool inside = p <= src->bytes / (size_t)sh;  // p * sh: one source frame
     const size_t sframe = inside ? p * (size_t)sh : 0, ss = stride ? stride : sframe;
     inside = inside && frames_fit(soff, (size_t)n, ss, sframe, src->bytes);
     if (dst) {
-        ht_plane_info pl;  // level 0 of the pyramid is the frame itself
-        if (ht_plane(L.ctx, 0, 0, &pl) != HT_OK || pl.width <= 0 || pl.height <= 0) {
-            napi_throw_error(env, nullptr, "drawFramesDevice: no geometry (setGeometry first)");
-            return nullptr;
-        }
-        const size_t fb = (size_t)pl.width * (size_t)pl.height * 4;  // <= 16384 * 16384 * 4
+        const size_t fb = frame_bytes(env, L.ctx, 4, "drawFramesDevice");
+        if (!fb) return nullptr;
         inside = inside && frames_fit(doff, (size_t)n, dstride ? dstride : fb, fb, dst->bytes);
     }
-    if (!inside) {
-        napi_throw_range_error(env, nullptr, (std::string(usage) + ": outside the device buffer").c_str());
-        return nullptr;
-    }
+    if (!inside) return range_error(env, (std::string(usage) + ": outside the device buffer").c_str());
     ht_status st = ht_draw_frames_device(L.ctx, static_cast<char *>(src->ptr) + soff, n, sw, sh, pitch, stride, rp, dst ? static_cast<char *>(dst->ptr) + doff : nullptr, dstride);
     if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_draw_frames_device");
     if (wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
@@ -1362,11 +1139,9 @@ napi_value DrawFramesDevice(napi_env env, napi_callback_info info) {
 }
 
 napi_value ctx_counter(napi_env env, napi_callback_info info, int which) {
-    size_t argc = 1;
-    napi_value argv[1];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    Args a(env, info, 1);
     Locked L;
-    if (too_few(env, argc, 1) || !lock_ctx(env, argv[0], &L)) return nullptr;
+    if (!a.ctx(1, &L)) return nullptr;
     napi_value v;
     const double x = which == 0 ? (double)ht_frames_bound(L.ctx) : which == 1 ? (double)ht_frames_enqueued(L.ctx) : (double)ht_graph_launches(L.ctx);
     NAPI_OK(napi_create_double(env, x, &v));
@@ -1403,21 +1178,16 @@ napi_value Init(napi_env env, napi_value exports) {
         if (napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.fn, nullptr, &fn) != napi_ok) return nullptr;
         if (napi_set_named_property(env, exports, f.name, fn) != napi_ok) return nullptr;
     }
-    napi_value v;
-    napi_create_int32(env, ht_abi_version(), &v);
-    napi_set_named_property(env, exports, "abiVersion", v);
-    napi_create_int32(env, HT_INPUT_GRAY_IN_R, &v);
-    napi_set_named_property(env, exports, "INPUT_GRAY_IN_R", v);
-    napi_create_int32(env, HT_INPUT_RGBA, &v);
-    napi_set_named_property(env, exports, "INPUT_RGBA", v);
-    napi_create_int32(env, HT_DETECT_WHITEBALANCE, &v);
-    napi_set_named_property(env, exports, "DETECT_WHITEBALANCE", v);
-    napi_create_int32(env, HT_SCAN_STATS, &v);
-    napi_set_named_property(env, exports, "SCAN_STATS", v);
-    napi_create_int32(env, HT_BP_RGBA8, &v);
-    napi_set_named_property(env, exports, "BP_RGBA8", v);
-    napi_create_int32(env, HT_BP_F64, &v);
-    napi_set_named_property(env, exports, "BP_F64", v);
+    const struct {
+        const char *name;
+        int32_t value;
+    } consts[] = {{"abiVersion", ht_abi_version()},   {"INPUT_GRAY_IN_R", HT_INPUT_GRAY_IN_R}, {"INPUT_RGBA", HT_INPUT_RGBA}, {"DETECT_WHITEBALANCE", HT_DETECT_WHITEBALANCE},
+                  {"SCAN_STATS", HT_SCAN_STATS},      {"BP_RGBA8", HT_BP_RGBA8},               {"BP_F64", HT_BP_F64}};
+    for (auto &c : consts) {
+        napi_value v;
+        napi_create_int32(env, c.value, &v);
+        napi_set_named_property(env, exports, c.name, v);
+    }
     return exports;
 }
 

@@ -10,7 +10,7 @@ const out = { ok: true, errors: [], calls: 0, threw: 0, silent: {} };
 function check(c, msg) { if (!c) { out.ok = false; if (out.errors.length < 20) out.errors.push(msg); } }
 for (const name of Object.keys(A)) {
   if (typeof A[name] !== 'function' || name === 'exitNow') continue; /* exitNow leaves the process by design */
-  for (let argc = 0; argc <= 8; argc++) {
+  for (let argc = 0; argc <= 13; argc++) { /* 13: drawFramesDevice, the longest signature */
     for (let trial = 0; trial < (argc === 0 ? 1 : 40); trial++) {
       const args = [];
       for (let i = 0; i < argc; i++) args.push(bad[(trial * 7 + i * 3 + argc) % bad.length]);
