@@ -4,7 +4,8 @@ The primary host language of this project is JavaScript (headtrackr_amd/js/headt
 module exposes the same operations to Python so that the parity tests (pytest) and bench.py can drive the same C ABI.
 Names follow the reference: ccv.grayscale / ccv.detect_objects (src/ccv.js:22,109), camshift.Tracker
 (src/camshift.js:148), getWhitebalance (src/whitebalance.js:5).  Every method calls the HIP library; none computes on
-the CPU except ccv's own O(n^2) grouping of a few dozen rectangles, which the C ABI keeps on the host by design.
+the CPU except ccv's own O(n^2) grouping of a few dozen rectangles on the default route (detect_collect_best); detect_best_enqueue /
+detect_best_collect run that stage on the device too.
 """
 from __future__ import annotations
 
@@ -180,6 +181,57 @@ class Context:
         total = C.c_uint32(0)
         self._check(self._lib.ht_detect_collect_best_requeue(self._h, min_neighbors, out.ctypes.data, C.byref(total), next_flags))
         return out[:n], total.value
+
+    # -- the same on the device: grouping and best face behind the scan (ht_group.hip) -----------------------------------------
+    def detect_best_enqueue(self, min_neighbors: int = 1, frame_base: int = 0):
+        """behind detect_enqueue(): bucket the batch's raw hits by frame, group them and select each frame's best face on the device"""
+        self._check(self._lib.ht_detect_best_enqueue(self._h, min_neighbors, frame_base))
+
+    def detect_best_collect(self, out: np.ndarray | None = None):
+        """collects a batch that detect_best_enqueue() followed: (best rect per frame, raw hit count) — one pinned copy, one wait"""
+        n = self._collected_n = int(self._lib.ht_frames_enqueued(self._h))
+        if out is None or len(out) < n:
+            out = np.zeros(max(1, n), dtype=RECT_DTYPE)
+        total = C.c_uint32(0)
+        self._check(self._lib.ht_detect_best_collect(self._h, out.ctypes.data, C.byref(total)))
+        return out[:n], total.value
+
+    def detect_best_collect_requeue(self, out: np.ndarray | None = None, next_flags: int = HT_INPUT_RGBA):
+        """detect_best_collect, and the next batch of the bound frames with its device grouping is enqueued right behind the wait"""
+        n = self._collected_n = int(self._lib.ht_frames_enqueued(self._h))
+        if out is None or len(out) < n:
+            out = np.zeros(max(1, n), dtype=RECT_DTYPE)
+        total = C.c_uint32(0)
+        self._check(self._lib.ht_detect_best_collect_requeue(self._h, out.ctypes.data, C.byref(total), next_flags))
+        return out[:n], total.value
+
+    def detect_grouped(self, frame: int) -> np.ndarray:
+        """the full grouped list (ccv.detect_objects' result) of one frame of the batch detect_best_collect() returned last"""
+        n = C.c_uint32(0)
+        st = self._lib.ht_detect_grouped(self._h, frame, None, 0, C.byref(n))
+        self._check(st, allow=(native.HT_ERR_CAPACITY,))
+        out = np.zeros(max(1, n.value), dtype=RECT_DTYPE)
+        if n.value:
+            self._check(self._lib.ht_detect_grouped(self._h, frame, out.ctypes.data, n.value, C.byref(n)))
+        return out[: n.value]
+
+    def detect_best_records_ptr(self):
+        """(device pointer, frames) of the 64-byte per-frame records [x, y, width, height, confidence, neighbors, frame index, 1.0] of the
+        device-grouped batch: valid until the next detect_best_enqueue() / group_hits() on this context"""
+        p, n = C.c_void_p(0), C.c_int32(0)
+        self._check(self._lib.ht_detect_best_records_device(self._h, C.byref(p), C.byref(n)))
+        return int(p.value or 0), int(n.value)
+
+    def group_hits(self, hits: np.ndarray, nframes: int, min_neighbors: int = 1):
+        """the device twin of best_faces() for an unsorted hit list: (best rect per frame, grouped rects of all frames back to back in
+        frame order, their per-frame counts)"""
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        best = np.zeros(max(1, nframes), dtype=RECT_DTYPE)
+        grouped = np.zeros(max(1, len(hits)), dtype=RECT_DTYPE)
+        ngrouped = np.zeros(max(1, nframes), dtype=np.uint32)
+        self._check(self._lib.ht_group_hits(self._h, hits.ctypes.data if len(hits) else None, len(hits), nframes, min_neighbors, best.ctypes.data,
+                                            grouped.ctypes.data, ngrouped.ctypes.data))
+        return best[:nframes], grouped[: int(ngrouped[:nframes].sum())], ngrouped[:nframes]
 
     def detect_raw(self, frames: np.ndarray, flags: int = HT_INPUT_RGBA, cap: int = 1 << 16):
         """ccv.grayscale + ccv.detect_objects(..., min_neighbors = 0) for a batch: (hits, per-frame counts)."""

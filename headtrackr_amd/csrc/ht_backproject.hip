@@ -240,6 +240,9 @@ void ht_backproject_free(ht_ctx *c) {  // ht_destroy (the stream has been synchr
 // code object besides the three that profiles/traffic.json fingerprints, and tests/test_backproject_cpu.py counts them.
 #include "ht_ingest.hip"
 
+// So is the device grouping of a detect batch's raw hits (ht_detect_best_* / ht_group_hits, k_grp_*): the scan object stays as recorded.
+#include "ht_group.hip"
+
 // So are the pair forms of the camshift calls (ht_camshift_init_pairs / ht_camshift_track_pairs, k_csp_*): new kernels must not enter the
 // fingerprinted camshift object, and the library keeps four code objects.
 #include "ht_cs_pairs.hip"

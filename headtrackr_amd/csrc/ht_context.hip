@@ -339,6 +339,7 @@ static bool apply_options(ht_ctx *c, const std::string &opts, std::string &why) 
         else if (key == "graph_max_frames") c->graph_max_frames = std::max(0, iv);
         else if (key == "host_threads") c->host_threads = std::min(64, std::max(0, iv));
         else if (key == "force_rccl") c->force_rccl = iv != 0;
+        else if (key == "group_cap") c->grp_cap_opt = std::max(1, iv);
 #ifdef HT_DEBUG_KNOBS
         else if (key == "stop_stage") c->dbg_stop_stage = iv;                        // the tile kernel stops before this stage
         else if (key == "cs_iters") c->dbg_cs_iters = std::min(10, std::max(0, iv));   // mean-shift iterations (camshift.js:284 has 10)
@@ -511,6 +512,7 @@ extern "C" void ht_destroy(ht_ctx *c) {
     ht_backproject_free(c);
     ht_ingest_free(c);
     ht_cs_pairs_free(c);
+    ht_group_free(c);
     if (c->d_gather) (void)hipFree(c->d_gather);
     for (auto &a : release) {
         if (a.orphan) {  // whatever a context that has meanwhile re-bound elsewhere still had enqueued against it has to be through
@@ -921,7 +923,29 @@ extern "C" ht_status ht_detect_enqueue(ht_ctx *c, uint32_t flags) {
     c->stats_enqueued = (flags & HT_SCAN_STATS) != 0;
     c->wb_enqueued = (flags & HT_DETECT_WHITEBALANCE) != 0;
     c->enqueued = true;
+    c->grp_enqueued = false;      // a device grouping belongs to the batch it was enqueued behind (ht_detect_best_enqueue), not to this one
     c->enq_nframes = c->nframes;  // ht_detect_collect reports THIS batch even if other frames were bound / swapped in meanwhile
+    return HT_OK;
+}
+
+// What every collect call leaves behind once the stream has been synchronised: the batch counts as collected, the whitebalance sums that
+// travelled to h_wb_pinned become the snapshot ht_detect_whitebalance reports (wb_snap), the stage counts are fetched.  Shared with the
+// device-grouped collect (ht_group.hip).
+ht_status ht_detect_mark_collected(ht_ctx *c, bool wb_snap) {
+    c->enqueued = false;
+    if (wb_snap) {
+        c->h_wb_sums.assign(c->h_wb_pinned, c->h_wb_pinned + 4 * (size_t)c->enq_nframes);
+        c->wb_collected_n = c->enq_nframes;
+    } else {
+        c->wb_collected_n = -1;
+    }
+    std::memset(c->h_stage_in, 0, sizeof(c->h_stage_in));
+    if (c->stats_enqueued) {
+        std::vector<unsigned long long> sh((size_t)64 * HT_STAT_SHARDS);
+        HT_HIP(c, hipMemcpy(sh.data(), c->d_stats, sh.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (int r = 0; r < HT_STAT_SHARDS; r++)
+            for (int j = 0; j < 64; j++) c->h_stage_in[j] += sh[(size_t)r * 64 + j];
+    }
     return HT_OK;
 }
 
@@ -953,20 +977,9 @@ extern "C" ht_status ht_detect_collect(ht_ctx *c, ht_hit *hits, uint32_t cap, ui
         HT_HIP(c, hipMemcpyAsync(c->h_wb_pinned, c->d_scratch, sizeof(unsigned long long) * 4 * (size_t)c->enq_nframes, hipMemcpyDeviceToHost, c->stream));
     HT_HIP(c, hipStreamSynchronize(c->stream));
     std::memcpy(&c->h_counters, c->h_pinned, sizeof(HtCounters));
-    c->enqueued = false;
-    if (wb_snap) {
-        c->h_wb_sums.assign(c->h_wb_pinned, c->h_wb_pinned + 4 * (size_t)c->enq_nframes);
-        c->wb_collected_n = c->enq_nframes;
-    } else {
-        c->wb_collected_n = -1;
-    }
-    std::memset(c->h_stage_in, 0, sizeof(c->h_stage_in));
-    if (c->stats_enqueued) {
-        std::vector<unsigned long long> sh((size_t)64 * HT_STAT_SHARDS);
-        HT_HIP(c, hipMemcpy(sh.data(), c->d_stats, sh.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        for (int r = 0; r < HT_STAT_SHARDS; r++)
-            for (int j = 0; j < 64; j++) c->h_stage_in[j] += sh[(size_t)r * 64 + j];
-    }
+    c->grp_enqueued = false;  // a device grouping enqueued behind this batch (ht_detect_best_enqueue) is dropped with it
+    const ht_status cst = ht_detect_mark_collected(c, wb_snap);
+    if (cst != HT_OK) return cst;
     const uint32_t found = c->h_counters.nhits;
     c->spec_hint = found;
     if (total) *total = found;
@@ -1226,8 +1239,18 @@ extern "C" ht_status ht_kernel_times(ht_ctx *c, ht_kernel_time *out, int32_t *n,
         }
         k++;
     }
+    // frames of device-grouped batches (ht_group.hip) whose status word said "over the cap" and that the host finished: counted like the
+    // forms above, profiling on or off
+    if (c->grp_over_cap_frames) {
+        if (out && k < cap) {
+            std::memset(&out[k], 0, sizeof(ht_kernel_time));
+            std::strncpy(out[k].name, "grp_over_cap_frames", sizeof(out[k].name) - 1);
+            out[k].launches = c->grp_over_cap_frames;
+        }
+        k++;
+    }
     *n = k;
-    if (reset) c->timers.clear(), c->cs_fused_launches[0] = c->cs_fused_launches[1] = 0;
+    if (reset) c->timers.clear(), c->cs_fused_launches[0] = c->cs_fused_launches[1] = 0, c->grp_over_cap_frames = 0;
     return HT_OK;
 }
 

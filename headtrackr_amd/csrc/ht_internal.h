@@ -357,6 +357,27 @@ struct ht_ctx {
 
     std::vector<std::pair<void *, size_t>> user_allocs;  // ht_device_alloc buffers still alive (pointer, bytes): freed by ht_destroy at the latest
 
+    // device grouping (ht_group.hip): a batch's raw hits bucketed by frame, grouped and reduced to one 64-byte record per frame on the
+    // device.  hits2 / rects hold hit_capacity entries and are allocated on first use; the result block (ht_group_plan.h: head, records,
+    // status, ngrouped, count, start) and the scatter cursors grow with the frame count; konst = [HT_MAX_LEVELS level scales][u32 n].
+    int grp_cap_opt = 1 << 30;           // option group_cap: hits of a frame one workgroup takes at most (ht_grp_cap clamps it)
+    ht_hit *d_grp_hits2 = nullptr;
+    ht_rect *d_grp_rects = nullptr;
+    uint8_t *d_grp_out = nullptr, *h_grp_out = nullptr;  // device block and its pinned copy
+    size_t grp_out_cap = 0, h_grp_out_cap = 0;           // bytes
+    uint32_t *d_grp_cursor = nullptr;
+    size_t grp_cursor_cap = 0;
+    double *d_grp_konst = nullptr;
+    ht_hit *d_grp_in = nullptr;          // ht_group_hits: the uploaded hit list
+    size_t grp_in_cap = 0;
+    bool grp_enqueued = false;           // ht_detect_best_enqueue was issued behind the batch in flight
+    bool grp_valid = false;              // the device buffers hold the batch collected last (until the next enqueue of this kind)
+    int grp_nframes = 0;                 // frames of the batch enqueued / collected last on this route
+    int32_t grp_min_neighbors = 1, grp_frame_base = 0;
+    std::vector<uint32_t> h_grp_ngrouped, h_grp_start, h_grp_status;   // per frame of the collected batch
+    std::vector<std::vector<ht_rect>> h_grp_over;                      // grouped lists of the frames the host finished (over the cap)
+    uint32_t grp_over_cap_frames = 0;    // such frames since the last ht_kernel_times(reset): reported there as grp_over_cap_frames
+
     // multi-GPU exchange buffer (ht_allgather.hip: ht_allgather_best_faces)
     void *d_gather = nullptr;
     size_t d_gather_bytes = 0;
@@ -424,6 +445,8 @@ void ht_camshift_free(ht_ctx *ctx);                         // ht_camshift.hip: 
 void ht_backproject_free(ht_ctx *ctx);                      // ht_backproject.hip: its scratch (ht_destroy)
 void ht_cs_pairs_free(ht_ctx *ctx);                         // ht_cs_pairs.hip: pair table, staging and histogram scratch (ht_destroy)
 void ht_ingest_free(ht_ctx *ctx);                           // ht_ingest.hip: the host form's source staging (ht_destroy)
+void ht_group_free(ht_ctx *ctx);                            // ht_group.hip: the device grouping's buffers (ht_destroy)
+ht_status ht_detect_mark_collected(ht_ctx *ctx, bool wb_snap);  // ht_context.hip: the state every collect call leaves behind
 ht_status ht_frames_own_reserve(ht_ctx *ctx, size_t need, const char *fn);  // ht_context.hip: the context's own frame buffer holds >= need bytes
 void ht_frames_bind_own(ht_ctx *ctx, int n);                // ht_context.hip: binds its first n frames (packed), as after ht_upload_frames
 ht_status ht_launch_pyramid(ht_ctx *ctx, uint32_t flags);   // ht_pyramid.hip

@@ -28,6 +28,12 @@
 //   uploadAsync(ctx, rgba, n) / swapFrames(ctx)          double-buffered ingest (rgba should come from hostAlloc)
 //   detectEnqueue(ctx, flags)             ht_detect_enqueue           detectCollect(ctx) -> hits object (ht_detect_collect)
 //   collectBest(ctx, minNeighbors, requeueFlags = -1) -> {best: Float64Array(6 n), hits}   ht_detect_collect_best(_requeue)
+//   detectBestEnqueue(ctx, minNeighbors, frameBase = 0)   ht_detect_best_enqueue: grouping + best face of the batch in flight on the device
+//   collectBestDevice(ctx, requeueFlags = -1) -> {best: Float64Array(6 n), hits}   ht_detect_best_collect(_requeue)
+//   detectGrouped(ctx, frame) -> Float64Array(6 k)       ht_detect_grouped: the full grouped list of one frame of that batch
+//   detectBestRecords(ctx) -> Float64Array(8 n)          the 64-byte records behind ht_detect_best_records_device, downloaded
+//   groupHits(ctx, Uint8Array hits, nframes, minNeighbors) -> {best: Float64Array(6 nframes), grouped: Float64Array(6 k), counts: Uint32Array(nframes)}
+//        ht_group_hits: hits = 24-byte ht_hit records in any order
 //   detectWhitebalance(ctx, n) -> Float64Array(n)        whitebalanceBound(ctx, n) -> Float64Array(n)
 //   camshiftInitBound(ctx, n, first, Int32Array rects[4n])   camshiftTrackBound(ctx, n, first, calcAngles, fetch = true) -> Float64Array(9n) | undefined
 //   camshiftTrackCollect(ctx, n) -> Float64Array(9n)
@@ -1106,6 +1112,105 @@ napi_value CollectBest(napi_env env, napi_callback_info info) {
     return obj;
 }
 
+// ---- the device route of the same post-processing (ht_group.hip).  Each entry point calls its export directly (no table of function
+// pointers): the symbols stay lazily bound, so an addon linked against a C ABI without them still loads.
+
+napi_value DetectBestEnqueue(napi_env env, napi_callback_info info) {
+    Args a(env, info, 3);
+    Locked L;
+    int32_t mn = 1, base = 0;
+    if (!a.ctx(2, &L)) return nullptr;
+    if (!a.i32(1, &mn)) return type_error(env, "detectBestEnqueue(ctx, minNeighbors, frameBase = 0)");
+    a.opt_i32(2, &base);
+    const ht_status st = ht_detect_best_enqueue(L.ctx, mn, base);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_detect_best_enqueue");
+    return nullptr;
+}
+
+napi_value CollectBestDevice(napi_env env, napi_callback_info info) {
+    Args a(env, info, 2);
+    Locked L;
+    int32_t rq = -1;
+    if (!a.ctx(1, &L)) return nullptr;
+    a.opt_i32(1, &rq);
+    const int32_t n = ht_frames_enqueued(L.ctx);
+    std::vector<ht_rect> best((size_t)(n > 0 ? n : 1));
+    uint32_t total = 0;
+    ht_status st;
+    if (rq >= 0) st = ht_detect_best_collect_requeue(L.ctx, best.data(), &total, (uint32_t)rq);
+    else st = ht_detect_best_collect(L.ctx, best.data(), &total);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_detect_best_collect");
+    napi_value obj, v, ta = rect6_result(env, best.data(), (size_t)(n > 0 ? n : 0));
+    if (!ta) return nullptr;
+    NAPI_OK(napi_create_object(env, &obj));
+    NAPI_OK(napi_set_named_property(env, obj, "best", ta));
+    NAPI_OK(napi_create_uint32(env, total, &v));
+    NAPI_OK(napi_set_named_property(env, obj, "hits", v));
+    return obj;
+}
+
+napi_value DetectGrouped(napi_env env, napi_callback_info info) {
+    Args a(env, info, 2);
+    Locked L;
+    int32_t frame = 0;
+    if (!a.ctx(2, &L)) return nullptr;
+    if (!a.i32(1, &frame)) return type_error(env, "detectGrouped(ctx, frame)");
+    uint32_t n = 0;
+    ht_status st = ht_detect_grouped(L.ctx, frame, nullptr, 0, &n);  // the length first
+    if (st != HT_OK && st != HT_ERR_CAPACITY) return throw_ht(env, L.ctx, st, "ht_detect_grouped");
+    std::vector<ht_rect> g((size_t)(n ? n : 1));
+    if (n && (st = ht_detect_grouped(L.ctx, frame, g.data(), n, &n)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_detect_grouped");
+    return rect6_result(env, g.data(), n);
+}
+
+napi_value DetectBestRecords(napi_env env, napi_callback_info info) {
+    Args a(env, info, 1);
+    Locked L;
+    if (!a.ctx(1, &L)) return nullptr;
+    const void *rec = nullptr;
+    int32_t n = 0;
+    ht_status st = ht_detect_best_records_device(L.ctx, &rec, &n);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_detect_best_records_device");
+    double *d = nullptr;
+    napi_value ta = f64_result(env, (size_t)n * 8, &d);
+    if (!ta) return nullptr;
+    if (n > 0 && (st = ht_device_download(L.ctx, d, rec, (size_t)n * 64)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_device_download");
+    return ta;
+}
+
+napi_value GroupHits(napi_env env, napi_callback_info info) {
+    static const char *usage = "groupHits(ctx, Uint8Array hits /* 24-byte ht_hit records */, nframes, minNeighbors)";
+    Args a(env, info, 4);
+    Locked L;
+    uint8_t *bytes = nullptr;
+    size_t len = 0;
+    int32_t nframes = 0, mn = 1;
+    if (!a.ctx(4, &L)) return nullptr;
+    if (!a.bytes(1, &bytes, &len) || !a.i32(2, &nframes) || !a.i32(3, &mn) || len % sizeof(ht_hit)) return type_error(env, usage);
+    if (nframes <= 0 || nframes > (1 << 20) || len / sizeof(ht_hit) > 0xffffffffu) return range_error(env, usage);
+    const size_t n = len / sizeof(ht_hit);
+    std::vector<ht_hit> hits(n ? n : 1);  // a typed array's storage need not be aligned for ht_hit
+    if (n) std::memcpy(hits.data(), bytes, len);
+    std::vector<ht_rect> best((size_t)nframes), grouped(n ? n : 1);
+    std::vector<uint32_t> ng((size_t)nframes);
+    const ht_status st = ht_group_hits(L.ctx, n ? hits.data() : nullptr, (uint32_t)n, nframes, mn, best.data(), grouped.data(), ng.data());
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_group_hits");
+    size_t total = 0;
+    for (uint32_t k : ng) total += k;
+    if (total > n) return throw_ht(env, L.ctx, HT_ERR_INVALID, "ht_group_hits (group counts)");
+    napi_value obj, ab, counts, tb = rect6_result(env, best.data(), (size_t)nframes), tg = tb ? rect6_result(env, grouped.data(), total) : nullptr;
+    if (!tb || !tg) return nullptr;
+    void *p = nullptr;
+    NAPI_OK(napi_create_arraybuffer(env, ng.size() * 4, &p, &ab));
+    std::memcpy(p, ng.data(), ng.size() * 4);
+    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, ng.size(), ab, 0, &counts));
+    NAPI_OK(napi_create_object(env, &obj));
+    NAPI_OK(napi_set_named_property(env, obj, "best", tb));
+    NAPI_OK(napi_set_named_property(env, obj, "grouped", tg));
+    NAPI_OK(napi_set_named_property(env, obj, "counts", counts));
+    return obj;
+}
+
 napi_value DrawFramesDevice(napi_env env, napi_callback_info info) {
     static const char *usage = "drawFramesDevice(ctx, srcDev, srcOffset, n, sw, sh, pitch, stride, rect | null, dstDev | null, dstOffset, dstStride, wait)";
     Args a(env, info, 13);
@@ -1172,6 +1277,8 @@ napi_value Init(napi_env env, napi_value exports) {
                {"camshiftBackProject", CamshiftBackProject}, {"camshiftBackProjectDevice", CamshiftBackProjectDevice},
                {"camshiftBackProjectPairs", CamshiftBackProjectPairs}, {"camshiftBackProjectPairsDevice", CamshiftBackProjectPairsDevice},
                {"drawFrames", DrawFrames},       {"drawFramesDevice", DrawFramesDevice},
+               {"detectBestEnqueue", DetectBestEnqueue}, {"collectBestDevice", CollectBestDevice}, {"detectGrouped", DetectGrouped},
+               {"detectBestRecords", DetectBestRecords}, {"groupHits", GroupHits},
                {"framesBound", FramesBound},     {"framesEnqueued", FramesEnqueued}, {"graphLaunches", GraphLaunches}};
     for (auto &f : fns) {
         napi_value fn;

@@ -369,7 +369,7 @@ headtrackr.ccv.detect_objects_batch = function (frames, n, w, h, cascade, interv
 };
 
 /* ---- device-resident batches: the pipelined path -------------------------------------------------------------------------
- * new ccv.DeviceBatch(w, h, n, {cascade, interval, device, depth, sets, trackers}):
+ * new ccv.DeviceBatch(w, h, n, {cascade, interval, device, depth, sets, trackers, grouping}):
  *   `sets` frame sets of n RGBA frames each live in ONE device buffer (HBM); `depth` native contexts (own HIP streams, own pyramid
  *   arenas) take detect batches in turn so that `depth` batches are in flight while the host groups the previous one
  *   (ht_detect_enqueue + ht_detect_collect_best_requeue: the C2 / C4 loop of bench.py, from JavaScript).
@@ -396,6 +396,9 @@ headtrackr.ccv.detect_objects_batch = function (frames, n, w, h, cascade, interv
  *     backProjectionPairs(set, pairs, kind) -> the same per (tracker, frame) pair, pair order: ht_camshift_backproject_pairs
  *     initPairs / trackPairs / trackPairsEnqueue / detectStepFinish(min_neighbors, {feeds})   trackers and frames paired freely (below);
                                            opts.trackers = tracker slots to reserve (default n)
+   opts.grouping = 'device': detectBest, detect, detectStepFinish and whitebalance take the device route — grouping and best face run
+   behind the scan on the GPU (ht_detect_best_enqueue / _collect), the host receives one record per frame; 'host' (default) keeps the
+   host route.  The results are the same bytes.
      destroy() */
 headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
   opts = opts || {};
@@ -405,6 +408,17 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
    * `batches` batches, loses 12 %: 1.03 M frames/s at 2, 0.90 M at 3 with 48-batch calls — pass {depth: 3} for long calls.) */
   const depth = Math.max(1, opts.depth || 2), sets = Math.max(1, opts.sets || 1);
   const A = addon(), fbytes = w * h * 4, setBytes = n * fbytes;
+  /* opts.grouping: where a batch's raw hits are grouped and each frame's best face is chosen — 'host' (default: ht_detect_collect_best's
+   * worker threads) or 'device' (ht_detect_best_enqueue behind every detect batch: one 64-byte record per frame comes back).  The same
+   * bytes either way. */
+  const grouping = opts.grouping === undefined ? 'host' : opts.grouping;
+  if (grouping !== 'host' && grouping !== 'device') throw new RangeError("DeviceBatch: opts.grouping is 'host' or 'device'");
+  const onDevice = grouping === 'device';
+  if (onDevice && (typeof A.detectBestEnqueue !== 'function' || typeof A.collectBestDevice !== 'function' || typeof A.detectGrouped !== 'function'))
+    throw new Error("DeviceBatch: this headtrackr_hip.node has no detectBestEnqueue / collectBestDevice / detectGrouped (rebuild it) — needed for grouping: 'device'");
+  /* the two halves of a batch on either route; the device route's requeue re-issues its grouping inside the library */
+  const enqueueBest = function (c, flags, min_neighbors) { A.detectEnqueue(c, flags); if (onDevice) A.detectBestEnqueue(c, min_neighbors, 0); };
+  const collectBest = function (c, min_neighbors, requeue) { return onDevice ? A.collectBestDevice(c, requeue) : A.collectBest(c, min_neighbors, requeue); };
   const blob = pack.packCascade(cascade), dims = levelDims(w, h, cascade, interval);
   const ctxs = [];
   for (let i = 0; i < depth; i++) {
@@ -417,7 +431,7 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
   let bound = -1, trackers = false;
   const pendingTrack = []; /* streams of the outstanding enqueue-only track steps, oldest first (pair steps need not have n) */
   const bind = function (set) { if (bound !== set) { ctxs.forEach(function (c) { A.bindDevice(c, dev, set * setBytes, n, fbytes); }); bound = set; } };
-  this.width = w; this.height = h; this.frames = n; this.depth = depth;
+  this.width = w; this.height = h; this.frames = n; this.depth = depth; this.grouping = grouping;
   this.upload = function (frames, set) {
     if (frames.length < setBytes) throw new RangeError('DeviceBatch.upload: need n*w*h*4 bytes');
     A.deviceUpload(ctxs[0], dev, (set || 0) * setBytes, frames.subarray(0, setBytes));
@@ -428,10 +442,10 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     flags = flags === undefined ? A.INPUT_RGBA : flags;
     min_neighbors = min_neighbors === undefined ? 1 : min_neighbors;
     let started = Math.min(depth, batches), r = null;
-    for (let i = 0; i < started; i++) A.detectEnqueue(ctxs[i], flags);
+    for (let i = 0; i < started; i++) enqueueBest(ctxs[i], flags, min_neighbors);
     for (let i = 0; i < batches; i++) { /* collect batch i; its context re-enqueues inside the call while batches remain */
       const more = started < batches;
-      r = A.collectBest(ctxs[i % depth], min_neighbors, more ? flags : -1);
+      r = collectBest(ctxs[i % depth], min_neighbors, more ? flags : -1);
       if (more) started++;
     }
     r.batches = batches;
@@ -439,6 +453,20 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
   };
   this.detect = function (min_neighbors, set) {
     bind(set || 0);
+    if (onDevice) { /* the frames' grouped lists are read from the device (ht_detect_grouped); min_neighbors 0: the seq list itself (ccv.js:232) */
+      const mn = min_neighbors > 0 ? min_neighbors : 0, lists = [];
+      enqueueBest(ctxs[0], A.INPUT_RGBA, mn);
+      A.collectBestDevice(ctxs[0], -1);
+      for (let f = 0; f < n; f++) {
+        const g = A.detectGrouped(ctxs[0], f), list = [];
+        for (let o = 0; o < g.length; o += 6) {
+          list.push(mn > 0 ? { x: g[o], y: g[o + 1], width: g[o + 2], height: g[o + 3], neighbors: g[o + 5], confidence: g[o + 4] }
+            : { x: g[o], y: g[o + 1], width: g[o + 2], height: g[o + 3], neighbor: 1, confidence: g[o + 4] });
+        }
+        lists.push(list);
+      }
+      return lists;
+    }
     A.detectEnqueue(ctxs[0], A.INPUT_RGBA);
     const hits = A.detectCollect(ctxs[0]), out = [];
     let k = 0;
@@ -447,8 +475,8 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
   };
   this.whitebalance = function (set) {
     bind(set || 0);
-    A.detectEnqueue(ctxs[0], A.INPUT_RGBA | A.DETECT_WHITEBALANCE);
-    A.collectBest(ctxs[0], 1, -1);
+    enqueueBest(ctxs[0], A.INPUT_RGBA | A.DETECT_WHITEBALANCE, 1);
+    collectBest(ctxs[0], 1, -1);
     return A.detectWhitebalance(ctxs[0], n);
   };
   this.initTrackers = function (rects, set) { /* rects: Int32Array [x, y, width, height] per stream (camshift.js:198-211) */
@@ -474,16 +502,24 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
   /*   detectStepEnqueue(set) / detectStepFinish(min_neighbors)   the two halves of detectStep: a streaming host enqueues the detect of
    *                                  step i right behind the track steps still in flight, collects THOSE (trackCollect), and only then
    *                                  waits for the best faces — the GPU does not idle while the host drains its pipeline */
-  this.detectStepEnqueue = function (set) {
+  /*                                  (grouping 'device': detectStepEnqueue(set, min_neighbors) also enqueues the grouping, so that it runs
+   *                                  behind the scan at once; detectStepFinish enqueues it itself when its min_neighbors differs) */
+  let stepGrouped = null; /* min_neighbors of the device grouping enqueued behind the step's detect, null: none yet */
+  this.detectStepEnqueue = function (set, min_neighbors) {
     bind0(set === undefined ? 0 : set);
     A.detectEnqueue(ctxs[0], A.INPUT_RGBA);
+    stepGrouped = null;
+    if (onDevice) { stepGrouped = min_neighbors === undefined ? 1 : min_neighbors; A.detectBestEnqueue(ctxs[0], stepGrouped, 0); }
   };
   this.detectStep = function (set, min_neighbors) {
-    this.detectStepEnqueue(set);
+    this.detectStepEnqueue(set, min_neighbors);
     return this.detectStepFinish(min_neighbors);
   };
   this.detectStepFinish = function (min_neighbors, sel) {
-    const r = A.collectBest(ctxs[0], min_neighbors === undefined ? 1 : min_neighbors, -1);
+    const mn = min_neighbors === undefined ? 1 : min_neighbors;
+    if (onDevice && stepGrouped !== mn) A.detectBestEnqueue(ctxs[0], mn, 0);
+    stepGrouped = null;
+    const r = collectBest(ctxs[0], mn, -1);
     if (sel && sel.feeds) { /* feeds in different states: trackers only for the LISTED feeds that found a face (facetrackr.js:97) */
       const found = [];
       for (let i = 0; i < sel.feeds.length; i++) {

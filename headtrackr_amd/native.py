@@ -67,7 +67,7 @@ SYMBOLS = [
     "ht_create", "ht_destroy", "ht_last_error", "ht_abi_version", "ht_set_geometry", "ht_num_levels", "ht_plane",
     "ht_windows_per_frame", "ht_pyramid_bytes_per_frame", "ht_upload_frames", "ht_upload_frames_async", "ht_swap_frames", "ht_bind_frames_device", "ht_frames_bound", "ht_frames_enqueued", "ht_host_alloc", "ht_host_free", "ht_device_alloc", "ht_device_free", "ht_device_upload", "ht_device_download", "ht_draw_frames_device", "ht_draw_frames", "ht_detect_enqueue",
     "ht_detect_collect", "ht_detect_batch", "ht_pyramid_readback", "ht_stage_counts", "ht_grayscale_batch",
-    "ht_whitebalance_batch", "ht_detect_whitebalance", "ht_hits_to_rects", "ht_group_rects", "ht_best_faces", "ht_detect_collect_best", "ht_detect_collect_best_requeue", "ht_camshift_reserve", "ht_camshift_init_batch",
+    "ht_whitebalance_batch", "ht_detect_whitebalance", "ht_hits_to_rects", "ht_group_rects", "ht_best_faces", "ht_detect_collect_best", "ht_detect_collect_best_requeue", "ht_detect_best_enqueue", "ht_detect_best_collect", "ht_detect_best_collect_requeue", "ht_detect_grouped", "ht_detect_best_records_device", "ht_group_hits", "ht_camshift_reserve", "ht_camshift_init_batch",
     "ht_camshift_track_batch", "ht_camshift_track_collect", "ht_camshift_init_pairs", "ht_camshift_track_pairs", "ht_camshift_track_sequence", "ht_camshift_sequence_collect", "ht_camshift_stats", "ht_camshift_debug_hist", "ht_camshift_backproject", "ht_camshift_backproject_device", "ht_camshift_backproject_pairs", "ht_camshift_backproject_pairs_device", "ht_allgather_records", "ht_allgather_best_faces", "ht_device_count", "ht_profile", "ht_kernel_times", "ht_stream", "ht_graph_launches", "ht_synchronize",
 ]
 
@@ -152,6 +152,18 @@ def lib():
     L.ht_detect_collect_best.argtypes = [vp, i32, vp, C.POINTER(u32)]
     L.ht_detect_collect_best_requeue.restype = i32
     L.ht_detect_collect_best_requeue.argtypes = [vp, i32, vp, vp, C.c_uint32]
+    L.ht_detect_best_enqueue.restype = i32
+    L.ht_detect_best_enqueue.argtypes = [vp, i32, i32]
+    L.ht_detect_best_collect.restype = i32
+    L.ht_detect_best_collect.argtypes = [vp, vp, C.POINTER(u32)]
+    L.ht_detect_best_collect_requeue.restype = i32
+    L.ht_detect_best_collect_requeue.argtypes = [vp, vp, C.POINTER(u32), u32]
+    L.ht_detect_grouped.restype = i32
+    L.ht_detect_grouped.argtypes = [vp, i32, vp, u32, C.POINTER(u32)]
+    L.ht_detect_best_records_device.restype = i32
+    L.ht_detect_best_records_device.argtypes = [vp, C.POINTER(vp), C.POINTER(i32)]
+    L.ht_group_hits.restype = i32
+    L.ht_group_hits.argtypes = [vp, vp, u32, i32, i32, vp, vp, vp]
     L.ht_camshift_reserve.restype = i32
     L.ht_camshift_reserve.argtypes = [vp, i32]
     L.ht_camshift_init_batch.restype = i32

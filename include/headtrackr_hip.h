@@ -81,6 +81,8 @@ typedef struct ht_config {
                              *   early_scan=1, rs_rpt, rs_minwg, rs_k, rs_group, rs_tailtable, rs_tailcap, rs_notail, rs_nofast, rs_nosort, rs_gennames
                              *   host_threads=N       worker threads of the host post-processing (0 = single-threaded)
                              *   force_rccl=1         ht_allgather_* goes through RCCL even with one rank
+                             *   group_cap=N          raw hits of one frame the device grouping takes (a power of two, 64 .. 1024 = default); frames above
+                             *                        it are finished on the host by the collect call
                              * Keys that make results incomplete by design (stop_stage, cs_iters, rs_maxgen) exist only in builds
                              * compiled with -DHT_DEBUG_KNOBS (tools/build_alt.py); the product library rejects them. */
 } ht_config;
@@ -227,7 +229,7 @@ ht_status ht_whitebalance_batch(ht_ctx *ctx, double *out, int32_t n);
  * facetrackr's white-balance gate, facetrackr.js:79-95, and its detection read the frame once). Call after ht_detect_collect. */
 ht_status ht_detect_whitebalance(ht_ctx *ctx, double *out, int32_t n);
 
-/* ---- host-side post-processing of raw hits (O(n^2) on tens of rects; stays on the CPU by design) ---------- */
+/* ---- host-side post-processing of raw hits (O(n^2) on tens of rects) ------------------------------------ */
 
 /* seq elements from hits (ccv.js:228-233, scale_x by repeated multiplication ccv.js:244-245). */
 ht_status ht_hits_to_rects(const ht_ctx *ctx, const ht_hit *hits, uint32_t n, ht_rect *out);
@@ -248,6 +250,42 @@ ht_status ht_detect_collect_best(ht_ctx *ctx, int32_t min_neighbors, ht_rect *be
  * next_flags (ht_detect_enqueue) — before this batch is sorted and grouped, so the GPU is not one batch short while the host
  * post-processes.  A streaming host that swaps in new frames first (ht_swap_frames) gets them in that next batch. */
 ht_status ht_detect_collect_best_requeue(ht_ctx *ctx, int32_t min_neighbors, ht_rect *best, uint32_t *total_hits, uint32_t next_flags);
+
+/* ---- the same post-processing on the device: grouping and best face behind the scan, nothing but records crosses to the host ------ */
+
+/* Enqueues, behind the detect batch in flight, the bucketing of its raw hits by frame and one workgroup per frame that orders them
+ * (scale, q, y, x), forms the seq rects, runs ccv's grouping (ccv.js:34-107, 249-332) with min_neighbors and selects facetrackr's best
+ * face (facetrackr.js:157-165).  Per frame f it leaves, in device buffers that live until the next call of this kind on the context, one
+ * 64-byte record [x, y, width, height, confidence, neighbors, frame_base + f, 1.0] (binary64; no face: confidence -10000, neighbors 0,
+ * rect 0), the frame's grouped list and a status word.  Legal between ht_detect_enqueue and the collect of that batch (HT_ERR_STATE
+ * otherwise); waits for nothing in the steady state (the first call of a context, or a larger batch, allocates).  Every byte equals
+ * ht_detect_collect_best's.  A frame with more raw hits than one workgroup takes (1024; option group_cap=N lowers it, results
+ * unchanged) is flagged and finished on the host by the collect call. */
+ht_status ht_detect_best_enqueue(ht_ctx *ctx, int32_t min_neighbors, int32_t frame_base);
+/* Collects a batch that ht_detect_best_enqueue followed: ONE pinned device-to-host copy (hit count, records, status words) and one
+ * synchronisation; best[f] for every frame of the batch, *total_hits = raw hits found.  HT_ERR_CAPACITY when the batch had more raw hits
+ * than ht_config.hit_capacity.  The batch counts as collected exactly as after ht_detect_collect (ht_frames_enqueued,
+ * ht_detect_whitebalance, ht_stage_counts). */
+ht_status ht_detect_best_collect(ht_ctx *ctx, ht_rect *best, uint32_t *total_hits);
+/* The same, and right behind the synchronisation the NEXT batch of the bound frames is enqueued with next_flags together with its
+ * ht_detect_best_enqueue (same min_neighbors and frame_base).  That overwrites the device buffers: afterwards ht_detect_grouped and
+ * ht_detect_best_records_device speak about the batch in flight, not the one just returned. */
+ht_status ht_detect_best_collect_requeue(ht_ctx *ctx, ht_rect *best, uint32_t *total_hits, uint32_t next_flags);
+/* The full grouped list of one frame of the batch collected last through ht_detect_best_collect — what ccv.detect_objects returns for
+ * it.  *n = its length; HT_ERR_CAPACITY when cap is smaller (the first cap rects are returned); HT_ERR_STATE when no such batch exists
+ * or a later ht_detect_best_enqueue / ht_group_hits has reused the buffers. */
+ht_status ht_detect_grouped(ht_ctx *ctx, int32_t frame, ht_rect *out, uint32_t cap, uint32_t *n);
+/* Device pointer of the 64-byte records (*nframes of them) for ht_allgather_records or a tensor view; fixed from ht_detect_best_enqueue
+ * on, complete for work enqueued on the ctx stream or once the collect call has returned, valid until the next ht_detect_best_enqueue /
+ * ht_group_hits on the context.  HT_ERR_STATE while no device-grouped batch exists. */
+ht_status ht_detect_best_records_device(ht_ctx *ctx, const void **records, int32_t *nframes);
+/* The device twin of ht_best_faces for hosts that hold raw hits: n hits in ANY order (each names its frame < nframes) go through the same
+ * kernels.  best[nframes]; grouped (may be NULL together with ngrouped): room for n rects, the frames' grouped lists back to back in frame
+ * order, ngrouped[f] rects each.  Waits for its result.  n <= ht_config.hit_capacity.  A hit whose frame or scale is out of range is
+ * skipped and the call returns HT_ERR_INVALID.  Two hits of one frame with the same (scale, q, y, x) — the scan never emits that — are
+ * ordered in an unspecified way.  HT_ERR_STATE while a device-grouped batch is in flight. */
+ht_status ht_group_hits(ht_ctx *ctx, const ht_hit *hits, uint32_t n, int32_t nframes, int32_t min_neighbors, ht_rect *best, ht_rect *grouped,
+                        uint32_t *ngrouped);
 
 /* ---- camshift: camshift.Tracker (camshift.js:148-354), one tracker per stream ----------------------------- */
 
