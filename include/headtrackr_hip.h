@@ -164,7 +164,9 @@ ht_status ht_upload_frames(ht_ctx *ctx, const uint8_t *host_rgba, int32_t n, siz
  * (the compute stream waits for the copy, no host synchronisation).  host_rgba must stay valid until the swap. */
 ht_status ht_upload_frames_async(ht_ctx *ctx, const uint8_t *host_rgba, int32_t n, size_t frame_stride);
 ht_status ht_swap_frames(ht_ctx *ctx);
-/* Uses frames already resident in device memory (no copy; must stay valid until the results were collected). */
+/* Uses frames already resident in device memory (no copy; must stay valid until the results were collected).  dev_rgba: any 4-byte-aligned
+ * address; frame_stride: any multiple of 4 that is >= width * height * 4 (anything else is HT_ERR_INVALID and leaves the binding as it was).
+ * Strided and 4- but not 16-byte-aligned bindings are exercised by tests/test_gpu_frame_layouts.py. */
 ht_status ht_bind_frames_device(ht_ctx *ctx, const void *dev_rgba, int32_t n, size_t frame_stride);
 
 /* Frames currently bound (ht_upload_frames / ht_swap_frames / ht_bind_frames_device) and frames of the batch enqueued last: the
