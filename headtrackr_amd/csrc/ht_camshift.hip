@@ -34,7 +34,7 @@ namespace {
 // window_moments*, meanshift_body
 #include "ht_cs_device.h"
 
-// k_cs_init, k_cs_hist and k_cs_meanshift are ht_cs_kernels.inc with the look-ups of a batch: stream first + s works on bound frame s,
+// k_cs_init, k_cs_init_rows, k_cs_hist, k_cs_meanshift, k_cs_lut and k_cs_meanshift_cluster are ht_cs_kernels.inc with the look-ups of a batch: stream first + s works on bound frame s,
 // whose chunk histograms are slot s, and its rect is rects[s]
 #define CS_K(name) k_cs_##name
 typedef int CsLookup;  // `first`
@@ -51,46 +51,8 @@ __device__ __forceinline__ int cs_slot_of(int, int s) { return s; }
 #define CS_KERNELS_PART 1  // k_cs_init
 #include "ht_cs_kernels.inc"
 
-// initTracker for a FEW streams with large rects (a live 1080p feed: 360 x 360 = 0.5 MB took the single workgroup above 54 us):
-// grid (G, streams), workgroup g takes rows g*4 + wavefront, + 4 G, ...; LDS histogram per workgroup, non-zero bins added to the
-// model (zeroed by the host) with global atomics — integer counts, any order gives the same model.
-__global__ __launch_bounds__(256) void k_cs_init_rows(const uint8_t *__restrict__ frames, size_t frame_stride, int W, int H,
-                                                      const ht_cs_rect *__restrict__ rects, HtCsState *__restrict__ states, int first) {
-    __shared__ uint32_t h[4096];
-    const int s = blockIdx.y, g = blockIdx.x, G = gridDim.x;
-    for (int i = threadIdx.x; i < 4096; i += 256) h[i] = 0;
-    __syncthreads();
-    const ht_cs_rect r = rects[s];
-    const uint32_t *img = reinterpret_cast<const uint32_t *>(frames + (size_t)s * frame_stride);
-    const int rw = max(r.width, 0), rh = max(r.height, 0);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int j = g * 4 + wave; j - wave < rh + 3; j += 4 * G) {  // same trip count for the four wavefronts of a workgroup
-        const int y = r.y + j;
-        for (int cb = 0; cb < rw; cb += 256) {
-            uint32_t px[4];
-            bool in[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const int c = cb + 64 * u + lane, x = r.x + c;
-                in[u] = c < rw && j < rh;
-                px[u] = (in[u] && x >= 0 && x < W && y >= 0 && y < H) ? img[(size_t)y * W + x] : 0u;  // outside the canvas: transparent black (camshift.js:206)
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) CS_BATCH_LOADED(px[u]);
-#pragma unroll
-            for (int u = 0; u < 4; u++) hist_add_wave(h, cs_bin(px[u]), 1u, in[u]);
-        }
-    }
-    __syncthreads();
-    HtCsState &st = states[first + s];
-    for (int i = threadIdx.x; i < 4096; i += 256)
-        if (h[i]) atomicAdd(&st.model[i], h[i]);
-    if (g == 0 && threadIdx.x == 0) {
-        st.sw[0] = r.x, st.sw[1] = r.y, st.sw[2] = r.width, st.sw[3] = r.height;  // camshift.js:209
-        st.x = st.y = st.width = st.height = st.angle = 0.0;                         // camshift.js:210
-        st.win_px = st.calls = 0;
-    }
-}
+#define CS_KERNELS_PART 3  // k_cs_init_rows
+#include "ht_cs_kernels.inc"
 
 #define CS_KERNELS_PART 2  // k_cs_hist, k_cs_meanshift: behind k_cs_init_rows, the order the recorded code object has
 #include "ht_cs_kernels.inc"
@@ -283,169 +245,9 @@ __global__ __launch_bounds__(NT, 4) void k_cs_track_fused(const CsFusedArgs args
 // sc1 store on one side and an sc1 load on the other.  Every workgroup sums the G partials in the same order, so all of them take
 // identical mean-shift decisions; workgroup 0 writes the state.  The grid (streams x G <= 256 workgroups) is always co-resident: the spin cannot starve a workgroup that has not started.
 // (CL_NT threads, <= CL_MAXG workgroups per stream, CL_SLOTS exchange slots: ht_cs_schedule.h)
-// "not written yet" mark of an exchange entry: a NaN no moment sum can be (the sums are finite and >= 0)
-constexpr unsigned long long CL_UNWRITTEN = 0xFFF8C0DEC0DE0001ull;
-
-// weight LUT of every stream from its chunk histograms (getWeights, camshift.js:314-330): grid (64, streams) x 512 threads;
-// a block owns 64 bins, its 8 wavefronts each sum every 8th chunk (a single 1080p stream has 127 chunk histograms = 2 MB)
-__global__ __launch_bounds__(512) void k_cs_lut(const uint32_t *__restrict__ hist, int nchunks, const HtCsState *__restrict__ states, int first,
-                                                double *__restrict__ lut, unsigned long long *__restrict__ cluster_parts) {
-    __shared__ uint32_t part[8][64];
-    const int s = blockIdx.y, lane = threadIdx.x & 63, grp = threadIdx.x >> 6, bin = blockIdx.x * 64 + lane;
-    {   // the stream's exchange slots of the cluster launch that follows: every entry "not written yet" (was a memset of its own)
-        const uint32_t i = blockIdx.x * 512u + threadIdx.x;
-        if (i < (uint32_t)(CL_SLOTS * CL_MAXG * 6)) cluster_parts[(size_t)s * CL_SLOTS * CL_MAXG * 6 + i] = CL_UNWRITTEN;
-    }
-    const uint32_t *cur = hist + (size_t)s * nchunks * 4096 + bin;
-    uint32_t ch = 0;
-#pragma unroll 4
-    for (int k = grp; k < nchunks; k += 8) ch += cur[(size_t)k * 4096];
-    part[grp][lane] = ch;
-    __syncthreads();
-    if (grp == 0) {
-        ch = 0;
-#pragma unroll
-        for (int q = 0; q < 8; q++) ch += part[q][lane];
-        double p = 0.0;
-        if (ch != 0) {
-            p = (double)states[first + s].model[bin] / (double)ch;
-            p = p < 1.0 ? p : 1.0;
-        }
-        lut[(size_t)s * 4096 + bin] = p;
-    }
-}
-
-// The wait is a spin on agent-scope loads, so it is BOUNDED: a thread that has waited `budget` shader-clock cycles (a quarter of a
-// second by default, against ~1-2 us for a healthy exchange) raises the context's error word and its workgroup stops waiting — at this
-// and every later exchange of the call (s_timeout is sticky).  The host reports HT_ERR_STATE with the next result read-back; the stream's
-// state is then garbage for this call, but nothing hangs.  Co-residency (the premise of the spin) is arranged by the host: one cluster
-// launch in flight per device and process, grid <= one workgroup per CU (launch_track).
-// Ordering: an entry is ONE 8-byte word, written by an sc1 (agent-scope) store and read by sc1 loads — single-copy atomic, nothing else
-// depends on it.  That is the gfx9 memory model; ht_create refuses any other arch.
-struct ClusterSync {
-    uint32_t *err;
-    uint32_t *err_host;  // pinned host word (plain system-scope store of 1): an enqueue-only call's host side reads it without a copy
-    long long budget;
-    int *s_timeout;  // LDS flag of the workgroup
-};
-template <bool SECOND>
-__device__ __forceinline__ Mom cluster_moments(const uint32_t *__restrict__ img, int W, const double *lut, int x, int y, int w, int h, double (*red)[CL_NT / 64],
-                                               double *s_part, int g, int G, double *__restrict__ parts, const ClusterSync &sync, int slot) {
-    constexpr int NW = CL_NT / 64, nv = SECOND ? 6 : 3;
-    Mom m = {0, 0, 0, 0, 0, 0};
-    const int ww = w - x, hh = h - y;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (ww > 0 && hh > 0) {
-        for (int j = g * NW + wave; j < hh; j += G * NW) {  // a row per (workgroup, wavefront); 8 column chunks of the row in flight
-            double rs = 0.0, ts = 0.0, us = 0.0;
-            const uint32_t *rowp = img + (size_t)(y + j) * W + x;
-            for (int cb = 0; cb < ww; cb += 512) {
-                uint32_t px[8];
-#pragma unroll
-                for (int u = 0; u < 8; u++) px[u] = rowp[min(cb + 64 * u + lane, ww - 1)];  // clamped address, value masked below
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    const int c = cb + 64 * u + lane;
-                    const double val = c < ww ? lut[cs_bin(px[u])] : 0.0;
-                    const double vx = (double)c;
-                    rs += val;
-                    ts += vx * val;
-                    if (SECOND) us += vx * vx * val;
-                }
-            }
-            const double vy = (double)j;
-            m.m00 += rs;
-            m.m10 += ts;
-            m.m01 += vy * rs;
-            if (SECOND) {
-                m.m11 += vy * ts;
-                m.m20 += us;
-                m.m02 += vy * vy * rs;
-            }
-        }
-    }
-    double v[6] = {m.m00, m.m10, m.m01, m.m11, m.m20, m.m02};
-    __syncthreads();  // red[] / s_part[] may still be read from the previous pass
-#pragma unroll
-    for (int k = 0; k < nv; k++) {
-        const double sum = wave_sum_f64(v[k]);
-        if (lane == 0) red[k][wave] = sum;
-    }
-    __syncthreads();
-    // this workgroup's partial sums -> its entries of the pass's exchange slot (agent-scope stores, fire and forget); then every entry
-    // of the slot is polled by a thread of its own until it no longer holds the "not written yet" mark k_cs_lut left there: the value
-    // that ends the wait IS the partial sum — no arrival counter, no drain of the stores, no second read (a pass used to be
-    // store -> s_waitcnt -> atomic add -> poll the counter -> read the G partials: three dependent round trips through L2).
-    unsigned long long *slot_parts = reinterpret_cast<unsigned long long *>(parts) + (size_t)slot * CL_MAXG * 6;
-    if (threadIdx.x < nv) {
-        double sum = 0.0;
-#pragma unroll
-        for (int q = 0; q < NW; q++) sum += red[threadIdx.x][q];
-        __hip_atomic_store(&slot_parts[g * 6 + threadIdx.x], (unsigned long long)__double_as_longlong(sum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if ((int)threadIdx.x < G * 6) {
-        unsigned long long bits = 0ull;  // +0.0 for the entries a first-moment pass does not use
-        if ((int)(threadIdx.x % 6u) < nv) {
-            bits = __hip_atomic_load(&slot_parts[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (bits == CL_UNWRITTEN && !*sync.s_timeout) {
-                const long long t0 = (long long)__builtin_readcyclecounter();
-                for (;;) {
-                    __builtin_amdgcn_s_sleep(1);
-                    bits = __hip_atomic_load(&slot_parts[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (bits != CL_UNWRITTEN) break;
-                    if ((long long)__builtin_readcyclecounter() - t0 > sync.budget) {  // bounded spin: give up, flag it, never wait again
-                        *sync.s_timeout = 1;
-                        atomicOr(sync.err, 1u);
-                        if (sync.err_host) __hip_atomic_store(sync.err_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        break;
-                    }
-                }
-            }
-            if (bits == CL_UNWRITTEN) bits = 0ull;  // timed out: the call's result is undefined (reported), but it stays a number
-        }
-        s_part[threadIdx.x] = __longlong_as_double((long long)bits);
-    }
-    __syncthreads();
-    {  // lane k of every wavefront adds moment k's G partials in the fixed order q = 0 .. G-1: every workgroup of the cluster gets the same bits
-        double sacc = 0.0;
-        if (lane < nv)
-            for (int q = 0; q < G; q++) sacc += s_part[q * 6 + lane];
-#pragma unroll
-        for (int k = 0; k < nv; k++)
-            v[k] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(sacc), k), __builtin_amdgcn_readlane(__double2loint(sacc), k));
-    }
-    m.m00 = v[0], m.m10 = v[1], m.m01 = v[2], m.m11 = v[3], m.m20 = v[4], m.m02 = v[5];
-    return m;
-}
-
-__global__ __launch_bounds__(CL_NT) void k_cs_meanshift_cluster(const uint8_t *__restrict__ frames, size_t frame_stride, int W, int H, const double *__restrict__ lut_g,
-                                                                HtCsState *__restrict__ states, int first, int calc_angles, int max_it, int G,
-                                                                double *__restrict__ parts,
-                                                                uint32_t *__restrict__ err, uint32_t *__restrict__ err_host, long long budget,
-                                                                ht_cs_trackobj *__restrict__ out, uint32_t *__restrict__ done_flags, uint32_t done_seq) {
-    __shared__ double lut[4096];
-    __shared__ double red[6][CL_NT / 64];
-    __shared__ double s_part[CL_MAXG * 6];
-    __shared__ int s_sw[4];
-    __shared__ int s_timeout;
-    if (threadIdx.x == 0) s_timeout = 0;
-    const int s = blockIdx.x / G, g = blockIdx.x - s * G;
-    HtCsState &st = states[first + s];
-    const uint32_t *img = reinterpret_cast<const uint32_t *>(frames + (size_t)s * frame_stride);
-    {
-        const double2 *src = reinterpret_cast<const double2 *>(lut_g + (size_t)s * 4096);
-        for (int i = threadIdx.x; i < 2048; i += CL_NT) reinterpret_cast<double2 *>(lut)[i] = src[i];
-    }
-    if (threadIdx.x < 4) s_sw[threadIdx.x] = st.sw[threadIdx.x];
-    __syncthreads();
-    double *my_parts = parts + (size_t)s * CL_SLOTS * CL_MAXG * 6;
-    const ClusterSync sync = {err, err_host, budget, &s_timeout};
-    int slot = 0;
-    meanshift_body(W, H, s_sw, st, calc_angles, max_it, out ? out + s : nullptr, nullptr, g == 0, [&](int x, int y, int w, int h) {
-        const int sl = slot++;
-        return cluster_moments<true>(img, W, lut, x, y, w, h, red, s_part, g, G, my_parts, sync, sl);
-    }, done_flags ? done_flags + s : nullptr, done_seq);
-}
+// (CL_UNWRITTEN, ClusterSync, cluster_moments: ht_cs_device.h)
+#define CS_KERNELS_PART 4  // k_cs_lut, k_cs_meanshift_cluster
+#include "ht_cs_kernels.inc"
 
 }  // namespace
 
@@ -495,9 +297,8 @@ void ht_capture_mark(ht_ctx *c, bool on) {
         c->capturing.store(false);
     }
 }
-namespace {
 // fetched with every result read-back: a cluster barrier that ran out of its cycle budget surfaces as a status code
-ht_status cs_check_err(ht_ctx *c, const char *where) {
+ht_status ht_cs_check_err(ht_ctx *c, const char *where) {
     const bool direct = c->h_cs_err_direct && __atomic_load_n(c->h_cs_err_direct, __ATOMIC_ACQUIRE) != 0;
     if (!direct && (!c->h_cs_err || *c->h_cs_err == 0)) return HT_OK;
     if (c->h_cs_err) *c->h_cs_err = 0;
@@ -505,7 +306,37 @@ ht_status cs_check_err(ht_ctx *c, const char *where) {
     (void)hipMemsetAsync(c->d_cs_err, 0, sizeof(uint32_t), c->stream);
     return ht_fail(c, HT_ERR_STATE, std::string(where) + ": a camshift cluster barrier timed out (workgroups of one stream were not co-resident); the affected streams' state is undefined — re-initialise them");
 }
-}  // namespace
+
+// The cluster gate around one launch of a grid that spins on its own workgroups (launch_track here, csp_launch_track in ht_cs_pairs.hip).
+// begin takes the gate's lock and, on success, keeps it until end; a failed begin has released it.
+ht_status ht_cs_cluster_gate_begin(ht_ctx *c) {
+    ClusterGate &gate = cluster_gate();
+    std::unique_lock<std::mutex> lk(gate.mu);
+    ClusterGate::Dev &gd = gate.dev[c->device];
+    if (std::find(gd.users.begin(), gd.users.end(), c) == gd.users.end()) {
+        // A single context's cluster grids are ordered by its own stream: no event traffic (a record is a barrier packet of its own
+        // between this step's last and the next step's first kernel).  When a second context of the device starts using the
+        // cluster path, the unrecorded grids of the first are drained once, and from then on every launch waits and records.
+        if (!gd.users.empty() && !gd.multi) {
+            HT_HIP(c, hipDeviceSynchronize());
+            gd.multi = true;
+        }
+        gd.users.push_back(c);
+    }
+    if (gd.multi) {
+        if (!gd.last) HT_HIP(c, hipEventCreateWithFlags(&gd.last, hipEventDisableTiming));
+        else HT_HIP(c, hipStreamWaitEvent(c->stream, gd.last, 0));  // the previous cluster grid on this device (any context) has drained
+    }
+    lk.release();  // held until ht_cs_cluster_gate_end
+    return HT_OK;
+}
+ht_status ht_cs_cluster_gate_end(ht_ctx *c) {
+    ClusterGate &gate = cluster_gate();
+    std::unique_lock<std::mutex> lk(gate.mu, std::adopt_lock);
+    ClusterGate::Dev &gd = gate.dev[c->device];
+    if (gd.multi && gd.last) HT_HIP(c, hipEventRecord(gd.last, c->stream));
+    return HT_OK;
+}
 
 // the histogram pass, also for callers outside this unit (ht_backproject.hip): host code only, the kernel stays here
 ht_status ht_cs_hist_launch(ht_ctx *c, const uint8_t *frames, size_t frame_stride, int n, uint32_t npix, uint32_t chunk_px, uint32_t nchunks, uint32_t *hist) {
@@ -737,28 +568,15 @@ static ht_status launch_track(ht_ctx *c, const uint8_t *frames, size_t frame_str
         }
         HtProfScope ps(c, p.meanshift.timer);
         if (flags_used) *flags_used = done_flags != nullptr;
-        ClusterGate &gate = cluster_gate();
-        std::lock_guard<std::mutex> lk(gate.mu);
-        ClusterGate::Dev &gd = gate.dev[c->device];
-        if (std::find(gd.users.begin(), gd.users.end(), c) == gd.users.end()) {
-            // A single context's cluster grids are ordered by its own stream: no event traffic (a record is a barrier packet of its own
-            // between this step's last and the next step's first kernel).  When a second context of the device starts using the
-            // cluster path, the unrecorded grids of the first are drained once, and from then on every launch waits and records.
-            if (!gd.users.empty() && !gd.multi) {
-                HT_HIP(c, hipDeviceSynchronize());
-                gd.multi = true;
-            }
-            gd.users.push_back(c);
-        }
-        if (gd.multi) {
-            if (!gd.last) HT_HIP(c, hipEventCreateWithFlags(&gd.last, hipEventDisableTiming));
-            else HT_HIP(c, hipStreamWaitEvent(c->stream, gd.last, 0));  // the previous cluster grid on this device (any context) has drained
-        }
+        ht_status gs = ht_cs_cluster_gate_begin(c);
+        if (gs != HT_OK) return gs;
         hipLaunchKernelGGL(k_cs_meanshift_cluster, dim3(p.meanshift.grid_x), dim3(p.meanshift.block), p.meanshift.lds, c->stream, frames, frame_stride, c->W,
                            c->H, lut, c->d_cs, first, calc_angles, c->dbg_cs_iters, p.G, c->d_cs_parts, c->d_cs_err, c->h_cs_err_direct,
                            (long long)c->cs_barrier_budget, d_out, done_flags, done_seq);
-        HT_HIP(c, hipGetLastError());
-        if (gd.multi) HT_HIP(c, hipEventRecord(gd.last, c->stream));
+        const hipError_t le = hipGetLastError();
+        gs = ht_cs_cluster_gate_end(c);
+        HT_HIP(c, le);
+        if (gs != HT_OK) return gs;
     } else {
         HtProfScope ps(c, p.meanshift.timer);
         hipLaunchKernelGGL(k_cs_meanshift, dim3(p.meanshift.grid_x), dim3(p.meanshift.block), p.meanshift.lds, c->stream, frames, frame_stride, c->W, c->H, hist,
@@ -796,11 +614,11 @@ static void cs_ring_pop(ht_ctx *c) {
 }
 
 // the copy-back route of a result read-back: `count` track objects and the error word, then the stream is synchronised and the word checked
-static ht_status cs_read_back(ht_ctx *c, const char *fn, ht_cs_trackobj *out, const ht_cs_trackobj *d_src, size_t count) {
+ht_status ht_cs_read_back(ht_ctx *c, const char *fn, ht_cs_trackobj *out, const ht_cs_trackobj *d_src, size_t count) {
     HT_HIP(c, hipMemcpyAsync(out, d_src, sizeof(ht_cs_trackobj) * count, hipMemcpyDeviceToHost, c->stream));
     HT_HIP(c, hipMemcpyAsync(c->h_cs_err, c->d_cs_err, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HT_HIP(c, hipStreamSynchronize(c->stream));
-    return cs_check_err(c, fn);
+    return ht_cs_check_err(c, fn);
 }
 
 extern "C" ht_status ht_camshift_track_batch(ht_ctx *c, int32_t first, int32_t n, int32_t calc_angles, ht_cs_trackobj *out) {
@@ -835,7 +653,7 @@ extern "C" ht_status ht_camshift_track_batch(ht_ctx *c, int32_t first, int32_t n
     }
     ht_status st = launch_track(c, c->d_frames, c->frame_stride, first, n, calc_angles, c->d_cs_out);
     if (st != HT_OK) return st;
-    return out ? cs_read_back(c, "ht_camshift_track_batch", out, c->d_cs_out, (size_t)n) : HT_OK;
+    return out ? ht_cs_read_back(c, "ht_camshift_track_batch", out, c->d_cs_out, (size_t)n) : HT_OK;
 }
 
 extern "C" ht_status ht_camshift_track_collect(ht_ctx *c, int32_t n, ht_cs_trackobj *out) {
@@ -869,7 +687,7 @@ extern "C" ht_status ht_camshift_track_collect(ht_ctx *c, int32_t n, ht_cs_track
     }
     std::memcpy(out, sl.h_out, sizeof(ht_cs_trackobj) * (size_t)n);
     cs_ring_pop(c);
-    return cs_check_err(c, "ht_camshift_track_collect");
+    return ht_cs_check_err(c, "ht_camshift_track_collect");
 }
 
 extern "C" ht_status ht_camshift_track_sequence(ht_ctx *c, int32_t first, int32_t n, int32_t calc_angles, const void *const *dev_frames,
@@ -908,7 +726,7 @@ extern "C" ht_status ht_camshift_track_sequence(ht_ctx *c, int32_t first, int32_
         }
     }
     c->cs_seq_pending_n = 0;
-    if (out) return cs_read_back(c, "ht_camshift_track_sequence", out, c->d_cs_seq_out, need);
+    if (out) return ht_cs_read_back(c, "ht_camshift_track_sequence", out, c->d_cs_seq_out, need);
     c->cs_seq_pending_n = n, c->cs_seq_pending_calls = ncalls, c->cs_seq_pending_all = out_all ? 1 : 0;  // what ht_camshift_sequence_collect may fetch
     return HT_OK;
 }
@@ -921,7 +739,7 @@ extern "C" ht_status ht_camshift_sequence_collect(ht_ctx *c, int32_t n, int32_t 
     if (!c->d_cs_seq_out || c->cs_seq_cap < need || c->cs_seq_pending_n != n || c->cs_seq_pending_calls != ncalls || c->cs_seq_pending_all != (out_all ? 1 : 0))
         return ht_fail(c, HT_ERR_STATE, "ht_camshift_sequence_collect: no enqueue-only sequence with this n / ncalls / out_all is pending");
     HT_HIP(c, hipSetDevice(c->device));
-    const ht_status st = cs_read_back(c, "ht_camshift_sequence_collect", out, c->d_cs_seq_out, need);
+    const ht_status st = ht_cs_read_back(c, "ht_camshift_sequence_collect", out, c->d_cs_seq_out, need);
     if (st != HT_ERR_HIP) c->cs_seq_pending_n = 0;  // fetched, whatever the error word says; a failed copy leaves the sequence pending
     return st;
 }

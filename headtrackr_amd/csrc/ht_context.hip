@@ -325,6 +325,7 @@ static bool apply_options(ht_ctx *c, const std::string &opts, std::string &why) 
         else if (key == "cs_flags") c->cs_flags = iv != 0;
         else if (key == "cs_sync_ring") c->cs_sync_ring = iv != 0;
         else if (key == "cs_pairs_force") c->cs_pairs_force = iv != 0;
+        else if (key == "cs_pairs_cluster") c->cs_pairs_cluster = iv != 0;
         else if (key == "fp_sparse") c->fp_sparse = iv != 0;
         else if (key == "deep_grid") c->deep_grid = std::max(1, iv);
         else if (key == "split") c->opt_split = std::max(1, iv);

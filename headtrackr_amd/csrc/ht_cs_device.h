@@ -1,5 +1,5 @@
 // ht_cs_device.h — device helpers of the camshift kernels: the histogram bin (cs_bin), the workgroup sizes, the load-laundering macro, the
-// wave-merged histogram update, the window moments and the mean-shift loop.  Included ONCE per translation unit, INSIDE the unit's
+// wave-merged histogram update, the window moments, the mean-shift loop and the cluster exchange (cluster_moments, ClusterSync).  Included ONCE per translation unit, INSIDE the unit's
 // anonymous namespace, ahead of its kernels: by ht_camshift.hip, and by ht_backproject.hip for its own kernels and for ht_cs_pairs.hip,
 // which it compiles.  Every helper has this one definition (tests/test_pairs_cpu.py counts them).  A change here changes the camshift
 // code object that profiles/traffic.json is tied to.
@@ -339,4 +339,112 @@ __device__ __forceinline__ void meanshift_body(int W, int H, const int *s_sw, Ht
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");  // system scope: the track object above is visible before the flag
         __hip_atomic_store(done_flag, done_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+}
+
+// ---- the cluster mean-shift (k_cs_meanshift_cluster / k_csp_meanshift_cluster in ht_cs_kernels.inc): G workgroups share every moment pass ----
+// "not written yet" mark of an exchange entry: a NaN no moment sum can be (the sums are finite and >= 0)
+constexpr unsigned long long CL_UNWRITTEN = 0xFFF8C0DEC0DE0001ull;
+
+
+// The wait is a spin on agent-scope loads, so it is BOUNDED: a thread that has waited `budget` shader-clock cycles (a quarter of a
+// second by default, against ~1-2 us for a healthy exchange) raises the context's error word and its workgroup stops waiting — at this
+// and every later exchange of the call (s_timeout is sticky).  The host reports HT_ERR_STATE with the next result read-back; the stream's
+// state is then garbage for this call, but nothing hangs.  Co-residency (the premise of the spin) is arranged by the host: one cluster
+// launch in flight per device and process, grid <= one workgroup per CU (launch_track).
+// Ordering: an entry is ONE 8-byte word, written by an sc1 (agent-scope) store and read by sc1 loads — single-copy atomic, nothing else
+// depends on it.  That is the gfx9 memory model; ht_create refuses any other arch.
+struct ClusterSync {
+    uint32_t *err;
+    uint32_t *err_host;  // pinned host word (plain system-scope store of 1): an enqueue-only call's host side reads it without a copy
+    long long budget;
+    int *s_timeout;  // LDS flag of the workgroup
+};
+template <bool SECOND>
+__device__ __forceinline__ Mom cluster_moments(const uint32_t *__restrict__ img, int W, const double *lut, int x, int y, int w, int h, double (*red)[CL_NT / 64],
+                                               double *s_part, int g, int G, double *__restrict__ parts, const ClusterSync &sync, int slot) {
+    constexpr int NW = CL_NT / 64, nv = SECOND ? 6 : 3;
+    Mom m = {0, 0, 0, 0, 0, 0};
+    const int ww = w - x, hh = h - y;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (ww > 0 && hh > 0) {
+        for (int j = g * NW + wave; j < hh; j += G * NW) {  // a row per (workgroup, wavefront); 8 column chunks of the row in flight
+            double rs = 0.0, ts = 0.0, us = 0.0;
+            const uint32_t *rowp = img + (size_t)(y + j) * W + x;
+            for (int cb = 0; cb < ww; cb += 512) {
+                uint32_t px[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) px[u] = rowp[min(cb + 64 * u + lane, ww - 1)];  // clamped address, value masked below
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const int c = cb + 64 * u + lane;
+                    const double val = c < ww ? lut[cs_bin(px[u])] : 0.0;
+                    const double vx = (double)c;
+                    rs += val;
+                    ts += vx * val;
+                    if (SECOND) us += vx * vx * val;
+                }
+            }
+            const double vy = (double)j;
+            m.m00 += rs;
+            m.m10 += ts;
+            m.m01 += vy * rs;
+            if (SECOND) {
+                m.m11 += vy * ts;
+                m.m20 += us;
+                m.m02 += vy * vy * rs;
+            }
+        }
+    }
+    double v[6] = {m.m00, m.m10, m.m01, m.m11, m.m20, m.m02};
+    __syncthreads();  // red[] / s_part[] may still be read from the previous pass
+#pragma unroll
+    for (int k = 0; k < nv; k++) {
+        const double sum = wave_sum_f64(v[k]);
+        if (lane == 0) red[k][wave] = sum;
+    }
+    __syncthreads();
+    // this workgroup's partial sums -> its entries of the pass's exchange slot (agent-scope stores, fire and forget); then every entry
+    // of the slot is polled by a thread of its own until it no longer holds the "not written yet" mark k_cs_lut left there: the value
+    // that ends the wait IS the partial sum — no arrival counter, no drain of the stores, no second read (a pass used to be
+    // store -> s_waitcnt -> atomic add -> poll the counter -> read the G partials: three dependent round trips through L2).
+    unsigned long long *slot_parts = reinterpret_cast<unsigned long long *>(parts) + (size_t)slot * CL_MAXG * 6;
+    if (threadIdx.x < nv) {
+        double sum = 0.0;
+#pragma unroll
+        for (int q = 0; q < NW; q++) sum += red[threadIdx.x][q];
+        __hip_atomic_store(&slot_parts[g * 6 + threadIdx.x], (unsigned long long)__double_as_longlong(sum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if ((int)threadIdx.x < G * 6) {
+        unsigned long long bits = 0ull;  // +0.0 for the entries a first-moment pass does not use
+        if ((int)(threadIdx.x % 6u) < nv) {
+            bits = __hip_atomic_load(&slot_parts[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (bits == CL_UNWRITTEN && !*sync.s_timeout) {
+                const long long t0 = (long long)__builtin_readcyclecounter();
+                for (;;) {
+                    __builtin_amdgcn_s_sleep(1);
+                    bits = __hip_atomic_load(&slot_parts[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (bits != CL_UNWRITTEN) break;
+                    if ((long long)__builtin_readcyclecounter() - t0 > sync.budget) {  // bounded spin: give up, flag it, never wait again
+                        *sync.s_timeout = 1;
+                        atomicOr(sync.err, 1u);
+                        if (sync.err_host) __hip_atomic_store(sync.err_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                        break;
+                    }
+                }
+            }
+            if (bits == CL_UNWRITTEN) bits = 0ull;  // timed out: the call's result is undefined (reported), but it stays a number
+        }
+        s_part[threadIdx.x] = __longlong_as_double((long long)bits);
+    }
+    __syncthreads();
+    {  // lane k of every wavefront adds moment k's G partials in the fixed order q = 0 .. G-1: every workgroup of the cluster gets the same bits
+        double sacc = 0.0;
+        if (lane < nv)
+            for (int q = 0; q < G; q++) sacc += s_part[q * 6 + lane];
+#pragma unroll
+        for (int k = 0; k < nv; k++)
+            v[k] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(sacc), k), __builtin_amdgcn_readlane(__double2loint(sacc), k));
+    }
+    m.m00 = v[0], m.m10 = v[1], m.m01 = v[2], m.m11 = v[3], m.m20 = v[4], m.m02 = v[5];
+    return m;
 }

@@ -1,6 +1,9 @@
-// ht_cs_kernels.inc — the init, histogram and mean-shift kernels of camshift, written once and compiled by two units: ht_camshift.hip
-// (k_cs_init / k_cs_hist / k_cs_meanshift: stream first + i on bound frame i) and ht_cs_pairs.hip (k_csp_*: any reserved stream on any
-// bound frame, from a device table).  The two forms differ in their look-ups only — which stream, which frame, which histogram slot,
+// ht_cs_kernels.inc — the init, histogram and mean-shift kernels of camshift and their few-large-streams forms (row-split init, LUT,
+// cluster mean-shift), written once and compiled by two units: ht_camshift.hip (k_cs_init / k_cs_hist / k_cs_meanshift / k_cs_init_rows /
+// k_cs_lut / k_cs_meanshift_cluster: stream first + i on bound frame i) and ht_cs_pairs.hip (k_csp_*: any reserved stream on any
+// bound frame, from a device table).  In the few-large-streams forms the LUT, the exchange slots and `out` are indexed by the
+// workgroup's position s in the call in both units; only state, pixels, histogram slot and rect go through the look-ups.
+// The two forms differ in their look-ups only — which stream, which frame, which histogram slot,
 // which rect — and the including unit supplies those.  Included INSIDE the unit's anonymous namespace, after ht_cs_device.h.
 //
 // The including unit defines, before the #include:
@@ -14,8 +17,10 @@
 //   CS_HIST_FRAMES_PARAM     the histogram kernel's parameter between chunk_px and hist: empty, or a frame list with its comma
 //   CS_HIST_FRAME(y)         the bound frame of grid row y.  A macro, not a function: y is the UNSIGNED blockIdx.y, and an int
 //                            in between costs the batch kernel a sign extension
-//   CS_KERNELS_PART          optional: 1 = only the init kernel, 2 = only the histogram and mean-shift kernels.  A code object's .text
-//                            is laid out in definition order, and ht_camshift.hip defines k_cs_init_rows between the two parts
+//   CS_KERNELS_PART          optional: 1 = only the init kernel, 2 = only the histogram and mean-shift kernels, 3 = only the row-split init
+//                            kernel, 4 = only the LUT and cluster mean-shift kernels.  A code object's .text is laid out in definition
+//                            order: ht_camshift.hip includes parts 1, 3, 2, defines k_cs_track_fused, then includes part 4 — the order
+//                            its recorded object has.  Without it (ht_cs_pairs.hip): everything
 //
 // Shared as TEXT on purpose.  profiles/traffic.json is tied to the machine code of the camshift code object, and the same bodies as
 // __device__ __forceinline__ functions called from thin kernels change it (the extra inlining level reorders the optimiser's passes:
@@ -168,6 +173,110 @@ __global__ __launch_bounds__(CS_NT) void CS_K(meanshift)(const uint8_t *__restri
     __syncthreads();
     meanshift_body(W, H, s_sw, st, calc_angles, max_it, out ? out + s : nullptr, nullptr, true,
                    [&](int x, int y, int w, int h) { return window_moments_any<true, CS_NT / 64>(img, W, lut, R, x, y, w, h, red); });
+}
+
+#endif
+#if !defined(CS_KERNELS_PART) || CS_KERNELS_PART == 3
+
+// initTracker for a FEW streams with large rects (a live 1080p feed: 360 x 360 = 0.5 MB took the single workgroup above 54 us):
+// grid (G, streams), workgroup g takes rows g*4 + wavefront, + 4 G, ...; LDS histogram per workgroup, non-zero bins added to the
+// model (zeroed by the host) with global atomics — integer counts, any order gives the same model.
+__global__ __launch_bounds__(256) void CS_K(init_rows)(const uint8_t *__restrict__ frames, size_t frame_stride, int W, int H, CS_INIT_PARAMS) {
+    __shared__ uint32_t h[4096];
+    const int s = blockIdx.y, g = blockIdx.x, G = gridDim.x;
+    for (int i = threadIdx.x; i < 4096; i += 256) h[i] = 0;
+    __syncthreads();
+    const ht_cs_rect r = CS_INIT_RECT(s);
+    const uint32_t *img = reinterpret_cast<const uint32_t *>(frames + (size_t)cs_frame_of(lk, s) * frame_stride);
+    const int rw = max(r.width, 0), rh = max(r.height, 0);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int j = g * 4 + wave; j - wave < rh + 3; j += 4 * G) {  // same trip count for the four wavefronts of a workgroup
+        const int y = r.y + j;
+        for (int cb = 0; cb < rw; cb += 256) {
+            uint32_t px[4];
+            bool in[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int c = cb + 64 * u + lane, x = r.x + c;
+                in[u] = c < rw && j < rh;
+                px[u] = (in[u] && x >= 0 && x < W && y >= 0 && y < H) ? img[(size_t)y * W + x] : 0u;  // outside the canvas: transparent black (camshift.js:206)
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) CS_BATCH_LOADED(px[u]);
+#pragma unroll
+            for (int u = 0; u < 4; u++) hist_add_wave(h, cs_bin(px[u]), 1u, in[u]);
+        }
+    }
+    __syncthreads();
+    HtCsState &st = states[cs_stream_of(lk, s)];
+    for (int i = threadIdx.x; i < 4096; i += 256)
+        if (h[i]) atomicAdd(&st.model[i], h[i]);
+    if (g == 0 && threadIdx.x == 0) {
+        st.sw[0] = r.x, st.sw[1] = r.y, st.sw[2] = r.width, st.sw[3] = r.height;  // camshift.js:209
+        st.x = st.y = st.width = st.height = st.angle = 0.0;                         // camshift.js:210
+        st.win_px = st.calls = 0;
+    }
+}
+
+#endif
+#if !defined(CS_KERNELS_PART) || CS_KERNELS_PART == 4
+
+// weight LUT of every stream from its chunk histograms (getWeights, camshift.js:314-330): grid (64, streams) x 512 threads;
+// a block owns 64 bins, its 8 wavefronts each sum every 8th chunk (a single 1080p stream has 127 chunk histograms = 2 MB)
+__global__ __launch_bounds__(512) void CS_K(lut)(const uint32_t *__restrict__ hist, int nchunks, const HtCsState *__restrict__ states, CsLookup lk,
+                                                double *__restrict__ lut, unsigned long long *__restrict__ cluster_parts) {
+    __shared__ uint32_t part[8][64];
+    const int s = blockIdx.y, lane = threadIdx.x & 63, grp = threadIdx.x >> 6, bin = blockIdx.x * 64 + lane;
+    {   // the stream's exchange slots of the cluster launch that follows: every entry "not written yet" (was a memset of its own)
+        const uint32_t i = blockIdx.x * 512u + threadIdx.x;
+        if (i < (uint32_t)(CL_SLOTS * CL_MAXG * 6)) cluster_parts[(size_t)s * CL_SLOTS * CL_MAXG * 6 + i] = CL_UNWRITTEN;
+    }
+    const uint32_t *cur = hist + (size_t)cs_slot_of(lk, s) * nchunks * 4096 + bin;
+    uint32_t ch = 0;
+#pragma unroll 4
+    for (int k = grp; k < nchunks; k += 8) ch += cur[(size_t)k * 4096];
+    part[grp][lane] = ch;
+    __syncthreads();
+    if (grp == 0) {
+        ch = 0;
+#pragma unroll
+        for (int q = 0; q < 8; q++) ch += part[q][lane];
+        double p = 0.0;
+        if (ch != 0) {
+            p = (double)states[cs_stream_of(lk, s)].model[bin] / (double)ch;
+            p = p < 1.0 ? p : 1.0;
+        }
+        lut[(size_t)s * 4096 + bin] = p;
+    }
+}
+
+__global__ __launch_bounds__(CL_NT) void CS_K(meanshift_cluster)(const uint8_t *__restrict__ frames, size_t frame_stride, int W, int H, const double *__restrict__ lut_g,
+                                                                HtCsState *__restrict__ states, CsLookup lk, int calc_angles, int max_it, int G,
+                                                                double *__restrict__ parts,
+                                                                uint32_t *__restrict__ err, uint32_t *__restrict__ err_host, long long budget,
+                                                                ht_cs_trackobj *__restrict__ out, uint32_t *__restrict__ done_flags, uint32_t done_seq) {
+    __shared__ double lut[4096];
+    __shared__ double red[6][CL_NT / 64];
+    __shared__ double s_part[CL_MAXG * 6];
+    __shared__ int s_sw[4];
+    __shared__ int s_timeout;
+    if (threadIdx.x == 0) s_timeout = 0;
+    const int s = blockIdx.x / G, g = blockIdx.x - s * G;
+    HtCsState &st = states[cs_stream_of(lk, s)];
+    const uint32_t *img = reinterpret_cast<const uint32_t *>(frames + (size_t)cs_frame_of(lk, s) * frame_stride);
+    {
+        const double2 *src = reinterpret_cast<const double2 *>(lut_g + (size_t)s * 4096);
+        for (int i = threadIdx.x; i < 2048; i += CL_NT) reinterpret_cast<double2 *>(lut)[i] = src[i];
+    }
+    if (threadIdx.x < 4) s_sw[threadIdx.x] = st.sw[threadIdx.x];
+    __syncthreads();
+    double *my_parts = parts + (size_t)s * CL_SLOTS * CL_MAXG * 6;
+    const ClusterSync sync = {err, err_host, budget, &s_timeout};
+    int slot = 0;
+    meanshift_body(W, H, s_sw, st, calc_angles, max_it, out ? out + s : nullptr, nullptr, g == 0, [&](int x, int y, int w, int h) {
+        const int sl = slot++;
+        return cluster_moments<true>(img, W, lut, x, y, w, h, red, s_part, g, G, my_parts, sync, sl);
+    }, done_flags ? done_flags + s : nullptr, done_seq);
 }
 
 #endif

@@ -9,7 +9,15 @@
 //   k_csp_meanshift  one CS_NT-thread workgroup per pair: k_cs_meanshift with three look-ups (state, pixels, histogram slot)
 //   k_csp_init       one workgroup per pair: k_cs_init with the same look-ups
 //
-// The three kernels are ht_cs_kernels.inc, the text ht_camshift.hip compiles its k_cs_* from; this unit supplies the look-ups through
+// and, under option cs_pairs_cluster=1, for a few pairs on large frames (ht_cs_plan_track_pairs / ht_cs_plan_init_pairs decide):
+//
+//   k_csp_lut                grid (64, pairs): k_cs_lut — the pair's weight LUT from its frame's chunk histograms, its exchange slots marked
+//   k_csp_meanshift_cluster  G workgroups per pair: k_cs_meanshift_cluster, behind the cluster gate (ht_cs_cluster_gate_begin / _end)
+//   k_csp_zero_models        one workgroup per pair zeroes the pair's model (the paired streams are not contiguous: no 2-D memset), for
+//   k_csp_init_rows          grid (G, pairs): k_cs_init_rows, which adds into the model with integer atomics
+//   LUT, exchange slots and `out` are indexed by the pair's position in the call; state, pixels and histogram slot come from the table.
+//
+// The kernels are ht_cs_kernels.inc, the text ht_camshift.hip compiles its k_cs_* from; this unit supplies the look-ups through
 // the call's device table (CspEntry).  Same wavefront count, same summation order, same bits as the few-stream schedule of
 // ht_camshift_track_batch (options cs_fused_min=large, cs_cluster=0).
 //
@@ -39,6 +47,12 @@ __device__ __forceinline__ int cs_slot_of(const CspEntry *e, int s) { return e[s
 #define CS_HIST_FRAMES_PARAM const int32_t *__restrict__ frame_list,  // the call's distinct frames, one per grid row
 #define CS_HIST_FRAME(y_) frame_list[y_]
 #include "ht_cs_kernels.inc"
+
+// the models of the call's pairs = 0, in front of k_csp_init_rows: workgroup s clears the 16 KB of pair s's stream, 16 bytes per thread
+__global__ __launch_bounds__(1024) void k_csp_zero_models(CsLookup lk, HtCsState *__restrict__ states) {
+    reinterpret_cast<uint4 *>(states[cs_stream_of(lk, blockIdx.x)].model)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+}
+static_assert(sizeof(HtCsState::model) == 1024 * sizeof(uint4), "k_csp_zero_models: one uint4 per thread");
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
 
@@ -116,17 +130,28 @@ ht_status csp_upload(ht_ctx *c, const char *fn, const CspPlan &plan, const CspEn
     return HT_OK;
 }
 
-// one track() of every pair: table, histograms of the distinct frames, one mean-shift workgroup per pair; results to d_out[0 .. n)
-ht_status csp_launch_track(ht_ctx *c, const CspPlan &plan, int32_t calc_angles, ht_cs_trackobj *d_out) {
+// the schedule of a pair call of n pairs on nd distinct frames with this context's geometry and options (ht_cs_schedule.h)
+HtCspTrackPlan csp_plan_track(ht_ctx *c, int n, int nd) {
+    HtCspTrackIn in;
+    in.n = n, in.nd = nd, in.W = c->W, in.H = c->H, in.num_cus = c->num_cus;
+    in.cs_pairs_cluster = c->cs_pairs_cluster, in.cs_cluster = c->cs_cluster, in.cs_cluster_min_px = c->cs_cluster_min_px;
+    in.dbg_cs_iters = c->dbg_cs_iters, in.cs_region_cap = c->cs_region_cap;
+    return ht_cs_plan_track_pairs(in);
+}
+
+// one track() of every pair: table, histograms of the distinct frames, then what the plan says — one mean-shift workgroup per pair, or
+// the pair's LUT and a cluster of G workgroups per pair; results to d_out[0 .. n).  *cluster: the call took the cluster form (its
+// read-back fetches the error word)
+ht_status csp_launch_track(ht_ctx *c, const CspPlan &plan, int32_t calc_angles, ht_cs_trackobj *d_out, bool *cluster) {
     const char *fn = "ht_camshift_track_pairs";
     const int n = (int)plan.entries.size(), nd = (int)plan.frames.size();
-    const uint32_t npix = (uint32_t)((size_t)c->W * c->H);
+    const HtCspTrackPlan p = csp_plan_track(c, n, nd);
+    *cluster = p.form == HT_CSP_CLUSTER;
     if (!c->csp_attr_set) {  // the cached search region needs more than the default 64 KB of LDS per workgroup
         HT_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_csp_meanshift), hipFuncAttributeMaxDynamicSharedMemorySize, CS_REGION_CAP * 2));
         c->csp_attr_set = true;
     }
-    uint32_t chunk_px = 0, nchunks = 0;
-    ht_cs_hist_plan(npix, nd, &chunk_px, &nchunks);
+    const uint32_t nchunks = p.nchunks;
     const size_t need = (size_t)nd * nchunks * 4096;
     // the scratch is about to be replaced: what ht_camshift_debug_hist would read must not point into the old one, also when the allocation fails
     if (c->csp_hist_cap < need && c->cs_last_hist && c->cs_last_hist != c->d_cs_hist) c->cs_last_hist = nullptr, c->cs_last_n = 0;
@@ -137,14 +162,34 @@ ht_status csp_launch_track(ht_ctx *c, const CspPlan &plan, int32_t calc_angles, 
     ht_status st = csp_upload(c, fn, plan, &d_entries, &d_flist);
     if (st != HT_OK) return st;
     {
-        HtProfScope ps(c, "csp_hist");
-        hipLaunchKernelGGL(k_csp_hist, dim3(nchunks, nd), dim3(HIST_NT), 0, c->stream, c->d_frames, c->frame_stride, npix, chunk_px, d_flist, c->d_csp_hist);
+        HtProfScope ps(c, p.hist.timer);
+        hipLaunchKernelGGL(k_csp_hist, dim3(p.hist.grid_x, p.hist.grid_y), dim3(p.hist.block), 0, c->stream, c->d_frames, c->frame_stride, p.npix, p.chunk_px, d_flist,
+                           c->d_csp_hist);
         HT_HIP(c, hipGetLastError());
     }
-    {
-        HtProfScope ps(c, "csp_meanshift");
-        hipLaunchKernelGGL(k_csp_meanshift, dim3(n), dim3(CS_NT), (size_t)CS_REGION_CAP * 2, c->stream, c->d_frames, c->frame_stride, c->W, c->H, c->d_csp_hist,
-                           (int)nchunks, c->d_cs, d_entries, calc_angles, c->dbg_cs_iters, c->cs_region_cap, d_out);
+    if (p.form == HT_CSP_CLUSTER) {
+        // d_cs_lut / d_cs_parts hold min(reserved, CL_MAX_STREAMS) streams (ht_cs_reserve_sizes) >= n here; the context's one stream orders
+        // them against the batch cluster calls
+        {
+            HtProfScope ps(c, p.lut.timer);
+            hipLaunchKernelGGL(k_csp_lut, dim3(p.lut.grid_x, p.lut.grid_y), dim3(p.lut.block), 0, c->stream, c->d_csp_hist, (int)nchunks, c->d_cs, d_entries, c->d_cs_lut,
+                               reinterpret_cast<unsigned long long *>(c->d_cs_parts));
+            HT_HIP(c, hipGetLastError());
+        }
+        HtProfScope ps(c, p.meanshift.timer);
+        st = ht_cs_cluster_gate_begin(c);
+        if (st != HT_OK) return st;
+        hipLaunchKernelGGL(k_csp_meanshift_cluster, dim3(p.meanshift.grid_x), dim3(p.meanshift.block), p.meanshift.lds, c->stream, c->d_frames, c->frame_stride, c->W,
+                           c->H, c->d_cs_lut, c->d_cs, d_entries, calc_angles, c->dbg_cs_iters, p.G, c->d_cs_parts, c->d_cs_err, c->h_cs_err_direct,
+                           (long long)c->cs_barrier_budget, d_out, static_cast<uint32_t *>(nullptr), 0u);  // completed by the slot's event
+        const hipError_t le = hipGetLastError();
+        st = ht_cs_cluster_gate_end(c);
+        HT_HIP(c, le);
+        if (st != HT_OK) return st;
+    } else {
+        HtProfScope ps(c, p.meanshift.timer);
+        hipLaunchKernelGGL(k_csp_meanshift, dim3(p.meanshift.grid_x), dim3(p.meanshift.block), p.meanshift.lds, c->stream, c->d_frames, c->frame_stride, c->W, c->H,
+                           c->d_csp_hist, (int)nchunks, c->d_cs, d_entries, calc_angles, c->dbg_cs_iters, p.region_cap, d_out);
         HT_HIP(c, hipGetLastError());
     }
     // what ht_camshift_debug_hist(current) reads: the slot of every paired stream's frame (the map stays on the host)
@@ -169,9 +214,19 @@ extern "C" ht_status ht_camshift_init_pairs(ht_ctx *c, const ht_cs_pair *pairs, 
     const int32_t *d_flist = nullptr;
     st = csp_upload(c, "ht_camshift_init_pairs", plan, &d_entries, &d_flist);
     if (st != HT_OK) return st;
-    HtProfScope ps(c, "csp_init");
-    hipLaunchKernelGGL(k_csp_init, dim3(n), dim3(INIT_NT), 0, c->stream, c->d_frames, c->frame_stride, c->W, c->H, d_entries, c->d_cs);
-    HT_HIP(c, hipGetLastError());
+    int max_rh = 0;
+    for (int32_t i = 0; i < n; i++) max_rh = std::max(max_rh, rects[i].height);
+    const HtCsInitPlan ip = ht_cs_plan_init_pairs(c->cs_pairs_cluster, n, max_rh, c->num_cus);
+    if (ip.rows) {
+        HtProfScope ps(c, "csp_init_rows");
+        hipLaunchKernelGGL(k_csp_zero_models, dim3(n), dim3(1024), 0, c->stream, d_entries, c->d_cs);
+        hipLaunchKernelGGL(k_csp_init_rows, dim3(ip.G, n), dim3(CS_INIT_ROWS_NT), 0, c->stream, c->d_frames, c->frame_stride, c->W, c->H, d_entries, c->d_cs);
+        HT_HIP(c, hipGetLastError());
+    } else {
+        HtProfScope ps(c, "csp_init");
+        hipLaunchKernelGGL(k_csp_init, dim3(n), dim3(INIT_NT), 0, c->stream, c->d_frames, c->frame_stride, c->W, c->H, d_entries, c->d_cs);
+        HT_HIP(c, hipGetLastError());
+    }
     return HT_OK;
 }
 
@@ -188,16 +243,18 @@ extern "C" ht_status ht_camshift_track_pairs(ht_ctx *c, const ht_cs_pair *pairs,
     ht_ctx::HtCsSlot *slot = nullptr;
     st = ht_cs_ring_begin(c, "ht_camshift_track_pairs", n, out, &via_ring, &slot);
     if (st != HT_OK) return st;
+    bool cluster = false;
     if (slot) {
-        st = csp_launch_track(c, plan, calc_angles, slot->h_out);
+        st = csp_launch_track(c, plan, calc_angles, slot->h_out, &cluster);
         if (st != HT_OK) return st;
         slot->seq = 0u;  // completed by the event
         HT_HIP(c, hipEventRecord(slot->ev, c->stream));
         ht_cs_ring_commit(c, slot, n);
         return via_ring ? ht_camshift_track_collect(c, n, out) : HT_OK;
     }
-    st = csp_launch_track(c, plan, calc_angles, c->d_cs_out);
+    st = csp_launch_track(c, plan, calc_angles, c->d_cs_out, &cluster);
     if (st != HT_OK) return st;
+    if (cluster) return ht_cs_read_back(c, "ht_camshift_track_pairs", out, c->d_cs_out, (size_t)n);  // the track objects and the cluster error word
     HT_HIP(c, hipMemcpyAsync(out, c->d_cs_out, sizeof(ht_cs_trackobj) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HT_HIP(c, hipStreamSynchronize(c->stream));
     return HT_OK;

@@ -144,6 +144,47 @@ inline HtCsTrackPlan ht_cs_plan_track(const HtCsTrackIn &in) {
     return p;
 }
 
+// ---- track() of (stream, frame) pairs (ht_camshift_track_pairs): one of two schedules --------------------------------------------------------
+// n pairs on nd distinct bound frames.  The chunk histograms are per DISTINCT frame (k_csp_hist), so the chunk plan follows nd; the
+// mean-shift is per pair.  The cluster form (option cs_pairs_cluster) is ht_cs_plan_track's cluster rule with n = pairs.
+enum HtCspForm {
+    HT_CSP_PER_PAIR,  // k_csp_hist + k_csp_meanshift: one workgroup per pair
+    HT_CSP_CLUSTER    // k_csp_hist + k_csp_lut + k_csp_meanshift_cluster: G workgroups per pair
+};
+struct HtCspTrackIn {
+    int n = 0, nd = 0;  // pairs, distinct frames
+    int W = 0, H = 0, num_cus = 256;
+    bool cs_pairs_cluster = false, cs_cluster = true;
+    uint32_t cs_cluster_min_px = 10000;
+    int dbg_cs_iters = 10, cs_region_cap = CS_REGION_CAP;
+};
+struct HtCspTrackPlan {
+    HtCspForm form = HT_CSP_PER_PAIR;
+    HtCsLaunch hist, lut, meanshift;
+    uint32_t npix = 0, chunk_px = 0, nchunks = 0;
+    int G = 0;           // workgroups per pair of the cluster form
+    int region_cap = 0;  // pixels of the LDS-cached search region (one-workgroup form)
+};
+inline HtCspTrackPlan ht_cs_plan_track_pairs(const HtCspTrackIn &in) {
+    HtCspTrackPlan p;
+    const int n = in.n;
+    p.npix = (uint32_t)((size_t)in.W * in.H);
+    ht_cs_hist_plan(p.npix, in.nd, &p.chunk_px, &p.nchunks);
+    p.hist.grid_x = p.nchunks, p.hist.grid_y = (uint32_t)in.nd, p.hist.block = HIST_NT, p.hist.timer = "csp_hist";
+    // the grid n * G never exceeds one workgroup per CU: co-resident whatever else is resident (see ht_cs_plan_track)
+    p.G = std::min(CL_MAXG, in.num_cus / std::max(n, 1));
+    const bool cluster = in.cs_pairs_cluster && in.cs_cluster && n <= CL_MAX_STREAMS && p.G >= 4 && p.npix >= in.cs_cluster_min_px && in.dbg_cs_iters > 0;
+    if (cluster) {
+        p.form = HT_CSP_CLUSTER;
+        p.lut.grid_x = 64, p.lut.grid_y = (uint32_t)n, p.lut.block = CS_LUT_NT, p.lut.timer = "csp_lut";
+        p.meanshift.grid_x = (uint32_t)(n * p.G), p.meanshift.block = CL_NT, p.meanshift.timer = "csp_meanshift_cluster";
+    } else {
+        p.meanshift.grid_x = (uint32_t)n, p.meanshift.block = CS_NT, p.meanshift.lds = (size_t)CS_REGION_CAP * 2, p.meanshift.timer = "csp_meanshift";
+        p.region_cap = in.cs_region_cap;
+    }
+    return p;
+}
+
 // ---- initTracker --------------------------------------------------------------------------------------------------------------------------
 // few streams with tall rects: rows spread over G workgroups per stream (k_cs_init_rows; one workgroup per stream would leave the chip
 // idle), otherwise one workgroup per stream (k_cs_init)
@@ -155,6 +196,13 @@ inline HtCsInitPlan ht_cs_plan_init(int n, int max_rect_height, int num_cus) {
     HtCsInitPlan p;
     p.G = std::min(std::min(32, std::max(1, num_cus * 2 / std::max(n, 1))), (max_rect_height + 15) / 16);
     p.rows = n < 64 && p.G >= 2;
+    return p;
+}
+// ht_camshift_init_pairs: the row form only under option cs_pairs_cluster (k_csp_init_rows), otherwise one workgroup per pair (k_csp_init)
+inline HtCsInitPlan ht_cs_plan_init_pairs(bool cs_pairs_cluster, int n, int max_rect_height, int num_cus) {
+    HtCsInitPlan p = ht_cs_plan_init(n, max_rect_height, num_cus);
+    if (!cs_pairs_cluster) p.rows = false;
+    if (!p.rows) p.G = 1;
     return p;
 }
 

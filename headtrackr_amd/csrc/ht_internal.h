@@ -348,6 +348,8 @@ struct ht_ctx {
     size_t csp_hist_cap = 0;
     bool csp_attr_set = false;       // > 64 KB dynamic LDS enabled for k_csp_meanshift on this context's device
     bool cs_pairs_force = false;     // option cs_pairs_force=1: identity layouts (first + i, i) go through the pair kernels too (tests, A/B)
+    bool cs_pairs_cluster = false;   // option cs_pairs_cluster=1: pair calls on a few large frames take the cluster schedule (k_csp_lut + k_csp_meanshift_cluster),
+                                     // tall rects of a few pairs the row-split initTracker (k_csp_init_rows); ht_cs_plan_track_pairs / ht_cs_plan_init_pairs
     std::vector<int32_t> cs_pair_slot;  // after a pair call: histogram slot of every stream it paired (-1: not part of it), for ht_camshift_debug_hist
     int cs_pair_chunks = 0;
 
@@ -441,6 +443,16 @@ ht_status ht_cs_hist_launch(ht_ctx *ctx, const uint8_t *frames, size_t frame_str
 // is outstanding
 ht_status ht_cs_ring_begin(ht_ctx *ctx, const char *fn, int32_t n, const ht_cs_trackobj *out, bool *via_ring, ht_ctx::HtCsSlot **slot);
 void ht_cs_ring_commit(ht_ctx *ctx, ht_ctx::HtCsSlot *slot, int32_t n);
+// ht_camshift.hip: the cluster gate — one grid whose workgroups spin on each other (k_cs_meanshift_cluster, k_csp_meanshift_cluster) in
+// flight per device and process once more than one context uses such grids.  begin: in front of the launch (takes the gate's lock; the
+// context's stream waits for the previous cluster grid of the device when several contexts use the path); end: behind the launch (records
+// it, releases the lock).  end must follow every begin, also a failed one and a failed launch.
+ht_status ht_cs_cluster_gate_begin(ht_ctx *ctx);
+ht_status ht_cs_cluster_gate_end(ht_ctx *ctx);
+// ht_camshift.hip: the cluster error word (d_cs_err / h_cs_err / h_cs_err_direct) as a status: HT_ERR_STATE with the barrier message when set
+ht_status ht_cs_check_err(ht_ctx *ctx, const char *where);
+// ht_camshift.hip: copy-back route of a result read-back: `count` track objects and the error word, stream synchronised, word checked
+ht_status ht_cs_read_back(ht_ctx *ctx, const char *fn, ht_cs_trackobj *out, const ht_cs_trackobj *d_src, size_t count);
 void ht_camshift_free(ht_ctx *ctx);                         // ht_camshift.hip: tracker state, scratch, result ring, the cluster gate's entry (ht_destroy)
 void ht_backproject_free(ht_ctx *ctx);                      // ht_backproject.hip: its scratch (ht_destroy)
 void ht_cs_pairs_free(ht_ctx *ctx);                         // ht_cs_pairs.hip: pair table, staging and histogram scratch (ht_destroy)

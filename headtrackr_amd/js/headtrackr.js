@@ -13,6 +13,7 @@
  *   ccv.array_group(seq,gfunc)                          ccv.js:34-107    (host, O(n^2) on a few dozen rects)
  *   camshift.Tracker / Histogram / Moments / Rectangle / TrackObj          camshift.js:49-378 -> ht_camshift_*
  *   camshift.MultiTracker                               several trackers on one canvas, one device call per frame -> ht_camshift_*_pairs;
+ *                                                       camshift.pairSchedule = 'cluster' (before the first tracker): G workgroups per pair on large canvases
  *                                                       getBackProjectionImg(i) / getBackProjectionImgs() / getPdf(i) -> ht_camshift_backproject_pairs
  *   facetrackr.Tracker / TrackObj                       facetrackr.js:37-255  (state machine WB -> VJ -> CS)
  *   getWhitebalance(canvas)                             whitebalance.js:5-30 -> ht_whitebalance_batch
@@ -61,17 +62,26 @@ Object.defineProperty(headtrackr, 'cascade', { /* cascade.js:19: the trained fac
 
 /* one native context per (cascade object, interval, GPU); contexts own device memory, so they are cached */
 const contexts = new WeakMap();
-function contextFor(cascade, interval, device) {
+function contextFor(cascade, interval, device, options) { /* options: ht_config.options string of the context (part of the cache key), or nothing */
   if (device === undefined) device = headtrackr.device | 0;
   let perCascade = contexts.get(cascade);
   if (!perCascade) { perCascade = new Map(); contexts.set(cascade, perCascade); }
-  const key = interval + '@' + device;
+  const key = interval + '@' + device + (options ? '?' + options : '');
   let c = perCascade.get(key);
   if (!c) {
-    c = { handle: addon().createContext({ cascade: pack.packCascade(cascade), interval: interval, device: device }), w: 0, h: 0, batch: 0, device: device };
+    const cfg = { cascade: pack.packCascade(cascade), interval: interval, device: device };
+    if (options) cfg.options = options;
+    c = { handle: addon().createContext(cfg), w: 0, h: 0, batch: 0, device: device };
     perCascade.set(key, c);
   }
   return c;
+}
+/* the two schedules of the (tracker, frame) pair calls: 'workgroup' = one workgroup per pair (no option), 'cluster' = option
+ * cs_pairs_cluster=1: a few pairs on large frames get G workgroups each and tall rects a row-split initTracker.  Same results. */
+function pairScheduleOptions(v, who) {
+  if (v === undefined || v === 'workgroup') return '';
+  if (v === 'cluster') return 'cs_pairs_cluster=1';
+  throw new RangeError(who + ": pairSchedule is 'workgroup' or 'cluster'");
 }
 headtrackr.device = 0; /* HIP device ordinal used by the single-frame (drop-in) entry points */
 headtrackr.deviceCount = function () { return addon().deviceCount(); }; /* GPUs the `devices` option of the batch entry points can name */
@@ -396,6 +406,8 @@ headtrackr.ccv.detect_objects_batch = function (frames, n, w, h, cascade, interv
  *     backProjectionPairs(set, pairs, kind) -> the same per (tracker, frame) pair, pair order: ht_camshift_backproject_pairs
  *     initPairs / trackPairs / trackPairsEnqueue / detectStepFinish(min_neighbors, {feeds})   trackers and frames paired freely (below);
                                            opts.trackers = tracker slots to reserve (default n)
+   opts.pairSchedule = 'cluster': the pair calls of a few pairs on large frames (1080p feeds) run G workgroups per pair and tall rects a
+   row-split initTracker (context option cs_pairs_cluster=1); 'workgroup' (default): one workgroup per pair.  The same results.
    opts.grouping = 'device': detectBest, detect, detectStepFinish and whitebalance take the device route — grouping and best face run
    behind the scan on the GPU (ht_detect_best_enqueue / _collect), the host receives one record per frame; 'host' (default) keeps the
    host route.  The results are the same bytes.
@@ -419,10 +431,16 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
   /* the two halves of a batch on either route; the device route's requeue re-issues its grouping inside the library */
   const enqueueBest = function (c, flags, min_neighbors) { A.detectEnqueue(c, flags); if (onDevice) A.detectBestEnqueue(c, min_neighbors, 0); };
   const collectBest = function (c, min_neighbors, requeue) { return onDevice ? A.collectBestDevice(c, requeue) : A.collectBest(c, min_neighbors, requeue); };
+  /* opts.pairSchedule: how initPairs / trackPairs / detectStepFinish(.., {feeds}) schedule their pairs — 'workgroup' (default) or
+   * 'cluster' (every context is created with options 'cs_pairs_cluster=1') */
+  const pairSchedule = opts.pairSchedule === undefined ? 'workgroup' : opts.pairSchedule;
+  const ctxOptions = pairScheduleOptions(pairSchedule, 'DeviceBatch');
   const blob = pack.packCascade(cascade), dims = levelDims(w, h, cascade, interval);
   const ctxs = [];
   for (let i = 0; i < depth; i++) {
-    const hnd = A.createContext({ cascade: blob, interval: interval, device: device });
+    const cfg = { cascade: blob, interval: interval, device: device };
+    if (ctxOptions) cfg.options = ctxOptions;
+    const hnd = A.createContext(cfg);
     A.setGeometry(hnd, w, h, n, dims);
     ctxs.push(hnd);
   }
@@ -431,7 +449,7 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
   let bound = -1, trackers = false;
   const pendingTrack = []; /* streams of the outstanding enqueue-only track steps, oldest first (pair steps need not have n) */
   const bind = function (set) { if (bound !== set) { ctxs.forEach(function (c) { A.bindDevice(c, dev, set * setBytes, n, fbytes); }); bound = set; } };
-  this.width = w; this.height = h; this.frames = n; this.depth = depth; this.grouping = grouping;
+  this.width = w; this.height = h; this.frames = n; this.depth = depth; this.grouping = grouping; this.pairSchedule = pairSchedule;
   this.upload = function (frames, set) {
     if (frames.length < setBytes) throw new RangeError('DeviceBatch.upload: need n*w*h*4 bytes');
     A.deviceUpload(ctxs[0], dev, (set || 0) * setBytes, frames.subarray(0, setBytes));
@@ -697,9 +715,9 @@ headtrackr.camshift.TrackObj = function () { /* camshift.js:362-378 */
 };
 
 /* every camshift.Tracker owns one device-side stream slot of a shared context */
-const csPool = { ctx: null, next: 0, free: [], reserved: 0 };
+const csPool = { ctx: null, next: 0, free: [], reserved: 0, pairSchedule: 'workgroup' };
 function csSlot() {
-  if (!csPool.ctx) csPool.ctx = contextFor(headtrackr.cascade, 5);
+  if (!csPool.ctx) csPool.ctx = contextFor(headtrackr.cascade, 5, undefined, pairScheduleOptions(csPool.pairSchedule, 'headtrackr.camshift') || undefined);
   const slot = csPool.free.length ? csPool.free.pop() : csPool.next++;
   if (csPool.next > csPool.reserved) { /* grow geometrically: a reservation re-allocates and copies every tracker's state */
     csPool.reserved = Math.max(csPool.next, 2 * csPool.reserved, 4);
@@ -708,6 +726,19 @@ function csSlot() {
   return slot;
 }
 headtrackr.camshift._pool = csPool; /* exposed for tests */
+/* headtrackr.camshift.pairSchedule = 'workgroup' (default) | 'cluster': the schedule of camshift.MultiTracker's pair calls (and the option of
+ * the context every camshift.Tracker shares with it).  Read when the pool's context is created, i.e. by the first Tracker / MultiTracker:
+ * set it BEFORE that; afterwards a change throws. */
+Object.defineProperty(headtrackr.camshift, 'pairSchedule', {
+  enumerable: true,
+  get: function () { return csPool.pairSchedule; },
+  set: function (v) {
+    pairScheduleOptions(v, 'headtrackr.camshift'); /* RangeError for anything else */
+    if (v === csPool.pairSchedule) return;
+    if (csPool.ctx) throw new Error('headtrackr.camshift.pairSchedule must be set before the first camshift.Tracker / MultiTracker is created (the camshift context exists already)');
+    csPool.pairSchedule = v;
+  }
+});
 
 /* getPdf() on the host (camshift.js:198-211, 314-353): `last` through the model of rect `mr` on `mframe` (both ImageData) */
 function hostPdf(last, mframe, mr) {

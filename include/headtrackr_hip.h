@@ -73,6 +73,8 @@ typedef struct ht_config {
                              *   cs_flags=0|1         enqueue-only track calls of the cluster path are completed by marks in the pinned slot (1) or an event
                              *   cs_sync_ring=0|1     a synchronous track call takes the enqueue-only route and collects at once (1) or copies back + synchronises (0)
                              *   cs_pairs_force=1     ht_camshift_*_pairs calls whose pairs are (first + i, i) run the pair kernels too instead of the batch schedules
+                             *   cs_pairs_cluster=1   ht_camshift_track_pairs on a few pairs of large frames (the cluster rule of track_batch with n = pairs, and
+                             *                        cs_cluster set) runs G workgroups per pair; ht_camshift_init_pairs splits tall rects of < 64 pairs by rows (0)
                              *   fp_sparse=0|1        tile kernel: sparse stages one lane per (window, feature) pair when <= 256 pairs are left (1)
                              *   graph_max_frames=N   batches up to N frames replay a captured hipGraph (256; 0 = never)
                              *   split=S, deep_bias=B, deep_v=2|4, deep_grid=N                    tile kernel -> deep kernel hand-off (grid kept >= 16 wavefronts)
@@ -319,7 +321,10 @@ ht_status ht_camshift_init_pairs(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n
  * together, four in total, oldest first) and ht_camshift_track_collect(ctx, n, out) fetches them in pair order.  The results are the
  * bits of ht_camshift_track_batch's few-stream schedule (one mean-shift workgroup per stream).  Pairs (first + i, i), i = 0 .. n - 1, ARE
  * ht_camshift_track_batch(first, n) and take its schedules (option cs_pairs_force=1 sends them through the pair kernels).  Afterwards
- * ht_camshift_debug_hist(stream, .., current) returns the histogram of the frame the stream was paired with. */
+ * ht_camshift_debug_hist(stream, .., current) returns the histogram of the frame the stream was paired with.
+ * Option cs_pairs_cluster=1: a call of <= 64 pairs on frames of >= cs_cluster_min_px pixels runs a cluster of workgroups per pair, with
+ * the bits of ht_camshift_track_batch's cluster schedule; a cluster that was not co-resident ends this call, or the collect of its slot,
+ * with HT_ERR_STATE (the paired streams' state is then undefined: re-initialise them), as ht_camshift_track_batch does. */
 ht_status ht_camshift_track_pairs(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, int32_t calc_angles, ht_cs_trackobj *out);
 /* ncalls successive track() calls (camshift.js:213-220 called once per video frame, main.js:168-180) for streams
  * [first, first+n) in ONE host call: call k uses the n device-resident frames at dev_frames[k] (frame_stride bytes apart;
