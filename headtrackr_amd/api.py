@@ -357,6 +357,30 @@ class Context:
             r[i] = (x, y, w, h)
         self._check(self._lib.ht_camshift_init_pairs(self._h, p.ctypes.data, len(p), r.ctypes.data))
 
+    def camshift_init_best(self, pairs, min_confidence: float = -10.0, fallback=None):
+        """The detect -> track hand-off on the device (facetrackr.js:97-107): stream pairs[i][0] is initialised on BOUND frame pairs[i][1]
+        from that frame's best-face record of the device-grouped batch (detect_best_enqueue: in flight, or collected) when the record has
+        neighbors > 0 and confidence > min_confidence, with the floored rect; otherwise with fallback[i] = (x, y, w, h) when fallback is
+        given, otherwise the stream keeps every byte.  A record that is not final on the device yet (a frame over the grouping cap before
+        the collect) defers the pair.  Enqueue only: no record crosses to the host; camshift_init_best_result tells what was decided."""
+        p = self._pairs(pairs)
+        fb = None
+        if fallback is not None:
+            if len(fallback) != len(p):
+                raise ValueError("camshift_init_best: one fallback rect per pair")
+            fb = np.zeros(len(p), dtype=native.CS_RECT_DTYPE)
+            for i, (x, y, w, h) in enumerate(fallback):
+                fb[i] = (x, y, w, h)
+        self._check(self._lib.ht_camshift_init_best(self._h, p.ctypes.data, len(p), float(min_confidence), fb.ctypes.data if fb is not None else None))
+
+    def camshift_init_best_result(self, n: int):
+        """(codes int32 [n], rects CS_RECT_DTYPE [n]) of the LAST camshift_init_best (same n): waits for that call only.  Codes are
+        native.HT_CSB_UNTOUCHED / _FACE / _FALLBACK / _DEFERRED; the rect is zeros for untouched and deferred pairs."""
+        codes = np.zeros(max(n, 0), dtype=np.int32)
+        rects = np.zeros(max(n, 0), dtype=native.CS_RECT_DTYPE)
+        self._check(self._lib.ht_camshift_init_best_result(self._h, n, codes.ctypes.data, rects.ctypes.data))
+        return codes, rects
+
     def camshift_track_pairs(self, pairs, calc_angles: bool = True, fetch: bool = True):
         """One track() of stream pairs[i][0] on bound frame pairs[i][1]; track objects in pair order.  The full-frame histogram is computed
         once per distinct frame.  fetch=False: enqueue only, collected with camshift_track_collect(len(pairs))."""

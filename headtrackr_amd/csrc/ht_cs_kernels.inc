@@ -17,6 +17,8 @@
 //   CS_HIST_FRAMES_PARAM     the histogram kernel's parameter between chunk_px and hist: empty, or a frame list with its comma
 //   CS_HIST_FRAME(y)         the bound frame of grid row y.  A macro, not a function: y is the UNSIGNED blockIdx.y, and an int
 //                            in between costs the batch kernel a sign extension
+//   CS_INIT_SKIP(s)          optional: a statement at the top of the two init kernels — a workgroup-uniform early return for workgroup s
+//                            (ht_cs_pairs.hip: the pair was resolved to "leave the stream alone").  Empty unless the unit defines it
 //   CS_KERNELS_PART          optional: 1 = only the init kernel, 2 = only the histogram and mean-shift kernels, 3 = only the row-split init
 //                            kernel, 4 = only the LUT and cluster mean-shift kernels.  A code object's .text is laid out in definition
 //                            order: ht_camshift.hip includes parts 1, 3, 2, defines k_cs_track_fused, then includes part 4 — the order
@@ -26,6 +28,10 @@
 // __device__ __forceinline__ functions called from thin kernels change it (the extra inlining level reorders the optimiser's passes:
 // LABLOG.md).  Included as text, the batch kernels are the recorded instructions.
 
+#ifndef CS_INIT_SKIP
+#define CS_INIT_SKIP(s_)
+#endif
+
 #if !defined(CS_KERNELS_PART) || CS_KERNELS_PART == 1
 
 // initTracker: one 1024-thread workgroup per stream; rows of the rect by wavefront, columns by lane (no per-pixel division),
@@ -33,6 +39,7 @@
 __global__ __launch_bounds__(INIT_NT) void CS_K(init)(const uint8_t *__restrict__ frames, size_t frame_stride, int W, int H, CS_INIT_PARAMS) {
     __shared__ uint32_t h[4096];
     const int s = blockIdx.x;
+    CS_INIT_SKIP(s)
     for (int i = threadIdx.x; i < 4096; i += INIT_NT) h[i] = 0;
     __syncthreads();
     const ht_cs_rect r = CS_INIT_RECT(s);
@@ -184,6 +191,7 @@ __global__ __launch_bounds__(CS_NT) void CS_K(meanshift)(const uint8_t *__restri
 __global__ __launch_bounds__(256) void CS_K(init_rows)(const uint8_t *__restrict__ frames, size_t frame_stride, int W, int H, CS_INIT_PARAMS) {
     __shared__ uint32_t h[4096];
     const int s = blockIdx.y, g = blockIdx.x, G = gridDim.x;
+    CS_INIT_SKIP(s)
     for (int i = threadIdx.x; i < 4096; i += 256) h[i] = 0;
     __syncthreads();
     const ht_cs_rect r = CS_INIT_RECT(s);

@@ -27,12 +27,15 @@
 #include <cstring>
 #include <vector>
 
+#define HT_CSB_FN __host__ __device__ inline  // k_csb_resolve (ht_cs_best.hip, behind this file) calls the header's functions on the device
+#include "ht_cs_best_plan.h"                 // the flag word of CspEntry.pad
+
 namespace {
 
 struct CspEntry {
     int32_t stream, frame;  // the pair
     int32_t slot;           // index of `frame` among the call's distinct frames = its chunk histograms in the scratch
-    int32_t pad;
+    int32_t pad;            // flag word (ht_cs_best_plan.h): 0 for every call but ht_camshift_init_best
     ht_cs_rect rect;        // k_csp_init only
 };
 static_assert(sizeof(CspEntry) == 32, "CspEntry");
@@ -44,12 +47,14 @@ __device__ __forceinline__ int cs_frame_of(const CspEntry *e, int s) { return e[
 __device__ __forceinline__ int cs_slot_of(const CspEntry *e, int s) { return e[s].slot; }
 #define CS_INIT_PARAMS CsLookup lk, HtCsState *__restrict__ states
 #define CS_INIT_RECT(s_) lk[s_].rect
+#define CS_INIT_SKIP(s_) if (lk[s_].pad & HT_CSB_F_SKIP) return;  // ht_camshift_init_best resolved the pair to "leave the stream alone"
 #define CS_HIST_FRAMES_PARAM const int32_t *__restrict__ frame_list,  // the call's distinct frames, one per grid row
 #define CS_HIST_FRAME(y_) frame_list[y_]
 #include "ht_cs_kernels.inc"
 
 // the models of the call's pairs = 0, in front of k_csp_init_rows: workgroup s clears the 16 KB of pair s's stream, 16 bytes per thread
 __global__ __launch_bounds__(1024) void k_csp_zero_models(CsLookup lk, HtCsState *__restrict__ states) {
+    CS_INIT_SKIP(blockIdx.x)
     reinterpret_cast<uint4 *>(states[cs_stream_of(lk, blockIdx.x)].model)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
 }
 static_assert(sizeof(HtCsState::model) == 1024 * sizeof(uint4), "k_csp_zero_models: one uint4 per thread");
@@ -271,3 +276,7 @@ void ht_cs_pairs_free(ht_ctx *c) {  // ht_destroy (the stream has been synchroni
     for (auto &h : c->h_csp_tab) h = nullptr;
     for (auto &e : c->ev_csp_tab) e = nullptr;
 }
+
+// The record-driven initTracker (ht_camshift_init_best, k_csb_resolve) is compiled right behind this file, whose plan, table upload and
+// init kernels it uses; ht_group.hip, whose records it reads, comes in front of both in ht_backproject.hip.
+#include "ht_cs_best.hip"

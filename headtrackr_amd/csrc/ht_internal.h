@@ -353,6 +353,14 @@ struct ht_ctx {
     std::vector<int32_t> cs_pair_slot;  // after a pair call: histogram slot of every stream it paired (-1: not part of it), for ht_camshift_debug_hist
     int cs_pair_chunks = 0;
 
+    // ht_camshift_init_best (ht_cs_best.hip): what its resolve kernel decided — [pairs codes][pairs rects of 4 int32] on the device, copied
+    // to the pinned twin by the call itself; the event behind the call's kernels is what ht_camshift_init_best_result waits for
+    int32_t *d_csb_res = nullptr, *h_csb_res = nullptr;
+    size_t csb_cap = 0;                // pairs both hold
+    hipEvent_t ev_csb = nullptr;
+    int csb_n = 0;                     // pairs of the last call (0: none)
+    const void *csb_states = nullptr;  // d_cs at that call: a later ht_camshift_reserve that reallocated the trackers ends the result's life
+
     // ingest (ht_ingest.hip): device staging of ht_draw_frames' host-resident source frames, grown on demand
     uint8_t *d_ingest_src = nullptr;
     size_t ingest_src_cap = 0;
@@ -456,6 +464,7 @@ ht_status ht_cs_read_back(ht_ctx *ctx, const char *fn, ht_cs_trackobj *out, cons
 void ht_camshift_free(ht_ctx *ctx);                         // ht_camshift.hip: tracker state, scratch, result ring, the cluster gate's entry (ht_destroy)
 void ht_backproject_free(ht_ctx *ctx);                      // ht_backproject.hip: its scratch (ht_destroy)
 void ht_cs_pairs_free(ht_ctx *ctx);                         // ht_cs_pairs.hip: pair table, staging and histogram scratch (ht_destroy)
+void ht_cs_best_free(ht_ctx *ctx);                          // ht_cs_best.hip: the result buffers of ht_camshift_init_best (ht_destroy)
 void ht_ingest_free(ht_ctx *ctx);                           // ht_ingest.hip: the host form's source staging (ht_destroy)
 void ht_group_free(ht_ctx *ctx);                            // ht_group.hip: the device grouping's buffers (ht_destroy)
 ht_status ht_detect_mark_collected(ht_ctx *ctx, bool wb_snap);  // ht_context.hip: the state every collect call leaves behind

@@ -39,6 +39,9 @@
 //   camshiftTrackCollect(ctx, n) -> Float64Array(9n)
 //   camshiftInitPairs(ctx, Int32Array pairs[2n], Int32Array rects[4n])   pairs = stream0, frame0, stream1, frame1, ... (ht_cs_pair)
 //   camshiftTrackPairs(ctx, Int32Array pairs[2n], calcAngles, fetch = true) -> Float64Array(9n) | undefined
+//   camshiftInitBest(ctx, Int32Array pairs[2n], minConfidence, Int32Array fallback[4n] | null = null)   ht_camshift_init_best: initTracker from the
+//        device's best-face records of the device-grouped batch, enqueue only
+//   camshiftInitBestResult(ctx, n) -> {codes: Int32Array(n), rects: Int32Array(4n)}   ht_camshift_init_best_result: what the last such call decided
 //   camshiftTrackSequence(ctx, first, n, calcAngles, dev, Float64Array byteOffsets, frameStride, outAll, fetch) -> Float64Array | undefined
 //   camshiftSequenceCollect(ctx, n, ncalls, outAll) -> Float64Array
 //   camshiftBackProject(ctx, n, first, kind) -> Uint8Array(4 n w h) (BP_RGBA8) | Float64Array(n w h) (BP_F64): back-projection of the bound frames
@@ -713,6 +716,52 @@ napi_value CamshiftInitPairs(napi_env env, napi_callback_info info) {
     return nullptr;
 }
 
+napi_value CamshiftInitBest(napi_env env, napi_callback_info info) {
+    Args a(env, info, 4);
+    Locked L;
+    const ht_cs_pair *pairs = nullptr;
+    int32_t n = 0;
+    double min_conf = 0;
+    View fb;
+    const ht_cs_rect *fallback = nullptr;
+    const char *usage = "camshiftInitBest(ctx, Int32Array pairs[2n], minConfidence, Int32Array fallback[4n] | null)";
+    if (!a.ctx(3, &L)) return nullptr;
+    if (!get_pairs(env, a.argv[1], &pairs, &n) || napi_get_value_double(env, a.argv[2], &min_conf) != napi_ok) return type_error(env, usage);
+    napi_valuetype vt = napi_undefined;
+    if (a.argc > 3 && napi_typeof(env, a.argv[3], &vt) != napi_ok) return type_error(env, usage);
+    if (vt != napi_undefined && vt != napi_null) {
+        if (!a.i32s(3, (size_t)n * 4, &fb)) return type_error(env, usage);
+        fallback = fb.as<ht_cs_rect>();
+    }
+    ht_status st = ht_camshift_init_best(L.ctx, pairs, n, min_conf, fallback);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_init_best");
+    return nullptr;
+}
+
+napi_value CamshiftInitBestResult(napi_env env, napi_callback_info info) {
+    Args a(env, info, 2);
+    Locked L;
+    int32_t n = 0;
+    if (!a.ctx(2, &L)) return nullptr;
+    if (!a.i32(1, &n) || n <= 0 || n > (1 << 24)) return type_error(env, "camshiftInitBestResult(ctx, n)");
+    std::vector<int32_t> codes((size_t)n);
+    std::vector<ht_cs_rect> rects((size_t)n);
+    ht_status st = ht_camshift_init_best_result(L.ctx, n, codes.data(), rects.data());
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_init_best_result");
+    napi_value obj, ab, ta;
+    void *p = nullptr;
+    NAPI_OK(napi_create_object(env, &obj));
+    NAPI_OK(napi_create_arraybuffer(env, (size_t)n * 4, &p, &ab));
+    memcpy(p, codes.data(), (size_t)n * 4);
+    NAPI_OK(napi_create_typedarray(env, napi_int32_array, (size_t)n, ab, 0, &ta));
+    NAPI_OK(napi_set_named_property(env, obj, "codes", ta));
+    NAPI_OK(napi_create_arraybuffer(env, (size_t)n * 16, &p, &ab));
+    memcpy(p, rects.data(), (size_t)n * 16);
+    NAPI_OK(napi_create_typedarray(env, napi_int32_array, (size_t)n * 4, ab, 0, &ta));
+    NAPI_OK(napi_set_named_property(env, obj, "rects", ta));
+    return obj;
+}
+
 napi_value CamshiftTrackPairs(napi_env env, napi_callback_info info) {
     Args a(env, info, 4);
     Locked L;
@@ -1273,6 +1322,7 @@ napi_value Init(napi_env env, napi_value exports) {
                {"detectWhitebalance", DetectWhitebalance}, {"whitebalanceBound", WhitebalanceBound},
                {"camshiftInitBound", CamshiftInitBound}, {"camshiftTrackBound", CamshiftTrackBound}, {"camshiftTrackCollect", CamshiftTrackCollect},
                {"camshiftInitPairs", CamshiftInitPairs}, {"camshiftTrackPairs", CamshiftTrackPairs},
+               {"camshiftInitBest", CamshiftInitBest}, {"camshiftInitBestResult", CamshiftInitBestResult},
                {"camshiftTrackSequence", CamshiftTrackSequence}, {"camshiftSequenceCollect", CamshiftSequenceCollect},
                {"camshiftBackProject", CamshiftBackProject}, {"camshiftBackProjectDevice", CamshiftBackProjectDevice},
                {"camshiftBackProjectPairs", CamshiftBackProjectPairs}, {"camshiftBackProjectPairsDevice", CamshiftBackProjectPairsDevice},
@@ -1289,7 +1339,8 @@ napi_value Init(napi_env env, napi_value exports) {
         const char *name;
         int32_t value;
     } consts[] = {{"abiVersion", ht_abi_version()},   {"INPUT_GRAY_IN_R", HT_INPUT_GRAY_IN_R}, {"INPUT_RGBA", HT_INPUT_RGBA}, {"DETECT_WHITEBALANCE", HT_DETECT_WHITEBALANCE},
-                  {"SCAN_STATS", HT_SCAN_STATS},      {"BP_RGBA8", HT_BP_RGBA8},               {"BP_F64", HT_BP_F64}};
+                  {"SCAN_STATS", HT_SCAN_STATS},      {"BP_RGBA8", HT_BP_RGBA8},               {"BP_F64", HT_BP_F64},
+                  {"CSB_UNTOUCHED", HT_CSB_UNTOUCHED}, {"CSB_FACE", HT_CSB_FACE},              {"CSB_FALLBACK", HT_CSB_FALLBACK}, {"CSB_DEFERRED", HT_CSB_DEFERRED}};
     for (auto &c : consts) {
         napi_value v;
         napi_create_int32(env, c.value, &v);

@@ -379,7 +379,7 @@ headtrackr.ccv.detect_objects_batch = function (frames, n, w, h, cascade, interv
 };
 
 /* ---- device-resident batches: the pipelined path -------------------------------------------------------------------------
- * new ccv.DeviceBatch(w, h, n, {cascade, interval, device, depth, sets, trackers, grouping}):
+ * new ccv.DeviceBatch(w, h, n, {cascade, interval, device, depth, sets, trackers, grouping, handoff}):
  *   `sets` frame sets of n RGBA frames each live in ONE device buffer (HBM); `depth` native contexts (own HIP streams, own pyramid
  *   arenas) take detect batches in turn so that `depth` batches are in flight while the host groups the previous one
  *   (ht_detect_enqueue + ht_detect_collect_best_requeue: the C2 / C4 loop of bench.py, from JavaScript).
@@ -411,6 +411,13 @@ headtrackr.ccv.detect_objects_batch = function (frames, n, w, h, cascade, interv
    opts.grouping = 'device': detectBest, detect, detectStepFinish and whitebalance take the device route — grouping and best face run
    behind the scan on the GPU (ht_detect_best_enqueue / _collect), the host receives one record per frame; 'host' (default) keeps the
    host route.  The results are the same bytes.
+   opts.handoff = 'device' (needs grouping: 'device'): the step from a detect step's best faces to camshift.initTracker (facetrackr.js:97-107:
+   confidence > -10, floor the rect) runs on the GPU too (ht_camshift_init_best).  detectStepEnqueue(set, min_neighbors, sel) then also
+   enqueues the trackers' initialisation from the device's records — every feed with the centre-half fallback, or the feeds of sel.feeds
+   without one — so that track steps may be enqueued at once, without waiting for the best faces; detectStepFinish(min_neighbors, sel)
+   collects the best faces whenever the host wants them and returns what the host hand-off returns.  ONE difference: the trackers are
+   re-initialised at the ENQUEUE point in stream order, not at the finish — a track step enqueued between the two already follows the new
+   face.  'host' (default): detectStepFinish initialises them, as before.
      destroy() */
 headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
   opts = opts || {};
@@ -428,6 +435,14 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
   const onDevice = grouping === 'device';
   if (onDevice && (typeof A.detectBestEnqueue !== 'function' || typeof A.collectBestDevice !== 'function' || typeof A.detectGrouped !== 'function'))
     throw new Error("DeviceBatch: this headtrackr_hip.node has no detectBestEnqueue / collectBestDevice / detectGrouped (rebuild it) — needed for grouping: 'device'");
+  /* opts.handoff: who decides, from a detect step's best faces, which trackers are initialised with which rect — 'host' (default:
+   * detectStepFinish, after it has collected them) or 'device' (ht_camshift_init_best behind the grouping, enqueued by detectStepEnqueue) */
+  const handoff = opts.handoff === undefined ? 'host' : opts.handoff;
+  if (handoff !== 'host' && handoff !== 'device') throw new RangeError("DeviceBatch: opts.handoff is 'host' or 'device'");
+  const handoffOnDevice = handoff === 'device';
+  if (handoffOnDevice && !onDevice) throw new RangeError("DeviceBatch: handoff: 'device' needs grouping: 'device'");
+  if (handoffOnDevice && (typeof A.camshiftInitBest !== 'function' || typeof A.camshiftInitBestResult !== 'function'))
+    throw new Error("DeviceBatch: this headtrackr_hip.node has no camshiftInitBest / camshiftInitBestResult (rebuild it) — needed for handoff: 'device'");
   /* the two halves of a batch on either route; the device route's requeue re-issues its grouping inside the library */
   const enqueueBest = function (c, flags, min_neighbors) { A.detectEnqueue(c, flags); if (onDevice) A.detectBestEnqueue(c, min_neighbors, 0); };
   const collectBest = function (c, min_neighbors, requeue) { return onDevice ? A.collectBestDevice(c, requeue) : A.collectBest(c, min_neighbors, requeue); };
@@ -449,7 +464,7 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
   let bound = -1, trackers = false;
   const pendingTrack = []; /* streams of the outstanding enqueue-only track steps, oldest first (pair steps need not have n) */
   const bind = function (set) { if (bound !== set) { ctxs.forEach(function (c) { A.bindDevice(c, dev, set * setBytes, n, fbytes); }); bound = set; } };
-  this.width = w; this.height = h; this.frames = n; this.depth = depth; this.grouping = grouping; this.pairSchedule = pairSchedule;
+  this.width = w; this.height = h; this.frames = n; this.depth = depth; this.grouping = grouping; this.handoff = handoff; this.pairSchedule = pairSchedule;
   this.upload = function (frames, set) {
     if (frames.length < setBytes) throw new RangeError('DeviceBatch.upload: need n*w*h*4 bytes');
     A.deviceUpload(ctxs[0], dev, (set || 0) * setBytes, frames.subarray(0, setBytes));
@@ -522,19 +537,81 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
    *                                  waits for the best faces — the GPU does not idle while the host drains its pipeline */
   /*                                  (grouping 'device': detectStepEnqueue(set, min_neighbors) also enqueues the grouping, so that it runs
    *                                  behind the scan at once; detectStepFinish enqueues it itself when its min_neighbors differs) */
+  /*                                  (handoff 'device': detectStepEnqueue(set, min_neighbors, sel) also enqueues initTracker from the device's
+   *                                  best-face records — the trackers change HERE in stream order, and track steps may follow at once;
+   *                                  detectStepFinish must be given the same min_neighbors and sel) */
   let stepGrouped = null; /* min_neighbors of the device grouping enqueued behind the step's detect, null: none yet */
-  this.detectStepEnqueue = function (set, min_neighbors) {
+  let stepHandoff = null; /* handoff 'device': {mn, feeds | null, pairs, fallback | null} of the initialisation the enqueue issued */
+  const stepFeeds = function (what, sel) {
+    if (!(sel && sel.feeds)) return null;
+    const feeds = [];
+    for (let i = 0; i < sel.feeds.length; i++) {
+      const f = sel.feeds[i];
+      if (!(f >= 0 && f < n)) throw new RangeError('DeviceBatch.' + what + ': feed ' + f + ' is not one of the ' + n + ' feeds');
+      feeds.push(f);
+    }
+    return feeds;
+  };
+  this.detectStepEnqueue = function (set, min_neighbors, sel) {
+    const feeds = handoffOnDevice ? stepFeeds('detectStepEnqueue', sel) : null; /* every check in front of the first enqueue */
     bind0(set === undefined ? 0 : set);
     A.detectEnqueue(ctxs[0], A.INPUT_RGBA);
-    stepGrouped = null;
+    stepGrouped = null; stepHandoff = null;
     if (onDevice) { stepGrouped = min_neighbors === undefined ? 1 : min_neighbors; A.detectBestEnqueue(ctxs[0], stepGrouped, 0); }
+    if (handoffOnDevice) {
+      const list = feeds || Array.from({ length: n }, function (_v, f) { return f; });
+      const pairs = new Int32Array(2 * list.length), fallback = feeds ? null : new Int32Array(4 * n);
+      list.forEach(function (f, i) { pairs[2 * i] = f; pairs[2 * i + 1] = f; }); /* feed f's tracker is stream f, its frame is frame f of the batch */
+      if (fallback) for (let f = 0; f < n; f++) fallback.set([w >> 2, h >> 2, w >> 1, h >> 1], 4 * f); /* no face: the centre half of the frame */
+      if (list.length) { reserve(); A.camshiftInitBest(ctxs[0], pairs, -10, fallback); } /* facetrackr.js:97: confidence > -10 */
+      stepHandoff = { mn: stepGrouped, feeds: feeds, pairs: pairs, fallback: fallback };
+    }
   };
   this.detectStep = function (set, min_neighbors) {
     this.detectStepEnqueue(set, min_neighbors);
     return this.detectStepFinish(min_neighbors);
   };
+  /* handoff 'device': the best faces, and what the enqueue's initialisation decided.  A pair whose record was not final on the device then
+   * (a frame over the grouping cap) was deferred: its record is complete after the collect, and it is initialised now. */
+  const finishOnDevice = function (mn, sel) {
+    const ho = stepHandoff, feeds = stepFeeds('detectStepFinish', sel);
+    if (!ho) throw new Error("DeviceBatch.detectStepFinish: no detectStepEnqueue outstanding (handoff: 'device')");
+    const same = (feeds === null) === (ho.feeds === null) && (feeds === null || (feeds.length === ho.feeds.length && feeds.every(function (f, i) { return f === ho.feeds[i]; })));
+    if (mn !== ho.mn || !same)
+      throw new RangeError("DeviceBatch.detectStepFinish: min_neighbors and sel must be those of detectStepEnqueue (handoff: 'device': the trackers are already initialised)");
+    stepGrouped = null; stepHandoff = null;
+    const r = collectBest(ctxs[0], mn, -1), np = ho.pairs.length >> 1;
+    let codes = new Int32Array(0), rects = new Int32Array(0);
+    if (np) {
+      const res = A.camshiftInitBestResult(ctxs[0], np);
+      codes = res.codes; rects = res.rects;
+      const late = [];
+      for (let i = 0; i < np; i++) if (codes[i] === A.CSB_DEFERRED) late.push(i);
+      if (late.length) {
+        const lp = new Int32Array(2 * late.length), lf = ho.fallback ? new Int32Array(4 * late.length) : null;
+        late.forEach(function (i, k) {
+          lp[2 * k] = ho.pairs[2 * i]; lp[2 * k + 1] = ho.pairs[2 * i + 1];
+          if (lf) lf.set(ho.fallback.subarray(4 * i, 4 * i + 4), 4 * k);
+        });
+        A.camshiftInitBest(ctxs[0], lp, -10, lf);
+        const res2 = A.camshiftInitBestResult(ctxs[0], late.length);
+        late.forEach(function (i, k) { codes[i] = res2.codes[k]; rects.set(res2.rects.subarray(4 * k, 4 * k + 4), 4 * i); });
+      }
+    }
+    if (ho.feeds) {
+      const found = [];
+      for (let i = 0; i < np; i++) if (codes[i] === A.CSB_FACE) found.push(i);
+      const rc = new Int32Array(4 * found.length);
+      found.forEach(function (i, k) { rc.set(rects.subarray(4 * i, 4 * i + 4), 4 * k); });
+      r.initialised = found.map(function (i) { return ho.feeds[i]; }); r.rects = rc;
+      return r;
+    }
+    r.rects = new Int32Array(rects);
+    return r;
+  };
   this.detectStepFinish = function (min_neighbors, sel) {
     const mn = min_neighbors === undefined ? 1 : min_neighbors;
+    if (handoffOnDevice) return finishOnDevice(mn, sel);
     if (onDevice && stepGrouped !== mn) A.detectBestEnqueue(ctxs[0], mn, 0);
     stepGrouped = null;
     const r = collectBest(ctxs[0], mn, -1);

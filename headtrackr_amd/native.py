@@ -27,6 +27,10 @@ HT_DETECT_WHITEBALANCE = 32
 HT_MAX_LEVELS = 96
 HT_BP_RGBA8 = 0  # ht_camshift_backproject kinds: 4 bytes (v, v, v, 255) per pixel ...
 HT_BP_F64 = 1    # ... or one binary64 (the pdf) per pixel
+HT_ERR_INVALID = -1
+HT_ERR_STATE = -6
+# ht_camshift_init_best's decision per pair
+HT_CSB_UNTOUCHED, HT_CSB_FACE, HT_CSB_FALLBACK, HT_CSB_DEFERRED = 0, 1, 2, 3
 
 
 class Config(C.Structure):
@@ -68,7 +72,7 @@ SYMBOLS = [
     "ht_windows_per_frame", "ht_pyramid_bytes_per_frame", "ht_upload_frames", "ht_upload_frames_async", "ht_swap_frames", "ht_bind_frames_device", "ht_frames_bound", "ht_frames_enqueued", "ht_host_alloc", "ht_host_free", "ht_device_alloc", "ht_device_free", "ht_device_upload", "ht_device_download", "ht_draw_frames_device", "ht_draw_frames", "ht_detect_enqueue",
     "ht_detect_collect", "ht_detect_batch", "ht_pyramid_readback", "ht_stage_counts", "ht_grayscale_batch",
     "ht_whitebalance_batch", "ht_detect_whitebalance", "ht_hits_to_rects", "ht_group_rects", "ht_best_faces", "ht_detect_collect_best", "ht_detect_collect_best_requeue", "ht_detect_best_enqueue", "ht_detect_best_collect", "ht_detect_best_collect_requeue", "ht_detect_grouped", "ht_detect_best_records_device", "ht_group_hits", "ht_camshift_reserve", "ht_camshift_init_batch",
-    "ht_camshift_track_batch", "ht_camshift_track_collect", "ht_camshift_init_pairs", "ht_camshift_track_pairs", "ht_camshift_track_sequence", "ht_camshift_sequence_collect", "ht_camshift_stats", "ht_camshift_debug_hist", "ht_camshift_backproject", "ht_camshift_backproject_device", "ht_camshift_backproject_pairs", "ht_camshift_backproject_pairs_device", "ht_allgather_records", "ht_allgather_best_faces", "ht_device_count", "ht_profile", "ht_kernel_times", "ht_stream", "ht_graph_launches", "ht_synchronize",
+    "ht_camshift_track_batch", "ht_camshift_track_collect", "ht_camshift_init_pairs", "ht_camshift_track_pairs", "ht_camshift_init_best", "ht_camshift_init_best_result", "ht_camshift_track_sequence", "ht_camshift_sequence_collect", "ht_camshift_stats", "ht_camshift_debug_hist", "ht_camshift_backproject", "ht_camshift_backproject_device", "ht_camshift_backproject_pairs", "ht_camshift_backproject_pairs_device", "ht_allgather_records", "ht_allgather_best_faces", "ht_device_count", "ht_profile", "ht_kernel_times", "ht_stream", "ht_graph_launches", "ht_synchronize",
 ]
 
 _lib = None
@@ -174,6 +178,10 @@ def lib():
     L.ht_camshift_init_pairs.argtypes = [vp, vp, i32, vp]
     L.ht_camshift_track_pairs.restype = i32
     L.ht_camshift_track_pairs.argtypes = [vp, vp, i32, i32, vp]
+    L.ht_camshift_init_best.restype = i32
+    L.ht_camshift_init_best.argtypes = [vp, vp, i32, C.c_double, vp]
+    L.ht_camshift_init_best_result.restype = i32
+    L.ht_camshift_init_best_result.argtypes = [vp, i32, vp, vp]
     L.ht_detect_whitebalance.restype = i32
     L.ht_detect_whitebalance.argtypes = [vp, vp, i32]
     L.ht_camshift_track_sequence.restype = i32

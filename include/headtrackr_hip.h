@@ -326,6 +326,25 @@ ht_status ht_camshift_init_pairs(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n
  * the bits of ht_camshift_track_batch's cluster schedule; a cluster that was not co-resident ends this call, or the collect of its slot,
  * with HT_ERR_STATE (the paired streams' state is then undefined: re-initialise them), as ht_camshift_track_batch does. */
 ht_status ht_camshift_track_pairs(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, int32_t calc_angles, ht_cs_trackobj *out);
+/* The hand-off from detection to tracking on the device (facetrackr.js:97-107: `confidence > threshold`, floor the rect, initTracker):
+ * pairs[i].frame names a bound frame AND that frame's best-face record of the context's device-grouped batch — the batch
+ * ht_detect_best_enqueue was issued behind, in flight or collected and not yet overwritten (HT_ERR_STATE without one).  Per pair, decided
+ * once on the device: HT_CSB_DEFERRED when the record is not final there (more raw hits than ht_config.hit_capacity, a raw hit out of
+ * range, or a frame over the grouping cap whose batch has not been collected yet: the collect completes it) — the stream keeps every
+ * byte; HT_CSB_FACE when neighbors > 0 and confidence > min_confidence (strict; the reference's threshold is -10): initTracker
+ * (camshift.js:198-211) of pairs[i].stream on bound frame pairs[i].frame with floor(x, y, width, height) of the record (int32, saturated,
+ * NaN -> 0); otherwise HT_CSB_FALLBACK: initTracker with fallback[i] when fallback != NULL; otherwise HT_CSB_UNTOUCHED: model, search
+ * window and track object keep every byte.  Enqueue only: ordered by the ctx stream behind the grouping and in front of whatever is
+ * enqueued next, never copies a record to the host, never waits in the steady state (the first call of a context allocates).  The pair
+ * list obeys the rules of ht_camshift_init_pairs; in addition pairs[i].frame must be below the grouped batch's frame count and
+ * min_confidence must not be NaN (HT_ERR_INVALID).  Every check happens before anything is enqueued; a refused call changes no tracker
+ * state.  The models are the bits ht_camshift_init_pairs produces for the same rects. */
+enum { HT_CSB_UNTOUCHED = 0, HT_CSB_FACE = 1, HT_CSB_FALLBACK = 2, HT_CSB_DEFERRED = 3 };
+ht_status ht_camshift_init_best(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, double min_confidence, const ht_cs_rect *fallback);
+/* What the LAST ht_camshift_init_best of the context decided (same n): waits for that call only (an event behind its kernels) and returns
+ * per pair the code and the rect that was used (zeros for untouched and deferred pairs); either pointer may be NULL.  May be called
+ * repeatedly.  HT_ERR_STATE when there is no such call, when n differs, or after an ht_camshift_reserve that grew the reservation. */
+ht_status ht_camshift_init_best_result(ht_ctx *ctx, int32_t n, int32_t *codes, ht_cs_rect *rects);
 /* ncalls successive track() calls (camshift.js:213-220 called once per video frame, main.js:168-180) for streams
  * [first, first+n) in ONE host call: call k uses the n device-resident frames at dev_frames[k] (frame_stride bytes apart;
  * same geometry as ht_set_geometry).  A stream's calls are sequentially dependent (its search window), so they are
