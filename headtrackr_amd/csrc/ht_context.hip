@@ -1,5 +1,5 @@
-// ht_context.hip — context lifetime, cascade tables, pyramid geometry, frame binding, result collection and the
-// host-side post-processing (rect conversion + grouping) of libheadtrackr_hip.so.
+// ht_context.hip — context lifetime, the cascade's and the geometry's plans on the device (ht_cascade_plan.h, ht_geometry_plan.h),
+// frame binding, result collection and the host-side post-processing (rect conversion + grouping) of libheadtrackr_hip.so.
 //
 // Reference behaviour restated here (paths under /root/reference/src/):
 //   geometry            ccv.js:110-147      (scale, scale_upto, level sizes, variant planes)
@@ -16,6 +16,7 @@
 #include "ht_internal.h"
 #include "ht_hostpost.h"
 #include "ht_geometry_plan.h"
+#include "ht_cascade_plan.h"
 
 static thread_local std::string g_create_err;
 
@@ -99,7 +100,7 @@ static void sweep_orphans(ht_ctx *c) {
     if (!release.empty() && c) (void)hipSetDevice(c->device);
 }
 
-static inline HtPostCfg post_cfg(const ht_ctx *c) { return HtPostCfg{c->interval, c->cw, c->ch}; }
+static inline HtPostCfg post_cfg(const ht_ctx *c) { return HtPostCfg{c->interval, c->cascade.cw, c->cascade.ch}; }
 
 // workers for a batch of `frames` frames holding `hits` raw hits: option host_threads, or (auto) up to 7 when the batch is worth it
 static int ht_host_workers(const ht_ctx *c, int frames, uint32_t hits) {
@@ -153,137 +154,6 @@ HtProfScope::~HtProfScope() {
 extern "C" int32_t ht_abi_version(void) { return HT_ABI_VERSION; }
 
 extern "C" const char *ht_last_error(const ht_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
-
-// ---------------------------------------------------------------------------------------------------------
-// cascade
-
-static bool parse_blob(const uint8_t *blob, size_t len, ht_ctx *c, std::string &why) {
-    if (!blob || len < 32 || std::memcmp(blob, "HTCB", 4) != 0) {
-        why = "cascade blob: bad magic";
-        return false;
-    }
-    uint32_t h[8];
-    std::memcpy(h, blob, 32);
-    if (h[1] != 1 || h[6] != HT_MAXPTS) {
-        why = "cascade blob: unsupported version";
-        return false;
-    }
-    c->nstages = h[2];
-    c->cw = h[3];
-    c->ch = h[4];
-    c->nfeat = h[5];
-    if (c->nstages == 0 || c->nstages > 63 || c->cw < 4 || c->ch < 4 || c->cw > 64 || c->ch > 64) {
-        why = "cascade blob: unsupported stage count or window size";
-        return false;
-    }
-    if (len != 32 + (size_t)c->nstages * sizeof(HtBlobStage) + (size_t)c->nfeat * sizeof(HtBlobFeature)) {
-        why = "cascade blob: truncated";
-        return false;
-    }
-    c->h_stages.resize(c->nstages);
-    c->h_feats.resize(c->nfeat);
-    std::memcpy(c->h_stages.data(), blob + 32, c->nstages * sizeof(HtBlobStage));
-    std::memcpy(c->h_feats.data(), blob + 32 + c->nstages * sizeof(HtBlobStage), c->nfeat * sizeof(HtBlobFeature));
-    uint32_t first = 0;
-    for (uint32_t j = 0; j < c->nstages; j++) {
-        if (c->h_stages[j].first != first || first + c->h_stages[j].count > c->nfeat) {
-            why = "cascade blob: inconsistent stage table";
-            return false;
-        }
-        first += c->h_stages[j].count;
-    }
-    for (uint32_t k = 0; k < c->nfeat; k++) {
-        const HtBlobFeature &f = c->h_feats[k];
-        // the reference reads slot 0 of both polarities unconditionally (ccv.js:191-192)
-        if (f.size == 0 || f.size > HT_MAXPTS || f.pz[0] < 0 || f.nz[0] < 0) {
-            why = "cascade blob: feature without a valid first point";
-            return false;
-        }
-        for (int q = 0; q < f.size; q++) {
-            const int lim[3] = {(int)c->cw, (int)c->cw / 2, (int)c->cw / 4};
-            const int limy[3] = {(int)c->ch, (int)c->ch / 2, (int)c->ch / 4};
-            if (f.pz[q] > 2 || f.nz[q] > 2 ||
-                (f.pz[q] >= 0 && (f.px[q] < 0 || f.py[q] < 0 || f.px[q] >= lim[f.pz[q]] || f.py[q] >= limy[f.pz[q]])) ||
-                (f.nz[q] >= 0 && (f.nx[q] < 0 || f.ny[q] < 0 || f.nx[q] >= lim[f.nz[q]] || f.ny[q] >= limy[f.nz[q]]))) {
-                why = "cascade blob: feature point outside the window";
-                return false;
-            }
-        }
-    }
-    return true;
-}
-
-// alpha * 1e8 is an exact integer iff the decimal literal had <= 8 fractional digits: then (double)k / 1e8 == alpha
-static bool as_decimal8(double v, int64_t *out) {
-    double s = v * 1e8;
-    if (!(std::fabs(s) < 9.0e15)) return false;
-    int64_t k = (int64_t)std::llround(s);
-    if ((double)k / 1e8 != v) return false;
-    *out = k;
-    return true;
-}
-
-static ht_status upload_cascade(ht_ctx *c) {
-    std::vector<HtDeepFeature> deep(c->nfeat);
-    std::vector<HtDevStage> st(c->nstages);
-    c->decimal_alphas = true;
-    for (uint32_t k = 0; k < c->nfeat; k++) {
-        const HtBlobFeature &f = c->h_feats[k];
-        HtDeepFeature &d = deep[k];
-        int np = 0, nn = 0;
-        for (int q = 0; q < f.size; q++) {
-            if (f.pz[q] >= 0) {
-                d.px[np] = f.px[q];
-                d.py[np] = f.py[q];
-                d.pz[np] = f.pz[q];
-                np++;
-            }
-            if (f.nz[q] >= 0) {
-                d.nx[nn] = f.nx[q];
-                d.ny[nn] = f.ny[q];
-                d.nz[nn] = f.nz[q];
-                nn++;
-            }
-        }
-        for (int q = np; q < HT_MAXPTS; q++) d.px[q] = d.px[0], d.py[q] = d.py[0], d.pz[q] = d.pz[0];
-        for (int q = nn; q < HT_MAXPTS; q++) d.nx[q] = d.nx[0], d.ny[q] = d.ny[0], d.nz[q] = d.nz[0];
-        d.a0 = f.alpha[0];
-        d.a1 = f.alpha[1];
-        d.a0i = d.a1i = 0;
-        if (!as_decimal8(d.a0, &d.a0i) || !as_decimal8(d.a1, &d.a1i)) c->decimal_alphas = false;
-    }
-    for (uint32_t j = 0; j < c->nstages; j++) {
-        st[j].first = c->h_stages[j].first;
-        st[j].count = c->h_stages[j].count;
-        st[j].threshold = c->h_stages[j].threshold;
-        st[j].thri = 0;
-        st[j].pad = 0;
-        if (!as_decimal8(st[j].threshold, &st[j].thri)) c->decimal_alphas = false;
-        uint32_t mp = 1;
-        for (uint32_t k = 0; k < st[j].count; k++) {
-            const HtBlobFeature &f = c->h_feats[st[j].first + k];
-            uint32_t np = 0, nn = 0;
-            for (int q = 0; q < f.size; q++) np += f.pz[q] >= 0, nn += f.nz[q] >= 0;
-            mp = std::max(mp, std::max(np, nn));
-        }
-        st[j].maxpts = mp;
-        // The integer decision "S < thri  <=>  the reference's binary64 sum < threshold" (off an exact tie) needs the
-        // rounding error of the reference's SEQUENTIAL sum to stay below half the 1e-8 grid: |err| <= count * 2^-52 *
-        // sum|alpha|.  True for the trained cascade (alphas O(1): bound ~1e-11); a custom cascade with huge alphas takes
-        // the sequential binary64 path everywhere instead of silently diverging from ccv.js:186-222.
-        double sabs = 0.0;
-        for (uint32_t k = 0; k < st[j].count; k++) {
-            const HtBlobFeature &f = c->h_feats[st[j].first + k];
-            sabs += std::max(std::fabs(f.alpha[0]), std::fabs(f.alpha[1]));
-        }
-        if (!((double)st[j].count * 2.220446049250313e-16 * (sabs + std::fabs(st[j].threshold)) < 0.5e-8)) c->decimal_alphas = false;
-    }
-    HT_HIP(c, hipMalloc(&c->d_deep_feats, deep.size() * sizeof(HtDeepFeature)));
-    HT_HIP(c, hipMalloc(&c->d_stages, st.size() * sizeof(HtDevStage)));
-    HT_HIP(c, hipMemcpy(c->d_deep_feats, deep.data(), deep.size() * sizeof(HtDeepFeature), hipMemcpyHostToDevice));
-    HT_HIP(c, hipMemcpy(c->d_stages, st.data(), st.size() * sizeof(HtDevStage), hipMemcpyHostToDevice));
-    return ht_scan_tile_tables(c);
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // ht_config.options: "key=value,key=value".  Every key selects among schedules with identical results; the three that do not
@@ -354,6 +224,15 @@ static bool apply_options(ht_ctx *c, const std::string &opts, std::string &why) 
     return true;
 }
 
+// one table of a plan (cascade, geometry) on the device
+template <typename T>
+static ht_status upload_table(ht_ctx *c, T *&dst, const std::vector<T> &src) {
+    if (src.empty()) return HT_OK;
+    HT_HIP(c, hipMalloc(&dst, src.size() * sizeof(T)));
+    HT_HIP(c, hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    return HT_OK;
+}
+
 extern "C" ht_status ht_create(const ht_config *cfg, const void *cascade_blob, size_t cascade_len, ht_ctx **out) {
     // ABI 1 callers pass the struct without its last member (options)
     if (!cfg || !out || (cfg->struct_size != sizeof(ht_config) && cfg->struct_size != offsetof(ht_config, options)))
@@ -377,7 +256,7 @@ extern "C" ht_status ht_create(const ht_config *cfg, const void *cascade_blob, s
     if (cfg->hit_capacity) c->hit_capacity = cfg->hit_capacity;
     c->queue_capacity_cfg = cfg->queue_capacity;
     std::string why;
-    if (!parse_blob((const uint8_t *)cascade_blob, cascade_len, c, why)) {
+    if (!ht_plan_cascade((const uint8_t *)cascade_blob, cascade_len, &c->cascade, &why)) {
         delete c;
         return ht_fail(nullptr, HT_ERR_INVALID, "ht_create: " + why);
     }
@@ -420,12 +299,12 @@ extern "C" ht_status ht_create(const ht_config *cfg, const void *cascade_blob, s
         }
     }
     c->builtin_cascade = ht_scan_is_builtin_cascade((const uint8_t *)cascade_blob, cascade_len) && c->interval >= 1;
-    // stages [0, split) always run in the tile kernel: the generated straight-line stages for the built-in cascade
-    c->split_stage = std::min<uint32_t>(c->builtin_cascade ? 8u : 4u, c->nstages);
-    if (c->opt_split > 0)  // option split: hand-off stage (<= 8 for the generated stage code)
-        c->split_stage = std::min<uint32_t>((uint32_t)c->opt_split, std::min<uint32_t>(c->builtin_cascade ? 8u : c->nstages, c->nstages));
-    if ((st = upload_cascade(c)) != HT_OK) return bail(st);
-    if ((st = ht_scan_pack_deep(c)) != HT_OK) return bail(st);
+    ht_plan_cascade_split(&c->cascade, c->builtin_cascade, c->opt_split);
+    const HtCascadePlan &P = c->cascade;
+    if ((st = upload_table(c, c->d_deep_feats, P.deep)) != HT_OK || (st = upload_table(c, c->d_stages, P.dev_stages)) != HT_OK ||
+        (st = upload_table(c, c->d_tile_feats, P.tile)) != HT_OK || (st = upload_table(c, c->d_fp_feats, P.fp)) != HT_OK ||
+        (st = upload_table(c, c->d_patch_feats, P.patch)) != HT_OK || (st = upload_table(c, c->d_packed_feats, P.packed)) != HT_OK)
+        return bail(st);
     if (hipHostMalloc(reinterpret_cast<void **>(&c->h_pinned), sizeof(HtCounters) + (size_t)HT_PINNED_HITS * sizeof(ht_hit), hipHostMallocDefault) != hipSuccess ||
         hipMalloc(&c->d_stats, sizeof(unsigned long long) * 64 * HT_STAT_SHARDS) != hipSuccess ||
         // counters and hits in ONE allocation, counters first: ht_detect_collect fetches both with a single copy
@@ -533,15 +412,6 @@ extern "C" void ht_destroy(ht_ctx *c) {
 // ---------------------------------------------------------------------------------------------------------
 // geometry, ccv.js:110-147: planned on the host by ht_plan_geometry (ht_geometry_plan.h), uploaded here
 
-// one table of the plan on the device
-template <typename T>
-static ht_status upload_table(ht_ctx *c, T *&dst, const std::vector<T> &src) {
-    if (src.empty()) return HT_OK;
-    HT_HIP(c, hipMalloc(&dst, src.size() * sizeof(T)));
-    HT_HIP(c, hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return HT_OK;
-}
-
 // Builds every table / allocation of one geometry.  On any failure the caller (ht_set_geometry) frees what was built and
 // leaves the context without a geometry, so a retry (e.g. with a smaller max_batch after HT_ERR_NOMEM) starts clean.
 static ht_status set_geometry_impl(ht_ctx *c, int32_t width, int32_t height, int32_t max_batch, const int32_t *level_dims, int n, int upto) {
@@ -552,7 +422,7 @@ static ht_status set_geometry_impl(ht_ctx *c, int32_t width, int32_t height, int
     c->upto = upto;
 
     HtPlanInputs in;
-    in.interval = c->interval, in.next = c->next, in.cw = c->cw, in.ch = c->ch;
+    in.interval = c->interval, in.next = c->next, in.cw = c->cascade.cw, in.ch = c->cascade.ch;
     in.rs_rpt = c->rs_rpt, in.rs_nofast = c->rs_nofast, in.rs_nosort = c->rs_nosort, in.rs_notail = c->rs_notail;
     in.rs_tailcap = c->rs_tailcap, in.rs_tailcap_forced = c->rs_tailcap_forced;
     in.tail_table = c->tail_table, in.tail_table_forced = c->tail_table_forced;
@@ -587,7 +457,7 @@ extern "C" ht_status ht_set_geometry(ht_ctx *c, int32_t width, int32_t height, i
     if (width <= 0 || height <= 0 || width > 16384 || height > 16384 || max_batch <= 0)
         return ht_fail(c, HT_ERR_INVALID, "ht_set_geometry: width/height must be 1..16384 and max_batch > 0");
     HT_HIP(c, hipSetDevice(c->device));
-    const int upto = (int)std::floor(std::log((double)std::min(c->cw, c->ch)) / std::log(ht_scale_of(c->interval)));  // ccv.js:112
+    const int upto = (int)std::floor(std::log((double)std::min(c->cascade.cw, c->cascade.ch)) / std::log(ht_scale_of(c->interval)));  // ccv.js:112
     const int n = upto + c->next * 2;  // ccv.js:113
     if (n > HT_MAX_LEVELS) return ht_fail(c, HT_ERR_INVALID, "ht_set_geometry: too many pyramid levels");
     if (level_dims && nlevels_in != n) return ht_fail(c, HT_ERR_INVALID, "ht_set_geometry: level_dims has the wrong number of levels");
@@ -1074,9 +944,9 @@ extern "C" ht_status ht_pyramid_readback(ht_ctx *c, int32_t frame, int32_t level
 }
 
 extern "C" ht_status ht_stage_counts(ht_ctx *c, uint64_t *counts, int32_t n) {
-    if (!c || !counts || n < (int32_t)c->nstages + 1) return HT_ERR_INVALID;
-    for (uint32_t j = 0; j <= c->nstages; j++) counts[j] = c->h_stage_in[j];
-    for (int32_t j = (int32_t)c->nstages + 1; j < std::min<int32_t>(n, 64); j++) counts[j] = c->h_stage_in[j];  // raw counter row (timeline builds)
+    if (!c || !counts || n < (int32_t)c->cascade.nstages + 1) return HT_ERR_INVALID;
+    for (uint32_t j = 0; j <= c->cascade.nstages; j++) counts[j] = c->h_stage_in[j];
+    for (int32_t j = (int32_t)c->cascade.nstages + 1; j < std::min<int32_t>(n, 64); j++) counts[j] = c->h_stage_in[j];  // raw counter row (timeline builds)
     return HT_OK;
 }
 

@@ -315,7 +315,7 @@ __global__ __launch_bounds__(NT) void k_grp_frames(const ht_hit *__restrict__ hi
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 
-inline HtPostCfg grp_cfg(const ht_ctx *c) { return HtPostCfg{c->interval, c->cw, c->ch}; }
+inline HtPostCfg grp_cfg(const ht_ctx *c) { return HtPostCfg{c->interval, c->cascade.cw, c->cascade.ch}; }
 inline uint32_t *grp_nword(ht_ctx *c) { return reinterpret_cast<uint32_t *>(c->d_grp_konst + HT_MAX_LEVELS); }
 
 // this unit's buffers that grow with the batch, through the library's one grow helper
@@ -380,11 +380,11 @@ ht_status grp_launch(ht_ctx *c, const ht_hit *d_hits, const uint32_t *d_nhits, u
     }
     {
         HtProfScope ps(c, "grp_frames");
-        hipLaunchKernelGGL(k_grp_frames<GRP_WAVE>, dim3(nframes), dim3(GRP_WAVE), 0, c->stream, c->d_grp_hits2, start, count, c->d_grp_konst, c->cw, c->ch, min_neighbors,
+        hipLaunchKernelGGL(k_grp_frames<GRP_WAVE>, dim3(nframes), dim3(GRP_WAVE), 0, c->stream, c->d_grp_hits2, start, count, c->d_grp_konst, c->cascade.cw, c->cascade.ch, min_neighbors,
                            frame_base, 0u, cap == (uint32_t)GRP_WAVE ? 1u : 0u, records, status, ngrouped, c->d_grp_rects);
         HT_HIP(c, hipGetLastError());
         if (cap > (uint32_t)GRP_WAVE) {
-            hipLaunchKernelGGL(k_grp_frames<GRP_CAP>, dim3(nframes), dim3(cap), 0, c->stream, c->d_grp_hits2, start, count, c->d_grp_konst, c->cw, c->ch, min_neighbors,
+            hipLaunchKernelGGL(k_grp_frames<GRP_CAP>, dim3(nframes), dim3(cap), 0, c->stream, c->d_grp_hits2, start, count, c->d_grp_konst, c->cascade.cw, c->cascade.ch, min_neighbors,
                                frame_base, (uint32_t)GRP_WAVE + 1u, 1u, records, status, ngrouped, c->d_grp_rects);
             HT_HIP(c, hipGetLastError());
         }

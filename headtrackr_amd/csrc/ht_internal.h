@@ -10,70 +10,10 @@
 
 #include "headtrackr_hip.h"
 
-#define HT_MAXPTS 8
-
 // ---------------------------------------------------------------------------------------------------------
-// Cascade, host view of the "HTCB" blob (headtrackr_amd/js/cascade_pack.js) == headtrackr.cascade (cascade.js:19)
-struct HtBlobFeature {
-    uint8_t size, pad[7];
-    int8_t px[HT_MAXPTS], py[HT_MAXPTS], pz[HT_MAXPTS];
-    int8_t nx[HT_MAXPTS], ny[HT_MAXPTS], nz[HT_MAXPTS];
-    double alpha[2];
-};
-struct HtBlobStage {
-    uint32_t count, first;
-    double threshold;
-};
-static_assert(sizeof(HtBlobFeature) == 72 && sizeof(HtBlobStage) == 16, "HTCB layout");
-
-// ---------------------------------------------------------------------------------------------------------
-// Device-side cascade tables.
-//
-// Tile kernel: every point of every feature as a byte offset into the workgroup's LDS tile, relative to the
-// window base (see ht_scan.hip "unified-base layout"); read with uniform (scalar) loads, one feature at a time.
-struct alignas(64) HtTileFeature {
-    uint32_t po[HT_MAXPTS / 2];  // positive-point offsets, two u16 per word (low half first); valid ones first, count = np
-    uint32_t no[HT_MAXPTS / 2];  // negative-point offsets, count = nn
-    uint32_t a[4];               // alpha[2k] (lo,hi words), alpha[2k+1] (lo,hi)  (ccv.js:194,219)
-    uint32_t np, nn;
-    uint32_t pad[2];
-};
-static_assert(sizeof(HtTileFeature) == 64, "HtTileFeature");
-
-// Deep kernel: coordinate form, one feature per lane.  Slots >= np / nn repeat slot 0 (min/max are idempotent).
-struct alignas(16) HtDeepFeature {
-    uint8_t px[HT_MAXPTS], py[HT_MAXPTS], pz[HT_MAXPTS];  // each array is read as one 64-bit word on the device
-    uint8_t nx[HT_MAXPTS], ny[HT_MAXPTS], nz[HT_MAXPTS];
-    int64_t a0i, a1i;  // alpha * 1e8 as exact integers (valid when the cascade is "decimal", see ht_context.hip)
-    double a0, a1;
-};
-static_assert(sizeof(HtDeepFeature) == 80, "HtDeepFeature");
-
-// Deep kernel: offsets into the per-wavefront window patch in LDS (24x24 + 12x12 + 6x6 bytes, see ht_scan.hip).
-struct alignas(16) HtPatchFeature {
-    uint16_t poff[HT_MAXPTS];  // slots >= np repeat slot 0
-    uint16_t noff[HT_MAXPTS];
-    int64_t a0i, a1i;          // alpha * 1e8 as exact integers
-    double a0, a1;
-};
-static_assert(sizeof(HtPatchFeature) == 64, "HtPatchFeature");
-
-// Deep kernel, LDS-resident form: 32-byte record, the whole tail of the cascade (stages >= split) is copied into LDS once
-// per workgroup.  Usable when every feature has <= 5 points per polarity and |alpha * 1e8| < 2^31 (decimal cascade).
-struct alignas(16) HtPackedFeature {
-    uint16_t off[10];  // p0..p4, n0..n4 patch offsets (unused slots repeat slot 0 of their polarity)
-    int32_t a0i, a1i;  // alpha * 1e8; the binary64 alpha is recovered exactly as (double)a / 1e8
-    uint32_t pad;
-};
-static_assert(sizeof(HtPackedFeature) == 32, "HtPackedFeature");
-
-struct HtDevStage {
-    uint32_t first, count;
-    uint32_t maxpts;  // max(np, nn) over the stage's features
-    uint32_t pad;
-    double threshold;
-    int64_t thri;  // threshold * 1e8
-};
+// The cascade's records (the "HTCB" blob's rows, the device-side feature and stage tables), the LDS layout constants their offsets address
+// and the plan that holds them live in a header without HIP, shared with the host-only planner (ht_cascade_plan.h).
+#include "ht_cascade_types.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // The plain records of a geometry's plan (levels, resample jobs / tile records, taps, tail generations, scan scales and tile records)
@@ -162,25 +102,18 @@ struct ht_ctx {
 
     // cascade
     int interval = 5, next = 6;
-    uint32_t cw = 24, ch = 24, nstages = 0, nfeat = 0;
-    bool decimal_alphas = false;  // all alphas / thresholds are k * 1e-8 exactly -> integer decisions allowed
-    std::vector<HtBlobStage> h_stages;
-    std::vector<HtBlobFeature> h_feats;
+    HtCascadePlan cascade;  // the host side of the cascade (ht_cascade_types.h), planned by ht_plan_cascade / ht_plan_cascade_split; below: its tables on the device
     HtTileFeature *d_tile_feats = nullptr;
     HtDeepFeature *d_deep_feats = nullptr;
     HtPatchFeature *d_patch_feats = nullptr;
-    HtPackedFeature *d_packed_feats = nullptr;  // features of stages >= split_stage (index 0 = first feature of that stage)
-    // every feature in the packed 32-byte form with TILE offsets (off[] relative to a window's LDS base, a1i = alpha[2k+1] * 1e8): the
-    // tile kernel's feature-parallel sparse phase reads one record per lane (nullptr: cascade not decimal / more than 5 points)
-    HtPackedFeature *d_fp_feats = nullptr;
+    HtPackedFeature *d_packed_feats = nullptr;  // cascade.packed (nullptr: empty)
+    HtPackedFeature *d_fp_feats = nullptr;      // cascade.fp (nullptr: empty)
     bool fp_sparse = true;  // option fp_sparse=0: the sparse stages always run as four feature slices (A/B)
-    uint32_t packed_count = 0, packed_first = 0; // number of packed features / global index of the first one (0 count = unusable)
     bool builtin_cascade = false;  // blob == the cascade ht_cascade_gen.inc was generated from
     uint32_t deep_bias = 1;        // tile kernel hands survivors to the deep kernel when n*bias*ceil(count/64) <= count
                                    // (measured on C2/C4: split 8 + bias 0..1 is the optimum, profiles/r01_sweeps.txt)
     int dbg_stop_stage = -1, dbg_force_exact = 0, dbg_deep_v = 4, deep_grid = 192;  // ht_config.options, parsed once in ht_create
     HtDevStage *d_stages = nullptr;
-    uint32_t split_stage = 4;  // stages [0, split) in the tile kernel, [split, nstages) in the deep kernel
     int opt_split = 0;         // option split (0 = default)
 
     // geometry
@@ -473,8 +406,6 @@ void ht_frames_bind_own(ht_ctx *ctx, int n);                // ht_context.hip: b
 ht_status ht_launch_pyramid(ht_ctx *ctx, uint32_t flags);   // ht_pyramid.hip
 ht_status ht_launch_scan(ht_ctx *ctx, uint32_t flags);      // ht_scan.hip
 ht_status ht_launch_scan_early(ht_ctx *ctx, uint32_t flags); // ht_scan.hip: called by ht_launch_pyramid after generation early_gen
-ht_status ht_scan_tile_tables(ht_ctx *ctx);                 // ht_scan.hip: LDS-offset feature table
-bool ht_scan_is_builtin_cascade(const uint8_t *blob, size_t len);  // ht_scan.hip
-ht_status ht_scan_pack_deep(ht_ctx *ctx);                           // ht_scan.hip: LDS-resident table for stages >= split_stage
+bool ht_scan_is_builtin_cascade(const uint8_t *blob, size_t len);  // ht_scan.hip: an input of ht_plan_cascade_split
 ht_status ht_launch_gray_inplace(ht_ctx *ctx, uint8_t *d_rgba, int n, size_t stride);  // ht_pyramid.hip
 ht_status ht_launch_whitebalance(ht_ctx *ctx, double *d_out, bool zero);                 // ht_pyramid.hip

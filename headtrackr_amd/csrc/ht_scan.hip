@@ -33,7 +33,8 @@
 
 namespace {
 
-// tile geometry (window = 24x24, see ht_scan_tile_tables for the check)
+// tile geometry (window = 24x24: ht_launch_scan sends every other cascade to k_scan_simple); the constants the host planner addresses by
+// stand in ht_cascade_types.h
 constexpr int TXH = HT_SCAN_TXH;        // tile width  in half-window steps X' (ht_plan_types.h: the planner cuts the scales by it)
 constexpr int TYH = HT_SCAN_TYH;        // tile height in half-window steps Y'
 constexpr int NT = 256;                 // threads per workgroup (256: 4 waves/SIMD at <=128 VGPRs; 512: 8 waves/SIMD at <=64)
@@ -46,22 +47,18 @@ constexpr int TILE_WPS = 6;
 // With 160 the step was 16 (mod 32): rows r and r+2 aliased, and compacted survivors — which cluster in 2-D blobs — hit the
 // same banks from every other row (36 % of the kernel's LDS cycles were bank conflicts; tools/sim_scan_lds.py models
 // 61 % -> 44 % overhead over conflict-free).  Multiple of 8: rows are staged as 16-byte loads split into two 8-byte LDS writes.
-constexpr int PITCH0 = 152;
+constexpr int PITCH0 = HT_SCAN_PITCH0;
 static_assert(PITCH0 >= 2 * TXH + 24 && PITCH0 % 8 == 0, "PITCH0");
-constexpr int ROWS0 = 2 * TYH + 22;     // 86
-constexpr int P0_BYTES = PITCH0 * ROWS0;  // 13760
-constexpr int GH = TYH + 11;               // plane-1 / plane-2 half-step grid: 75 x 43 cells of 2 bytes
-constexpr int G_PITCH = 2 * PITCH0;          // 320
-constexpr int P12_BASE = P0_BYTES;
-constexpr int LDS_TILE_BYTES = P0_BYTES + GH * G_PITCH;  // 27520
+constexpr int ROWS0 = HT_SCAN_ROWS0;     // 2 * TYH + 22 = 86
+constexpr int P0_BYTES = PITCH0 * ROWS0;  // 13072
+constexpr int GH = HT_SCAN_GH;             // TYH + 11: plane-1 / plane-2 half-step grid: 75 x 43 cells of 2 bytes
+constexpr int G_PITCH = HT_SCAN_G_PITCH;     // 2 * PITCH0
+constexpr int P12_BASE = HT_SCAN_P12_BASE;
+constexpr int LDS_TILE_BYTES = HT_SCAN_LDS_TILE_BYTES;  // P0_BYTES + GH * G_PITCH
 constexpr int MAXWIN = TXH * TYH;            // 2048 windows per tile
-static_assert(P0_BYTES % 16 == 0, "alignment");
+static_assert(P0_BYTES % 16 == 0 && P12_BASE == P0_BYTES, "alignment");
 
-// unified-base LDS offsets of a feature point (x, y) on plane 0 / 1 / 2, relative to the window base B
-#define HT_O0(x, y) ((y) * PITCH0 + (x))                      // level i:        1 B/px, row pitch P
-#define HT_O1(x, y) (P12_BASE + (y) * G_PITCH + 2 * (x))      // level i+6:      2 B/px, row pitch 2P
-#define HT_O2(x, y) (P12_BASE + 1 + 4 * (y) * PITCH0 + 4 * (x))  // level i+12 q: odd bytes, 4 B/px, row pitch 4P
-
+// (HT_O0 / HT_O1 / HT_O2, the unified-base LDS offsets of a feature point relative to the window base B: ht_cascade_types.h)
 #include "ht_cascade_gen.inc"  // straight-line code for the first HT_GEN_STAGES stages of the built-in cascade
 
 __device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
@@ -638,7 +635,7 @@ __device__ __forceinline__ long long wave_sum_i64(long long v) {
 // ---- deep kernel ------------------------------------------------------------------------------------------------
 // Per-wavefront window patch in LDS: the 24x24 window of level i, its 12x12 counterpart on level i+6 and the 6x6 one on
 // variant q of level i+12 = 756 bytes, loaded once per window; every later stage reads pixels from there.
-constexpr int PATCH1 = 576, PATCH2 = 720, PATCH_BYTES = 768;
+constexpr int PATCH1 = HT_PATCH1, PATCH2 = HT_PATCH2, PATCH_BYTES = HT_PATCH_BYTES;
 constexpr int DEEP_WAVES = 4;  // waves per workgroup
 
 __device__ __forceinline__ bool patch_fire(const uint8_t *patch, const HtPatchFeature *__restrict__ fp, uint32_t maxpts) {
@@ -839,8 +836,9 @@ __global__ __launch_bounds__(64 * DEEP_WAVES) void k_scan_deep(const uint8_t *__
 // C2 batch, which is what it spends its time on.  Here the tail of the cascade (stages >= split, 1868 features x 32 B = 60 KB)
 // is copied into LDS once per workgroup (one 1024-thread workgroup per CU); every wavefront then owns a window at a time
 // exactly like k_scan_deep, but feature records and pixels both come from LDS.
-constexpr uint32_t DEEP_LDS_TABLE_BYTES = 64 * 1024;
+constexpr uint32_t DEEP_LDS_TABLE_BYTES = HT_DEEP_LDS_TABLE_BYTES;
 constexpr int DEEPL_WAVES = 12;  // 12 waves x 2 workgroups per CU (2 x 77 KB of LDS) beat 16 x 1: measured 0.044 vs 0.055 ms on C2
+static_assert(DEEP_LDS_TABLE_BYTES + 64 * sizeof(HtDevStage) + DEEPL_WAVES * (PATCH_BYTES + 512) <= 96 * 1024, "the largest packed tail the planner builds fits the dynamic LDS ht_launch_scan asks for");
 
 __device__ __forceinline__ bool packed_fire(const uint8_t *patch, const uint4 A, const uint32_t B0) {
     // A = off[0..7], B0 = off[8..9]
@@ -1203,135 +1201,6 @@ __global__ __launch_bounds__(256) void k_scan_simple(const uint8_t *__restrict__
 // ----------------------------------------------------------------------------------------------------------------
 // host side
 
-// LDS-offset form of every feature for k_scan_tiles (unified-base layout, see the file header)
-ht_status ht_scan_tile_tables(ht_ctx *c) {
-    std::vector<HtTileFeature> tf(c->nfeat);
-    const bool tile_ok = (c->cw == 24 && c->ch == 24);
-    for (uint32_t k = 0; k < c->nfeat; k++) {
-        const HtBlobFeature &f = c->h_feats[k];
-        HtTileFeature &t = tf[k];
-        std::memset(&t, 0, sizeof(t));
-        auto off = [](int x, int y, int z) -> uint16_t {
-            if (z == 0) return (uint16_t)(y * PITCH0 + x);                       // level i: 1 B/px, pitch P
-            if (z == 1) return (uint16_t)(P12_BASE + y * G_PITCH + 2 * x);       // level i+6: 2 B/px, pitch 2P
-            return (uint16_t)(P12_BASE + 1 + 4 * y * PITCH0 + 4 * x);            // level i+12 variants: odd bytes, 4 B/px, pitch 4P
-        };
-        for (int q = 0; q < f.size; q++) {
-            if (f.pz[q] >= 0) {
-                t.po[t.np >> 1] |= (uint32_t)off(f.px[q], f.py[q], f.pz[q]) << (16 * (t.np & 1));
-                t.np++;
-            }
-            if (f.nz[q] >= 0) {
-                t.no[t.nn >> 1] |= (uint32_t)off(f.nx[q], f.ny[q], f.nz[q]) << (16 * (t.nn & 1));
-                t.nn++;
-            }
-        }
-        std::memcpy(&t.a[0], &f.alpha[0], 8);
-        std::memcpy(&t.a[2], &f.alpha[1], 8);
-    }
-    (void)tile_ok;
-    HT_HIP(c, hipMalloc(&c->d_tile_feats, tf.size() * sizeof(HtTileFeature)));
-    HT_HIP(c, hipMemcpy(c->d_tile_feats, tf.data(), tf.size() * sizeof(HtTileFeature), hipMemcpyHostToDevice));
-    {   // packed per-lane form of the same offsets for the tile kernel's feature-parallel sparse phase: slots past a polarity's point
-        // count repeat its first point (min / max are idempotent), alpha[2k+1] * 1e8 as the integer the generated stages add
-        std::vector<HtPackedFeature> fp(c->nfeat);
-        bool ok = c->decimal_alphas;
-        for (uint32_t k = 0; k < c->nfeat && ok; k++) {
-            const HtTileFeature &t = tf[k];
-            const HtBlobFeature &f = c->h_feats[k];
-            HtPackedFeature &q = fp[k];
-            std::memset(&q, 0, sizeof(q));
-            if (t.np == 0 || t.nn == 0 || t.np > 5 || t.nn > 5) ok = false;
-            for (uint32_t j = 0; j < 5 && ok; j++) {
-                const uint32_t jp = j < t.np ? j : 0u, jn = j < t.nn ? j : 0u;
-                q.off[j] = (uint16_t)((t.po[jp >> 1] >> (16 * (jp & 1))) & 0xffffu);
-                q.off[5 + j] = (uint16_t)((t.no[jn >> 1] >> (16 * (jn & 1))) & 0xffffu);
-            }
-            const double a0 = std::nearbyint(f.alpha[0] * 1e8), a1 = std::nearbyint(f.alpha[1] * 1e8);
-            if (!(a1 > 0 && a1 < 2147483648.0 && a0 == -a1)) ok = false;
-            q.a0i = (int32_t)a0, q.a1i = (int32_t)a1;
-        }
-        if (ok && c->nfeat) {
-            HT_HIP(c, hipMalloc(&c->d_fp_feats, fp.size() * sizeof(HtPackedFeature)));
-            HT_HIP(c, hipMemcpy(c->d_fp_feats, fp.data(), fp.size() * sizeof(HtPackedFeature), hipMemcpyHostToDevice));
-        }
-    }
-
-    // patch-offset form for k_scan_deep
-    std::vector<HtPatchFeature> pf(c->nfeat);
-    for (uint32_t k = 0; k < c->nfeat; k++) {
-        const HtBlobFeature &f = c->h_feats[k];
-        HtPatchFeature &t = pf[k];
-        std::memset(&t, 0, sizeof(t));
-        auto poff = [&](int x, int y, int z) -> uint16_t {
-            if (z == 0) return (uint16_t)(y * (int)c->cw + x);
-            if (z == 1) return (uint16_t)(PATCH1 + y * (int)(c->cw / 2) + x);
-            return (uint16_t)(PATCH2 + y * (int)(c->cw / 4) + x);
-        };
-        int np = 0, nn = 0;
-        for (int q = 0; q < f.size; q++) {
-            if (f.pz[q] >= 0) t.poff[np++] = poff(f.px[q], f.py[q], f.pz[q]);
-            if (f.nz[q] >= 0) t.noff[nn++] = poff(f.nx[q], f.ny[q], f.nz[q]);
-        }
-        for (int q = np; q < HT_MAXPTS; q++) t.poff[q] = t.poff[0];
-        for (int q = nn; q < HT_MAXPTS; q++) t.noff[q] = t.noff[0];
-        t.a0 = f.alpha[0];
-        t.a1 = f.alpha[1];
-        double s0 = t.a0 * 1e8, s1 = t.a1 * 1e8;
-        t.a0i = (int64_t)llround(s0);
-        t.a1i = (int64_t)llround(s1);
-    }
-    HT_HIP(c, hipMalloc(&c->d_patch_feats, pf.size() * sizeof(HtPatchFeature)));
-    HT_HIP(c, hipMemcpy(c->d_patch_feats, pf.data(), pf.size() * sizeof(HtPatchFeature), hipMemcpyHostToDevice));
-
-    return HT_OK;
-}
-
-// LDS-resident deep table: features of stages [split, nstages) in HtPackedFeature form; leaves packed_count = 0 when the
-// cascade does not fit the format (then k_scan_deep is used)
-ht_status ht_scan_pack_deep(ht_ctx *c) {
-    if (c->d_packed_feats) (void)hipFree(c->d_packed_feats), c->d_packed_feats = nullptr;
-    c->packed_count = 0;
-    if (!c->decimal_alphas || c->split_stage >= c->nstages || c->cw != 24 || c->ch != 24) return HT_OK;
-    const uint32_t first = c->h_stages[c->split_stage].first;
-    const uint32_t n = c->nfeat - first;
-    if (n == 0 || n * sizeof(HtPackedFeature) > DEEP_LDS_TABLE_BYTES) return HT_OK;
-    std::vector<HtPackedFeature> pk(n);
-    for (uint32_t k = 0; k < n; k++) {
-        const HtBlobFeature &f = c->h_feats[first + k];
-        HtPackedFeature &t = pk[k];
-        std::memset(&t, 0, sizeof(t));
-        auto poff = [&](int x, int y, int z) -> uint16_t {
-            if (z == 0) return (uint16_t)(y * 24 + x);
-            if (z == 1) return (uint16_t)(PATCH1 + y * 12 + x);
-            return (uint16_t)(PATCH2 + y * 6 + x);
-        };
-        int np = 0, nn = 0;
-        for (int q = 0; q < f.size; q++) {
-            if (f.pz[q] >= 0) {
-                if (np >= 5) return HT_OK;
-                t.off[np++] = poff(f.px[q], f.py[q], f.pz[q]);
-            }
-            if (f.nz[q] >= 0) {
-                if (nn >= 5) return HT_OK;
-                t.off[5 + nn++] = poff(f.nx[q], f.ny[q], f.nz[q]);
-            }
-        }
-        for (int q = np; q < 5; q++) t.off[q] = t.off[0];
-        for (int q = nn; q < 5; q++) t.off[5 + q] = t.off[5];
-        const double s0 = f.alpha[0] * 1e8, s1 = f.alpha[1] * 1e8;
-        if (!(std::fabs(s0) < 2.0e9) || !(std::fabs(s1) < 2.0e9)) return HT_OK;
-        t.a0i = (int32_t)llround(s0);
-        t.a1i = (int32_t)llround(s1);
-        if ((double)t.a0i / 1e8 != f.alpha[0] || (double)t.a1i / 1e8 != f.alpha[1]) return HT_OK;
-    }
-    HT_HIP(c, hipMalloc(&c->d_packed_feats, pk.size() * sizeof(HtPackedFeature)));
-    HT_HIP(c, hipMemcpy(c->d_packed_feats, pk.data(), pk.size() * sizeof(HtPackedFeature), hipMemcpyHostToDevice));
-    c->packed_count = n;
-    c->packed_first = first;
-    return HT_OK;
-}
-
 // true iff blob is byte-identical to the cascade ht_cascade_gen.inc was generated from (FNV-1a 64 + length)
 bool ht_scan_is_builtin_cascade(const uint8_t *blob, size_t len) {
     if (len != HT_GEN_CASCADE_LEN) return false;
@@ -1343,22 +1212,22 @@ bool ht_scan_is_builtin_cascade(const uint8_t *blob, size_t len) {
 // tile kernel over tiles [first, first + count) of every frame's tile list, on `stream`
 static ht_status launch_tiles(ht_ctx *c, uint32_t flags, hipStream_t stream, uint32_t first, uint32_t count) {
     unsigned long long *stats = (flags & HT_SCAN_STATS) ? c->d_stats : nullptr;
-    const int split = (flags & HT_SCAN_NO_SPLIT) ? (int)c->nstages : (int)std::min<uint32_t>(c->split_stage, c->nstages);
+    const int split = (flags & HT_SCAN_NO_SPLIT) ? (int)c->cascade.nstages : (int)std::min<uint32_t>(c->cascade.split_stage, c->cascade.nstages);
     const uint64_t total64 = (uint64_t)count * (uint64_t)c->nframes;
     if (total64 > 0x7fffff00ull) return ht_fail(c, HT_ERR_INVALID, "ht_detect: batch too large for one launch");
     const uint32_t total = (uint32_t)total64;
     const bool gen = c->builtin_cascade && !(flags & HT_SCAN_GENERIC);
     // measurement knob: stop the tile kernel before a stage; test knob: treat every integer stage decision as an exact tie,
-    // i.e. always take the sequential-binary64 fallback (both read from the environment once, in ht_create)
+    // i.e. always take the sequential-binary64 fallback (options stop_stage / force_exact of ht_config.options, parsed once in ht_create)
     const int stop_stage = c->dbg_stop_stage, force_exact = c->dbg_force_exact;
     HtProfScope ps(c, "scan_tiles", stream);
     if (gen)
         hipLaunchKernelGGL(k_scan_tiles<true>, dim3((total + 7u) & ~7u), dim3(NT), 0, stream, c->d_arena, c->plan.arena_stride,
-                           c->d_tile_recs + first, c->d_tile_feats, c->fp_sparse ? c->d_fp_feats : nullptr, c->d_stages, (int)c->nstages, split, c->deep_bias, stop_stage, force_exact, count, total,
+                           c->d_tile_recs + first, c->d_tile_feats, c->fp_sparse ? c->d_fp_feats : nullptr, c->d_stages, (int)c->cascade.nstages, split, c->deep_bias, stop_stage, force_exact, count, total,
                            c->d_queue, c->plan.queue_capacity, c->d_hits, c->hit_capacity, c->d_counters, stats);
     else
         hipLaunchKernelGGL(k_scan_tiles<false>, dim3((total + 7u) & ~7u), dim3(NT), 0, stream, c->d_arena, c->plan.arena_stride,
-                           c->d_tile_recs + first, c->d_tile_feats, c->fp_sparse ? c->d_fp_feats : nullptr, c->d_stages, (int)c->nstages, split, c->deep_bias, stop_stage, force_exact, count, total,
+                           c->d_tile_recs + first, c->d_tile_feats, c->fp_sparse ? c->d_fp_feats : nullptr, c->d_stages, (int)c->cascade.nstages, split, c->deep_bias, stop_stage, force_exact, count, total,
                            c->d_queue, c->plan.queue_capacity, c->d_hits, c->hit_capacity, c->d_counters, stats);
     HT_HIP(c, hipGetLastError());
     return HT_OK;
@@ -1367,7 +1236,7 @@ static ht_status launch_tiles(ht_ctx *c, uint32_t flags, hipStream_t stream, uin
 // Called by ht_launch_pyramid right after the generation that completes the early scales' planes: their tiles are scanned on the
 // second stream while the main stream builds the remaining small generations (which are latency-, not throughput-bound).
 ht_status ht_launch_scan_early(ht_ctx *c, uint32_t flags) {
-    if (c->plan.early_tiles == 0 || !c->aux_stream || (flags & HT_SCAN_SIMPLE) || c->cw != 24 || c->ch != 24) return HT_OK;
+    if (c->plan.early_tiles == 0 || !c->aux_stream || (flags & HT_SCAN_SIMPLE) || c->cascade.cw != 24 || c->cascade.ch != 24) return HT_OK;
     HT_HIP(c, hipEventRecord(c->ev_early_ready, c->stream));
     HT_HIP(c, hipStreamWaitEvent(c->aux_stream, c->ev_early_ready, 0));
     ht_status st = launch_tiles(c, flags, c->aux_stream, 0, c->plan.early_tiles);
@@ -1381,17 +1250,17 @@ ht_status ht_launch_scan(ht_ctx *c, uint32_t flags) {
     if (c->plan.scales.empty() || c->plan.tiles_per_frame == 0) return HT_OK;  // image too small for any window
     const int nscales = (int)c->plan.scales.size();
     unsigned long long *stats = (flags & HT_SCAN_STATS) ? c->d_stats : nullptr;
-    const bool tile_ok = (c->cw == 24 && c->ch == 24);
+    const bool tile_ok = (c->cascade.cw == 24 && c->cascade.ch == 24);
     if ((flags & HT_SCAN_SIMPLE) || !tile_ok) {
         HtProfScope ps(c, "scan_simple");
         dim3 grid((uint32_t)((c->plan.windows_per_frame + 255) / 256), c->nframes);
         hipLaunchKernelGGL(k_scan_simple, grid, dim3(256), 0, c->stream, c->d_arena, c->plan.arena_stride, c->d_levels, c->next, c->d_scales,
-                           nscales, (uint32_t)c->plan.windows_per_frame, c->d_deep_feats, c->d_stages, (int)c->nstages, c->d_hits,
+                           nscales, (uint32_t)c->plan.windows_per_frame, c->d_deep_feats, c->d_stages, (int)c->cascade.nstages, c->d_hits,
                            c->hit_capacity, c->d_counters, stats);
         HT_HIP(c, hipGetLastError());
         return HT_OK;
     }
-    const int split = (flags & HT_SCAN_NO_SPLIT) ? (int)c->nstages : (int)std::min<uint32_t>(c->split_stage, c->nstages);
+    const int split = (flags & HT_SCAN_NO_SPLIT) ? (int)c->cascade.nstages : (int)std::min<uint32_t>(c->cascade.split_stage, c->cascade.nstages);
     const int force_exact = c->dbg_force_exact;
     {
         const uint32_t first = c->early_launched ? c->plan.early_tiles : 0u;
@@ -1399,11 +1268,11 @@ ht_status ht_launch_scan(ht_ctx *c, uint32_t flags) {
         if (st != HT_OK) return st;
         if (c->early_launched) HT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_early_done, 0));  // the deep kernel needs every tile's survivors
     }
-    if (split < (int)c->nstages) {
+    if (split < (int)c->cascade.nstages) {
         HtProfScope ps(c, "scan_deep");
         const int deep_v = c->dbg_deep_v;
-        if (deep_v == 4 && c->packed_count && c->h_stages[split].first >= c->packed_first) {
-            const size_t lds = (size_t)c->packed_count * sizeof(HtPackedFeature) + 64 * sizeof(HtDevStage) + (size_t)DEEPL_WAVES * (PATCH_BYTES + 512);
+        if (deep_v == 4 && !c->cascade.packed.empty() && c->cascade.stages[split].first >= c->cascade.packed_first) {
+            const size_t lds = c->cascade.packed.size() * sizeof(HtPackedFeature) + 64 * sizeof(HtDevStage) + (size_t)DEEPL_WAVES * (PATCH_BYTES + 512);
             if (!c->deep_attr_set) {  // per context (= per device): a single-process multi-GPU host has one context per GPU
                 HT_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_scan_deep_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
                 c->deep_attr_set = true;
@@ -1418,11 +1287,11 @@ ht_status ht_launch_scan(ht_ctx *c, uint32_t flags) {
             // handed out by counter c): a grid below 16 wavefronts (option deep_grid=1) would silently skip queue entries
             const uint32_t deep_grid = std::max<uint32_t>((uint32_t)c->deep_grid, (HT_DEEP_CTRS + DEEPL_WAVES - 1) / DEEPL_WAVES);
             hipLaunchKernelGGL(k_scan_deep_lds, dim3(deep_grid), dim3(64 * DEEPL_WAVES), lds, c->stream, c->d_arena, c->plan.arena_stride, c->d_levels, c->next,
-                               c->d_packed_feats, c->packed_count, c->packed_first, c->d_stages, (int)c->nstages, force_exact, c->d_queue, c->plan.queue_capacity,
+                               c->d_packed_feats, (uint32_t)c->cascade.packed.size(), c->cascade.packed_first, c->d_stages, (int)c->cascade.nstages, force_exact, c->d_queue, c->plan.queue_capacity,
                                c->d_hits, c->hit_capacity, c->d_counters, stats);
         } else
         hipLaunchKernelGGL(k_scan_deep, dim3(2048), dim3(64 * DEEP_WAVES), 0, c->stream, c->d_arena, c->plan.arena_stride, c->d_levels, c->next,
-                           c->d_patch_feats, c->d_stages, (int)c->nstages, c->decimal_alphas ? (force_exact ? 2 : 1) : 0, c->d_queue, c->plan.queue_capacity, c->d_hits,
+                           c->d_patch_feats, c->d_stages, (int)c->cascade.nstages, c->cascade.decimal_alphas ? (force_exact ? 2 : 1) : 0, c->d_queue, c->plan.queue_capacity, c->d_hits,
                            c->hit_capacity, c->d_counters, stats);
         HT_HIP(c, hipGetLastError());
     }
