@@ -147,6 +147,43 @@ class Context:
         if dst is None:
             self.nframes = n
 
+    # -- the same draw for YUV 4:2:0 frames (NV12 / I420): conversion fused into the draw -------------------------
+    @staticmethod
+    def _yuv_code(table, v, what):
+        if isinstance(v, str):
+            if v not in table:
+                raise ValueError(f"{what} is one of {sorted(table)}")
+            return table[v]
+        return int(v)
+
+    def draw_frames_yuv(self, planes, fmt="nv12", matrix="bt601", rect=None):
+        """planes: host arrays of n frames — NV12: (y uint8 [n, h, w], uv uint8 [n, ch, cw, 2]); I420: (y, u [n, ch, cw], v [n, ch, cw]) with
+        cw = ceil(w / 2), ch = ceil(h / 2) — packed frame by frame and drawn like draw_frames(): converted with the declared integer matrix
+        ('bt601', 'bt709', 'bt601-full', 'bt709-full' or 0 .. 3), scaled on the device, result bound."""
+        fmt, matrix = self._yuv_code(native.YUV_FORMATS, fmt, "fmt"), self._yuv_code(native.YUV_MATRICES, matrix, "matrix")
+        planes = [np.ascontiguousarray(p, dtype=np.uint8) for p in planes]
+        n, h, w = planes[0].shape
+        assert len(planes) == (2 if fmt == native.HT_YUV_NV12 else 3) and all(len(p) == n for p in planes)
+        host = np.concatenate([p.reshape(n, -1) for p in planes], axis=1)
+        assert host.shape[1] == w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2), "chroma planes are ceil(w / 2) x ceil(h / 2)"
+        self.draw_frames_yuv_ptr(host.ctypes.data, n, w, h, fmt, matrix, 0, rect)
+
+    def draw_frames_yuv_ptr(self, host_ptr: int, n: int, w: int, h: int, fmt: int, matrix: int, frame_stride: int = 0, rect=None):
+        """ht_draw_frames_yuv on a raw host pointer: n tightly packed frames (Y, then UV or U, V), frame_stride bytes apart (0 = packed)"""
+        r = self._cs_rect(rect)
+        self._check(self._lib.ht_draw_frames_yuv(self._h, host_ptr, n, w, h, fmt, matrix, frame_stride, r.ctypes.data if r is not None else None))
+        self.nframes = n
+
+    def draw_frames_yuv_device(self, y: int, u: int, v: int | None, n: int, w: int, h: int, fmt="nv12", matrix="bt601", y_pitch: int = 0, c_pitch: int = 0,
+                               stride: int = 0, rect=None, dst: int | None = None, dst_stride: int = 0):
+        """The same for planes resident in device memory at y / u / v (NV12: u = the interleaved plane, v None), rows y_pitch / c_pitch bytes
+        (0 = packed), frames `stride` bytes apart in every plane.  dst as draw_frames_device()."""
+        d = native.YUV_FRAMES(y, u, v, y_pitch, c_pitch, stride, w, h, self._yuv_code(native.YUV_FORMATS, fmt, "fmt"), self._yuv_code(native.YUV_MATRICES, matrix, "matrix"))
+        r = self._cs_rect(rect)
+        self._check(self._lib.ht_draw_frames_yuv_device(self._h, C.byref(d), n, r.ctypes.data if r is not None else None, dst, dst_stride))
+        if dst is None:
+            self.nframes = n
+
     # -- detect -----------------------------------------------------------------------------------------------
     def detect_enqueue(self, flags: int = HT_INPUT_RGBA):
         self._check(self._lib.ht_detect_enqueue(self._h, flags))

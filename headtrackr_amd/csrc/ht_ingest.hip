@@ -212,3 +212,5 @@ void ht_ingest_free(ht_ctx *c) {  // ht_destroy (the stream has been synchronise
     if (c->d_ingest_src) (void)hipFree(c->d_ingest_src);
     c->d_ingest_src = nullptr, c->ingest_src_cap = 0;
 }
+
+#include "ht_ingest_yuv.hip"  // the same draw for YUV 4:2:0 frames (shares ig_channel and the tile constants)

@@ -1,0 +1,221 @@
+// ht_ingest_yuv.hip — the video -> canvas draw for frames that arrive as YUV 4:2:0 (NV12 from hardware decoders, I420 from software
+// decoders): the colour conversion a browser's drawImage(video, ..) hides, fused into the draw.  Included at the end of ht_ingest.hip, so
+// it is part of the same code object and shares that file's text: the tile constants, ig_channel, ig_overlap.
+//
+// The result is DEFINED as what ht_draw_frames_device gives on the RGBA frame the declared conversion (ht_yuv_plan.h) makes of the
+// planes, byte for byte, for every rect, ratio and size: a destination pixel's four tap pixels are converted to RGBA8 dwords with the
+// integer formula and then go through ig_channel unchanged.  A 1 : 1 whole-frame draw is therefore the bare conversion.
+//
+// k_draw_yuv<FMT> tiles like k_draw_frames (64 x 16 destination pixels, 256 threads, taps once per tile in LDS, one column and four rows
+// per thread).  Per row pair a thread reads
+//   Y       the tap pair (a, a + 1) as ONE 2-byte read at byte granularity (anchored one pixel to the left at the rect's last column, as
+//           k_draw_frames anchors its pixel pair; a 1-pixel-wide rect is read byte by byte);
+//   chroma  the two chroma samples the pair can name, (a >> 1) and (a >> 1) + 1, as ONE read anchored at min(a >> 1, cw - 2): NV12 4
+//           bytes U V U V at a 2-byte-aligned address (the chroma base and pitch are even), I420 2 bytes from each of the two planes;
+//           a frame of 1 or 2 pixels' width has one chroma column and is read sample by sample.
+// All 16 (NV12) or 24 (I420) reads of a thread are issued before the first use.  DESIGN.md §2.3 gives the reasoning.
+#include "ht_yuv_plan.h"
+
+static_assert(HT_YUV_NV12 == HT_YUV_FMT_NV12 && HT_YUV_I420 == HT_YUV_FMT_I420, "format numbers of the header and of the plan");
+static_assert(HT_YUV_BT601_LIMITED == 0 && HT_YUV_BT709_LIMITED == 1 && HT_YUV_BT601_FULL == 2 && HT_YUV_BT709_FULL == 3, "matrix numbers");
+
+namespace {
+
+// byte-granular reads: the address is aligned only as far as the type says (legal for global memory on gfx950)
+typedef uint16_t ig_u16b __attribute__((aligned(1)));
+typedef uint32_t ig_u32h __attribute__((aligned(2)));
+
+// the chroma of one source row at the anchor column: NV12 form, bytes U0 V0 U1 V1 (sample 0 = the anchor, 1 = its right neighbour)
+template <int FMT>
+__device__ __forceinline__ uint32_t ig_chroma_read(const uint8_t *u, const uint8_t *v, size_t off, bool cpair) {
+    if (FMT == HT_YUV_FMT_NV12) {
+        if (cpair) return *reinterpret_cast<const ig_u32h *>(u + 2 * off);
+        return *reinterpret_cast<const uint16_t *>(u + 2 * off);
+    }
+    uint32_t uu, vv;
+    if (cpair) uu = *reinterpret_cast<const ig_u16b *>(u + off), vv = *reinterpret_cast<const ig_u16b *>(v + off);
+    else uu = u[off], vv = v[off];
+    return (uu & 0xffu) | ((vv & 0xffu) << 8) | ((uu & 0xff00u) << 8) | ((vv & 0xff00u) << 16);
+}
+
+// yp / up / vp: frame 0 of each plane (NV12: up = the interleaved plane, vp unused), rows y_pitch / c_pitch bytes, frames `stride` bytes
+// apart in every plane; cw: chroma samples per row of the FRAME; the rest as k_draw_frames
+template <int FMT>
+__global__ __launch_bounds__(IG_NT) void k_draw_yuv(const uint8_t *__restrict__ yp, const uint8_t *__restrict__ up, const uint8_t *__restrict__ vp,
+                                                    size_t y_pitch, size_t c_pitch, size_t stride, uint8_t *__restrict__ dst, size_t dst_stride, int sx,
+                                                    int sy, int sw, int sh, int cw, int dw, int dh, double rx, double ry, HtYuvCoef kc) {
+    __shared__ RsTap s_col[IG_TW], s_row[IG_TH];
+    const int X0 = blockIdx.x * IG_TW, Y0 = blockIdx.y * IG_TH;
+    if (threadIdx.x < IG_TW) s_col[threadIdx.x] = rs_tap(min(X0 + (int)threadIdx.x, dw - 1), rx, sw, sx);
+    else if (threadIdx.x < IG_TW + IG_TH) s_row[threadIdx.x - IG_TW] = rs_tap(min(Y0 + (int)threadIdx.x - IG_TW, dh - 1), ry, sh, sy);
+    __syncthreads();
+    const int col = threadIdx.x & (IG_TW - 1), r0 = threadIdx.x / IG_TW, x = X0 + col;
+    if (x >= dw) return;
+    const RsTap cx = s_col[col];
+    const bool pair = sw >= 2;
+    const int xa = pair ? min(cx.a, sx + sw - 2) : cx.a;  // the Y pair's anchor, inside the rect
+    const int ya_sel = cx.a - xa, yb_sel = cx.b - xa;      // 0 / 1: which byte of the pair each tap takes
+    const bool cpair = cw >= 2;
+    const int ca = cpair ? min(cx.a >> 1, cw - 2) : 0;     // the chroma pair's anchor, inside the frame's chroma row
+    const int ca_sel = (cx.a >> 1) - ca, cb_sel = (cx.b >> 1) - ca;
+    const size_t foff = (size_t)blockIdx.z * stride;
+    const uint8_t *yf = yp + foff + (size_t)xa, *uf = up + foff, *vf = FMT == HT_YUV_FMT_NV12 ? uf : vp + foff;
+    uint32_t ytop[IG_RPT], ybot[IG_RPT], ctop[IG_RPT], cbot[IG_RPT];
+    double ru[IG_RPT], rt[IG_RPT];
+    bool on[IG_RPT];
+#pragma unroll
+    for (int k = 0; k < IG_RPT; k++) {
+        const int j = r0 + k * (IG_NT / IG_TW);
+        on[k] = Y0 + j < dh;
+        const RsTap ty = s_row[j];
+        ru[k] = ty.u, rt[k] = ty.t;
+        ytop[k] = ybot[k] = ctop[k] = cbot[k] = 0u;
+        if (on[k]) {
+            const uint8_t *pa = yf + (size_t)ty.a * y_pitch, *pb = yf + (size_t)ty.b * y_pitch;
+            if (pair) {
+                ytop[k] = *reinterpret_cast<const ig_u16b *>(pa);
+                ybot[k] = *reinterpret_cast<const ig_u16b *>(pb);
+            } else {
+                ytop[k] = *pa;
+                ybot[k] = *pb;
+            }
+            ctop[k] = ig_chroma_read<FMT>(uf, vf, (size_t)(ty.a >> 1) * (FMT == HT_YUV_FMT_NV12 ? c_pitch / 2 : c_pitch) + (size_t)ca, cpair);
+            cbot[k] = ig_chroma_read<FMT>(uf, vf, (size_t)(ty.b >> 1) * (FMT == HT_YUV_FMT_NV12 ? c_pitch / 2 : c_pitch) + (size_t)ca, cpair);
+        }
+    }
+    uint32_t *out = reinterpret_cast<uint32_t *>(dst + (size_t)blockIdx.z * dst_stride) + x;
+#pragma unroll
+    for (int k = 0; k < IG_RPT; k++) {
+        if (!on[k]) continue;
+        // the four tap pixels as the RGBA8 dwords k_draw_frames would have read
+        const uint32_t ta = ctop[k] >> (16 * ca_sel), tb = ctop[k] >> (16 * cb_sel), ba = cbot[k] >> (16 * ca_sel), bb = cbot[k] >> (16 * cb_sel);
+        const uint32_t p00 = ht_yuv_to_rgba((ytop[k] >> (8 * ya_sel)) & 0xffu, ta & 0xffu, (ta >> 8) & 0xffu, kc);
+        const uint32_t p01 = ht_yuv_to_rgba((ytop[k] >> (8 * yb_sel)) & 0xffu, tb & 0xffu, (tb >> 8) & 0xffu, kc);
+        const uint32_t p10 = ht_yuv_to_rgba((ybot[k] >> (8 * ya_sel)) & 0xffu, ba & 0xffu, (ba >> 8) & 0xffu, kc);
+        const uint32_t p11 = ht_yuv_to_rgba((ybot[k] >> (8 * yb_sel)) & 0xffu, bb & 0xffu, (bb >> 8) & 0xffu, kc);
+        uint32_t o = 0;
+#pragma unroll
+        for (int ch = 0; ch < 4; ch++) o |= ig_channel(p00, p01, p10, p11, 8 * ch, cx.u, cx.t, ru[k], rt[k]);
+        out[(size_t)(Y0 + r0 + k * (IG_NT / IG_TW)) * dw] = o;
+    }
+}
+
+struct IgYuvCall {  // a validated call: the source as the device will see it
+    HtYuvPlan plan;
+    int32_t format, matrix;
+    int32_t sx, sy, sw, sh;
+    size_t fbytes;  // bytes of one destination frame
+};
+
+// the checks both entry points share
+ht_status igy_check(ht_ctx *c, const char *fn, int32_t n, int32_t width, int32_t height, int32_t format, int32_t matrix, size_t y_pitch, size_t c_pitch,
+                    size_t frame_stride, const ht_cs_rect *rect, IgYuvCall *q) {
+    const std::string f(fn);
+    if (c->W == 0) return ht_fail(c, HT_ERR_STATE, f + ": call ht_set_geometry first");
+    const int ps = ht_yuv_plan(width, height, format, matrix, y_pitch, c_pitch, frame_stride, n, &q->plan);
+    if (ps != HT_YUV_PLAN_OK) return ht_fail(c, HT_ERR_INVALID, f + ": " + ht_yuv_plan_message(ps));
+    q->format = format, q->matrix = matrix;
+    q->sx = q->sy = 0, q->sw = width, q->sh = height;
+    if (rect) {
+        if (rect->x < 0 || rect->y < 0 || rect->width <= 0 || rect->height <= 0 || rect->width > width - rect->x || rect->height > height - rect->y)
+            return ht_fail(c, HT_ERR_INVALID, f + ": source rect must lie wholly inside the source frame");
+        q->sx = rect->x, q->sy = rect->y, q->sw = rect->width, q->sh = rect->height;
+    }
+    q->fbytes = (size_t)c->W * c->H * 4;
+    return HT_OK;
+}
+
+ht_status igy_launch(ht_ctx *c, const IgYuvCall &q, const uint8_t *y, const uint8_t *u, const uint8_t *v, int32_t n, uint8_t *dst, size_t dstride) {
+    HtProfScope ps(c, "draw_yuv");
+    const double rx = (double)q.sw / (double)c->W, ry = (double)q.sh / (double)c->H;  // canvas_shim.js: one binary64 division each
+    const dim3 grid((c->W + IG_TW - 1) / IG_TW, (c->H + IG_TH - 1) / IG_TH, n);
+    const HtYuvPlan &p = q.plan;
+    const HtYuvCoef kc = HT_YUV_COEF[q.matrix];
+    if (q.format == HT_YUV_FMT_NV12)
+        hipLaunchKernelGGL(k_draw_yuv<HT_YUV_FMT_NV12>, grid, dim3(IG_NT), 0, c->stream, y, u, u, p.y_pitch, p.c_pitch, p.stride, dst, dstride, q.sx, q.sy, q.sw,
+                           q.sh, p.cw, c->W, c->H, rx, ry, kc);
+    else
+        hipLaunchKernelGGL(k_draw_yuv<HT_YUV_FMT_I420>, grid, dim3(IG_NT), 0, c->stream, y, u, v, p.y_pitch, p.c_pitch, p.stride, dst, dstride, q.sx, q.sy, q.sw,
+                           q.sh, p.cw, c->W, c->H, rx, ry, kc);
+    HT_HIP(c, hipGetLastError());
+    return HT_OK;
+}
+
+// into the context's own frame buffer, bound on success: the contract of ig_draw_bound
+ht_status igy_draw_bound(ht_ctx *c, const char *fn, const IgYuvCall &q, const uint8_t *y, const uint8_t *u, const uint8_t *v, int32_t n) {
+    ht_status st = ht_frames_own_reserve(c, q.fbytes * (size_t)n, fn);
+    if (st != HT_OK) return st;
+    if ((st = igy_launch(c, q, y, u, v, n, c->d_frames_own, q.fbytes)) != HT_OK) return st;
+    ht_frames_bind_own(c, n);
+    return HT_OK;
+}
+
+}  // namespace
+
+extern "C" ht_status ht_draw_frames_yuv_device(ht_ctx *c, const ht_yuv_frames *s, int32_t n, const ht_cs_rect *src_rect, void *dst_dev, size_t dst_frame_stride) {
+    if (!c) return HT_ERR_INVALID;
+    HtRange range("ht_draw_frames_yuv_device");
+    const char *fn = "ht_draw_frames_yuv_device";
+    if (!s) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": NULL source description");
+    IgYuvCall q;
+    ht_status st = igy_check(c, fn, n, s->width, s->height, s->format, s->matrix, s->y_pitch, s->c_pitch, s->frame_stride, src_rect, &q);
+    if (st != HT_OK) return st;
+    const bool nv12 = q.format == HT_YUV_FMT_NV12;
+    if (!s->y || !s->u || (!nv12 && !s->v)) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": NULL plane");
+    if (nv12 && ((uintptr_t)s->u & 1)) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": the NV12 chroma plane must start at an even address");
+    if ((uintptr_t)dst_dev & 3) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": misaligned destination (4-byte alignment required)");
+    const uint8_t *y = static_cast<const uint8_t *>(s->y), *u = static_cast<const uint8_t *>(s->u), *v = nv12 ? nullptr : static_cast<const uint8_t *>(s->v);
+    const HtYuvPlan &p = q.plan;
+    const auto overlaps = [&](const void *d, size_t nd) { return ig_overlap(y, p.y_extent, d, nd) || ig_overlap(u, p.c_extent, d, nd) || ig_overlap(v, p.c_extent, d, nd); };
+    HT_HIP(c, hipSetDevice(c->device));
+    if (!dst_dev) {
+        if (n > c->max_batch) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": more frames than the geometry's batch capacity");
+        if (overlaps(c->d_frames_own, std::max(c->d_frames_own_bytes, q.fbytes * (size_t)n)))  // defensive only: see ht_draw_frames_device
+            return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": a source plane lies inside the context's own frame buffer");
+        return igy_draw_bound(c, fn, q, y, u, v, n);
+    }
+    const size_t dstride = dst_frame_stride ? dst_frame_stride : q.fbytes;
+    if ((dstride & 3) || dstride < q.fbytes) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": destination frame stride smaller than a frame or not a multiple of 4");
+    if (overlaps(dst_dev, (size_t)(n - 1) * dstride + q.fbytes)) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": a source plane and the destination overlap");
+    return igy_launch(c, q, y, u, v, n, static_cast<uint8_t *>(dst_dev), dstride);
+}
+
+extern "C" ht_status ht_draw_frames_yuv(ht_ctx *c, const uint8_t *host, int32_t n, int32_t width, int32_t height, int32_t format, int32_t matrix,
+                                        size_t frame_stride, const ht_cs_rect *src_rect) {
+    if (!c) return HT_ERR_INVALID;
+    HtRange range("ht_draw_frames_yuv");
+    const char *fn = "ht_draw_frames_yuv";
+    // staged tightly packed, Y then chroma, at 1.5 B/px.  NV12 wants its chroma plane at an even address: a frame of odd width AND odd
+    // height has an odd Y plane, so it is staged one byte into the buffer (the Y plane needs no alignment) and frames one byte further
+    // apart
+    HtYuvPlan p0;
+    const size_t fsz = ht_yuv_plan(width, height, format, matrix, 0, 0, 0, 1, &p0) == HT_YUV_PLAN_OK ? p0.packed_frame : 0;
+    const size_t lead = (format == HT_YUV_FMT_NV12) ? (fsz & 1) : 0, dstep = fsz + lead;
+    IgYuvCall q;
+    ht_status st = igy_check(c, fn, n, width, height, format, matrix, 0, 0, dstep, src_rect, &q);  // (reports what made fsz 0, if anything did)
+    if (st != HT_OK) return st;
+    if (frame_stride && frame_stride < fsz) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": source frame stride smaller than a frame");
+    if (!host) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": NULL source");
+    if (n > c->max_batch) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": more frames than the geometry's batch capacity");
+    HT_HIP(c, hipSetDevice(c->device));
+    const size_t need = lead + dstep * (size_t)n;
+    if (c->ingest_src_cap < need) {  // a reallocation waits for the work in flight first, like every reallocation of the library
+        HT_HIP(c, hipStreamSynchronize(c->stream));
+        if (c->d_ingest_src) (void)hipFree(c->d_ingest_src);
+        c->d_ingest_src = nullptr, c->ingest_src_cap = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&c->d_ingest_src), need) != hipSuccess) {
+            (void)hipGetLastError();
+            return ht_fail(c, HT_ERR_NOMEM, std::string(fn) + ": hipMalloc failed (source staging)");
+        }
+        c->ingest_src_cap = need;
+    }
+    uint8_t *stage = c->d_ingest_src + lead;
+    const size_t sstep = frame_stride ? frame_stride : fsz;
+    // one copy when both sides are packed; otherwise one per frame (a strided hipMemcpy2DAsync into the byte-offset staging left the head
+    // of frame 0 stale on the GPU tests' pageable sources, and n is a batch of feeds, not of pixels)
+    if (n == 1 || (sstep == fsz && dstep == fsz)) HT_HIP(c, hipMemcpyAsync(stage, host, n == 1 ? fsz : fsz * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    else
+        for (int32_t f = 0; f < n; f++) HT_HIP(c, hipMemcpyAsync(stage + (size_t)f * dstep, host + (size_t)f * sstep, fsz, hipMemcpyHostToDevice, c->stream));
+    const uint8_t *y = stage, *u = stage + (size_t)width * (size_t)height, *v = format == HT_YUV_FMT_NV12 ? nullptr : u + (size_t)q.plan.cw * (size_t)q.plan.ch;
+    return igy_draw_bound(c, fn, q, y, u, v, n);
+}

@@ -52,6 +52,10 @@
 //        frames of sw x sh onto the context's geometry, on the device; the result becomes the bound frames
 //   drawFramesDevice(ctx, srcDev, srcOffset, n, sw, sh, pitch, stride, rect | null, dstDev | null, dstOffset, dstStride, wait)   ht_draw_frames_device between
 //        deviceAlloc() buffers (dstDev null: into the context's own buffer, bound); wait = true ends with ht_synchronize
+//   drawFramesYuv(ctx, Uint8Array planes, n, w, h, format, matrix, Int32Array rect[4] | null)   ht_draw_frames_yuv: the same draw for n host frames in
+//       YUV 4:2:0 (format 0 = NV12, 1 = I420; matrix 0 .. 3), each tightly packed (Y, then UV or U, V); the conversion is fused into the draw
+//   drawFramesYuvDevice(ctx, srcDev, srcOffset, n, w, h, format, matrix, stride, rect | null, dstDev | null, dstOffset, dstStride, wait)
+//       ht_draw_frames_yuv_device on frames packed the same way inside a device buffer, `stride` bytes apart (0 = packed)
 //   framesBound(ctx), framesEnqueued(ctx), graphLaunches(ctx)
 #include <node_api.h>
 
@@ -229,13 +233,13 @@ bool frames_fit(size_t off, size_t n, size_t stride, size_t frame, size_t bytes)
     return n == 1 || stride <= (bytes - off - frame) / (n - 1);
 }
 
-// One entry point's arguments: napi_get_cb_info once for the `max` arguments of its signature (13 = the longest, drawFramesDevice; those
+// One entry point's arguments: napi_get_cb_info once for the `max` arguments of its signature (14 = the longest, drawFramesYuvDevice; those
 // of them that the caller left out read as undefined; argv[max] and beyond are never read), the arity check, and typed getters by argument
 // index.  Lives on the stack of the entry point: this is the Node host's per-frame path.
 struct Args {
     napi_env env;
     size_t argc;  // in: max; out: what the caller passed, which may be more
-    napi_value argv[13];
+    napi_value argv[14];
     bool ok;
     Args(napi_env e, napi_callback_info info, size_t max) : env(e), argc(max) { ok = napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) == napi_ok; }
     bool arity(size_t need) const {
@@ -633,6 +637,31 @@ napi_value DrawFrames(napi_env env, napi_callback_info info) {
     if (!get_rect(env, a.argv[5], &r, &rp)) return type_error(env, "drawFrames(ctx, Uint8Array rgba, n, sw, sh, Int32Array rect[4] | null)");
     ht_status st = ht_draw_frames(f.ctx, f.rgba, f.n, f.w, f.h, 0, rp);
     if (st != HT_OK) return throw_ht(env, f.ctx, st, "ht_draw_frames");
+    return nullptr;
+}
+
+// bytes of one tightly packed YUV 4:2:0 frame (Y, then the chroma planes); 0: no such frame
+size_t yuv_frame_bytes(int32_t w, int32_t h) {
+    if (w <= 0 || h <= 0 || w > 16384 || h > 16384) return 0;
+    return (size_t)w * h + 2 * (size_t)((w + 1) / 2) * ((h + 1) / 2);
+}
+
+napi_value DrawFramesYuv(napi_env env, napi_callback_info info) {
+    static const char *usage = "drawFramesYuv(ctx, Uint8Array planes, n, w, h, format, matrix, Int32Array rect[4] | null) with planes.length >= n * (w*h + 2*ceil(w/2)*ceil(h/2))";
+    Args a(env, info, 8);
+    Locked L;
+    uint8_t *data = nullptr;
+    size_t len = 0;
+    int32_t n = 0, w = 0, h = 0, format = 0, matrix = 0;
+    ht_cs_rect r;
+    const ht_cs_rect *rp = nullptr;
+    if (!a.ctx(7, &L)) return nullptr;
+    if (!a.bytes(1, &data, &len) || !a.i32(2, &n) || !a.i32(3, &w) || !a.i32(4, &h) || !a.i32(5, &format) || !a.i32(6, &matrix) || !get_rect(env, a.argv[7], &r, &rp) || n <= 0)
+        return type_error(env, usage);
+    const size_t fsz = yuv_frame_bytes(w, h);
+    if (!fsz || !frames_fit(0, (size_t)n, fsz, fsz, len)) return range_error(env, usage);
+    ht_status st = ht_draw_frames_yuv(L.ctx, data, n, w, h, format, matrix, 0, rp);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_draw_frames_yuv");
     return nullptr;
 }
 
@@ -1292,6 +1321,43 @@ napi_value DrawFramesDevice(napi_env env, napi_callback_info info) {
     return nullptr;
 }
 
+napi_value DrawFramesYuvDevice(napi_env env, napi_callback_info info) {
+    static const char *usage = "drawFramesYuvDevice(ctx, srcDev, srcOffset, n, w, h, format, matrix, stride, rect | null, dstDev | null, dstOffset, dstStride, wait)";
+    Args a(env, info, 14);
+    Locked L;
+    DevBuf *src = nullptr, *dst = nullptr;
+    int32_t n = 0, w = 0, h = 0, format = 0, matrix = 0;
+    size_t soff = 0, stride = 0, doff = 0, dstride = 0;
+    ht_cs_rect r;
+    const ht_cs_rect *rp = nullptr;
+    bool wait = false;
+    if (!a.ctx(13, &L) || !a.devbuf(1, &src) || !a.devbuf_or_null(10, &dst)) return nullptr;
+    if (!a.offset(2, &soff) || !a.i32(3, &n) || !a.i32(4, &w) || !a.i32(5, &h) || !a.i32(6, &format) || !a.i32(7, &matrix) || !a.offset(8, &stride) ||
+        !get_rect(env, a.argv[9], &r, &rp) || !a.offset(11, &doff) || !a.offset(12, &dstride) || n <= 0)
+        return type_error(env, usage);
+    a.opt_bool(13, &wait);
+    // what the library checks itself — format, matrix, strides smaller than a plane, alignment, overlap — is left to it
+    const size_t fsz = yuv_frame_bytes(w, h);
+    bool inside = fsz && frames_fit(soff, (size_t)n, stride ? stride : fsz, fsz, src->bytes);
+    if (dst) {
+        const size_t fb = frame_bytes(env, L.ctx, 4, "drawFramesYuvDevice");
+        if (!fb) return nullptr;
+        inside = inside && frames_fit(doff, (size_t)n, dstride ? dstride : fb, fb, dst->bytes);
+    }
+    if (!inside) return range_error(env, (std::string(usage) + ": outside the device buffer").c_str());
+    ht_yuv_frames d;
+    std::memset(&d, 0, sizeof(d));
+    const char *base = static_cast<char *>(src->ptr) + soff;
+    const size_t cplane = (size_t)((w + 1) / 2) * ((h + 1) / 2);
+    d.y = base, d.u = base + (size_t)w * h, d.v = format == HT_YUV_I420 ? base + (size_t)w * h + cplane : nullptr;
+    d.frame_stride = stride ? stride : (n > 1 ? fsz : 0);
+    d.width = w, d.height = h, d.format = format, d.matrix = matrix;
+    ht_status st = ht_draw_frames_yuv_device(L.ctx, &d, n, rp, dst ? static_cast<char *>(dst->ptr) + doff : nullptr, dstride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_draw_frames_yuv_device");
+    if (wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
+    return nullptr;
+}
+
 napi_value ctx_counter(napi_env env, napi_callback_info info, int which) {
     Args a(env, info, 1);
     Locked L;
@@ -1327,6 +1393,7 @@ napi_value Init(napi_env env, napi_value exports) {
                {"camshiftBackProject", CamshiftBackProject}, {"camshiftBackProjectDevice", CamshiftBackProjectDevice},
                {"camshiftBackProjectPairs", CamshiftBackProjectPairs}, {"camshiftBackProjectPairsDevice", CamshiftBackProjectPairsDevice},
                {"drawFrames", DrawFrames},       {"drawFramesDevice", DrawFramesDevice},
+               {"drawFramesYuv", DrawFramesYuv}, {"drawFramesYuvDevice", DrawFramesYuvDevice},
                {"detectBestEnqueue", DetectBestEnqueue}, {"collectBestDevice", CollectBestDevice}, {"detectGrouped", DetectGrouped},
                {"detectBestRecords", DetectBestRecords}, {"groupHits", GroupHits},
                {"framesBound", FramesBound},     {"framesEnqueued", FramesEnqueued}, {"graphLaunches", GraphLaunches}};
@@ -1340,6 +1407,7 @@ napi_value Init(napi_env env, napi_value exports) {
         int32_t value;
     } consts[] = {{"abiVersion", ht_abi_version()},   {"INPUT_GRAY_IN_R", HT_INPUT_GRAY_IN_R}, {"INPUT_RGBA", HT_INPUT_RGBA}, {"DETECT_WHITEBALANCE", HT_DETECT_WHITEBALANCE},
                   {"SCAN_STATS", HT_SCAN_STATS},      {"BP_RGBA8", HT_BP_RGBA8},               {"BP_F64", HT_BP_F64},
+                  {"YUV_NV12", HT_YUV_NV12},          {"YUV_I420", HT_YUV_I420},
                   {"CSB_UNTOUCHED", HT_CSB_UNTOUCHED}, {"CSB_FACE", HT_CSB_FACE},              {"CSB_FALLBACK", HT_CSB_FALLBACK}, {"CSB_DEFERRED", HT_CSB_DEFERRED}};
     for (auto &c : consts) {
         napi_value v;

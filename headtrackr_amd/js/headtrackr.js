@@ -23,7 +23,8 @@
  *                                        collect-best / re-enqueue), fused whitebalance, camshift call sequences — the JS form
  *                                        of the loop bench.py times; every C-ABI export has a JS name (INTEGRATION.md)
  *   hostAlloc(bytes)                     pinned host memory for frames that cross PCIe every call
- *   ccv.drawFrames(video, canvas[, rect])  the loop's video -> canvas drawImage (main.js:170) scaled on the device -> ht_draw_frames_device
+ *   ccv.drawFrames(video, canvas[, rect])  the loop's video -> canvas drawImage (main.js:170) scaled on the device -> ht_draw_frames_device;
+ *                                           video may be {width, height, format: 'nv12' | 'i420', matrix, data} -> ht_draw_frames_yuv_device
  *
  * "canvas" is anything with width, height and getContext('2d') -> {getImageData, putImageData, drawImage,
  * createImageData}; ./canvas.js provides one for Node.  Failure conventions are the reference's: empty arrays,
@@ -155,8 +156,44 @@ headtrackr.ccv.grayscale = function (canvas) { /* ccv.js:22-32, in place, return
  * canvas.height), or with rect = [sx, sy, sw, sh] (wholly inside the video) the 9-argument form.  The video's pixels are uploaded, scaled
  * with the declared resampler (ht_draw_frames_device) and copied back into the canvas: the bytes canvas.js's drawImage writes.  With an
  * addon that lacks the calls the canvas's own drawImage does it. */
+/* YUV 4:2:0 sources (NV12 / I420): names -> the numbers of include/headtrackr_hip.h, and the packed layout every YUV call here uses: a
+ * frame is Y (w h bytes), then UV (NV12) or U, V (I420), ceil(w/2) x ceil(h/2) chroma samples.  NV12's chroma plane has to start at an
+ * even device address: a frame of odd width and odd height is placed `lead` = 1 byte into its buffer, frames `step` = bytes + 1 apart. */
+const YUV_FORMATS = { nv12: 0, i420: 1 }, YUV_MATRICES = { bt601: 0, bt709: 1, 'bt601-full': 2, 'bt709-full': 3 };
+function yuvLayout(width, height, format, matrix, who) {
+  const fmt = YUV_FORMATS[format], mat = YUV_MATRICES[matrix === undefined ? 'bt601' : matrix];
+  if (fmt === undefined) throw new RangeError(who + ": format is 'nv12' or 'i420'");
+  if (mat === undefined) throw new RangeError(who + ": matrix is 'bt601', 'bt709', 'bt601-full' or 'bt709-full'");
+  if (!(width > 0 && height > 0)) throw new RangeError(who + ': width and height must be positive');
+  const bytes = width * height + 2 * ((width + 1) >> 1) * ((height + 1) >> 1), lead = fmt === 0 ? (bytes & 1) : 0;
+  return { fmt: fmt, mat: mat, bytes: bytes, lead: lead, step: bytes + lead };
+}
+
 headtrackr.ccv.drawFrames = function (video, canvas, rect) {
   const w = canvas.width, h = canvas.height, vw = video.width, vh = video.height, ctx2d = canvas.getContext('2d'), A = addon();
+  const grow = function (c, key, bytes) { /* two device buffers per context, kept between calls */
+    if (!c[key] || c[key + 'Bytes'] < bytes) {
+      if (c[key]) A.deviceFree(c.handle, c[key]);
+      c[key] = A.deviceAlloc(c.handle, bytes); c[key + 'Bytes'] = bytes;
+    }
+    return c[key];
+  };
+  if (video.format !== undefined && video.format !== 'rgba') {
+    /* a video-like object {width, height, format: 'nv12' | 'i420', matrix, data: Uint8Array}: there is no host route — a canvas cannot
+     * draw planes — so an addon without the call is an error */
+    const L = yuvLayout(vw, vh, video.format, video.matrix, 'ccv.drawFrames');
+    if (typeof A.drawFramesYuvDevice !== 'function') throw new Error('ccv.drawFrames: this headtrackr_hip.node has no drawFramesYuvDevice (rebuild it)');
+    if (!(video.data instanceof Uint8Array) || video.data.length < L.bytes) throw new RangeError('ccv.drawFrames: video.data is a Uint8Array of w*h + 2*ceil(w/2)*ceil(h/2) bytes');
+    if (!(w > 0 && h > 0)) return canvas;
+    const c = contextFor(headtrackr.cascade, 5);
+    ensureGeometry(c, w, h, 1, headtrackr.cascade, 5);
+    const out = ctx2d.createImageData(w, h), dsrc = grow(c, 'drawSrc', L.lead + L.bytes), ddst = grow(c, 'drawDst', w * h * 4);
+    A.deviceUpload(c.handle, dsrc, L.lead, video.data.subarray(0, L.bytes));
+    A.drawFramesYuvDevice(c.handle, dsrc, L.lead, 1, vw, vh, L.fmt, L.mat, 0, rect ? Int32Array.from(rect) : null, ddst, 0, 0, false);
+    A.deviceDownload(c.handle, ddst, 0, out.data);
+    ctx2d.putImageData(out, 0, 0);
+    return canvas;
+  }
   if (typeof A.drawFramesDevice !== 'function' || typeof A.deviceDownload !== 'function' || !(w > 0 && h > 0 && vw > 0 && vh > 0)) {
     if (rect) ctx2d.drawImage(video, rect[0], rect[1], rect[2], rect[3], 0, 0, w, h); else ctx2d.drawImage(video, 0, 0, w, h);
     return canvas;
@@ -164,14 +201,7 @@ headtrackr.ccv.drawFrames = function (video, canvas, rect) {
   const c = contextFor(headtrackr.cascade, 5);
   ensureGeometry(c, w, h, 1, headtrackr.cascade, 5);
   const src = video.getContext('2d').getImageData(0, 0, vw, vh), out = ctx2d.createImageData(w, h);
-  const grow = function (key, bytes) { /* two device buffers per context, kept between calls */
-    if (!c[key] || c[key + 'Bytes'] < bytes) {
-      if (c[key]) A.deviceFree(c.handle, c[key]);
-      c[key] = A.deviceAlloc(c.handle, bytes); c[key + 'Bytes'] = bytes;
-    }
-    return c[key];
-  };
-  const dsrc = grow('drawSrc', vw * vh * 4), ddst = grow('drawDst', w * h * 4);
+  const dsrc = grow(c, 'drawSrc', vw * vh * 4), ddst = grow(c, 'drawDst', w * h * 4);
   A.deviceUpload(c.handle, dsrc, 0, src.data);
   A.drawFramesDevice(c.handle, dsrc, 0, 1, vw, vh, 0, 0, rect ? Int32Array.from(rect) : null, ddst, 0, 0, false);
   A.deviceDownload(c.handle, ddst, 0, out.data); /* behind the draw on the context's stream; waits */
@@ -398,6 +428,9 @@ headtrackr.ccv.detect_objects_batch = function (frames, n, w, h, cascade, interv
  *   opts.source = {width, height, sets}: a second device buffer of `sets` SOURCE-size frame sets (n frames of width x height each) and the
  *   loop's video -> canvas drawImage (main.js:170) between the two buffers, on the device (ht_draw_frames_device):
  *     uploadSource(frames, sset = 0)       host -> HBM once (frames: Uint8Array of n*width*height*4 bytes)
+ *   opts.sourceFormat = 'nv12' | 'i420' (+ opts.sourceMatrix = 'bt601' (default) | 'bt709' | 'bt601-full' | 'bt709-full'): the source sets
+ *   hold YUV 4:2:0 frames, each packed Y, then UV or U, V (width*height + 2*ceil(width/2)*ceil(height/2) bytes): uploadSource, draw and
+ *   drawBound then move and read 1.5 B/px, the colour conversion is fused into the draw (ht_draw_frames_yuv_device)
  *     draw(sset, set, rect)                source set `sset` scaled onto work set `set` (rect: Int32Array [x, y, width, height] inside a source
  *                                           frame, default the whole frame); enqueue only, except that with depth > 1 it waits — the other
  *                                           contexts read the work set on streams of their own
@@ -710,21 +743,31 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     return A.camshiftBackProjectPairs(ctxs[0], pairs, kind === 'f64' ? A.BP_F64 : A.BP_RGBA8);
   };
   const source = opts.source || null;
-  const ssetBytes = source ? n * source.width * source.height * 4 : 0;
+  /* opts.sourceFormat 'nv12' | 'i420' (+ opts.sourceMatrix): the source sets hold YUV 4:2:0 frames at 1.5 B/px, packed as yuvLayout says */
+  const yuv = source && opts.sourceFormat !== undefined && opts.sourceFormat !== 'rgba' ? yuvLayout(source.width, source.height, opts.sourceFormat, opts.sourceMatrix, 'DeviceBatch') : null;
+  if (yuv && typeof A.drawFramesYuvDevice !== 'function') throw new Error('DeviceBatch: this headtrackr_hip.node has no drawFramesYuvDevice (rebuild it) — needed for opts.sourceFormat');
+  const sframeBytes = source ? (yuv ? yuv.bytes : source.width * source.height * 4) : 0;
+  const ssetBytes = source ? (yuv ? n * yuv.step + 2 * yuv.lead : n * sframeBytes) : 0; /* (a YUV set keeps the parity of its base) */
   const sdev = source ? A.deviceAlloc(ctxs[0], Math.max(1, source.sets || 1) * ssetBytes) : null;
   const needSource = function (what) { if (!sdev) throw new Error('DeviceBatch.' + what + ': created without opts.source'); };
+  const ssetBase = function (sset) { return (sset || 0) * ssetBytes + (yuv ? yuv.lead : 0); };
   this.uploadSource = function (frames, sset) {
     needSource('uploadSource');
-    if (frames.length < ssetBytes) throw new RangeError('DeviceBatch.uploadSource: need n*width*height*4 bytes');
-    A.deviceUpload(ctxs[0], sdev, (sset || 0) * ssetBytes, frames.subarray(0, ssetBytes));
+    if (frames.length < n * sframeBytes) throw new RangeError('DeviceBatch.uploadSource: need ' + (yuv ? 'n*(width*height + 2*ceil(width/2)*ceil(height/2))' : 'n*width*height*4') + ' bytes');
+    if (!yuv || yuv.step === yuv.bytes) { A.deviceUpload(ctxs[0], sdev, ssetBase(sset), frames.subarray(0, n * sframeBytes)); return; }
+    for (let f = 0; f < n; f++) A.deviceUpload(ctxs[0], sdev, ssetBase(sset) + f * yuv.step, frames.subarray(f * yuv.bytes, (f + 1) * yuv.bytes));
+  };
+  const drawSource = function (sset, rect, dst, doff, wait) {
+    if (yuv) A.drawFramesYuvDevice(ctxs[0], sdev, ssetBase(sset), n, source.width, source.height, yuv.fmt, yuv.mat, yuv.step, rect || null, dst, doff, 0, wait);
+    else A.drawFramesDevice(ctxs[0], sdev, ssetBase(sset), n, source.width, source.height, 0, 0, rect || null, dst, doff, 0, wait);
   };
   this.draw = function (sset, set, rect) {
     needSource('draw');
-    A.drawFramesDevice(ctxs[0], sdev, (sset || 0) * ssetBytes, n, source.width, source.height, 0, 0, rect || null, dev, (set || 0) * setBytes, 0, depth > 1);
+    drawSource(sset, rect, dev, (set || 0) * setBytes, depth > 1);
   };
   this.drawBound = function (sset, rect) {
     needSource('drawBound');
-    A.drawFramesDevice(ctxs[0], sdev, (sset || 0) * ssetBytes, n, source.width, source.height, 0, 0, rect || null, null, 0, 0, false);
+    drawSource(sset, rect, null, 0, false);
     bound = -1;
   };
   this.graphLaunches = function () { return ctxs.reduce(function (s, c) { return s + A.graphLaunches(c); }, 0); };

@@ -206,6 +206,30 @@ ht_status ht_draw_frames_device(ht_ctx *ctx, const void *src_dev, int32_t n, int
 ht_status ht_draw_frames(ht_ctx *ctx, const uint8_t *host_rgba, int32_t n, int32_t src_width, int32_t src_height,
                          size_t src_frame_stride, const ht_cs_rect *src_rect);
 
+/* The same draw for frames that arrive as YUV 4:2:0, 8 bits per sample: the colour conversion a browser's drawImage(video, ..) hides is
+ * fused into the draw.  The conversion is DECLARED (csrc/ht_yuv_plan.h), integer-only and so the same bits everywhere: with C = Y - yoff,
+ * D = U - 128, E = V - 128, R = clamp((cy C + crv E + 128) >> 8), G = clamp((cy C + cgu D + cgv E + 128) >> 8), B = clamp((cy C + cbu D +
+ * 128) >> 8), A = 255.  The chroma sample of source pixel (x, y) is sample (x >> 1, y >> 1) of the FRAME, replicated; odd widths and
+ * heights are legal, the chroma planes are ceil(w / 2) x ceil(h / 2).  The result is, byte for byte, what ht_draw_frames_device gives on
+ * the RGBA frame that conversion produces. */
+enum { HT_YUV_NV12 = 0 /* Y plane + one plane of interleaved U V pairs */, HT_YUV_I420 = 1 /* Y, U, V planes */ };
+enum { HT_YUV_BT601_LIMITED = 0, HT_YUV_BT709_LIMITED = 1, HT_YUV_BT601_FULL = 2, HT_YUV_BT709_FULL = 3 };
+typedef struct ht_yuv_frames {
+    const void *y, *u, *v;   /* NV12: u = the interleaved UV plane, v = NULL */
+    size_t y_pitch;          /* 0 = width */
+    size_t c_pitch;          /* 0 = packed */
+    size_t frame_stride;     /* added to every plane pointer per frame; 0 = device form refuses n > 1 */
+    int32_t width, height, format, matrix;
+} ht_yuv_frames;
+/* Device-resident planes.  dst_dev, dst_frame_stride, src_rect, binding and errors as ht_draw_frames_device; the overlap refusals apply
+ * per plane.  NV12's chroma base, chroma pitch and frame stride must be even; the Y plane and I420's chroma planes need no alignment. */
+ht_status ht_draw_frames_yuv_device(ht_ctx *ctx, const ht_yuv_frames *src_dev, int32_t n, const ht_cs_rect *src_rect, void *dst_dev,
+                                    size_t dst_frame_stride);
+/* Host-resident frames, each tightly packed: Y, then UV (NV12) or U, then V (I420), w h + 2 cw ch bytes, frames frame_stride apart
+ * (0 = packed).  Staged through the context-owned device buffer of ht_draw_frames at 1.5 B/px; result bound; host reusable on return. */
+ht_status ht_draw_frames_yuv(ht_ctx *ctx, const uint8_t *host, int32_t n, int32_t width, int32_t height, int32_t format, int32_t matrix,
+                             size_t frame_stride, const ht_cs_rect *src_rect);
+
 /* ---- detect: ccv.grayscale + ccv.detect_objects (ccv.js:22-32, 109-246) ---------------------------------- */
 
 /* Enqueues gray -> pyramid -> cascade scan for the bound frames on the stream and returns immediately. */
