@@ -184,6 +184,27 @@ class Context:
         if dst is None:
             self.nframes = n
 
+    # -- one launch for a list of per-feed sources ----------------------------------------------------------------
+    def draw_list(self, entries, dst: int | None = None, dst_stride: int = 0):
+        """entries: one dict per feed, drawn onto destination frame i in ONE launch (ht_draw_list_device) —
+        {"format": 'rgba' | 'nv12' | 'i420' (or the code), "width", "height", "p0", "p1", "p2" (device pointers: RGBA p0; NV12 Y, UV; I420
+        Y, U, V), "pitch0", "pitch1" (bytes per row, 0 = packed), "matrix" (as draw_frames_yuv_device, ignored for RGBA), "rect" (x, y,
+        width, height) or None = the whole source}.  Every feed may have its own allocation, size, format, matrix and rect; pointers may
+        repeat.  dst as draw_frames_device()."""
+        n = len(entries)
+        arr = (native.DRAW_SOURCE * max(n, 1))()
+        for s, e in zip(arr, entries):
+            s.p0, s.p1, s.p2 = e.get("p0"), e.get("p1"), e.get("p2")
+            s.pitch0, s.pitch1 = int(e.get("pitch0", 0)), int(e.get("pitch1", 0))
+            s.width, s.height = int(e["width"]), int(e["height"])
+            s.format = self._yuv_code(native.DRAW_FORMATS, e.get("format", "rgba"), "format")
+            s.matrix = self._yuv_code(native.YUV_MATRICES, e.get("matrix", "bt601"), "matrix")
+            if e.get("rect") is not None:
+                s.rect = native.CS_RECT(*(int(v) for v in e["rect"]))
+        self._check(self._lib.ht_draw_list_device(self._h, arr, n, dst, dst_stride))
+        if dst is None:
+            self.nframes = n
+
     # -- detect -----------------------------------------------------------------------------------------------
     def detect_enqueue(self, flags: int = HT_INPUT_RGBA):
         self._check(self._lib.ht_detect_enqueue(self._h, flags))

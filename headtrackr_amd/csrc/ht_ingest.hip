@@ -21,6 +21,7 @@
 // code object besides those three (tests/test_backproject_cpu.py).
 #include <algorithm>
 #include <string>
+#include <type_traits>
 
 #include "ht_internal.h"
 #include "ht_resample_tap.h"
@@ -47,50 +48,11 @@ __device__ __forceinline__ uint32_t ig_channel(uint32_t p00, uint32_t p01, uint3
 __global__ __launch_bounds__(IG_NT) void k_draw_frames(const uint8_t *__restrict__ src, size_t src_pitch, size_t src_stride, uint8_t *__restrict__ dst,
                                                        size_t dst_stride, int sx, int sy, int sw, int sh, int dw, int dh, double rx, double ry) {
     __shared__ RsTap s_col[IG_TW], s_row[IG_TH];
-    const int X0 = blockIdx.x * IG_TW, Y0 = blockIdx.y * IG_TH;
-    if (threadIdx.x < IG_TW) s_col[threadIdx.x] = rs_tap(min(X0 + (int)threadIdx.x, dw - 1), rx, sw, sx);
-    else if (threadIdx.x < IG_TW + IG_TH) s_row[threadIdx.x - IG_TW] = rs_tap(min(Y0 + (int)threadIdx.x - IG_TW, dh - 1), ry, sh, sy);
+#define IG_BODY_PART 1  // IG_BODY_TAPS
+#include "ht_ingest_bodies.inc"
     __syncthreads();
-    const int col = threadIdx.x & (IG_TW - 1), r0 = threadIdx.x / IG_TW, x = X0 + col;
-    if (x >= dw) return;
-    const RsTap cx = s_col[col];
-    // the tap pair (a, b) as ONE 8-byte read: b == a + 1 unless a is the rect's last column (then b == a and the pair is read one
-    // pixel to the left, both taps taking its right half); a 1-pixel-wide rect has no pair and is read pixel by pixel
-    const bool pair = sw >= 2;
-    const int xa = pair ? min(cx.a, sx + sw - 2) : cx.a;
-    const bool right = cx.a != xa;
-    const uint8_t *frame = src + (size_t)blockIdx.z * src_stride + (size_t)xa * 4;
-    ig_u32x2 top2[IG_RPT], bot2[IG_RPT];
-    double ru[IG_RPT], rt[IG_RPT];
-    bool on[IG_RPT];
-#pragma unroll
-    for (int k = 0; k < IG_RPT; k++) {
-        const int j = r0 + k * (IG_NT / IG_TW);
-        on[k] = Y0 + j < dh;
-        const RsTap ty = s_row[j];
-        ru[k] = ty.u, rt[k] = ty.t;
-        top2[k] = bot2[k] = ig_u32x2{0u, 0u};
-        if (on[k]) {
-            const uint8_t *pa = frame + (size_t)ty.a * src_pitch, *pb = frame + (size_t)ty.b * src_pitch;
-            if (pair) {
-                top2[k] = *reinterpret_cast<const ig_u32x2 *>(pa);
-                bot2[k] = *reinterpret_cast<const ig_u32x2 *>(pb);
-            } else {
-                top2[k].x = top2[k].y = *reinterpret_cast<const uint32_t *>(pa);
-                bot2[k].x = bot2[k].y = *reinterpret_cast<const uint32_t *>(pb);
-            }
-        }
-    }
-    uint32_t *out = reinterpret_cast<uint32_t *>(dst + (size_t)blockIdx.z * dst_stride) + x;
-#pragma unroll
-    for (int k = 0; k < IG_RPT; k++) {
-        if (!on[k]) continue;
-        const uint32_t p00 = right ? top2[k].y : top2[k].x, p01 = top2[k].y, p10 = right ? bot2[k].y : bot2[k].x, p11 = bot2[k].y;
-        uint32_t o = 0;
-#pragma unroll
-        for (int ch = 0; ch < 4; ch++) o |= ig_channel(p00, p01, p10, p11, 8 * ch, cx.u, cx.t, ru[k], rt[k]);
-        out[(size_t)(Y0 + r0 + k * (IG_NT / IG_TW)) * dw] = o;
-    }
+#define IG_BODY_PART 2  // IG_BODY_RGBA: per pixel, four times ig_channel(p00, p01, p10, p11, ..)
+#include "ht_ingest_bodies.inc"
 }
 
 struct IgPlan {  // a validated call
@@ -211,6 +173,16 @@ extern "C" ht_status ht_draw_frames(ht_ctx *c, const uint8_t *host_rgba, int32_t
 void ht_ingest_free(ht_ctx *c) {  // ht_destroy (the stream has been synchronised)
     if (c->d_ingest_src) (void)hipFree(c->d_ingest_src);
     c->d_ingest_src = nullptr, c->ingest_src_cap = 0;
+    // ht_draw_list_device's descriptor table, its pinned staging slots and their events (ht_draw_list.hip)
+    if (c->d_dl_tab) (void)hipFree(c->d_dl_tab);
+    c->d_dl_tab = nullptr, c->dl_tab_cap = 0;
+    for (int k = 0; k < ht_ctx::HT_DL_STAGE; k++) {
+        if (c->h_dl_tab[k]) (void)hipHostFree(c->h_dl_tab[k]);
+        if (c->ev_dl_tab[k]) (void)hipEventDestroy(c->ev_dl_tab[k]);
+        c->h_dl_tab[k] = nullptr, c->ev_dl_tab[k] = nullptr;
+    }
+    c->dl_stage_next = 0;
 }
 
 #include "ht_ingest_yuv.hip"  // the same draw for YUV 4:2:0 frames (shares ig_channel and the tile constants)
+#include "ht_draw_list.hip"   // one launch for a list of per-feed sources (shares the pixel bodies of both files)

@@ -45,59 +45,11 @@ __global__ __launch_bounds__(IG_NT) void k_draw_yuv(const uint8_t *__restrict__ 
                                                     size_t y_pitch, size_t c_pitch, size_t stride, uint8_t *__restrict__ dst, size_t dst_stride, int sx,
                                                     int sy, int sw, int sh, int cw, int dw, int dh, double rx, double ry, HtYuvCoef kc) {
     __shared__ RsTap s_col[IG_TW], s_row[IG_TH];
-    const int X0 = blockIdx.x * IG_TW, Y0 = blockIdx.y * IG_TH;
-    if (threadIdx.x < IG_TW) s_col[threadIdx.x] = rs_tap(min(X0 + (int)threadIdx.x, dw - 1), rx, sw, sx);
-    else if (threadIdx.x < IG_TW + IG_TH) s_row[threadIdx.x - IG_TW] = rs_tap(min(Y0 + (int)threadIdx.x - IG_TW, dh - 1), ry, sh, sy);
+#define IG_BODY_PART 1  // IG_BODY_TAPS
+#include "ht_ingest_bodies.inc"
     __syncthreads();
-    const int col = threadIdx.x & (IG_TW - 1), r0 = threadIdx.x / IG_TW, x = X0 + col;
-    if (x >= dw) return;
-    const RsTap cx = s_col[col];
-    const bool pair = sw >= 2;
-    const int xa = pair ? min(cx.a, sx + sw - 2) : cx.a;  // the Y pair's anchor, inside the rect
-    const int ya_sel = cx.a - xa, yb_sel = cx.b - xa;      // 0 / 1: which byte of the pair each tap takes
-    const bool cpair = cw >= 2;
-    const int ca = cpair ? min(cx.a >> 1, cw - 2) : 0;     // the chroma pair's anchor, inside the frame's chroma row
-    const int ca_sel = (cx.a >> 1) - ca, cb_sel = (cx.b >> 1) - ca;
-    const size_t foff = (size_t)blockIdx.z * stride;
-    const uint8_t *yf = yp + foff + (size_t)xa, *uf = up + foff, *vf = FMT == HT_YUV_FMT_NV12 ? uf : vp + foff;
-    uint32_t ytop[IG_RPT], ybot[IG_RPT], ctop[IG_RPT], cbot[IG_RPT];
-    double ru[IG_RPT], rt[IG_RPT];
-    bool on[IG_RPT];
-#pragma unroll
-    for (int k = 0; k < IG_RPT; k++) {
-        const int j = r0 + k * (IG_NT / IG_TW);
-        on[k] = Y0 + j < dh;
-        const RsTap ty = s_row[j];
-        ru[k] = ty.u, rt[k] = ty.t;
-        ytop[k] = ybot[k] = ctop[k] = cbot[k] = 0u;
-        if (on[k]) {
-            const uint8_t *pa = yf + (size_t)ty.a * y_pitch, *pb = yf + (size_t)ty.b * y_pitch;
-            if (pair) {
-                ytop[k] = *reinterpret_cast<const ig_u16b *>(pa);
-                ybot[k] = *reinterpret_cast<const ig_u16b *>(pb);
-            } else {
-                ytop[k] = *pa;
-                ybot[k] = *pb;
-            }
-            ctop[k] = ig_chroma_read<FMT>(uf, vf, (size_t)(ty.a >> 1) * (FMT == HT_YUV_FMT_NV12 ? c_pitch / 2 : c_pitch) + (size_t)ca, cpair);
-            cbot[k] = ig_chroma_read<FMT>(uf, vf, (size_t)(ty.b >> 1) * (FMT == HT_YUV_FMT_NV12 ? c_pitch / 2 : c_pitch) + (size_t)ca, cpair);
-        }
-    }
-    uint32_t *out = reinterpret_cast<uint32_t *>(dst + (size_t)blockIdx.z * dst_stride) + x;
-#pragma unroll
-    for (int k = 0; k < IG_RPT; k++) {
-        if (!on[k]) continue;
-        // the four tap pixels as the RGBA8 dwords k_draw_frames would have read
-        const uint32_t ta = ctop[k] >> (16 * ca_sel), tb = ctop[k] >> (16 * cb_sel), ba = cbot[k] >> (16 * ca_sel), bb = cbot[k] >> (16 * cb_sel);
-        const uint32_t p00 = ht_yuv_to_rgba((ytop[k] >> (8 * ya_sel)) & 0xffu, ta & 0xffu, (ta >> 8) & 0xffu, kc);
-        const uint32_t p01 = ht_yuv_to_rgba((ytop[k] >> (8 * yb_sel)) & 0xffu, tb & 0xffu, (tb >> 8) & 0xffu, kc);
-        const uint32_t p10 = ht_yuv_to_rgba((ybot[k] >> (8 * ya_sel)) & 0xffu, ba & 0xffu, (ba >> 8) & 0xffu, kc);
-        const uint32_t p11 = ht_yuv_to_rgba((ybot[k] >> (8 * yb_sel)) & 0xffu, bb & 0xffu, (bb >> 8) & 0xffu, kc);
-        uint32_t o = 0;
-#pragma unroll
-        for (int ch = 0; ch < 4; ch++) o |= ig_channel(p00, p01, p10, p11, 8 * ch, cx.u, cx.t, ru[k], rt[k]);
-        out[(size_t)(Y0 + r0 + k * (IG_NT / IG_TW)) * dw] = o;
-    }
+#define IG_BODY_PART 3  // IG_BODY_YUV: the four tap pixels converted by ht_yuv_to_rgba, then ig_channel(p00, p01, p10, p11, ..) per channel
+#include "ht_ingest_bodies.inc"
 }
 
 struct IgYuvCall {  // a validated call: the source as the device will see it

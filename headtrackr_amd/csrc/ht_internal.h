@@ -297,6 +297,13 @@ struct ht_ctx {
     // ingest (ht_ingest.hip): device staging of ht_draw_frames' host-resident source frames, grown on demand
     uint8_t *d_ingest_src = nullptr;
     size_t ingest_src_cap = 0;
+    // ht_draw_list_device (ht_draw_list.hip): the descriptor table on the device and the ring of pinned slots a call's table is staged
+    // in; a slot's event is recorded behind its copy, and the slot is written again only after that event (both hold dl_tab_cap bytes)
+    static constexpr int HT_DL_STAGE = 4;
+    uint8_t *d_dl_tab = nullptr, *h_dl_tab[HT_DL_STAGE] = {};
+    hipEvent_t ev_dl_tab[HT_DL_STAGE] = {};
+    size_t dl_tab_cap = 0;
+    int dl_stage_next = 0;
 
     std::vector<std::pair<void *, size_t>> user_allocs;  // ht_device_alloc buffers still alive (pointer, bytes): freed by ht_destroy at the latest
 
@@ -398,7 +405,7 @@ void ht_camshift_free(ht_ctx *ctx);                         // ht_camshift.hip: 
 void ht_backproject_free(ht_ctx *ctx);                      // ht_backproject.hip: its scratch (ht_destroy)
 void ht_cs_pairs_free(ht_ctx *ctx);                         // ht_cs_pairs.hip: pair table, staging and histogram scratch (ht_destroy)
 void ht_cs_best_free(ht_ctx *ctx);                          // ht_cs_best.hip: the result buffers of ht_camshift_init_best (ht_destroy)
-void ht_ingest_free(ht_ctx *ctx);                           // ht_ingest.hip: the host form's source staging (ht_destroy)
+void ht_ingest_free(ht_ctx *ctx);                           // ht_ingest.hip: the host form's source staging, the draw list's table (ht_destroy)
 void ht_group_free(ht_ctx *ctx);                            // ht_group.hip: the device grouping's buffers (ht_destroy)
 ht_status ht_detect_mark_collected(ht_ctx *ctx, bool wb_snap);  // ht_context.hip: the state every collect call leaves behind
 ht_status ht_frames_own_reserve(ht_ctx *ctx, size_t need, const char *fn);  // ht_context.hip: the context's own frame buffer holds >= need bytes

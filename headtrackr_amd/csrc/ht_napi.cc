@@ -56,6 +56,9 @@
 //       YUV 4:2:0 (format 0 = NV12, 1 = I420; matrix 0 .. 3), each tightly packed (Y, then UV or U, V); the conversion is fused into the draw
 //   drawFramesYuvDevice(ctx, srcDev, srcOffset, n, w, h, format, matrix, stride, rect | null, dstDev | null, dstOffset, dstStride, wait)
 //       ht_draw_frames_yuv_device on frames packed the same way inside a device buffer, `stride` bytes apart (0 = packed)
+//   drawListDevice(ctx, entries, dstDev | null, dstStride, dstOffset = 0, wait = false)   ht_draw_list_device: ONE launch draws entries[i] onto
+//       frame i; an entry is {dev, offset, width, height, format (YUV_NV12 | YUV_I420 | DRAW_RGBA), matrix, rect: Int32Array[4] | null} and
+//       names ONE frame packed at byte `offset` of its own deviceAlloc() buffer (RGBA rows; Y, then UV or U, V)
 //   framesBound(ctx), framesEnqueued(ctx), graphLaunches(ctx)
 #include <node_api.h>
 
@@ -1358,6 +1361,74 @@ napi_value DrawFramesYuvDevice(napi_env env, napi_callback_info info) {
     return nullptr;
 }
 
+// one entry of drawListDevice: the properties through the getters every entry point uses, the frame checked against its buffer
+bool get_draw_entry(napi_env env, napi_value e, ht_draw_source *s) {
+    napi_valuetype vt;
+    napi_value v;
+    DevBuf *dev = nullptr;
+    size_t off = 0;
+    std::memset(s, 0, sizeof(*s));
+    if (napi_typeof(env, e, &vt) != napi_ok || vt != napi_object) return type_error(env, "drawListDevice: an entry is {dev, offset, width, height, format, matrix, rect}") != nullptr;
+    if (!get_prop(env, e, "dev", &v) || !get_devbuf(env, v, &dev)) {
+        bool pending = false;
+        if (napi_is_exception_pending(env, &pending) == napi_ok && !pending) type_error(env, "drawListDevice: entry.dev must be a live device buffer");
+        return false;
+    }
+    if (!get_prop(env, e, "width", &v) || !get_i32(env, v, &s->width) || !get_prop(env, e, "height", &v) || !get_i32(env, v, &s->height))
+        return type_error(env, "drawListDevice: entry.width and entry.height are integers") != nullptr;
+    if (!get_prop(env, e, "format", &v) || !get_i32(env, v, &s->format)) return type_error(env, "drawListDevice: entry.format is YUV_NV12, YUV_I420 or DRAW_RGBA") != nullptr;
+    // optional like the trailing arguments of the entry points: absent or undefined is 0; anything else has to be a byte offset
+    if (get_prop(env, e, "offset", &v) && napi_typeof(env, v, &vt) == napi_ok && vt != napi_undefined && !get_offset(env, v, &off))
+        return type_error(env, "drawListDevice: entry.offset is a byte offset") != nullptr;
+    prop_i32(env, e, "matrix", &s->matrix);
+    const ht_cs_rect *rp = nullptr;
+    if (get_prop(env, e, "rect", &v) && !get_rect(env, v, &s->rect, &rp)) return type_error(env, "drawListDevice: entry.rect is null or an Int32Array [x, y, width, height]") != nullptr;
+    if (rp && rp->width == 0 && rp->height == 0) s->rect.width = -1;  // an empty rect is an error, not "the whole source": the library refuses it
+    // what the library checks itself — format, matrix, alignment, the rect, overlap — is left to it
+    const bool rgba = s->format == HT_DRAW_RGBA;
+    const size_t ysz = s->width > 0 && s->height > 0 && s->width <= 16384 && s->height <= 16384 ? (size_t)s->width * (size_t)s->height : 0;
+    const size_t fsz = rgba ? ysz * 4 : yuv_frame_bytes(s->width, s->height);
+    if (!fsz || !frames_fit(off, 1, fsz, fsz, dev->bytes)) return range_error(env, "drawListDevice: an entry's frame lies outside its device buffer") != nullptr;
+    const char *base = static_cast<char *>(dev->ptr) + off;
+    s->p0 = base;
+    if (!rgba) {
+        s->p1 = base + ysz;
+        s->p2 = s->format == HT_YUV_I420 ? base + ysz + (size_t)((s->width + 1) / 2) * ((s->height + 1) / 2) : nullptr;
+    }
+    return true;
+}
+
+napi_value DrawListDevice(napi_env env, napi_callback_info info) {
+    static const char *usage = "drawListDevice(ctx, entries, dstDev | null, dstStride, dstOffset = 0, wait = false)";
+    Args a(env, info, 6);
+    Locked L;
+    DevBuf *dst = nullptr;
+    size_t dstride = 0, doff = 0;
+    bool wait = false, is_array = false;
+    uint32_t n = 0;
+    if (!a.ctx(4, &L) || !a.devbuf_or_null(2, &dst)) return nullptr;
+    if (napi_is_array(env, a.argv[1], &is_array) != napi_ok || !is_array || napi_get_array_length(env, a.argv[1], &n) != napi_ok || !a.offset(3, &dstride) ||
+        (a.argc > 4 && !a.offset(4, &doff)))
+        return type_error(env, usage);
+    a.opt_bool(5, &wait);
+    if (n < 1 || n > 65535) return range_error(env, (std::string(usage) + ": 1..65535 entries").c_str());
+    std::vector<ht_draw_source> srcs(n);
+    for (uint32_t i = 0; i < n; i++) {
+        napi_value e;
+        NAPI_OK(napi_get_element(env, a.argv[1], i, &e));
+        if (!get_draw_entry(env, e, &srcs[i])) return nullptr;
+    }
+    if (dst) {
+        const size_t fb = frame_bytes(env, L.ctx, 4, "drawListDevice");
+        if (!fb) return nullptr;
+        if (!frames_fit(doff, (size_t)n, dstride ? dstride : fb, fb, dst->bytes)) return range_error(env, (std::string(usage) + ": outside the device buffer").c_str());
+    }
+    ht_status st = ht_draw_list_device(L.ctx, srcs.data(), (int32_t)n, dst ? static_cast<char *>(dst->ptr) + doff : nullptr, dstride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_draw_list_device");
+    if (wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
+    return nullptr;
+}
+
 napi_value ctx_counter(napi_env env, napi_callback_info info, int which) {
     Args a(env, info, 1);
     Locked L;
@@ -1393,7 +1464,7 @@ napi_value Init(napi_env env, napi_value exports) {
                {"camshiftBackProject", CamshiftBackProject}, {"camshiftBackProjectDevice", CamshiftBackProjectDevice},
                {"camshiftBackProjectPairs", CamshiftBackProjectPairs}, {"camshiftBackProjectPairsDevice", CamshiftBackProjectPairsDevice},
                {"drawFrames", DrawFrames},       {"drawFramesDevice", DrawFramesDevice},
-               {"drawFramesYuv", DrawFramesYuv}, {"drawFramesYuvDevice", DrawFramesYuvDevice},
+               {"drawFramesYuv", DrawFramesYuv}, {"drawFramesYuvDevice", DrawFramesYuvDevice}, {"drawListDevice", DrawListDevice},
                {"detectBestEnqueue", DetectBestEnqueue}, {"collectBestDevice", CollectBestDevice}, {"detectGrouped", DetectGrouped},
                {"detectBestRecords", DetectBestRecords}, {"groupHits", GroupHits},
                {"framesBound", FramesBound},     {"framesEnqueued", FramesEnqueued}, {"graphLaunches", GraphLaunches}};
@@ -1407,7 +1478,7 @@ napi_value Init(napi_env env, napi_value exports) {
         int32_t value;
     } consts[] = {{"abiVersion", ht_abi_version()},   {"INPUT_GRAY_IN_R", HT_INPUT_GRAY_IN_R}, {"INPUT_RGBA", HT_INPUT_RGBA}, {"DETECT_WHITEBALANCE", HT_DETECT_WHITEBALANCE},
                   {"SCAN_STATS", HT_SCAN_STATS},      {"BP_RGBA8", HT_BP_RGBA8},               {"BP_F64", HT_BP_F64},
-                  {"YUV_NV12", HT_YUV_NV12},          {"YUV_I420", HT_YUV_I420},
+                  {"YUV_NV12", HT_YUV_NV12},          {"YUV_I420", HT_YUV_I420},               {"DRAW_RGBA", HT_DRAW_RGBA},
                   {"CSB_UNTOUCHED", HT_CSB_UNTOUCHED}, {"CSB_FACE", HT_CSB_FACE},              {"CSB_FALLBACK", HT_CSB_FALLBACK}, {"CSB_DEFERRED", HT_CSB_DEFERRED}};
     for (auto &c : consts) {
         napi_value v;

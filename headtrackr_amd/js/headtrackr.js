@@ -434,6 +434,11 @@ headtrackr.ccv.detect_objects_batch = function (frames, n, w, h, cascade, interv
  *     draw(sset, set, rect)                source set `sset` scaled onto work set `set` (rect: Int32Array [x, y, width, height] inside a source
  *                                           frame, default the whole frame); enqueue only, except that with depth > 1 it waits — the other
  *                                           contexts read the work set on streams of their own
+ *   opts.sources = [{width, height, format = 'rgba' | 'nv12' | 'i420', matrix, sets = 1}, ...] (instead of opts.source): one entry per feed,
+ *   every feed with its own device buffer, size and format; ONE launch draws them all (ht_draw_list_device)
+ *     uploadSourceOf(i, frame, sset = 0)   feed i's packed frame host -> HBM
+ *     drawList(sset, set, rects)           every feed onto its frame of frame set `set`; rects: null, or a rect / null per feed
+ *     drawListBound(sset, rects)           the same into context 0's own frame buffer (bound): follow with the step functions at set = -1
  *     drawBound(sset, rect)                the same into context 0's own frame buffer, which becomes its bound frames: follow with the step
  *                                           functions at set = -1
  *     backProjectionPairs(set, pairs, kind) -> the same per (tracker, frame) pair, pair order: ht_camshift_backproject_pairs
@@ -770,9 +775,62 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     drawSource(sset, rect, null, 0, false);
     bound = -1;
   };
+  /* opts.sources = [{width, height, format = 'rgba' | 'nv12' | 'i420', matrix, sets = 1}, ...]: one entry per feed, each feed with a device
+   * buffer of its own that holds `sets` packed frames (RGBA rows; Y, then UV or U, V — an odd x odd NV12 frame one byte into its slot, as
+   * yuvLayout says).  drawList / drawListBound draw all n feeds in ONE launch (ht_draw_list_device), every feed under a rect of its own. */
+  const DRAW_RGBA = 16; /* HT_DRAW_RGBA */
+  if (opts.sources !== undefined && opts.sources !== null && source) throw new Error('DeviceBatch: opts.sources together with opts.source (one or the other)');
+  let feeds = null;
+  if (opts.sources !== undefined && opts.sources !== null) {
+    if (!Array.isArray(opts.sources) || opts.sources.length !== n) throw new RangeError('DeviceBatch: opts.sources is an array with one entry per feed (' + n + ')');
+    if (typeof A.drawListDevice !== 'function') throw new Error('DeviceBatch: this headtrackr_hip.node has no drawListDevice (rebuild it) — needed for opts.sources');
+    const layouts = opts.sources.map(function (s, i) {
+      if (!s || typeof s !== 'object') throw new TypeError('DeviceBatch: opts.sources[' + i + '] is {width, height, format, matrix, sets}');
+      if (!(Number.isInteger(s.width) && Number.isInteger(s.height) && s.width > 0 && s.height > 0)) throw new RangeError('DeviceBatch: opts.sources[' + i + ']: width and height must be positive integers');
+      const sets = s.sets === undefined ? 1 : s.sets;
+      if (!(Number.isInteger(sets) && sets >= 1)) throw new RangeError('DeviceBatch: opts.sources[' + i + ']: sets must be >= 1');
+      if (s.format === undefined || s.format === 'rgba') return { width: s.width, height: s.height, fmt: DRAW_RGBA, mat: 0, bytes: s.width * s.height * 4, lead: 0, step: s.width * s.height * 4, sets: sets };
+      const L = yuvLayout(s.width, s.height, s.format, s.matrix, 'DeviceBatch: opts.sources[' + i + ']');
+      return { width: s.width, height: s.height, fmt: L.fmt, mat: L.mat, bytes: L.bytes, lead: L.lead, step: L.step, sets: sets };
+    });
+    feeds = layouts.map(function (f) { f.dev = A.deviceAlloc(ctxs[0], f.sets * f.step + 2 * f.lead); return f; });
+  }
+  const needFeeds = function (what) { if (!feeds) throw new Error('DeviceBatch.' + what + ': created without opts.sources'); };
+  const feedBase = function (f, sset, what) {
+    const k = sset === undefined ? 0 : sset;
+    if (!(Number.isInteger(k) && k >= 0 && k < f.sets)) throw new RangeError('DeviceBatch.' + what + ': source set ' + sset + ' is not one of the feed\'s ' + f.sets);
+    return k * f.step + f.lead;
+  };
+  this.uploadSourceOf = function (i, frame, sset) {
+    needFeeds('uploadSourceOf');
+    if (!(Number.isInteger(i) && i >= 0 && i < n)) throw new RangeError('DeviceBatch.uploadSourceOf: feed ' + i + ' is not one of the ' + n + ' feeds');
+    const f = feeds[i];
+    if (!frame || !(frame.length >= f.bytes)) throw new RangeError('DeviceBatch.uploadSourceOf: feed ' + i + ' needs ' + f.bytes + ' bytes');
+    A.deviceUpload(ctxs[0], f.dev, feedBase(f, sset, 'uploadSourceOf'), frame.subarray(0, f.bytes));
+  };
+  const listEntries = function (sset, rects, what) {
+    needFeeds(what);
+    if (rects !== null && rects !== undefined && (!Array.isArray(rects) || rects.length !== n)) throw new TypeError('DeviceBatch.' + what + ': rects is null or an array with a rect or null per feed');
+    return feeds.map(function (f, i) {
+      let r = rects ? rects[i] : null;
+      if (r !== null && r !== undefined) {
+        const ok = (Array.isArray(r) || r instanceof Int32Array) && r.length === 4 && Array.prototype.every.call(r, Number.isInteger);
+        if (!ok) throw new TypeError('DeviceBatch.' + what + ': rects[' + i + '] is [x, y, width, height] (integers) or null');
+        r = Int32Array.from(r);
+      }
+      return { dev: f.dev, offset: feedBase(f, sset, what), width: f.width, height: f.height, format: f.fmt, matrix: f.mat, rect: r || null };
+    });
+  };
+  this.drawList = function (sset, set, rects) {
+    A.drawListDevice(ctxs[0], listEntries(sset, rects, 'drawList'), dev, 0, (set || 0) * setBytes, depth > 1);
+  };
+  this.drawListBound = function (sset, rects) {
+    A.drawListDevice(ctxs[0], listEntries(sset, rects, 'drawListBound'), null, 0, 0, false);
+    bound = -1;
+  };
   this.graphLaunches = function () { return ctxs.reduce(function (s, c) { return s + A.graphLaunches(c); }, 0); };
   /* the frame buffer is shared by all `depth` contexts: the others go first (ht_device_free refuses while they have it bound) */
-  this.destroy = function () { for (let i = ctxs.length - 1; i >= 1; i--) A.destroy(ctxs[i]); if (sdev) A.deviceFree(ctxs[0], sdev); A.deviceFree(ctxs[0], dev); A.destroy(ctxs[0]); ctxs.length = 0; };
+  this.destroy = function () { for (let i = ctxs.length - 1; i >= 1; i--) A.destroy(ctxs[i]); if (sdev) A.deviceFree(ctxs[0], sdev); if (feeds) feeds.forEach(function (f) { A.deviceFree(ctxs[0], f.dev); }); A.deviceFree(ctxs[0], dev); A.destroy(ctxs[0]); ctxs.length = 0; };
 };
 
 /* ---- whitebalance ----------------------------------------------------------------------------------------------------- */

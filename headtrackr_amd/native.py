@@ -72,15 +72,27 @@ class YUV_FRAMES(C.Structure):
                 ("width", C.c_int32), ("height", C.c_int32), ("format", C.c_int32), ("matrix", C.c_int32)]
 
 
+class CS_RECT(C.Structure):
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class DRAW_SOURCE(C.Structure):
+    """ht_draw_source: one entry of ht_draw_list_device — a source with an allocation, size, format, matrix and rect of its own"""
+    _fields_ = [("p0", C.c_void_p), ("p1", C.c_void_p), ("p2", C.c_void_p), ("pitch0", C.c_size_t), ("pitch1", C.c_size_t),
+                ("width", C.c_int32), ("height", C.c_int32), ("format", C.c_int32), ("matrix", C.c_int32), ("rect", CS_RECT)]
+
+
 HT_YUV_NV12, HT_YUV_I420 = 0, 1
+HT_DRAW_RGBA = 16  # ht_draw_source.format beside the two above (outside the range the YUV entry points take)
 HT_YUV_BT601_LIMITED, HT_YUV_BT709_LIMITED, HT_YUV_BT601_FULL, HT_YUV_BT709_FULL = 0, 1, 2, 3
 YUV_FORMATS = {"nv12": HT_YUV_NV12, "i420": HT_YUV_I420}
+DRAW_FORMATS = dict(YUV_FORMATS, rgba=HT_DRAW_RGBA)
 YUV_MATRICES = {"bt601": HT_YUV_BT601_LIMITED, "bt709": HT_YUV_BT709_LIMITED, "bt601-full": HT_YUV_BT601_FULL, "bt709-full": HT_YUV_BT709_FULL}
 
 # every symbol include/headtrackr_hip.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = [
     "ht_create", "ht_destroy", "ht_last_error", "ht_abi_version", "ht_set_geometry", "ht_num_levels", "ht_plane",
-    "ht_windows_per_frame", "ht_pyramid_bytes_per_frame", "ht_upload_frames", "ht_upload_frames_async", "ht_swap_frames", "ht_bind_frames_device", "ht_frames_bound", "ht_frames_enqueued", "ht_host_alloc", "ht_host_free", "ht_device_alloc", "ht_device_free", "ht_device_upload", "ht_device_download", "ht_draw_frames_device", "ht_draw_frames", "ht_draw_frames_yuv_device", "ht_draw_frames_yuv", "ht_detect_enqueue",
+    "ht_windows_per_frame", "ht_pyramid_bytes_per_frame", "ht_upload_frames", "ht_upload_frames_async", "ht_swap_frames", "ht_bind_frames_device", "ht_frames_bound", "ht_frames_enqueued", "ht_host_alloc", "ht_host_free", "ht_device_alloc", "ht_device_free", "ht_device_upload", "ht_device_download", "ht_draw_frames_device", "ht_draw_frames", "ht_draw_frames_yuv_device", "ht_draw_frames_yuv", "ht_draw_list_device", "ht_detect_enqueue",
     "ht_detect_collect", "ht_detect_batch", "ht_pyramid_readback", "ht_stage_counts", "ht_grayscale_batch",
     "ht_whitebalance_batch", "ht_detect_whitebalance", "ht_hits_to_rects", "ht_group_rects", "ht_best_faces", "ht_detect_collect_best", "ht_detect_collect_best_requeue", "ht_detect_best_enqueue", "ht_detect_best_collect", "ht_detect_best_collect_requeue", "ht_detect_grouped", "ht_detect_best_records_device", "ht_group_hits", "ht_camshift_reserve", "ht_camshift_init_batch",
     "ht_camshift_track_batch", "ht_camshift_track_collect", "ht_camshift_init_pairs", "ht_camshift_track_pairs", "ht_camshift_init_best", "ht_camshift_init_best_result", "ht_camshift_track_sequence", "ht_camshift_sequence_collect", "ht_camshift_stats", "ht_camshift_debug_hist", "ht_camshift_backproject", "ht_camshift_backproject_device", "ht_camshift_backproject_pairs", "ht_camshift_backproject_pairs_device", "ht_allgather_records", "ht_allgather_best_faces", "ht_device_count", "ht_profile", "ht_kernel_times", "ht_stream", "ht_graph_launches", "ht_synchronize",
@@ -147,6 +159,8 @@ def lib():
     L.ht_draw_frames_yuv_device.argtypes = [vp, C.POINTER(YUV_FRAMES), i32, vp, vp, sz]
     L.ht_draw_frames_yuv.restype = i32
     L.ht_draw_frames_yuv.argtypes = [vp, u8p, i32, i32, i32, i32, i32, sz, vp]
+    L.ht_draw_list_device.restype = i32
+    L.ht_draw_list_device.argtypes = [vp, C.POINTER(DRAW_SOURCE), i32, vp, sz]
     L.ht_detect_enqueue.restype = i32
     L.ht_detect_enqueue.argtypes = [vp, u32]
     L.ht_detect_collect.restype = i32

@@ -230,6 +230,32 @@ ht_status ht_draw_frames_yuv_device(ht_ctx *ctx, const ht_yuv_frames *src_dev, i
 ht_status ht_draw_frames_yuv(ht_ctx *ctx, const uint8_t *host, int32_t n, int32_t width, int32_t height, int32_t format, int32_t matrix,
                              size_t frame_stride, const ht_cs_rect *src_rect);
 
+/* The K-feed form of the draw (the reference's loop is one drawImage per feed, main.js:170): ONE launch draws a list of sources that share
+ * nothing — every entry names its own device allocation(s), size, pitches, format, matrix and source rect.  Entry i is
+ * drawImage(source_i, sx,sy,sw,sh, 0,0,W,H) onto destination frame i, with the bytes ht_draw_frames_device (HT_DRAW_RGBA) or
+ * ht_draw_frames_yuv_device (HT_YUV_NV12 / HT_YUV_I420) gives for that entry alone.  Plane pointers of different entries may be equal or
+ * overlap (one decoded surface under several rects).  Per entry, the rules of those calls with n = 1: RGBA base and pitch multiples of 4;
+ * NV12 chroma base and pitch even; width / height 1..16384; matrix 0..3 (ignored for RGBA); rect wholly inside the source, or width == 0
+ * && height == 0 for the whole source (x, y are then not looked at).  HT_DRAW_RGBA lies outside the HT_YUV_* format range: the YUV entry
+ * points refuse it. */
+enum { HT_DRAW_RGBA = 16 };
+typedef struct ht_draw_source {
+    const void *p0, *p1, *p2; /* RGBA: p0.  NV12: Y, UV.  I420: Y, U, V.  Device pointers; the unused ones are not looked at. */
+    size_t pitch0, pitch1;    /* bytes per row of p0 / of the chroma plane(s); 0 = packed */
+    int32_t width, height;    /* of THIS source */
+    int32_t format;           /* HT_YUV_NV12, HT_YUV_I420 or HT_DRAW_RGBA */
+    int32_t matrix;           /* HT_YUV_* matrix; ignored for RGBA */
+    ht_cs_rect rect;          /* width == 0 && height == 0: whole source */
+} ht_draw_source;
+/* srcs: a HOST array of n entries, 1 <= n <= 65535, read before the call returns.  dst_dev NULL: into the context's own frame buffer, n
+ * frames bound (n <= max_batch), exactly as ht_draw_frames_device does; otherwise frames dst_frame_stride apart (0 = packed) in the
+ * caller's buffer, binding untouched.  Every plane of every entry is refused when it overlaps the destination range (bind form: the
+ * context's own buffer).  Every check happens before anything is enqueued: a refused call (HT_ERR_INVALID) changes nothing and its message
+ * names the first offending entry as "entry <i>".  Enqueue-only: the descriptor table travels through pinned staging slots and one
+ * hipMemcpyAsync on the ctx stream (a slot is reused only after an event shows its copy has run), so the call never copies to the host and
+ * never waits in the steady state; the first call of a context, or a longer list, allocates. */
+ht_status ht_draw_list_device(ht_ctx *ctx, const ht_draw_source *srcs, int32_t n, void *dst_dev, size_t dst_frame_stride);
+
 /* ---- detect: ccv.grayscale + ccv.detect_objects (ccv.js:22-32, 109-246) ---------------------------------- */
 
 /* Enqueues gray -> pyramid -> cascade scan for the bound frames on the stream and returns immediately. */
