@@ -192,7 +192,13 @@ class Context:
         width, height) or None = the whole source}.  Every feed may have its own allocation, size, format, matrix and rect; pointers may
         repeat.  dst as draw_frames_device()."""
         n = len(entries)
-        arr = (native.DRAW_SOURCE * max(n, 1))()
+        self._check(self._lib.ht_draw_list_device(self._h, self._draw_sources(entries), n, dst, dst_stride))
+        if dst is None:
+            self.nframes = n
+
+    def _draw_sources(self, entries):
+        """the ht_draw_source array of a list of entry dicts (draw_list, camshift_crop_sources_device)"""
+        arr = (native.DRAW_SOURCE * max(len(entries), 1))()
         for s, e in zip(arr, entries):
             s.p0, s.p1, s.p2 = e.get("p0"), e.get("p1"), e.get("p2")
             s.pitch0, s.pitch1 = int(e.get("pitch0", 0)), int(e.get("pitch1", 0))
@@ -201,9 +207,7 @@ class Context:
             s.matrix = self._yuv_code(native.YUV_MATRICES, e.get("matrix", "bt601"), "matrix")
             if e.get("rect") is not None:
                 s.rect = native.CS_RECT(*(int(v) for v in e["rect"]))
-        self._check(self._lib.ht_draw_list_device(self._h, arr, n, dst, dst_stride))
-        if dst is None:
-            self.nframes = n
+        return arr
 
     # -- detect -----------------------------------------------------------------------------------------------
     def detect_enqueue(self, flags: int = HT_INPUT_RGBA):
@@ -516,6 +520,43 @@ class Context:
         no wait."""
         p = self._pairs(pairs)
         self._check(self._lib.ht_camshift_backproject_pairs_device(self._h, p.ctypes.data, len(p), int(self._BP_KINDS.get(kind, kind)), dev_ptr, stride))
+
+    # -- face crops: each tracker's box cut from its feed ----------------------------------------------------------
+    @staticmethod
+    def _crop_params(width: int, height: int, margin: float, square: bool):
+        return native.CROP_PARAMS(int(width), int(height), int(round(float(margin) * 256)), native.HT_CROP_SQUARE if square else 0)
+
+    def camshift_crop_pairs_device(self, dev_ptr: int, pairs, width: int, height: int, margin: float = 1.0, square: bool = False, stride: int = 0):
+        """Patch i = the box of stream pairs[i][0]'s track object cut from BOUND frame pairs[i][1] and scaled to width x height RGBA by the
+        declared resampler, into device memory at dev_ptr (patches `stride` bytes apart, 0 = packed).  margin widens the box around its
+        centre (1.0 = as tracked; it becomes 1/256 steps, 0.25 .. 4); square grows the shorter side first.  A lost or never tracked stream
+        gives zeros.  Enqueued behind the outstanding track steps: no copy, no wait.  Streams may repeat."""
+        p = self._pairs(pairs)
+        prm = self._crop_params(width, height, margin, square)
+        self._check(self._lib.ht_camshift_crop_pairs_device(self._h, p.ctypes.data, len(p), C.byref(prm), dev_ptr, stride))
+
+    def camshift_crop_sources_device(self, dev_ptr: int, streams, entries, width: int, height: int, margin: float = 1.0, square: bool = False, stride: int = 0):
+        """The same from the feeds' own frames: entries[i] as in draw_list, its "rect" the rect that was drawn onto the canvas stream
+        streams[i] tracks on; the box is mapped back through it and may reach beyond it, up to the source's edges."""
+        if len(streams) != len(entries):
+            raise ValueError("camshift_crop_sources_device: one stream per entry")
+        st = np.ascontiguousarray(np.asarray(streams, dtype=np.int32).reshape(-1))
+        prm = self._crop_params(width, height, margin, square)
+        self._check(self._lib.ht_camshift_crop_sources_device(self._h, st.ctypes.data if len(st) else None, self._draw_sources(entries), len(entries), C.byref(prm),
+                                                              dev_ptr, stride))
+
+    def camshift_crop_result(self, n: int) -> np.ndarray:
+        """CROP_RECORD_DTYPE [n] of the LAST crop call (same n): code (native.HT_CROP_EMPTY / _FACE), stream, the rect in source pixels and
+        the two ratios.  Waits for that call only."""
+        out = np.zeros(max(n, 0), dtype=native.CROP_RECORD_DTYPE)
+        self._check(self._lib.ht_camshift_crop_result(self._h, n, out.ctypes.data))
+        return out
+
+    def camshift_crop_records_ptr(self):
+        """(device pointer, n) of the last crop call's records, valid until the next crop call"""
+        ptr, n = C.c_void_p(), C.c_int32()
+        self._check(self._lib.ht_camshift_crop_records_device(self._h, C.byref(ptr), C.byref(n)))
+        return ptr.value, n.value
 
     # -- measurement --------------------------------------------------------------------------------------------
     def profile(self, on: bool = True):

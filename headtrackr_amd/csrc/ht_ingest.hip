@@ -182,7 +182,13 @@ void ht_ingest_free(ht_ctx *c) {  // ht_destroy (the stream has been synchronise
         c->h_dl_tab[k] = nullptr, c->ev_dl_tab[k] = nullptr;
     }
     c->dl_stage_next = 0;
+    ht_crop_free(c);  // the face crops' table, records and events (ht_crop.hip)
 }
 
 #include "ht_ingest_yuv.hip"  // the same draw for YUV 4:2:0 frames (shares ig_channel and the tile constants)
 #include "ht_draw_list.hip"   // one launch for a list of per-feed sources (shares the pixel bodies of both files)
+// the face crops: each tracker's box cut from its feed (the draw list's kernel with a rect the device works out itself).  Its rule header
+// is host AND device text; ht_cs_pairs.hip, later in this code object, spells HT_CSB_FN with the same tokens
+#define HT_CSB_FN __host__ __device__ inline
+#define HT_CROP_FN __host__ __device__ inline
+#include "ht_crop.hip"

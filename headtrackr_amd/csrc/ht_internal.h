@@ -304,6 +304,17 @@ struct ht_ctx {
     hipEvent_t ev_dl_tab[HT_DL_STAGE] = {};
     size_t dl_tab_cap = 0;
     int dl_stage_next = 0;
+    // the face crops (ht_crop.hip): a descriptor table and staging ring of their OWN, moved as the draw list's is (a crop call and a draw
+    // call of one step never share a slot or the device table), and the records of the last call: on the device, and in a pinned twin the
+    // call copies them to; the event behind that copy is what ht_camshift_crop_result waits for
+    uint8_t *d_crop_tab = nullptr, *h_crop_tab[HT_DL_STAGE] = {};
+    hipEvent_t ev_crop_tab[HT_DL_STAGE] = {};
+    size_t crop_tab_cap = 0;
+    int crop_stage_next = 0;
+    uint8_t *d_crop_rec = nullptr, *h_crop_rec = nullptr;
+    size_t crop_rec_cap = 0;  // records both hold
+    hipEvent_t ev_crop = nullptr;
+    int crop_n = 0;           // entries of the last call (0: none)
 
     std::vector<std::pair<void *, size_t>> user_allocs;  // ht_device_alloc buffers still alive (pointer, bytes): freed by ht_destroy at the latest
 
@@ -406,6 +417,7 @@ void ht_backproject_free(ht_ctx *ctx);                      // ht_backproject.hi
 void ht_cs_pairs_free(ht_ctx *ctx);                         // ht_cs_pairs.hip: pair table, staging and histogram scratch (ht_destroy)
 void ht_cs_best_free(ht_ctx *ctx);                          // ht_cs_best.hip: the result buffers of ht_camshift_init_best (ht_destroy)
 void ht_ingest_free(ht_ctx *ctx);                           // ht_ingest.hip: the host form's source staging, the draw list's table (ht_destroy)
+void ht_crop_free(ht_ctx *ctx);                             // ht_crop.hip: the face crops' table, records and events (called by ht_ingest_free)
 void ht_group_free(ht_ctx *ctx);                            // ht_group.hip: the device grouping's buffers (ht_destroy)
 ht_status ht_detect_mark_collected(ht_ctx *ctx, bool wb_snap);  // ht_context.hip: the state every collect call leaves behind
 ht_status ht_frames_own_reserve(ht_ctx *ctx, size_t need, const char *fn);  // ht_context.hip: the context's own frame buffer holds >= need bytes

@@ -1429,6 +1429,103 @@ napi_value DrawListDevice(napi_env env, napi_callback_info info) {
     return nullptr;
 }
 
+// ---- face crops: each tracker's box cut from its feed (ht_camshift_crop_*_device) ---------------------------------------------------------
+
+// the arguments both crop forms share behind their lists: Int32Array params [width, height, marginQ8, flags] at argument i, then outDev, outStride,
+// outOffset = 0, wait = false.  The patch size is checked here because the range handed to the library with the buffer's pointer depends on it;
+// margin and flags are the library's to refuse.
+struct CropOut {
+    ht_crop_params prm;
+    char *out = nullptr;
+    size_t stride = 0;
+    bool wait = false;
+};
+bool get_crop_out(const Args &a, size_t i, size_t n, const char *usage, CropOut *c) {
+    View prm;
+    DevBuf *out = nullptr;
+    size_t off = 0;
+    if (!a.devbuf(i + 1, &out)) return false;
+    if (!a.i32s(i, 4, &prm) || prm.len != 4 || !a.offset(i + 2, &c->stride) || (a.argc > i + 3 && !a.offset(i + 3, &off))) return type_error(a.env, usage) != nullptr;
+    a.opt_bool(i + 4, &c->wait);
+    const int32_t *v = prm.as<int32_t>();
+    c->prm.out_width = v[0], c->prm.out_height = v[1], c->prm.margin_q8 = v[2], c->prm.flags = (uint32_t)v[3];
+    if (v[0] < 1 || v[0] > 1024 || v[1] < 1 || v[1] > 1024) return range_error(a.env, (std::string(usage) + ": width and height are 1..1024").c_str()) != nullptr;
+    const size_t pb = (size_t)v[0] * (size_t)v[1] * 4;
+    if (!frames_fit(off, n, c->stride ? c->stride : pb, pb, out->bytes)) return range_error(a.env, (std::string(usage) + ": outside the device buffer").c_str()) != nullptr;
+    c->out = static_cast<char *>(out->ptr) + off;
+    return true;
+}
+
+napi_value CropPairsDevice(napi_env env, napi_callback_info info) {
+    static const char *usage = "cropPairsDevice(ctx, Int32Array pairs[2n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
+    Args a(env, info, 7);
+    Locked L;
+    const ht_cs_pair *pairs = nullptr;
+    int32_t n = 0;
+    CropOut c;
+    if (!a.ctx(5, &L)) return nullptr;
+    if (!get_pairs(env, a.argv[1], &pairs, &n)) return type_error(env, usage);
+    if (n > 65535) return range_error(env, (std::string(usage) + ": 1..65535 pairs").c_str());
+    if (!get_crop_out(a, 2, (size_t)n, usage, &c)) return nullptr;
+    ht_status st = ht_camshift_crop_pairs_device(L.ctx, pairs, n, &c.prm, c.out, c.stride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_crop_pairs_device");
+    if (c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
+    return nullptr;
+}
+
+napi_value CropSourcesDevice(napi_env env, napi_callback_info info) {
+    static const char *usage = "cropSourcesDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
+    Args a(env, info, 8);
+    Locked L;
+    View streams;
+    bool is_array = false;
+    uint32_t n = 0;
+    CropOut c;
+    if (!a.ctx(6, &L)) return nullptr;
+    if (!a.i32s(1, 0, &streams) || napi_is_array(env, a.argv[2], &is_array) != napi_ok || !is_array || napi_get_array_length(env, a.argv[2], &n) != napi_ok)
+        return type_error(env, usage);
+    if (n < 1 || n > 65535) return range_error(env, (std::string(usage) + ": 1..65535 entries").c_str());
+    if (streams.len != n) return range_error(env, (std::string(usage) + ": one stream per entry").c_str());
+    std::vector<ht_draw_source> srcs(n);
+    for (uint32_t i = 0; i < n; i++) {  // an entry is drawListDevice's: {dev, offset, width, height, format, matrix, rect}
+        napi_value e;
+        NAPI_OK(napi_get_element(env, a.argv[2], i, &e));
+        if (!get_draw_entry(env, e, &srcs[i])) return nullptr;
+    }
+    if (!get_crop_out(a, 3, (size_t)n, usage, &c)) return nullptr;
+    ht_status st = ht_camshift_crop_sources_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &c.prm, c.out, c.stride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_crop_sources_device");
+    if (c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
+    return nullptr;
+}
+
+// {records: Int32Array [6n] = code, stream, x, y, width, height per entry; ratios: Float64Array [2n] = rx, ry}
+napi_value CropResult(napi_env env, napi_callback_info info) {
+    Args a(env, info, 2);
+    Locked L;
+    int32_t n = 0;
+    if (!a.ctx(2, &L)) return nullptr;
+    if (!a.i32(1, &n) || n <= 0 || n > 65535) return type_error(env, "cropResult(ctx, n)");
+    std::vector<ht_crop_record> rec((size_t)n);
+    ht_status st = ht_camshift_crop_result(L.ctx, n, rec.data());
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_crop_result");
+    napi_value obj, ab, ta;
+    void *p = nullptr;
+    double *ratios = nullptr;
+    NAPI_OK(napi_create_object(env, &obj));
+    NAPI_OK(napi_create_arraybuffer(env, (size_t)n * 24, &p, &ab));
+    NAPI_OK(napi_create_typedarray(env, napi_int32_array, (size_t)n * 6, ab, 0, &ta));
+    NAPI_OK(napi_set_named_property(env, obj, "records", ta));
+    napi_value rt = f64_result(env, (size_t)n * 2, &ratios);
+    if (!rt) return nullptr;
+    NAPI_OK(napi_set_named_property(env, obj, "ratios", rt));
+    for (int32_t i = 0; i < n; i++) {
+        memcpy(static_cast<char *>(p) + (size_t)i * 24, &rec[(size_t)i], 24);  // code, stream and the rect lead the record
+        ratios[2 * i] = rec[(size_t)i].rx, ratios[2 * i + 1] = rec[(size_t)i].ry;
+    }
+    return obj;
+}
+
 napi_value ctx_counter(napi_env env, napi_callback_info info, int which) {
     Args a(env, info, 1);
     Locked L;
@@ -1465,6 +1562,7 @@ napi_value Init(napi_env env, napi_value exports) {
                {"camshiftBackProjectPairs", CamshiftBackProjectPairs}, {"camshiftBackProjectPairsDevice", CamshiftBackProjectPairsDevice},
                {"drawFrames", DrawFrames},       {"drawFramesDevice", DrawFramesDevice},
                {"drawFramesYuv", DrawFramesYuv}, {"drawFramesYuvDevice", DrawFramesYuvDevice}, {"drawListDevice", DrawListDevice},
+               {"cropPairsDevice", CropPairsDevice}, {"cropSourcesDevice", CropSourcesDevice}, {"cropResult", CropResult},
                {"detectBestEnqueue", DetectBestEnqueue}, {"collectBestDevice", CollectBestDevice}, {"detectGrouped", DetectGrouped},
                {"detectBestRecords", DetectBestRecords}, {"groupHits", GroupHits},
                {"framesBound", FramesBound},     {"framesEnqueued", FramesEnqueued}, {"graphLaunches", GraphLaunches}};
@@ -1479,7 +1577,8 @@ napi_value Init(napi_env env, napi_value exports) {
     } consts[] = {{"abiVersion", ht_abi_version()},   {"INPUT_GRAY_IN_R", HT_INPUT_GRAY_IN_R}, {"INPUT_RGBA", HT_INPUT_RGBA}, {"DETECT_WHITEBALANCE", HT_DETECT_WHITEBALANCE},
                   {"SCAN_STATS", HT_SCAN_STATS},      {"BP_RGBA8", HT_BP_RGBA8},               {"BP_F64", HT_BP_F64},
                   {"YUV_NV12", HT_YUV_NV12},          {"YUV_I420", HT_YUV_I420},               {"DRAW_RGBA", HT_DRAW_RGBA},
-                  {"CSB_UNTOUCHED", HT_CSB_UNTOUCHED}, {"CSB_FACE", HT_CSB_FACE},              {"CSB_FALLBACK", HT_CSB_FALLBACK}, {"CSB_DEFERRED", HT_CSB_DEFERRED}};
+                  {"CSB_UNTOUCHED", HT_CSB_UNTOUCHED}, {"CSB_FACE", HT_CSB_FACE},              {"CSB_FALLBACK", HT_CSB_FALLBACK}, {"CSB_DEFERRED", HT_CSB_DEFERRED},
+                  {"CROP_EMPTY", HT_CROP_EMPTY},      {"CROP_FACE", HT_CROP_FACE},             {"CROP_SQUARE", HT_CROP_SQUARE}};
     for (auto &c : consts) {
         napi_value v;
         napi_create_int32(env, c.value, &v);

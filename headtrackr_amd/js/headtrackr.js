@@ -442,6 +442,8 @@ headtrackr.ccv.detect_objects_batch = function (frames, n, w, h, cascade, interv
  *     drawBound(sset, rect)                the same into context 0's own frame buffer, which becomes its bound frames: follow with the step
  *                                           functions at set = -1
  *     backProjectionPairs(set, pairs, kind) -> the same per (tracker, frame) pair, pair order: ht_camshift_backproject_pairs
+ *     cropPairs(set, pairs, opts) / cropFeeds(sset, streams, opts) / cropResult()   each tracker's box cut from its frame / from its feed's own
+ *                                           frame and scaled to a patch, on the device (below: "Face crops")
  *     initPairs / trackPairs / trackPairsEnqueue / detectStepFinish(min_neighbors, {feeds})   trackers and frames paired freely (below);
                                            opts.trackers = tracker slots to reserve (default n)
    opts.pairSchedule = 'cluster': the pair calls of a few pairs on large frames (1080p feeds) run G workgroups per pair and tall rects a
@@ -828,9 +830,62 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     A.drawListDevice(ctxs[0], listEntries(sset, rects, 'drawListBound'), null, 0, 0, false);
     bound = -1;
   };
+  /* Face crops on the device (ht_camshift_crop_pairs_device / ht_camshift_crop_sources_device): each tracker's box, as its last track step
+   * — enqueue-only ones included — leaves it on the device, is cut from the frame and scaled to opts.width x opts.height RGBA.  Enqueue
+   * only: nothing is fetched until cropResult().
+   *   cropPairs(set, pairs, opts)      patch i: tracker pairs[2i] cut from frame pairs[2i + 1] of frame set `set` (-1: whatever is bound)
+   *   cropFeeds(sset, streams, opts)   opts.sources batches: patch i: tracker streams[i] cut from feed i's OWN frame of source set `sset`;
+   *                                    opts.rects = the rects that were drawn onto the canvas (drawList's rects; default the whole sources)
+   *   cropResult()                     -> {n, width, height, records: Int32Array(6 n) [code, stream, x, y, width, height] (source pixels; code
+   *                                    CROP_EMPTY: a lost or never tracked tracker, zeros), ratios: Float64Array(2 n), patches: Uint8Array(n width height 4)}
+   *                                    of the LAST crop call; waits for it
+   *   opts = {width, height (1..1024), margin = 1 (0.25..4: the box widened around its centre, in steps of 1/256), square = false} */
+  let cropDev = null, cropBytes = 0, lastCrop = null;
+  const needCrop = function (what) {
+    if (typeof A.cropPairsDevice !== 'function' || typeof A.cropSourcesDevice !== 'function' || typeof A.cropResult !== 'function')
+      throw new Error('DeviceBatch.' + what + ': this headtrackr_hip.node has no cropPairsDevice / cropSourcesDevice / cropResult (rebuild it)');
+    if (!trackers) throw new Error('DeviceBatch.' + what + ': no trackers yet (initPairs, initTrackers or detectStep first)');
+  };
+  const cropParams = function (what, o) {
+    if (!o || typeof o !== 'object') throw new TypeError('DeviceBatch.' + what + ': opts is {width, height, margin, square}');
+    if (!(Number.isInteger(o.width) && Number.isInteger(o.height) && o.width >= 1 && o.width <= 1024 && o.height >= 1 && o.height <= 1024))
+      throw new RangeError('DeviceBatch.' + what + ': opts.width and opts.height are integers 1..1024');
+    const margin = o.margin === undefined ? 1 : o.margin;
+    if (typeof margin !== 'number' || !(margin >= 0.25 && margin <= 4)) throw new RangeError('DeviceBatch.' + what + ': opts.margin is a number 0.25..4');
+    return Int32Array.from([o.width, o.height, Math.round(margin * 256), o.square ? 1 : 0]);
+  };
+  const cropOut = function (count, prm) { /* the patch buffer, grown on demand */
+    const need = count * prm[0] * prm[1] * 4;
+    if (cropBytes < need) {
+      if (cropDev) A.deviceFree(ctxs[0], cropDev); /* waits for the work in flight */
+      cropDev = A.deviceAlloc(ctxs[0], need); cropBytes = need;
+    }
+    lastCrop = { n: count, width: prm[0], height: prm[1] };
+    return cropDev;
+  };
+  this.cropPairs = function (set, pairs, o) {
+    needCrop('cropPairs'); pairList('cropPairs', pairs);
+    if (pairs.length > 2 * 65535) throw new RangeError('DeviceBatch.cropPairs: at most 65535 pairs');
+    const prm = cropParams('cropPairs', o);
+    bind0(set === undefined ? 0 : set);
+    A.cropPairsDevice(ctxs[0], pairs, prm, cropOut(pairs.length >> 1, prm), 0, 0, false);
+  };
+  this.cropFeeds = function (sset, streams, o) {
+    needCrop('cropFeeds');
+    if (!(streams instanceof Int32Array) || streams.length !== n) throw new TypeError('DeviceBatch.cropFeeds: streams is an Int32Array with one tracker per feed (' + n + ')');
+    const prm = cropParams('cropFeeds', o), entries = listEntries(sset, o.rects, 'cropFeeds');
+    A.cropSourcesDevice(ctxs[0], streams, entries, prm, cropOut(n, prm), 0, 0, false);
+  };
+  this.cropResult = function () {
+    if (!lastCrop) throw new Error('DeviceBatch.cropResult: no cropPairs / cropFeeds yet');
+    const r = A.cropResult(ctxs[0], lastCrop.n), bytes = lastCrop.n * lastCrop.width * lastCrop.height * 4;
+    const patches = new Uint8Array(bytes);
+    A.deviceDownload(ctxs[0], cropDev, 0, patches);
+    return { n: lastCrop.n, width: lastCrop.width, height: lastCrop.height, records: r.records, ratios: r.ratios, patches: patches };
+  };
   this.graphLaunches = function () { return ctxs.reduce(function (s, c) { return s + A.graphLaunches(c); }, 0); };
   /* the frame buffer is shared by all `depth` contexts: the others go first (ht_device_free refuses while they have it bound) */
-  this.destroy = function () { for (let i = ctxs.length - 1; i >= 1; i--) A.destroy(ctxs[i]); if (sdev) A.deviceFree(ctxs[0], sdev); if (feeds) feeds.forEach(function (f) { A.deviceFree(ctxs[0], f.dev); }); A.deviceFree(ctxs[0], dev); A.destroy(ctxs[0]); ctxs.length = 0; };
+  this.destroy = function () { for (let i = ctxs.length - 1; i >= 1; i--) A.destroy(ctxs[i]); if (sdev) A.deviceFree(ctxs[0], sdev); if (feeds) feeds.forEach(function (f) { A.deviceFree(ctxs[0], f.dev); }); if (cropDev) A.deviceFree(ctxs[0], cropDev); A.deviceFree(ctxs[0], dev); A.destroy(ctxs[0]); ctxs.length = 0; };
 };
 
 /* ---- whitebalance ----------------------------------------------------------------------------------------------------- */

@@ -436,6 +436,49 @@ ht_status ht_camshift_backproject_device(ht_ctx *ctx, int32_t first, int32_t n, 
 ht_status ht_camshift_backproject_pairs(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, int32_t kind, void *out_host, size_t out_stride);
 ht_status ht_camshift_backproject_pairs_device(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, int32_t kind, void *out_dev, size_t out_stride);
 
+/* ---- face crops: each tracker's box cut from its feed, on the device ------------------------------------------------------ */
+
+/* Patch i is the box of a stream's track object — as the last track step enqueued before this call leaves it on the device —, widened by
+ * margin_q8 / 256 around its centre (camshift.js:253-254: x, y is the centre), mapped from canvas coordinates back into the source through
+ * the rect that was drawn onto the canvas, rounded outwards to whole source pixels, with HT_CROP_SQUARE grown to a square around its
+ * middle, clamped to the source frame, and scaled to out_width x out_height by the declared resampler: drawImage(source, l, t, w, h, 0, 0,
+ * out_width, out_height), byte for byte what ht_draw_list_device gives for that rect on a canvas of the patch size.  The rule is integer
+ * arithmetic on the floored object (headtrackr_amd/csrc/ht_crop_plan.h states it); the ratios rx = w / out_width and ry = h / out_height
+ * are one binary64 division each, done on the device.  HT_CROP_EMPTY — a lost 0 x 0 object, a stream that was never tracked, a box wider
+ * than 65536 or centred beyond +-2^20, a box wholly outside the source — writes every byte of the patch as 0.  Rotation by the object's
+ * angle is not part of this. */
+enum { HT_CROP_EMPTY = 0, HT_CROP_FACE = 1 };
+enum { HT_CROP_SQUARE = 1 };
+typedef struct ht_crop_params {
+    int32_t out_width, out_height; /* 1..1024 */
+    int32_t margin_q8;             /* 64..1024; 256 is the box as tracked */
+    uint32_t flags;                /* HT_CROP_SQUARE or 0 */
+} ht_crop_params;
+typedef struct ht_crop_record {
+    int32_t code, stream; /* HT_CROP_*; the stream of the entry */
+    ht_cs_rect rect;      /* source pixels; zeros when empty */
+    double rx, ry;        /* 0 when empty */
+} ht_crop_record;         /* 40 bytes */
+/* Both calls: enqueue-only on the ctx stream behind whatever is outstanding; they never copy to the host and never wait in the steady state
+ * (the first call of a context, or a longer list, allocates), and change nothing a later track step, ht_camshift_stats or
+ * ht_camshift_debug_hist reads.  Patches are out_width * out_height * 4 bytes, out_stride apart (0 = packed, otherwise a multiple of 4 and
+ * >= a patch) from out_dev (device memory, 4-byte aligned, not NULL).  1 <= n <= 65535; streams are any reserved slots and may repeat.
+ * Any source plane that overlaps the output range is refused.  Every check happens before anything is enqueued: a refused call changes
+ * nothing and names the offending entry as "entry <i>".  HT_ERR_STATE without geometry, without reserved streams and (pairs form)
+ * without bound frames; HT_ERR_INVALID otherwise.
+ * Pairs form: the source of pair i is bound frame pairs[i].frame (W x H RGBA, drawn 1:1), any index below ht_frames_bound(). */
+ht_status ht_camshift_crop_pairs_device(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, const ht_crop_params *params, void *out_dev, size_t out_stride);
+/* Sources form: the source of entry i is srcs[i], described and checked as an entry of ht_draw_list_device; srcs[i].rect is the rect that
+ * was drawn onto the canvas stream streams[i] tracks on (width == 0 && height == 0: the whole source). */
+ht_status ht_camshift_crop_sources_device(ht_ctx *ctx, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_crop_params *params,
+                                          void *out_dev, size_t out_stride);
+/* One record per entry of the LAST crop call of the context (same n): waits for that call only (an event behind its kernel).  May be called
+ * repeatedly.  HT_ERR_STATE when there is no such call or n differs. */
+ht_status ht_camshift_crop_result(ht_ctx *ctx, int32_t n, ht_crop_record *out);
+/* Device pointer of those records (*n of them), complete for work enqueued on the ctx stream behind the crop call; valid until the next
+ * crop call of the context.  HT_ERR_STATE while there is none. */
+ht_status ht_camshift_crop_records_device(ht_ctx *ctx, const void **records, int32_t *n);
+
 /* ---- multi-GPU: fixed-size result records, all-gathered over RCCL/xGMI ------------------------------------ */
 
 /* Single-process helper for hosts that drive several GPUs from one process (the Node addon): ctxs[i] are contexts

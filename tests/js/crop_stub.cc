@@ -1,0 +1,67 @@
+// crop_stub.cc — the C-ABI functions of the face crops that tests/js/abi_stub.cc (left as it is) does not have: recording
+// ht_camshift_crop_pairs_device / ht_camshift_crop_sources_device and an ht_camshift_crop_result with fixed records, linked together with
+// that stub and csrc/ht_napi.cc into a temporary .node by tests/test_crop_cpu.py, so that the shim's cropPairsDevice, cropSourcesDevice and
+// cropResult — the argument readers, the range checks, the output offset and stride — run on the CPU.  Never linked into the product
+// addon.  Every crop call appends one JSON line to the file named by HT_CROP_STUB_LOG; pointers are logged relative to `out` (sources
+// form: p0 of an entry relative to out, p1 / p2 relative to the entry's p0).  n == 3 fails with HT_ERR_INVALID, to pin the error path.
+#include <cstdio>
+#include <cstdlib>
+
+#include "headtrackr_hip.h"
+
+static FILE *open_log() {
+    const char *fn = getenv("HT_CROP_STUB_LOG");
+    return fn ? fopen(fn, "a") : nullptr;
+}
+static void rel(FILE *f, const void *p, const void *base) {
+    if (!p) fprintf(f, "null");
+    else fprintf(f, "%lld", (long long)((const char *)p - (const char *)base));
+}
+static void tail(FILE *f, const ht_crop_params *p, size_t stride) {
+    fprintf(f, ", \"params\": [%d, %d, %d, %u], \"stride\": %zu}\n", p->out_width, p->out_height, p->margin_q8, p->flags, stride);
+    fclose(f);
+}
+
+extern "C" ht_status ht_camshift_crop_pairs_device(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, const ht_crop_params *p, void *out, size_t stride) {
+    if (FILE *f = open_log()) {
+        fprintf(f, "{\"fn\": \"pairs\", \"ctx\": %s, \"n\": %d, \"out\": %d, \"pairs\": [", ctx ? "true" : "false", n, out ? 1 : 0);
+        for (int32_t i = 0; i < n; i++) fprintf(f, "%s[%d, %d]", i ? ", " : "", pairs[i].stream, pairs[i].frame);
+        fprintf(f, "]");
+        tail(f, p, stride);
+    }
+    return n == 3 ? HT_ERR_INVALID : HT_OK;
+}
+
+extern "C" ht_status ht_camshift_crop_sources_device(ht_ctx *ctx, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_crop_params *p, void *out,
+                                                     size_t stride) {
+    if (FILE *f = open_log()) {
+        fprintf(f, "{\"fn\": \"sources\", \"ctx\": %s, \"n\": %d, \"streams\": [", ctx ? "true" : "false", n);
+        for (int32_t i = 0; i < n; i++) fprintf(f, "%s%d", i ? ", " : "", streams[i]);
+        fprintf(f, "], \"entries\": [");
+        for (int32_t i = 0; i < n; i++) {
+            const ht_draw_source &s = srcs[i];
+            fprintf(f, "%s{\"p0\": ", i ? ", " : "");
+            rel(f, s.p0, out);
+            fprintf(f, ", \"p1\": ");
+            rel(f, s.p1, s.p0);
+            fprintf(f, ", \"p2\": ");
+            rel(f, s.p2, s.p0);
+            fprintf(f, ", \"size\": [%d, %d], \"format\": %d, \"matrix\": %d, \"rect\": [%d, %d, %d, %d]}", s.width, s.height, s.format, s.matrix, s.rect.x, s.rect.y,
+                    s.rect.width, s.rect.height);
+        }
+        fprintf(f, "]");
+        tail(f, p, stride);
+    }
+    return n == 3 ? HT_ERR_INVALID : HT_OK;
+}
+
+// record i: code i & 1, stream 10 + i, rect (i, 2 i, 3 i + 1, 4 i + 1), rx = i + 0.25, ry = 1 / (i + 3); n == 5 is refused
+extern "C" ht_status ht_camshift_crop_result(ht_ctx *, int32_t n, ht_crop_record *out) {
+    if (n == 5) return HT_ERR_STATE;
+    for (int32_t i = 0; i < n; i++) {
+        out[i].code = i & 1, out[i].stream = 10 + i;
+        out[i].rect = ht_cs_rect{i, 2 * i, 3 * i + 1, 4 * i + 1};
+        out[i].rx = i + 0.25, out[i].ry = 1.0 / (i + 3);
+    }
+    return HT_OK;
+}
