@@ -558,6 +558,44 @@ class Context:
         self._check(self._lib.ht_camshift_crop_records_device(self._h, C.byref(ptr), C.byref(n)))
         return ptr.value, n.value
 
+    # -- angle-aligned face crops: each tracker's rotated box, upright ---------------------------------------------
+    @staticmethod
+    def _align_params(width: int, height: int, margin: float, square: bool):
+        return native.ALIGN_PARAMS(int(width), int(height), int(round(float(margin) * 256)), native.HT_ALIGN_SQUARE if square else 0)
+
+    def camshift_align_pairs_device(self, dev_ptr: int, pairs, width: int, height: int, margin: float = 1.0, square: bool = False, stride: int = 0):
+        """Patch i = the ROTATED box of stream pairs[i][0]'s track object (width and height along the blob's axes, turned by its angle as
+        the overlay draws it) sampled upright from BOUND frame pairs[i][1] into width x height RGBA at dev_ptr (patches `stride` bytes
+        apart, 0 = packed).  margin and square as for camshift_crop_pairs_device; square makes both sides the longer one.  Pixels whose
+        sample centre lies outside the frame are zeros, and so is the patch of a lost or never tracked stream.  Enqueued behind the
+        outstanding track steps: no copy, no wait.  Streams may repeat."""
+        p = self._pairs(pairs)
+        prm = self._align_params(width, height, margin, square)
+        self._check(self._lib.ht_camshift_align_pairs_device(self._h, p.ctypes.data, len(p), C.byref(prm), dev_ptr, stride))
+
+    def camshift_align_sources_device(self, dev_ptr: int, streams, entries, width: int, height: int, margin: float = 1.0, square: bool = False, stride: int = 0):
+        """The same from the feeds' own frames: entries[i] as in draw_list, its "rect" the rect that was drawn onto the canvas stream
+        streams[i] tracks on; the box is mapped back through it (an affine image) and may reach beyond it, up to the source's edges."""
+        if len(streams) != len(entries):
+            raise ValueError("camshift_align_sources_device: one stream per entry")
+        st = np.ascontiguousarray(np.asarray(streams, dtype=np.int32).reshape(-1))
+        prm = self._align_params(width, height, margin, square)
+        self._check(self._lib.ht_camshift_align_sources_device(self._h, st.ctypes.data if len(st) else None, self._draw_sources(entries), len(entries), C.byref(prm),
+                                                               dev_ptr, stride))
+
+    def camshift_align_result(self, n: int) -> np.ndarray:
+        """ALIGN_RECORD_DTYPE [n] of the LAST align call (same n): code (native.HT_ALIGN_EMPTY / _FACE), stream, the angle in 1/4096 turn,
+        the centre and the patch's two vectors in Q16 source pixels.  Waits for that call only."""
+        out = np.zeros(max(n, 0), dtype=native.ALIGN_RECORD_DTYPE)
+        self._check(self._lib.ht_camshift_align_result(self._h, n, out.ctypes.data))
+        return out
+
+    def camshift_align_records_ptr(self):
+        """(device pointer, n) of the last align call's records, valid until the next align call"""
+        ptr, n = C.c_void_p(), C.c_int32()
+        self._check(self._lib.ht_camshift_align_records_device(self._h, C.byref(ptr), C.byref(n)))
+        return ptr.value, n.value
+
     # -- measurement --------------------------------------------------------------------------------------------
     def profile(self, on: bool = True):
         self._check(self._lib.ht_profile(self._h, int(on)))

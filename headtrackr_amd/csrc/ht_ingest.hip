@@ -183,6 +183,7 @@ void ht_ingest_free(ht_ctx *c) {  // ht_destroy (the stream has been synchronise
     }
     c->dl_stage_next = 0;
     ht_crop_free(c);  // the face crops' table, records and events (ht_crop.hip)
+    ht_align_free(c);  // the aligned crops' likewise (ht_align.hip)
 }
 
 #include "ht_ingest_yuv.hip"  // the same draw for YUV 4:2:0 frames (shares ig_channel and the tile constants)
@@ -192,3 +193,6 @@ void ht_ingest_free(ht_ctx *c) {  // ht_destroy (the stream has been synchronise
 #define HT_CSB_FN __host__ __device__ inline
 #define HT_CROP_FN __host__ __device__ inline
 #include "ht_crop.hip"
+// the aligned crops: the rotated box of each tracker, upright (a kernel of its own: a gather along tilted lines, integer blend)
+#define HT_ALIGN_FN __host__ __device__ inline
+#include "ht_align.hip"

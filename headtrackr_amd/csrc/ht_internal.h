@@ -315,6 +315,15 @@ struct ht_ctx {
     size_t crop_rec_cap = 0;  // records both hold
     hipEvent_t ev_crop = nullptr;
     int crop_n = 0;           // entries of the last call (0: none)
+    // the aligned crops (ht_align.hip): the same again, their OWN — a crop call and an align call of one step share nothing
+    uint8_t *d_align_tab = nullptr, *h_align_tab[HT_DL_STAGE] = {};
+    hipEvent_t ev_align_tab[HT_DL_STAGE] = {};
+    size_t align_tab_cap = 0;
+    int align_stage_next = 0;
+    uint8_t *d_align_rec = nullptr, *h_align_rec = nullptr;
+    size_t align_rec_cap = 0;
+    hipEvent_t ev_align = nullptr;
+    int align_n = 0;
 
     std::vector<std::pair<void *, size_t>> user_allocs;  // ht_device_alloc buffers still alive (pointer, bytes): freed by ht_destroy at the latest
 
@@ -417,6 +426,7 @@ void ht_backproject_free(ht_ctx *ctx);                      // ht_backproject.hi
 void ht_cs_pairs_free(ht_ctx *ctx);                         // ht_cs_pairs.hip: pair table, staging and histogram scratch (ht_destroy)
 void ht_cs_best_free(ht_ctx *ctx);                          // ht_cs_best.hip: the result buffers of ht_camshift_init_best (ht_destroy)
 void ht_ingest_free(ht_ctx *ctx);                           // ht_ingest.hip: the host form's source staging, the draw list's table (ht_destroy)
+void ht_align_free(ht_ctx *ctx);                            // ht_align.hip: the aligned crops' table, records and events (called by ht_ingest_free)
 void ht_crop_free(ht_ctx *ctx);                             // ht_crop.hip: the face crops' table, records and events (called by ht_ingest_free)
 void ht_group_free(ht_ctx *ctx);                            // ht_group.hip: the device grouping's buffers (ht_destroy)
 ht_status ht_detect_mark_collected(ht_ctx *ctx, bool wb_snap);  // ht_context.hip: the state every collect call leaves behind

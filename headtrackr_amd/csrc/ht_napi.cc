@@ -1526,6 +1526,90 @@ napi_value CropResult(napi_env env, napi_callback_info info) {
     return obj;
 }
 
+// ---- angle-aligned face crops: each tracker's rotated box, upright (ht_camshift_align_*_device) -------------------------------------------
+// The arguments are the crop calls', read by the same reader (get_pairs, get_draw_entry, get_crop_out: ht_align_params has ht_crop_params' fields).
+
+ht_align_params align_params(const CropOut &c) {
+    ht_align_params p;
+    p.out_width = c.prm.out_width, p.out_height = c.prm.out_height, p.margin_q8 = c.prm.margin_q8, p.flags = c.prm.flags;
+    return p;
+}
+
+napi_value AlignPairsDevice(napi_env env, napi_callback_info info) {
+    static const char *usage = "alignPairsDevice(ctx, Int32Array pairs[2n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
+    Args a(env, info, 7);
+    Locked L;
+    const ht_cs_pair *pairs = nullptr;
+    int32_t n = 0;
+    CropOut c;
+    if (!a.ctx(5, &L)) return nullptr;
+    if (!get_pairs(env, a.argv[1], &pairs, &n)) return type_error(env, usage);
+    if (n > 65535) return range_error(env, (std::string(usage) + ": 1..65535 pairs").c_str());
+    if (!get_crop_out(a, 2, (size_t)n, usage, &c)) return nullptr;
+    const ht_align_params prm = align_params(c);
+    ht_status st = ht_camshift_align_pairs_device(L.ctx, pairs, n, &prm, c.out, c.stride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_align_pairs_device");
+    if (c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
+    return nullptr;
+}
+
+napi_value AlignSourcesDevice(napi_env env, napi_callback_info info) {
+    static const char *usage = "alignSourcesDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
+    Args a(env, info, 8);
+    Locked L;
+    View streams;
+    bool is_array = false;
+    uint32_t n = 0;
+    CropOut c;
+    if (!a.ctx(6, &L)) return nullptr;
+    if (!a.i32s(1, 0, &streams) || napi_is_array(env, a.argv[2], &is_array) != napi_ok || !is_array || napi_get_array_length(env, a.argv[2], &n) != napi_ok)
+        return type_error(env, usage);
+    if (n < 1 || n > 65535) return range_error(env, (std::string(usage) + ": 1..65535 entries").c_str());
+    if (streams.len != n) return range_error(env, (std::string(usage) + ": one stream per entry").c_str());
+    std::vector<ht_draw_source> srcs(n);
+    for (uint32_t i = 0; i < n; i++) {  // an entry is drawListDevice's: {dev, offset, width, height, format, matrix, rect}
+        napi_value e;
+        NAPI_OK(napi_get_element(env, a.argv[2], i, &e));
+        if (!get_draw_entry(env, e, &srcs[i])) return nullptr;
+    }
+    if (!get_crop_out(a, 3, (size_t)n, usage, &c)) return nullptr;
+    const ht_align_params prm = align_params(c);
+    ht_status st = ht_camshift_align_sources_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &prm, c.out, c.stride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_align_sources_device");
+    if (c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
+    return nullptr;
+}
+
+// {records: Int32Array [4n] = code, stream, a12, 0 per entry; terms: Float64Array [6n] = cx, cy, ux, uy, vx, vy in Q16 source pixels
+// (|value| < 2^52: exact in a binary64)}
+napi_value AlignResult(napi_env env, napi_callback_info info) {
+    Args a(env, info, 2);
+    Locked L;
+    int32_t n = 0;
+    if (!a.ctx(2, &L)) return nullptr;
+    if (!a.i32(1, &n) || n <= 0 || n > 65535) return type_error(env, "alignResult(ctx, n)");
+    std::vector<ht_align_record> rec((size_t)n);
+    ht_status st = ht_camshift_align_result(L.ctx, n, rec.data());
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_align_result");
+    napi_value obj, ab, ta;
+    void *p = nullptr;
+    double *terms = nullptr;
+    NAPI_OK(napi_create_object(env, &obj));
+    NAPI_OK(napi_create_arraybuffer(env, (size_t)n * 16, &p, &ab));
+    NAPI_OK(napi_create_typedarray(env, napi_int32_array, (size_t)n * 4, ab, 0, &ta));
+    NAPI_OK(napi_set_named_property(env, obj, "records", ta));
+    napi_value tt = f64_result(env, (size_t)n * 6, &terms);
+    if (!tt) return nullptr;
+    NAPI_OK(napi_set_named_property(env, obj, "terms", tt));
+    for (int32_t i = 0; i < n; i++) {
+        const ht_align_record &r = rec[(size_t)i];
+        memcpy(static_cast<char *>(p) + (size_t)i * 16, &r, 16);  // code, stream, a12 and pad lead the record
+        const int64_t q[6] = {r.cx, r.cy, r.ux, r.uy, r.vx, r.vy};
+        for (int k = 0; k < 6; k++) terms[6 * i + k] = (double)q[k];
+    }
+    return obj;
+}
+
 napi_value ctx_counter(napi_env env, napi_callback_info info, int which) {
     Args a(env, info, 1);
     Locked L;
@@ -1563,6 +1647,7 @@ napi_value Init(napi_env env, napi_value exports) {
                {"drawFrames", DrawFrames},       {"drawFramesDevice", DrawFramesDevice},
                {"drawFramesYuv", DrawFramesYuv}, {"drawFramesYuvDevice", DrawFramesYuvDevice}, {"drawListDevice", DrawListDevice},
                {"cropPairsDevice", CropPairsDevice}, {"cropSourcesDevice", CropSourcesDevice}, {"cropResult", CropResult},
+               {"alignPairsDevice", AlignPairsDevice}, {"alignSourcesDevice", AlignSourcesDevice}, {"alignResult", AlignResult},
                {"detectBestEnqueue", DetectBestEnqueue}, {"collectBestDevice", CollectBestDevice}, {"detectGrouped", DetectGrouped},
                {"detectBestRecords", DetectBestRecords}, {"groupHits", GroupHits},
                {"framesBound", FramesBound},     {"framesEnqueued", FramesEnqueued}, {"graphLaunches", GraphLaunches}};
@@ -1578,7 +1663,8 @@ napi_value Init(napi_env env, napi_value exports) {
                   {"SCAN_STATS", HT_SCAN_STATS},      {"BP_RGBA8", HT_BP_RGBA8},               {"BP_F64", HT_BP_F64},
                   {"YUV_NV12", HT_YUV_NV12},          {"YUV_I420", HT_YUV_I420},               {"DRAW_RGBA", HT_DRAW_RGBA},
                   {"CSB_UNTOUCHED", HT_CSB_UNTOUCHED}, {"CSB_FACE", HT_CSB_FACE},              {"CSB_FALLBACK", HT_CSB_FALLBACK}, {"CSB_DEFERRED", HT_CSB_DEFERRED},
-                  {"CROP_EMPTY", HT_CROP_EMPTY},      {"CROP_FACE", HT_CROP_FACE},             {"CROP_SQUARE", HT_CROP_SQUARE}};
+                  {"CROP_EMPTY", HT_CROP_EMPTY},      {"CROP_FACE", HT_CROP_FACE},             {"CROP_SQUARE", HT_CROP_SQUARE},
+                  {"ALIGN_EMPTY", HT_ALIGN_EMPTY},    {"ALIGN_FACE", HT_ALIGN_FACE},           {"ALIGN_SQUARE", HT_ALIGN_SQUARE}};
     for (auto &c : consts) {
         napi_value v;
         napi_create_int32(env, c.value, &v);

@@ -444,6 +444,8 @@ headtrackr.ccv.detect_objects_batch = function (frames, n, w, h, cascade, interv
  *     backProjectionPairs(set, pairs, kind) -> the same per (tracker, frame) pair, pair order: ht_camshift_backproject_pairs
  *     cropPairs(set, pairs, opts) / cropFeeds(sset, streams, opts) / cropResult()   each tracker's box cut from its frame / from its feed's own
  *                                           frame and scaled to a patch, on the device (below: "Face crops")
+ *     alignPairs(set, pairs, opts) / alignFeeds(sset, streams, opts) / alignResult()   the same for the box ROTATED by the tracker's angle: the
+ *                                           face upright (below: "Angle-aligned face crops")
  *     initPairs / trackPairs / trackPairsEnqueue / detectStepFinish(min_neighbors, {feeds})   trackers and frames paired freely (below);
                                            opts.trackers = tracker slots to reserve (default n)
    opts.pairSchedule = 'cluster': the pair calls of a few pairs on large frames (1080p feeds) run G workgroups per pair and tall rects a
@@ -883,9 +885,51 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     A.deviceDownload(ctxs[0], cropDev, 0, patches);
     return { n: lastCrop.n, width: lastCrop.width, height: lastCrop.height, records: r.records, ratios: r.ratios, patches: patches };
   };
+  /* Angle-aligned face crops (ht_camshift_align_pairs_device / ht_camshift_align_sources_device): the ROTATED box of each tracker — width and
+   * height along the blob's axes, turned by its angle as the overlay draws it — sampled upright into opts.width x opts.height RGBA; pixels
+   * whose sample centre lies outside the frame are zeros.  Same arguments, options and exclusivity as the crop calls; a patch buffer of their own.
+   *   alignPairs(set, pairs, opts) / alignFeeds(sset, streams, opts)
+   *   alignResult()                    -> {n, width, height, records: Int32Array(4 n) [code, stream, a12 (the angle in 1/4096 turn), 0],
+   *                                    terms: Float64Array(6 n) [cx, cy, ux, uy, vx, vy] (the centre and the patch's two vectors in the source,
+   *                                    1/65536 pixel), patches: Uint8Array(n width height 4)} of the LAST align call; waits for it */
+  let alignDev = null, alignBytes = 0, lastAlign = null;
+  const needAlign = function (what) {
+    if (typeof A.alignPairsDevice !== 'function' || typeof A.alignSourcesDevice !== 'function' || typeof A.alignResult !== 'function')
+      throw new Error('DeviceBatch.' + what + ': this headtrackr_hip.node has no alignPairsDevice / alignSourcesDevice / alignResult (rebuild it)');
+    if (!trackers) throw new Error('DeviceBatch.' + what + ': no trackers yet (initPairs, initTrackers or detectStep first)');
+  };
+  const alignOut = function (count, prm) { /* the patch buffer, grown on demand */
+    const need = count * prm[0] * prm[1] * 4;
+    if (alignBytes < need) {
+      if (alignDev) A.deviceFree(ctxs[0], alignDev); /* waits for the work in flight */
+      alignDev = A.deviceAlloc(ctxs[0], need); alignBytes = need;
+    }
+    lastAlign = { n: count, width: prm[0], height: prm[1] };
+    return alignDev;
+  };
+  this.alignPairs = function (set, pairs, o) {
+    needAlign('alignPairs'); pairList('alignPairs', pairs);
+    if (pairs.length > 2 * 65535) throw new RangeError('DeviceBatch.alignPairs: at most 65535 pairs');
+    const prm = cropParams('alignPairs', o);
+    bind0(set === undefined ? 0 : set);
+    A.alignPairsDevice(ctxs[0], pairs, prm, alignOut(pairs.length >> 1, prm), 0, 0, false);
+  };
+  this.alignFeeds = function (sset, streams, o) {
+    needAlign('alignFeeds');
+    if (!(streams instanceof Int32Array) || streams.length !== n) throw new TypeError('DeviceBatch.alignFeeds: streams is an Int32Array with one tracker per feed (' + n + ')');
+    const prm = cropParams('alignFeeds', o), entries = listEntries(sset, o.rects, 'alignFeeds');
+    A.alignSourcesDevice(ctxs[0], streams, entries, prm, alignOut(n, prm), 0, 0, false);
+  };
+  this.alignResult = function () {
+    if (!lastAlign) throw new Error('DeviceBatch.alignResult: no alignPairs / alignFeeds yet');
+    const r = A.alignResult(ctxs[0], lastAlign.n), bytes = lastAlign.n * lastAlign.width * lastAlign.height * 4;
+    const patches = new Uint8Array(bytes);
+    A.deviceDownload(ctxs[0], alignDev, 0, patches);
+    return { n: lastAlign.n, width: lastAlign.width, height: lastAlign.height, records: r.records, terms: r.terms, patches: patches };
+  };
   this.graphLaunches = function () { return ctxs.reduce(function (s, c) { return s + A.graphLaunches(c); }, 0); };
   /* the frame buffer is shared by all `depth` contexts: the others go first (ht_device_free refuses while they have it bound) */
-  this.destroy = function () { for (let i = ctxs.length - 1; i >= 1; i--) A.destroy(ctxs[i]); if (sdev) A.deviceFree(ctxs[0], sdev); if (feeds) feeds.forEach(function (f) { A.deviceFree(ctxs[0], f.dev); }); if (cropDev) A.deviceFree(ctxs[0], cropDev); A.deviceFree(ctxs[0], dev); A.destroy(ctxs[0]); ctxs.length = 0; };
+  this.destroy = function () { for (let i = ctxs.length - 1; i >= 1; i--) A.destroy(ctxs[i]); if (sdev) A.deviceFree(ctxs[0], sdev); if (feeds) feeds.forEach(function (f) { A.deviceFree(ctxs[0], f.dev); }); if (cropDev) A.deviceFree(ctxs[0], cropDev); if (alignDev) A.deviceFree(ctxs[0], alignDev); A.deviceFree(ctxs[0], dev); A.destroy(ctxs[0]); ctxs.length = 0; };
 };
 
 /* ---- whitebalance ----------------------------------------------------------------------------------------------------- */

@@ -97,6 +97,24 @@ assert C.sizeof(CROP_RECORD) == CROP_RECORD_DTYPE.itemsize == 40 and C.sizeof(CR
 HT_CROP_EMPTY, HT_CROP_FACE = 0, 1
 HT_CROP_SQUARE = 1
 
+
+class ALIGN_PARAMS(C.Structure):
+    """ht_align_params: patch size, margin in 1/256 and flags of an align call"""
+    _fields_ = [("out_width", C.c_int32), ("out_height", C.c_int32), ("margin_q8", C.c_int32), ("flags", C.c_uint32)]
+
+
+class ALIGN_RECORD(C.Structure):
+    """ht_align_record: what an align call decided for one entry (centre and the patch's two vectors in Q16 source pixels)"""
+    _fields_ = [("code", C.c_int32), ("stream", C.c_int32), ("a12", C.c_int32), ("pad", C.c_int32), ("cx", C.c_int64), ("cy", C.c_int64), ("ux", C.c_int64),
+                ("uy", C.c_int64), ("vx", C.c_int64), ("vy", C.c_int64)]
+
+
+ALIGN_RECORD_DTYPE = np.dtype([("code", "<i4"), ("stream", "<i4"), ("a12", "<i4"), ("pad", "<i4"), ("cx", "<i8"), ("cy", "<i8"), ("ux", "<i8"), ("uy", "<i8"), ("vx", "<i8"),
+                               ("vy", "<i8")])
+assert C.sizeof(ALIGN_RECORD) == ALIGN_RECORD_DTYPE.itemsize == 64 and C.sizeof(ALIGN_PARAMS) == 16
+HT_ALIGN_EMPTY, HT_ALIGN_FACE = 0, 1
+HT_ALIGN_SQUARE = 1
+
 HT_YUV_NV12, HT_YUV_I420 = 0, 1
 HT_DRAW_RGBA = 16  # ht_draw_source.format beside the two above (outside the range the YUV entry points take)
 HT_YUV_BT601_LIMITED, HT_YUV_BT709_LIMITED, HT_YUV_BT601_FULL, HT_YUV_BT709_FULL = 0, 1, 2, 3
@@ -110,7 +128,7 @@ SYMBOLS = [
     "ht_windows_per_frame", "ht_pyramid_bytes_per_frame", "ht_upload_frames", "ht_upload_frames_async", "ht_swap_frames", "ht_bind_frames_device", "ht_frames_bound", "ht_frames_enqueued", "ht_host_alloc", "ht_host_free", "ht_device_alloc", "ht_device_free", "ht_device_upload", "ht_device_download", "ht_draw_frames_device", "ht_draw_frames", "ht_draw_frames_yuv_device", "ht_draw_frames_yuv", "ht_draw_list_device", "ht_detect_enqueue",
     "ht_detect_collect", "ht_detect_batch", "ht_pyramid_readback", "ht_stage_counts", "ht_grayscale_batch",
     "ht_whitebalance_batch", "ht_detect_whitebalance", "ht_hits_to_rects", "ht_group_rects", "ht_best_faces", "ht_detect_collect_best", "ht_detect_collect_best_requeue", "ht_detect_best_enqueue", "ht_detect_best_collect", "ht_detect_best_collect_requeue", "ht_detect_grouped", "ht_detect_best_records_device", "ht_group_hits", "ht_camshift_reserve", "ht_camshift_init_batch",
-    "ht_camshift_track_batch", "ht_camshift_track_collect", "ht_camshift_init_pairs", "ht_camshift_track_pairs", "ht_camshift_init_best", "ht_camshift_init_best_result", "ht_camshift_track_sequence", "ht_camshift_sequence_collect", "ht_camshift_stats", "ht_camshift_debug_hist", "ht_camshift_backproject", "ht_camshift_backproject_device", "ht_camshift_backproject_pairs", "ht_camshift_backproject_pairs_device", "ht_camshift_crop_pairs_device", "ht_camshift_crop_sources_device", "ht_camshift_crop_result", "ht_camshift_crop_records_device", "ht_allgather_records", "ht_allgather_best_faces", "ht_device_count", "ht_profile", "ht_kernel_times", "ht_stream", "ht_graph_launches", "ht_synchronize",
+    "ht_camshift_track_batch", "ht_camshift_track_collect", "ht_camshift_init_pairs", "ht_camshift_track_pairs", "ht_camshift_init_best", "ht_camshift_init_best_result", "ht_camshift_track_sequence", "ht_camshift_sequence_collect", "ht_camshift_stats", "ht_camshift_debug_hist", "ht_camshift_backproject", "ht_camshift_backproject_device", "ht_camshift_backproject_pairs", "ht_camshift_backproject_pairs_device", "ht_camshift_crop_pairs_device", "ht_camshift_crop_sources_device", "ht_camshift_crop_result", "ht_camshift_crop_records_device", "ht_camshift_align_pairs_device", "ht_camshift_align_sources_device", "ht_camshift_align_result", "ht_camshift_align_records_device", "ht_allgather_records", "ht_allgather_best_faces", "ht_device_count", "ht_profile", "ht_kernel_times", "ht_stream", "ht_graph_launches", "ht_synchronize",
 ]
 
 _lib = None
@@ -252,6 +270,14 @@ def lib():
     L.ht_camshift_crop_result.argtypes = [vp, i32, vp]
     L.ht_camshift_crop_records_device.restype = i32
     L.ht_camshift_crop_records_device.argtypes = [vp, C.POINTER(vp), C.POINTER(i32)]
+    L.ht_camshift_align_pairs_device.restype = i32
+    L.ht_camshift_align_pairs_device.argtypes = [vp, vp, i32, C.POINTER(ALIGN_PARAMS), vp, sz]
+    L.ht_camshift_align_sources_device.restype = i32
+    L.ht_camshift_align_sources_device.argtypes = [vp, vp, C.POINTER(DRAW_SOURCE), i32, C.POINTER(ALIGN_PARAMS), vp, sz]
+    L.ht_camshift_align_result.restype = i32
+    L.ht_camshift_align_result.argtypes = [vp, i32, vp]
+    L.ht_camshift_align_records_device.restype = i32
+    L.ht_camshift_align_records_device.argtypes = [vp, C.POINTER(vp), C.POINTER(i32)]
     L.ht_allgather_records.restype = i32
     L.ht_allgather_records.argtypes = [vp, i32, vp, sz]
     L.ht_allgather_best_faces.restype = i32

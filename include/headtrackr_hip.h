@@ -479,6 +479,46 @@ ht_status ht_camshift_crop_result(ht_ctx *ctx, int32_t n, ht_crop_record *out);
  * crop call of the context.  HT_ERR_STATE while there is none. */
 ht_status ht_camshift_crop_records_device(ht_ctx *ctx, const void **records, int32_t *n);
 
+/* ---- angle-aligned face crops: each tracker's ROTATED box cut from its feed, upright, on the device ---------------------- */
+
+/* With calcAngles (camshift.Tracker's default) width and height lie along the blob's principal axes and angle is the direction of the long
+ * one; main.js:213-216 draws translate(x, y); rotate(angle - pi / 2); strokeRect(-w / 2, -h / 2, w, h).  Patch i is that rotated box of a
+ * stream's track object — as the last track step enqueued before this call leaves it on the device —, widened by margin_q8 / 256 around its
+ * centre, with HT_ALIGN_SQUARE both sides the longer one, mapped from canvas coordinates back into the source through the rect that was drawn
+ * onto the canvas (an affine image: the mapping may be anisotropic), and sampled at out_width x out_height pixel centres: patch +x is
+ * (sin a, -cos a) on the canvas, patch +y is (cos a, sin a), so at angle == pi / 2 the patch is the box as it stands.  The angle is rounded
+ * to the nearest of 4096 steps per turn (a12); everything behind it is integer arithmetic in Q16 source pixels
+ * (headtrackr_amd/csrc/ht_align_plan.h states the rule).  Each pixel is a bilinear blend, with 8-bit weights, of the source's declared RGBA
+ * view, taps clamped to the source frame; a pixel whose sample centre lies outside the source frame is four zero bytes.  HT_ALIGN_EMPTY — a
+ * lost 0 x 0 object, a stream that was never tracked, a box wider than 65536 or centred beyond +-2^20, an angle that is not finite or beyond
+ * +-1024 — writes every byte of the patch as 0.  Not part of this: sub-pixel centres (x, y are floored as the crop calls floor them), a
+ * prefilter for strong downscales, planar or float output. */
+enum { HT_ALIGN_EMPTY = 0, HT_ALIGN_FACE = 1 };
+enum { HT_ALIGN_SQUARE = 1 };
+typedef struct ht_align_params {
+    int32_t out_width, out_height; /* 1..1024 */
+    int32_t margin_q8;             /* 64..1024; 256 is the box as tracked */
+    uint32_t flags;                /* HT_ALIGN_SQUARE or 0 */
+} ht_align_params;
+typedef struct ht_align_record {
+    int32_t code, stream, a12, pad; /* HT_ALIGN_*; the stream of the entry; the angle in 1/4096 turn (0 when empty); 0 */
+    int64_t cx, cy;                 /* the box centre in the source, Q16; zeros when empty, as everything below */
+    int64_t ux, uy;                 /* the patch's full-width vector in the source, Q16 */
+    int64_t vx, vy;                 /* the patch's full-height vector in the source, Q16 */
+} ht_align_record;                  /* 64 bytes */
+/* Arguments, checks, refusals ("entry <i>"), status codes, output layout (RGBA8 patches out_stride apart, 0 = packed), the overlap refusal
+ * and the enqueue-only contract are those of ht_camshift_crop_pairs_device / ht_camshift_crop_sources_device.  The calls keep a descriptor
+ * table, staging ring and records of their own: an align call and a crop call of one step share nothing. */
+ht_status ht_camshift_align_pairs_device(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, const ht_align_params *params, void *out_dev, size_t out_stride);
+ht_status ht_camshift_align_sources_device(ht_ctx *ctx, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_align_params *params,
+                                           void *out_dev, size_t out_stride);
+/* One record per entry of the LAST align call of the context (same n): waits for that call only.  HT_ERR_STATE when there is no such call
+ * or n differs. */
+ht_status ht_camshift_align_result(ht_ctx *ctx, int32_t n, ht_align_record *out);
+/* Device pointer of those records (*n of them), complete for work enqueued on the ctx stream behind the align call; valid until the next
+ * align call of the context.  HT_ERR_STATE while there is none. */
+ht_status ht_camshift_align_records_device(ht_ctx *ctx, const void **records, int32_t *n);
+
 /* ---- multi-GPU: fixed-size result records, all-gathered over RCCL/xGMI ------------------------------------ */
 
 /* Single-process helper for hosts that drive several GPUs from one process (the Node addon): ctxs[i] are contexts
