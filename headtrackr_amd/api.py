@@ -19,6 +19,63 @@ from .native import (HIT_DTYPE, HT_INPUT_GRAY_IN_R, HT_INPUT_RGBA, HT_SCAN_NO_SP
                      HtError)
 
 
+class PatchFormat:
+    """The output of a tensor call (ht_patch_format): every element is fl32(fl32(byte * scale[c]) + bias[c]) rounded to `dtype` — "f32",
+    "f16" or "bf16" — in `layout` "chw" or "hwc" with `channels` "rgb", "bgr" or "gray" (one channel: the grayscale byte).  scale and bias
+    are one number for all channels or one per output channel; each is 0 or of a magnitude within 2^-64 .. 2^64."""
+
+    def __init__(self, dtype: str = "f16", layout: str = "chw", channels: str = "rgb", scale=1.0 / 255.0, bias=0.0):
+        for what, value, table in (("dtype", dtype, native.PATCH_DTYPES), ("layout", layout, native.PATCH_LAYOUTS), ("channels", channels, native.PATCH_CHANNELS)):
+            if value not in table:
+                raise ValueError(f"PatchFormat: {what} must be one of {sorted(table)}, not {value!r}")
+        self.dtype, self.layout, self.channels = dtype, layout, channels
+        self.scale, self.bias = self._per_channel("scale", scale), self._per_channel("bias", bias)
+
+    @property
+    def nchannels(self) -> int:
+        return 1 if self.channels == "gray" else 3
+
+    @property
+    def itemsize(self) -> int:
+        return 4 if self.dtype == "f32" else 2
+
+    def _per_channel(self, what, v):
+        n = self.nchannels
+        vals = [float(x) for x in np.asarray(v, dtype=np.float64).reshape(-1)]
+        if len(vals) == 1:
+            vals = vals * n
+        if len(vals) != n:
+            raise ValueError(f"PatchFormat: {what} takes one value or {n} (one per output channel)")
+        return tuple(float(np.float32(x)) for x in vals)  # binary64 -> binary32, round to nearest even
+
+    @classmethod
+    def mean_std(cls, mean, std, dtype: str = "f16", layout: str = "chw", channels: str = "rgb"):
+        """(byte / 255 - mean) / std per output channel: scale = 1 / (255 std), bias = -mean / std, computed in binary64 and then rounded
+        to binary32"""
+        mean, std = np.asarray(mean, dtype=np.float64).reshape(-1), np.asarray(std, dtype=np.float64).reshape(-1)
+        return cls(dtype, layout, channels, scale=1.0 / (255.0 * std), bias=-mean / std)
+
+    def patch_bytes(self, width: int, height: int) -> int:
+        return self.nchannels * int(width) * int(height) * self.itemsize
+
+    def default_stride(self, width: int, height: int) -> int:
+        return (self.patch_bytes(width, height) + 3) & ~3
+
+    def shape(self, width: int, height: int):
+        return (self.nchannels, int(height), int(width)) if self.layout == "chw" else (int(height), int(width), self.nchannels)
+
+    def struct(self) -> "native.PATCH_FORMAT":
+        f = native.PATCH_FORMAT(native.PATCH_DTYPES[self.dtype], native.PATCH_LAYOUTS[self.layout], native.PATCH_CHANNELS[self.channels], 0)
+        for c in range(self.nchannels):
+            f.scale[c], f.bias[c] = self.scale[c], self.bias[c]
+        return f
+
+    @classmethod
+    def of(cls, fmt):
+        """a PatchFormat, or a dict of its constructor's arguments"""
+        return fmt if isinstance(fmt, cls) else cls(**fmt)
+
+
 class Context:
     """One ht_ctx: one GPU, one cascade, one stream."""
 
@@ -36,6 +93,7 @@ class Context:
         if st != 0:
             raise HtError(st, self._lib.ht_last_error(None).decode())
         self._h = h
+        self.device = device
         self.interval = interval
         self.width = self.height = 0
         self._collected_n = 0
@@ -595,6 +653,41 @@ class Context:
         ptr, n = C.c_void_p(), C.c_int32()
         self._check(self._lib.ht_camshift_align_records_device(self._h, C.byref(ptr), C.byref(n)))
         return ptr.value, n.value
+
+    # -- model-input tensors: the crop and align calls with a float output stage -----------------------------------
+    def camshift_crop_pairs_tensor_device(self, dev_ptr: int, pairs, width: int, height: int, fmt, margin: float = 1.0, square: bool = False, stride: int = 0):
+        """camshift_crop_pairs_device with fmt (a PatchFormat or a dict of its arguments) as the output: patch i becomes the model's input
+        tensor — fmt.nchannels * width * height elements of fmt.dtype, `stride` bytes apart (0 = a patch's bytes rounded up to 4) —, every
+        element fl32(fl32(byte * scale[c]) + bias[c]) rounded to the dtype, in the same single launch.  A lost or never tracked stream gives
+        bias[c] everywhere (read camshift_crop_result's code).  This IS the context's last crop call."""
+        p, f = self._pairs(pairs), PatchFormat.of(fmt).struct()
+        prm = self._crop_params(width, height, margin, square)
+        self._check(self._lib.ht_camshift_crop_pairs_tensor_device(self._h, p.ctypes.data, len(p), C.byref(prm), C.byref(f), dev_ptr, stride))
+
+    def camshift_crop_sources_tensor_device(self, dev_ptr: int, streams, entries, width: int, height: int, fmt, margin: float = 1.0, square: bool = False, stride: int = 0):
+        """camshift_crop_sources_device with fmt as the output (see camshift_crop_pairs_tensor_device)"""
+        if len(streams) != len(entries):
+            raise ValueError("camshift_crop_sources_tensor_device: one stream per entry")
+        st, f = np.ascontiguousarray(np.asarray(streams, dtype=np.int32).reshape(-1)), PatchFormat.of(fmt).struct()
+        prm = self._crop_params(width, height, margin, square)
+        self._check(self._lib.ht_camshift_crop_sources_tensor_device(self._h, st.ctypes.data if len(st) else None, self._draw_sources(entries), len(entries), C.byref(prm),
+                                                                     C.byref(f), dev_ptr, stride))
+
+    def camshift_align_pairs_tensor_device(self, dev_ptr: int, pairs, width: int, height: int, fmt, margin: float = 1.0, square: bool = False, stride: int = 0):
+        """camshift_align_pairs_device with fmt as the output; a pixel whose sample centre lies outside the source is bias[c], as every
+        element of an empty entry is.  This IS the context's last align call."""
+        p, f = self._pairs(pairs), PatchFormat.of(fmt).struct()
+        prm = self._align_params(width, height, margin, square)
+        self._check(self._lib.ht_camshift_align_pairs_tensor_device(self._h, p.ctypes.data, len(p), C.byref(prm), C.byref(f), dev_ptr, stride))
+
+    def camshift_align_sources_tensor_device(self, dev_ptr: int, streams, entries, width: int, height: int, fmt, margin: float = 1.0, square: bool = False, stride: int = 0):
+        """camshift_align_sources_device with fmt as the output (see camshift_align_pairs_tensor_device)"""
+        if len(streams) != len(entries):
+            raise ValueError("camshift_align_sources_tensor_device: one stream per entry")
+        st, f = np.ascontiguousarray(np.asarray(streams, dtype=np.int32).reshape(-1)), PatchFormat.of(fmt).struct()
+        prm = self._align_params(width, height, margin, square)
+        self._check(self._lib.ht_camshift_align_sources_tensor_device(self._h, st.ctypes.data if len(st) else None, self._draw_sources(entries), len(entries), C.byref(prm),
+                                                                      C.byref(f), dev_ptr, stride))
 
     # -- measurement --------------------------------------------------------------------------------------------
     def profile(self, on: bool = True):

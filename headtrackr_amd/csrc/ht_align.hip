@@ -38,17 +38,24 @@ __device__ __forceinline__ uint32_t al_tap(const uint8_t *__restrict__ p0, const
     return ht_yuv_to_rgba((int32_t)yy, (int32_t)u, (int32_t)v, kc);
 }
 
-// the four rows of a thread's column, behind the barrier
-template <int FMT>
+// the output stage of k_align_list: the pixel's RGBA8 dword into packed rows of dw pixels
+struct AlDwordStore {
+    uint32_t *__restrict__ base;  // the entry's patch
+    int dw;
+    __device__ __forceinline__ void operator()(uint32_t o, int x, int y) const { (base + x)[(size_t)y * dw] = o; }
+};
+
+// the four rows of a thread's column, behind the barrier; every pixel ends in ONE output stage, store(o, x, y), o the pixel's RGBA8 dword
+// (k_align_list: AlDwordStore; ht_patch.hip: the model-input tensors)
+template <int FMT, class STORE>
 __device__ __forceinline__ void al_pixels(const DlDesc &d, int SW, int SH, const int64_t *s_cx, const int64_t *s_cy, const int64_t *s_rx, const int64_t *s_ry,
-                                          uint8_t *__restrict__ dst, size_t dst_stride, int dw, int dh) {
+                                          const STORE &store, int dw, int dh) {
     const int col = threadIdx.x & (IG_TW - 1), r0 = threadIdx.x / IG_TW, x = blockIdx.x * IG_TW + col, Y0 = blockIdx.y * IG_TH;
     if (x >= dw) return;
     const uint8_t *__restrict__ p0 = (const uint8_t *)d.p0, *__restrict__ p1 = (const uint8_t *)d.p1, *__restrict__ p2 = (const uint8_t *)d.p2;
     const size_t pitch0 = d.pitch0, pitch1 = d.pitch1;
     const HtYuvCoef kc = d.kc;
     const int64_t cfx = s_cx[col], cfy = s_cy[col];
-    uint32_t *out = reinterpret_cast<uint32_t *>(dst + (size_t)blockIdx.z * dst_stride) + x;
 #pragma unroll
     for (int k = 0; k < IG_RPT; k++) {
         const int j = r0 + k * (IG_NT / IG_TW), y = Y0 + j;
@@ -65,7 +72,7 @@ __device__ __forceinline__ void al_pixels(const DlDesc &d, int SW, int SH, const
 #pragma unroll
             for (int ch = 0; ch < 4; ch++) o |= ht_align_channel(p00, p01, p10, p11, 8 * ch, tx, ty);
         }
-        out[(size_t)y * dw] = o;
+        store(o, x, y);
     }
 }
 
@@ -107,9 +114,10 @@ __global__ __launch_bounds__(IG_NT) void k_align_list(const CrDesc *__restrict__
         s_ry[threadIdx.x - IG_TW] = ht_align_term(j, dh, pl.vy);
     }
     __syncthreads();
-    if (format == HT_DRAW_RGBA) al_pixels<HT_DRAW_RGBA>(d, SW, SH, s_cx, s_cy, s_rx, s_ry, dst, dst_stride, dw, dh);
-    else if (format == HT_YUV_FMT_NV12) al_pixels<HT_YUV_FMT_NV12>(d, SW, SH, s_cx, s_cy, s_rx, s_ry, dst, dst_stride, dw, dh);
-    else al_pixels<HT_YUV_FMT_I420>(d, SW, SH, s_cx, s_cy, s_rx, s_ry, dst, dst_stride, dw, dh);
+    const AlDwordStore store = {reinterpret_cast<uint32_t *>(dst + (size_t)blockIdx.z * dst_stride), dw};
+    if (format == HT_DRAW_RGBA) al_pixels<HT_DRAW_RGBA>(d, SW, SH, s_cx, s_cy, s_rx, s_ry, store, dw, dh);
+    else if (format == HT_YUV_FMT_NV12) al_pixels<HT_YUV_FMT_NV12>(d, SW, SH, s_cx, s_cy, s_rx, s_ry, store, dw, dh);
+    else al_pixels<HT_YUV_FMT_I420>(d, SW, SH, s_cx, s_cy, s_rx, s_ry, store, dw, dh);
 }
 
 // the buffers of a call of n entries, as crop_reserve's: allocates (and then waits for the stream) only on the first call or for a longer list
@@ -143,15 +151,19 @@ ht_status align_reserve(ht_ctx *c, const char *fn, size_t n) {
 
 // the checks both forms share, in front of their entries, are the crop calls' OWN (crop_check, ht_crop.hip): same fields, same bounds, same words
 static_assert(HT_ALIGN_SQUARE == HT_CROP_SQUARE && sizeof(ht_align_params) == sizeof(ht_crop_params), "align params are crop params");
+void pt_launch_upright(ht_ctx *c, dim3 grid, const CrDesc *tab, const HtCsState *states, uint8_t *out, size_t ostride, const ht_align_params &p,
+                       const ht_patch_format &fmt, ht_align_record *recs);  // ht_patch.hip
+
 ht_status align_check(ht_ctx *c, const std::string &f, bool pairs_form, const void *list, int32_t n, const ht_align_params *p, const void *out_dev, size_t out_stride,
-                      size_t *pbytes, size_t *ostride) {
+                      size_t *pbytes, size_t *ostride, bool tensor = false, const ht_patch_format *fmt = nullptr) {
     ht_crop_params q = {};
     if (p) q.out_width = p->out_width, q.out_height = p->out_height, q.margin_q8 = p->margin_q8, q.flags = p->flags;
-    return crop_check(c, f, pairs_form, list, n, p ? &q : nullptr, out_dev, out_stride, pbytes, ostride);
+    return crop_check(c, f, pairs_form, list, n, p ? &q : nullptr, out_dev, out_stride, pbytes, ostride, tensor, fmt);
 }
 
 // everything has been checked: table, kernel, records to the pinned twin
-ht_status align_launch(ht_ctx *c, const char *fn, const std::vector<HtCropDesc> &desc, const ht_align_params &p, uint8_t *out, size_t ostride) {
+ht_status align_launch(ht_ctx *c, const char *fn, const std::vector<HtCropDesc> &desc, const ht_align_params &p, uint8_t *out, size_t ostride,
+                       const ht_patch_format *fmt = nullptr) {
     const size_t n = desc.size(), need = n * sizeof(HtCropDesc);
     HT_HIP(c, hipSetDevice(c->device));
     ht_status st = align_reserve(c, fn, n);
@@ -163,9 +175,13 @@ ht_status align_launch(ht_ctx *c, const char *fn, const std::vector<HtCropDesc> 
     HT_HIP(c, hipMemcpyAsync(c->d_align_tab, c->h_align_tab[k], need, hipMemcpyHostToDevice, c->stream));
     HT_HIP(c, hipEventRecord(c->ev_align_tab[k], c->stream));
     c->align_n = 0;  // until this call's copy is behind its kernel
-    {
+    const dim3 grid((p.out_width + IG_TW - 1) / IG_TW, (p.out_height + IG_TH - 1) / IG_TH, (unsigned)n);
+    if (fmt) {
+        HtProfScope ps(c, "upright_tensor");
+        pt_launch_upright(c, grid, reinterpret_cast<const CrDesc *>(c->d_align_tab), (const HtCsState *)c->d_cs, out, ostride, p, *fmt, reinterpret_cast<ht_align_record *>(c->d_align_rec));
+        HT_HIP(c, hipGetLastError());
+    } else {
         HtProfScope ps(c, "align_list");
-        const dim3 grid((p.out_width + IG_TW - 1) / IG_TW, (p.out_height + IG_TH - 1) / IG_TH, (unsigned)n);
         hipLaunchKernelGGL(k_align_list, grid, dim3(IG_NT), 0, c->stream, reinterpret_cast<const CrDesc *>(c->d_align_tab), (const HtCsState *)c->d_cs, out, ostride,
                            (int)p.out_width, (int)p.out_height, c->W, c->H, (int)p.margin_q8, p.flags, reinterpret_cast<ht_align_record *>(c->d_align_rec));
         HT_HIP(c, hipGetLastError());
@@ -176,15 +192,14 @@ ht_status align_launch(ht_ctx *c, const char *fn, const std::vector<HtCropDesc> 
     return HT_OK;
 }
 
-}  // namespace
-
-extern "C" ht_status ht_camshift_align_pairs_device(ht_ctx *c, const ht_cs_pair *pairs, int32_t n, const ht_align_params *params, void *out_dev, size_t out_stride) {
+// both pairs-form calls: fn names the export; tensor: ht_camshift_align_pairs_tensor_device (ht_patch.hip)
+ht_status align_pairs(ht_ctx *c, const char *fn, const ht_cs_pair *pairs, int32_t n, const ht_align_params *params, bool tensor, const ht_patch_format *fmt, void *out_dev,
+                      size_t out_stride) {
     if (!c) return HT_ERR_INVALID;
-    HtRange range("ht_camshift_align_pairs_device");
-    const char *fn = "ht_camshift_align_pairs_device";
+    HtRange range(fn);
     const std::string f(fn);
     size_t pbytes = 0, ostride = 0;
-    ht_status st = align_check(c, f, true, pairs, n, params, out_dev, out_stride, &pbytes, &ostride);
+    ht_status st = align_check(c, f, true, pairs, n, params, out_dev, out_stride, &pbytes, &ostride, tensor, fmt);
     if (st != HT_OK) return st;
     const size_t fbytes = (size_t)c->W * c->H * 4, total = (size_t)(n - 1) * ostride + pbytes;
     std::vector<HtCropDesc> desc((size_t)n);
@@ -201,17 +216,17 @@ extern "C" ht_status ht_camshift_align_pairs_device(ht_ctx *c, const ht_cs_pair 
         e.SW = c->W, e.SH = c->H, e.stream = s;
         desc[(size_t)i] = e;
     }
-    return align_launch(c, fn, desc, *params, static_cast<uint8_t *>(out_dev), ostride);
+    return align_launch(c, fn, desc, *params, static_cast<uint8_t *>(out_dev), ostride, fmt);
 }
 
-extern "C" ht_status ht_camshift_align_sources_device(ht_ctx *c, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_align_params *params,
-                                                      void *out_dev, size_t out_stride) {
+// both sources-form calls
+ht_status align_sources(ht_ctx *c, const char *fn, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_align_params *params, bool tensor,
+                        const ht_patch_format *fmt, void *out_dev, size_t out_stride) {
     if (!c) return HT_ERR_INVALID;
-    HtRange range("ht_camshift_align_sources_device");
-    const char *fn = "ht_camshift_align_sources_device";
+    HtRange range(fn);
     const std::string f(fn);
     size_t pbytes = 0, ostride = 0;
-    ht_status st = align_check(c, f, false, srcs, n, params, out_dev, out_stride, &pbytes, &ostride);
+    ht_status st = align_check(c, f, false, srcs, n, params, out_dev, out_stride, &pbytes, &ostride, tensor, fmt);
     if (st != HT_OK) return st;
     if (!streams) return ht_fail(c, HT_ERR_INVALID, f + ": NULL streams");
     std::vector<HtCropDesc> desc((size_t)n);
@@ -227,7 +242,18 @@ extern "C" ht_status ht_camshift_align_sources_device(ht_ctx *c, const int32_t *
     }
     const int32_t bad = ht_draw_list_overlap(ext.data(), n, out_dev, (size_t)(n - 1) * ostride + pbytes);
     if (bad >= 0) return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": a source plane and the output overlap");
-    return align_launch(c, fn, desc, *params, static_cast<uint8_t *>(out_dev), ostride);
+    return align_launch(c, fn, desc, *params, static_cast<uint8_t *>(out_dev), ostride, fmt);
+}
+
+}  // namespace
+
+extern "C" ht_status ht_camshift_align_pairs_device(ht_ctx *c, const ht_cs_pair *pairs, int32_t n, const ht_align_params *params, void *out_dev, size_t out_stride) {
+    return align_pairs(c, "ht_camshift_align_pairs_device", pairs, n, params, false, nullptr, out_dev, out_stride);
+}
+
+extern "C" ht_status ht_camshift_align_sources_device(ht_ctx *c, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_align_params *params,
+                                                      void *out_dev, size_t out_stride) {
+    return align_sources(c, "ht_camshift_align_sources_device", streams, srcs, n, params, false, nullptr, out_dev, out_stride);
 }
 
 extern "C" ht_status ht_camshift_align_result(ht_ctx *c, int32_t n, ht_align_record *out) {

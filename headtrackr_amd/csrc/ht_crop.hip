@@ -14,6 +14,7 @@
 // size.  An empty entry stores zeros for its tile instead and returns in front of the barrier (uniformly).  Workgroup (0, 0) of an entry
 // writes its 40-byte record.  The table travels as dl_upload's does, through a ring and a device table of its own (ht_internal.h).
 #include "ht_crop_plan.h"  // HT_CROP_FN and HT_CSB_FN are defined in front of this file's #include (ht_ingest.hip)
+#include "ht_patch_plan.h"  // the model-input tensors' format (ht_patch.hip): checked here, with everything else a call is checked for
 
 namespace {
 
@@ -111,9 +112,14 @@ ht_status crop_reserve(ht_ctx *c, const char *fn, size_t n) {
     return HT_OK;
 }
 
-// the checks both forms share, in front of their entries: the context's state first, then the call's own arguments
+// the tensor forms' launches (ht_patch.hip, behind ht_align.hip): the same grid and arguments, another output stage
+void pt_launch_cut(ht_ctx *c, dim3 grid, const CrDesc *tab, const HtCsState *states, uint8_t *out, size_t ostride, const ht_crop_params &p, const ht_patch_format &fmt,
+                   ht_crop_record *recs);
+
+// the checks both forms share, in front of their entries: the context's state first, then the call's own arguments.  tensor: the output
+// is fmt's tensor (ht_patch_plan.h) instead of RGBA8 — fmt is checked here and a patch's bytes and the default stride are the tensor's
 ht_status crop_check(ht_ctx *c, const std::string &f, bool pairs_form, const void *list, int32_t n, const ht_crop_params *p, const void *out_dev, size_t out_stride,
-                     size_t *pbytes, size_t *ostride) {
+                     size_t *pbytes, size_t *ostride, bool tensor = false, const ht_patch_format *fmt = nullptr) {
     if (c->W == 0) return ht_fail(c, HT_ERR_STATE, f + ": call ht_set_geometry first");
     if (c->cs_streams <= 0 || !c->d_cs) return ht_fail(c, HT_ERR_STATE, f + ": call ht_camshift_reserve first");
     if (pairs_form && (!c->d_frames || c->nframes <= 0)) return ht_fail(c, HT_ERR_STATE, f + ": bind frames first");
@@ -123,14 +129,21 @@ ht_status crop_check(ht_ctx *c, const std::string &f, bool pairs_form, const voi
         return ht_fail(c, HT_ERR_INVALID, f + ": out_width / out_height must be 1..1024");
     if (p->margin_q8 < HT_CROP_MIN_MARGIN || p->margin_q8 > HT_CROP_MAX_MARGIN) return ht_fail(c, HT_ERR_INVALID, f + ": margin_q8 must be 64..1024");
     if (p->flags & ~(uint32_t)HT_CROP_SQUARE) return ht_fail(c, HT_ERR_INVALID, f + ": unknown flag");
+    if (tensor) {
+        if (!fmt) return ht_fail(c, HT_ERR_INVALID, f + ": NULL format");
+        const int fs = ht_patch_check_format(fmt);
+        if (fs != HT_PATCH_FMT_OK) return ht_fail(c, HT_ERR_INVALID, f + ": format: " + ht_patch_format_message(fs));
+    }
     if (!out_dev || ((uintptr_t)out_dev & 3)) return ht_fail(c, HT_ERR_INVALID, f + ": NULL or misaligned output (4-byte alignment required)");
-    *pbytes = (size_t)p->out_width * p->out_height * 4, *ostride = out_stride ? out_stride : *pbytes;
+    *pbytes = tensor ? ht_patch_bytes(p->out_width, p->out_height, fmt->dtype, fmt->channels) : (size_t)p->out_width * p->out_height * 4;
+    *ostride = out_stride ? out_stride : ht_patch_default_stride(*pbytes);
     if ((*ostride & 3) || *ostride < *pbytes) return ht_fail(c, HT_ERR_INVALID, f + ": output stride smaller than a patch or not a multiple of 4");
     return HT_OK;
 }
 
 // everything has been checked: table, kernel, records to the pinned twin
-ht_status crop_launch(ht_ctx *c, const char *fn, const std::vector<HtCropDesc> &desc, const ht_crop_params &p, uint8_t *out, size_t ostride) {
+ht_status crop_launch(ht_ctx *c, const char *fn, const std::vector<HtCropDesc> &desc, const ht_crop_params &p, uint8_t *out, size_t ostride,
+                      const ht_patch_format *fmt = nullptr) {
     const size_t n = desc.size(), need = n * sizeof(HtCropDesc);
     HT_HIP(c, hipSetDevice(c->device));
     ht_status st = crop_reserve(c, fn, n);
@@ -142,9 +155,13 @@ ht_status crop_launch(ht_ctx *c, const char *fn, const std::vector<HtCropDesc> &
     HT_HIP(c, hipMemcpyAsync(c->d_crop_tab, c->h_crop_tab[k], need, hipMemcpyHostToDevice, c->stream));
     HT_HIP(c, hipEventRecord(c->ev_crop_tab[k], c->stream));
     c->crop_n = 0;  // until this call's copy is behind its kernel
-    {
+    const dim3 grid((p.out_width + IG_TW - 1) / IG_TW, (p.out_height + IG_TH - 1) / IG_TH, (unsigned)n);
+    if (fmt) {
+        HtProfScope ps(c, "cut_tensor");
+        pt_launch_cut(c, grid, reinterpret_cast<const CrDesc *>(c->d_crop_tab), (const HtCsState *)c->d_cs, out, ostride, p, *fmt, reinterpret_cast<ht_crop_record *>(c->d_crop_rec));
+        HT_HIP(c, hipGetLastError());
+    } else {
         HtProfScope ps(c, "crop_list");
-        const dim3 grid((p.out_width + IG_TW - 1) / IG_TW, (p.out_height + IG_TH - 1) / IG_TH, (unsigned)n);
         hipLaunchKernelGGL(k_crop_list, grid, dim3(IG_NT), 0, c->stream, reinterpret_cast<const CrDesc *>(c->d_crop_tab), (const HtCsState *)c->d_cs, out, ostride,
                            (int)p.out_width, (int)p.out_height, c->W, c->H, (int)p.margin_q8, p.flags, reinterpret_cast<ht_crop_record *>(c->d_crop_rec));
         HT_HIP(c, hipGetLastError());
@@ -155,15 +172,14 @@ ht_status crop_launch(ht_ctx *c, const char *fn, const std::vector<HtCropDesc> &
     return HT_OK;
 }
 
-}  // namespace
-
-extern "C" ht_status ht_camshift_crop_pairs_device(ht_ctx *c, const ht_cs_pair *pairs, int32_t n, const ht_crop_params *params, void *out_dev, size_t out_stride) {
+// both pairs-form calls: fn names the export; tensor: ht_camshift_crop_pairs_tensor_device (ht_patch.hip)
+ht_status crop_pairs(ht_ctx *c, const char *fn, const ht_cs_pair *pairs, int32_t n, const ht_crop_params *params, bool tensor, const ht_patch_format *fmt, void *out_dev,
+                     size_t out_stride) {
     if (!c) return HT_ERR_INVALID;
-    HtRange range("ht_camshift_crop_pairs_device");
-    const char *fn = "ht_camshift_crop_pairs_device";
+    HtRange range(fn);
     const std::string f(fn);
     size_t pbytes = 0, ostride = 0;
-    ht_status st = crop_check(c, f, true, pairs, n, params, out_dev, out_stride, &pbytes, &ostride);
+    ht_status st = crop_check(c, f, true, pairs, n, params, out_dev, out_stride, &pbytes, &ostride, tensor, fmt);
     if (st != HT_OK) return st;
     const size_t fbytes = (size_t)c->W * c->H * 4, total = (size_t)(n - 1) * ostride + pbytes;
     std::vector<HtCropDesc> desc((size_t)n);
@@ -180,17 +196,17 @@ extern "C" ht_status ht_camshift_crop_pairs_device(ht_ctx *c, const ht_cs_pair *
         e.SW = c->W, e.SH = c->H, e.stream = s;
         desc[(size_t)i] = e;
     }
-    return crop_launch(c, fn, desc, *params, static_cast<uint8_t *>(out_dev), ostride);
+    return crop_launch(c, fn, desc, *params, static_cast<uint8_t *>(out_dev), ostride, fmt);
 }
 
-extern "C" ht_status ht_camshift_crop_sources_device(ht_ctx *c, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_crop_params *params,
-                                                     void *out_dev, size_t out_stride) {
+// both sources-form calls
+ht_status crop_sources(ht_ctx *c, const char *fn, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_crop_params *params, bool tensor,
+                       const ht_patch_format *fmt, void *out_dev, size_t out_stride) {
     if (!c) return HT_ERR_INVALID;
-    HtRange range("ht_camshift_crop_sources_device");
-    const char *fn = "ht_camshift_crop_sources_device";
+    HtRange range(fn);
     const std::string f(fn);
     size_t pbytes = 0, ostride = 0;
-    ht_status st = crop_check(c, f, false, srcs, n, params, out_dev, out_stride, &pbytes, &ostride);
+    ht_status st = crop_check(c, f, false, srcs, n, params, out_dev, out_stride, &pbytes, &ostride, tensor, fmt);
     if (st != HT_OK) return st;
     if (!streams) return ht_fail(c, HT_ERR_INVALID, f + ": NULL streams");
     std::vector<HtCropDesc> desc((size_t)n);
@@ -206,7 +222,18 @@ extern "C" ht_status ht_camshift_crop_sources_device(ht_ctx *c, const int32_t *s
     }
     const int32_t bad = ht_draw_list_overlap(ext.data(), n, out_dev, (size_t)(n - 1) * ostride + pbytes);
     if (bad >= 0) return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": a source plane and the output overlap");
-    return crop_launch(c, fn, desc, *params, static_cast<uint8_t *>(out_dev), ostride);
+    return crop_launch(c, fn, desc, *params, static_cast<uint8_t *>(out_dev), ostride, fmt);
+}
+
+}  // namespace
+
+extern "C" ht_status ht_camshift_crop_pairs_device(ht_ctx *c, const ht_cs_pair *pairs, int32_t n, const ht_crop_params *params, void *out_dev, size_t out_stride) {
+    return crop_pairs(c, "ht_camshift_crop_pairs_device", pairs, n, params, false, nullptr, out_dev, out_stride);
+}
+
+extern "C" ht_status ht_camshift_crop_sources_device(ht_ctx *c, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_crop_params *params,
+                                                     void *out_dev, size_t out_stride) {
+    return crop_sources(c, "ht_camshift_crop_sources_device", streams, srcs, n, params, false, nullptr, out_dev, out_stride);
 }
 
 extern "C" ht_status ht_camshift_crop_result(ht_ctx *c, int32_t n, ht_crop_record *out) {

@@ -192,7 +192,10 @@ void ht_ingest_free(ht_ctx *c) {  // ht_destroy (the stream has been synchronise
 // is host AND device text; ht_cs_pairs.hip, later in this code object, spells HT_CSB_FN with the same tokens
 #define HT_CSB_FN __host__ __device__ inline
 #define HT_CROP_FN __host__ __device__ inline
+#define HT_PATCH_FN __host__ __device__ inline  // ht_patch_plan.h: ht_crop.hip checks a tensor call's format, ht_patch.hip compiles the rule
 #include "ht_crop.hip"
 // the aligned crops: the rotated box of each tracker, upright (a kernel of its own: a gather along tilted lines, integer blend)
 #define HT_ALIGN_FN __host__ __device__ inline
 #include "ht_align.hip"
+// model-input tensors from both: the same kernels with a planar / float output stage (ht_patch_plan.h states the rule)
+#include "ht_patch.hip"

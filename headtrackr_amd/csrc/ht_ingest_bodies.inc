@@ -20,6 +20,13 @@
 #ifndef IG_NEEDS
 #define IG_NEEDS(name, type) static_assert(std::is_convertible<decltype(name), type>::value && sizeof(name) == sizeof(type), "ht_ingest_bodies.inc needs " #name " as " #type)
 #endif
+// The pixel bodies end in ONE output stage, IG_STORE(o, x, y): o is the pixel's RGBA8 dword, (x, y) its place in the destination.  The default
+// is the dword store into `out` (the destination's base + x) that every draw kernel and k_crop_list take; a kernel with another output
+// stage (ht_patch.hip: the model-input tensors) defines IG_STORE before it includes a piece and puts the default back behind itself.
+#define IG_STORE_DWORD(o, x, y) out[(size_t)(y) * dw] = (o)
+#ifndef IG_STORE
+#define IG_STORE IG_STORE_DWORD
+#endif
 #define IG_BODY_TAPS 1
 #define IG_BODY_RGBA 2
 #define IG_BODY_YUV 3
@@ -72,7 +79,7 @@
         uint32_t o = 0;
 #pragma unroll
         for (int ch = 0; ch < 4; ch++) o |= ig_channel(p00, p01, p10, p11, 8 * ch, cx.u, cx.t, ru[k], rt[k]);
-        out[(size_t)(Y0 + r0 + k * (IG_NT / IG_TW)) * dw] = o;
+        IG_STORE(o, x, Y0 + r0 + k * (IG_NT / IG_TW));
     }
 
 #elif IG_BODY_PART == IG_BODY_YUV
@@ -126,7 +133,7 @@
         uint32_t o = 0;
 #pragma unroll
         for (int ch = 0; ch < 4; ch++) o |= ig_channel(p00, p01, p10, p11, 8 * ch, cx.u, cx.t, ru[k], rt[k]);
-        out[(size_t)(Y0 + r0 + k * (IG_NT / IG_TW)) * dw] = o;
+        IG_STORE(o, x, Y0 + r0 + k * (IG_NT / IG_TW));
     }
 
 #else

@@ -1440,48 +1440,77 @@ struct CropOut {
     size_t stride = 0;
     bool wait = false;
 };
-bool get_crop_out(const Args &a, size_t i, size_t n, const char *usage, CropOut *c) {
+// fmt (the tensor forms): a patch is the tensor's C * width * height elements and the default stride its bytes rounded up to 4
+bool get_crop_out(const Args &a, size_t i, size_t n, const char *usage, CropOut *c, const ht_patch_format *fmt = nullptr) {
     View prm;
     DevBuf *out = nullptr;
     size_t off = 0;
-    if (!a.devbuf(i + 1, &out)) return false;
-    if (!a.i32s(i, 4, &prm) || prm.len != 4 || !a.offset(i + 2, &c->stride) || (a.argc > i + 3 && !a.offset(i + 3, &off))) return type_error(a.env, usage) != nullptr;
-    a.opt_bool(i + 4, &c->wait);
+    const size_t o = i + (fmt ? 2 : 1);  // outDev: behind the params, or behind the tensor forms' format object
+    if (!a.devbuf(o, &out)) return false;
+    if (!a.i32s(i, 4, &prm) || prm.len != 4 || !a.offset(o + 1, &c->stride) || (a.argc > o + 2 && !a.offset(o + 2, &off))) return type_error(a.env, usage) != nullptr;
+    a.opt_bool(o + 3, &c->wait);
     const int32_t *v = prm.as<int32_t>();
     c->prm.out_width = v[0], c->prm.out_height = v[1], c->prm.margin_q8 = v[2], c->prm.flags = (uint32_t)v[3];
     if (v[0] < 1 || v[0] > 1024 || v[1] < 1 || v[1] > 1024) return range_error(a.env, (std::string(usage) + ": width and height are 1..1024").c_str()) != nullptr;
-    const size_t pb = (size_t)v[0] * (size_t)v[1] * 4;
-    if (!frames_fit(off, n, c->stride ? c->stride : pb, pb, out->bytes)) return range_error(a.env, (std::string(usage) + ": outside the device buffer").c_str()) != nullptr;
+    const size_t pb = (size_t)v[0] * (size_t)v[1] * (fmt ? (size_t)(fmt->channels == HT_PATCH_GRAY ? 1 : 3) * (fmt->dtype == HT_PATCH_F32 ? 4 : 2) : 4);
+    if (!frames_fit(off, n, c->stride ? c->stride : (pb + 3) & ~(size_t)3, pb, out->bytes)) return range_error(a.env, (std::string(usage) + ": outside the device buffer").c_str()) != nullptr;
     c->out = static_cast<char *>(out->ptr) + off;
     return true;
 }
 
-napi_value CropPairsDevice(napi_env env, napi_callback_info info) {
-    static const char *usage = "cropPairsDevice(ctx, Int32Array pairs[2n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
-    Args a(env, info, 7);
+// the format object of the tensor forms (ht_patch_format): {dtype, layout, channels: integers, scale, bias: Float32Array[3]}, in front of
+// outDev.  Its kinds are checked here; its values are the library's to refuse.
+bool get_patch_format(napi_env env, napi_value v, const char *usage, ht_patch_format *f) {
+    napi_valuetype vt;
+    napi_value p;
+    View scale, bias;
+    std::memset(f, 0, sizeof(*f));
+    if (napi_typeof(env, v, &vt) != napi_ok || vt != napi_object || !get_prop(env, v, "dtype", &p) || !get_i32(env, p, &f->dtype) || !get_prop(env, v, "layout", &p) ||
+        !get_i32(env, p, &f->layout) || !get_prop(env, v, "channels", &p) || !get_i32(env, p, &f->channels) || !get_prop(env, v, "scale", &p) ||
+        !scale.get(env, p, napi_float32_array, 3) || scale.len != 3 || !get_prop(env, v, "bias", &p) || !bias.get(env, p, napi_float32_array, 3) || bias.len != 3)
+        return type_error(env, usage) != nullptr;
+    std::memcpy(f->scale, scale.as<float>(), sizeof f->scale);
+    std::memcpy(f->bias, bias.as<float>(), sizeof f->bias);
+    return true;
+}
+
+// cropPairsDevice and cropPairsTensorDevice: the tensor form has the format object in front of outDev
+napi_value crop_pairs_call(napi_env env, napi_callback_info info, bool tensor) {
+    const char *usage = tensor ? "cropPairsTensorDevice(ctx, Int32Array pairs[2n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)"
+                               : "cropPairsDevice(ctx, Int32Array pairs[2n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
+    const size_t t = tensor ? 1 : 0;
+    Args a(env, info, 7 + t);
     Locked L;
     const ht_cs_pair *pairs = nullptr;
     int32_t n = 0;
     CropOut c;
-    if (!a.ctx(5, &L)) return nullptr;
+    ht_patch_format fmt;
+    if (!a.ctx(5 + t, &L)) return nullptr;
     if (!get_pairs(env, a.argv[1], &pairs, &n)) return type_error(env, usage);
     if (n > 65535) return range_error(env, (std::string(usage) + ": 1..65535 pairs").c_str());
-    if (!get_crop_out(a, 2, (size_t)n, usage, &c)) return nullptr;
-    ht_status st = ht_camshift_crop_pairs_device(L.ctx, pairs, n, &c.prm, c.out, c.stride);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_crop_pairs_device");
+    if (tensor && !get_patch_format(env, a.argv[3], usage, &fmt)) return nullptr;
+    if (!get_crop_out(a, 2, (size_t)n, usage, &c, tensor ? &fmt : nullptr)) return nullptr;
+    ht_status st = tensor ? ht_camshift_crop_pairs_tensor_device(L.ctx, pairs, n, &c.prm, &fmt, c.out, c.stride) : ht_camshift_crop_pairs_device(L.ctx, pairs, n, &c.prm, c.out, c.stride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, tensor ? "ht_camshift_crop_pairs_tensor_device" : "ht_camshift_crop_pairs_device");
     if (c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
     return nullptr;
 }
 
-napi_value CropSourcesDevice(napi_env env, napi_callback_info info) {
-    static const char *usage = "cropSourcesDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
-    Args a(env, info, 8);
+napi_value CropPairsDevice(napi_env env, napi_callback_info info) { return crop_pairs_call(env, info, false); }
+napi_value CropPairsTensorDevice(napi_env env, napi_callback_info info) { return crop_pairs_call(env, info, true); }
+
+napi_value crop_sources_call(napi_env env, napi_callback_info info, bool tensor) {
+    const char *usage = tensor ? "cropSourcesTensorDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)"
+                               : "cropSourcesDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
+    const size_t t = tensor ? 1 : 0;
+    Args a(env, info, 8 + t);
     Locked L;
     View streams;
     bool is_array = false;
     uint32_t n = 0;
     CropOut c;
-    if (!a.ctx(6, &L)) return nullptr;
+    ht_patch_format fmt;
+    if (!a.ctx(6 + t, &L)) return nullptr;
     if (!a.i32s(1, 0, &streams) || napi_is_array(env, a.argv[2], &is_array) != napi_ok || !is_array || napi_get_array_length(env, a.argv[2], &n) != napi_ok)
         return type_error(env, usage);
     if (n < 1 || n > 65535) return range_error(env, (std::string(usage) + ": 1..65535 entries").c_str());
@@ -1492,12 +1521,17 @@ napi_value CropSourcesDevice(napi_env env, napi_callback_info info) {
         NAPI_OK(napi_get_element(env, a.argv[2], i, &e));
         if (!get_draw_entry(env, e, &srcs[i])) return nullptr;
     }
-    if (!get_crop_out(a, 3, (size_t)n, usage, &c)) return nullptr;
-    ht_status st = ht_camshift_crop_sources_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &c.prm, c.out, c.stride);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_crop_sources_device");
+    if (tensor && !get_patch_format(env, a.argv[4], usage, &fmt)) return nullptr;
+    if (!get_crop_out(a, 3, (size_t)n, usage, &c, tensor ? &fmt : nullptr)) return nullptr;
+    ht_status st = tensor ? ht_camshift_crop_sources_tensor_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &c.prm, &fmt, c.out, c.stride)
+                          : ht_camshift_crop_sources_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &c.prm, c.out, c.stride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, tensor ? "ht_camshift_crop_sources_tensor_device" : "ht_camshift_crop_sources_device");
     if (c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
     return nullptr;
 }
+
+napi_value CropSourcesDevice(napi_env env, napi_callback_info info) { return crop_sources_call(env, info, false); }
+napi_value CropSourcesTensorDevice(napi_env env, napi_callback_info info) { return crop_sources_call(env, info, true); }
 
 // {records: Int32Array [6n] = code, stream, x, y, width, height per entry; ratios: Float64Array [2n] = rx, ry}
 napi_value CropResult(napi_env env, napi_callback_info info) {
@@ -1535,33 +1569,43 @@ ht_align_params align_params(const CropOut &c) {
     return p;
 }
 
-napi_value AlignPairsDevice(napi_env env, napi_callback_info info) {
-    static const char *usage = "alignPairsDevice(ctx, Int32Array pairs[2n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
-    Args a(env, info, 7);
+napi_value align_pairs_call(napi_env env, napi_callback_info info, bool tensor) {
+    const char *usage = tensor ? "alignPairsTensorDevice(ctx, Int32Array pairs[2n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)"
+                               : "alignPairsDevice(ctx, Int32Array pairs[2n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
+    const size_t t = tensor ? 1 : 0;
+    Args a(env, info, 7 + t);
     Locked L;
     const ht_cs_pair *pairs = nullptr;
     int32_t n = 0;
     CropOut c;
-    if (!a.ctx(5, &L)) return nullptr;
+    ht_patch_format fmt;
+    if (!a.ctx(5 + t, &L)) return nullptr;
     if (!get_pairs(env, a.argv[1], &pairs, &n)) return type_error(env, usage);
     if (n > 65535) return range_error(env, (std::string(usage) + ": 1..65535 pairs").c_str());
-    if (!get_crop_out(a, 2, (size_t)n, usage, &c)) return nullptr;
+    if (tensor && !get_patch_format(env, a.argv[3], usage, &fmt)) return nullptr;
+    if (!get_crop_out(a, 2, (size_t)n, usage, &c, tensor ? &fmt : nullptr)) return nullptr;
     const ht_align_params prm = align_params(c);
-    ht_status st = ht_camshift_align_pairs_device(L.ctx, pairs, n, &prm, c.out, c.stride);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_align_pairs_device");
+    ht_status st = tensor ? ht_camshift_align_pairs_tensor_device(L.ctx, pairs, n, &prm, &fmt, c.out, c.stride) : ht_camshift_align_pairs_device(L.ctx, pairs, n, &prm, c.out, c.stride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, tensor ? "ht_camshift_align_pairs_tensor_device" : "ht_camshift_align_pairs_device");
     if (c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
     return nullptr;
 }
 
-napi_value AlignSourcesDevice(napi_env env, napi_callback_info info) {
-    static const char *usage = "alignSourcesDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
-    Args a(env, info, 8);
+napi_value AlignPairsDevice(napi_env env, napi_callback_info info) { return align_pairs_call(env, info, false); }
+napi_value AlignPairsTensorDevice(napi_env env, napi_callback_info info) { return align_pairs_call(env, info, true); }
+
+napi_value align_sources_call(napi_env env, napi_callback_info info, bool tensor) {
+    const char *usage = tensor ? "alignSourcesTensorDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)"
+                               : "alignSourcesDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
+    const size_t t = tensor ? 1 : 0;
+    Args a(env, info, 8 + t);
     Locked L;
     View streams;
     bool is_array = false;
     uint32_t n = 0;
     CropOut c;
-    if (!a.ctx(6, &L)) return nullptr;
+    ht_patch_format fmt;
+    if (!a.ctx(6 + t, &L)) return nullptr;
     if (!a.i32s(1, 0, &streams) || napi_is_array(env, a.argv[2], &is_array) != napi_ok || !is_array || napi_get_array_length(env, a.argv[2], &n) != napi_ok)
         return type_error(env, usage);
     if (n < 1 || n > 65535) return range_error(env, (std::string(usage) + ": 1..65535 entries").c_str());
@@ -1572,13 +1616,18 @@ napi_value AlignSourcesDevice(napi_env env, napi_callback_info info) {
         NAPI_OK(napi_get_element(env, a.argv[2], i, &e));
         if (!get_draw_entry(env, e, &srcs[i])) return nullptr;
     }
-    if (!get_crop_out(a, 3, (size_t)n, usage, &c)) return nullptr;
+    if (tensor && !get_patch_format(env, a.argv[4], usage, &fmt)) return nullptr;
+    if (!get_crop_out(a, 3, (size_t)n, usage, &c, tensor ? &fmt : nullptr)) return nullptr;
     const ht_align_params prm = align_params(c);
-    ht_status st = ht_camshift_align_sources_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &prm, c.out, c.stride);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_align_sources_device");
+    ht_status st = tensor ? ht_camshift_align_sources_tensor_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &prm, &fmt, c.out, c.stride)
+                          : ht_camshift_align_sources_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &prm, c.out, c.stride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, tensor ? "ht_camshift_align_sources_tensor_device" : "ht_camshift_align_sources_device");
     if (c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
     return nullptr;
 }
+
+napi_value AlignSourcesDevice(napi_env env, napi_callback_info info) { return align_sources_call(env, info, false); }
+napi_value AlignSourcesTensorDevice(napi_env env, napi_callback_info info) { return align_sources_call(env, info, true); }
 
 // {records: Int32Array [4n] = code, stream, a12, 0 per entry; terms: Float64Array [6n] = cx, cy, ux, uy, vx, vy in Q16 source pixels
 // (|value| < 2^52: exact in a binary64)}
@@ -1648,6 +1697,8 @@ napi_value Init(napi_env env, napi_value exports) {
                {"drawFramesYuv", DrawFramesYuv}, {"drawFramesYuvDevice", DrawFramesYuvDevice}, {"drawListDevice", DrawListDevice},
                {"cropPairsDevice", CropPairsDevice}, {"cropSourcesDevice", CropSourcesDevice}, {"cropResult", CropResult},
                {"alignPairsDevice", AlignPairsDevice}, {"alignSourcesDevice", AlignSourcesDevice}, {"alignResult", AlignResult},
+               {"cropPairsTensorDevice", CropPairsTensorDevice}, {"cropSourcesTensorDevice", CropSourcesTensorDevice},
+               {"alignPairsTensorDevice", AlignPairsTensorDevice}, {"alignSourcesTensorDevice", AlignSourcesTensorDevice},
                {"detectBestEnqueue", DetectBestEnqueue}, {"collectBestDevice", CollectBestDevice}, {"detectGrouped", DetectGrouped},
                {"detectBestRecords", DetectBestRecords}, {"groupHits", GroupHits},
                {"framesBound", FramesBound},     {"framesEnqueued", FramesEnqueued}, {"graphLaunches", GraphLaunches}};
@@ -1664,7 +1715,10 @@ napi_value Init(napi_env env, napi_value exports) {
                   {"YUV_NV12", HT_YUV_NV12},          {"YUV_I420", HT_YUV_I420},               {"DRAW_RGBA", HT_DRAW_RGBA},
                   {"CSB_UNTOUCHED", HT_CSB_UNTOUCHED}, {"CSB_FACE", HT_CSB_FACE},              {"CSB_FALLBACK", HT_CSB_FALLBACK}, {"CSB_DEFERRED", HT_CSB_DEFERRED},
                   {"CROP_EMPTY", HT_CROP_EMPTY},      {"CROP_FACE", HT_CROP_FACE},             {"CROP_SQUARE", HT_CROP_SQUARE},
-                  {"ALIGN_EMPTY", HT_ALIGN_EMPTY},    {"ALIGN_FACE", HT_ALIGN_FACE},           {"ALIGN_SQUARE", HT_ALIGN_SQUARE}};
+                  {"ALIGN_EMPTY", HT_ALIGN_EMPTY},    {"ALIGN_FACE", HT_ALIGN_FACE},           {"ALIGN_SQUARE", HT_ALIGN_SQUARE},
+                  {"PATCH_F32", HT_PATCH_F32},        {"PATCH_F16", HT_PATCH_F16},             {"PATCH_BF16", HT_PATCH_BF16},
+                  {"PATCH_CHW", HT_PATCH_CHW},        {"PATCH_HWC", HT_PATCH_HWC},             {"PATCH_RGB", HT_PATCH_RGB},
+                  {"PATCH_BGR", HT_PATCH_BGR},        {"PATCH_GRAY", HT_PATCH_GRAY}};
     for (auto &c : consts) {
         napi_value v;
         napi_create_int32(env, c.value, &v);

@@ -20,6 +20,8 @@
 
 #include "ht_internal.h"
 #include "ht_resample_tap.h"
+#define HT_GRAY_FN __device__ __forceinline__
+#include "ht_gray.h"
 
 namespace {
 
@@ -37,12 +39,7 @@ __device__ __forceinline__ bool xcd_item(uint32_t per_frame, uint32_t nframes, u
     return true;
 }
 
-__device__ __forceinline__ uint32_t gray_of(uint32_t px) {  // ccv.js:29
-    const double r = (double)(px & 0xffu), g = (double)((px >> 8) & 0xffu), b = (double)((px >> 16) & 0xffu);
-    const double v = __dadd_rn(__dadd_rn(__dmul_rn(r, 0.3), __dmul_rn(g, 0.59)), __dmul_rn(b, 0.11));
-    const int q = (int)__builtin_rint(v);  // round half to even (Uint8ClampedArray)
-    return (uint32_t)min(max(q, 0), 255);
-}
+__device__ __forceinline__ uint32_t gray_of(uint32_t px) { return ht_gray_of(px); }  // ccv.js:29: the text is ht_gray.h's, shared with ht_patch_plan.h
 
 // RGBA -> planar gray (level 0).  ALIGNED: W % 4 == 0, so plane and frame are both linear and 16-byte aligned per
 // group of 4 pixels: one dwordx4 load + one dword store per thread, fully coalesced.

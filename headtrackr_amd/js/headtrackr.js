@@ -842,6 +842,50 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
    *                                    CROP_EMPTY: a lost or never tracked tracker, zeros), ratios: Float64Array(2 n), patches: Uint8Array(n width height 4)}
    *                                    of the LAST crop call; waits for it
    *   opts = {width, height (1..1024), margin = 1 (0.25..4: the box widened around its centre, in steps of 1/256), square = false} */
+  /* Model-input tensors: with opts.tensor = {dtype: 'f32' | 'f16' | 'bf16', layout: 'chw' | 'hwc', channels: 'rgb' | 'bgr' | 'gray', scale, bias}
+   * (scale, bias: a number for all channels or an array with one per output channel; defaults 1 / 255 and 0) the four calls write the
+   * network's input instead of RGBA — every element fl32(fl32(byte * scale[c]) + bias[c]) rounded to the dtype, in the same single launch
+   * (ht_camshift_*_tensor_device) — and cropResult() / alignResult() return `patches` as a Float32Array, or as a Uint16Array of the raw
+   * f16 / bf16 bits, with `tensor: {dtype, layout, channels, shape}`.  An empty entry is bias[c] everywhere: read the record's code. */
+  const TENSOR_DTYPES = { f32: 0, f16: 1, bf16: 2 }, TENSOR_LAYOUTS = { chw: 0, hwc: 1 }, TENSOR_CHANNELS = { rgb: 0, bgr: 1, gray: 2 };
+  const tensorFormat = function (what, t, names) {
+    if (t === undefined || t === null) return null;
+    if (typeof t !== 'object') throw new TypeError('DeviceBatch.' + what + ': opts.tensor is {dtype, layout, channels, scale, bias}');
+    if (names.some(function (f) { return typeof A[f] !== 'function'; }))
+      throw new Error('DeviceBatch.' + what + ': this headtrackr_hip.node has no ' + names.join(' / ') + ' (rebuild it)');
+    const dtype = t.dtype === undefined ? 'f16' : t.dtype, layout = t.layout === undefined ? 'chw' : t.layout, channels = t.channels === undefined ? 'rgb' : t.channels;
+    if (!(dtype in TENSOR_DTYPES)) throw new RangeError('DeviceBatch.' + what + ": opts.tensor.dtype is 'f32', 'f16' or 'bf16'");
+    if (!(layout in TENSOR_LAYOUTS)) throw new RangeError('DeviceBatch.' + what + ": opts.tensor.layout is 'chw' or 'hwc'");
+    if (!(channels in TENSOR_CHANNELS)) throw new RangeError('DeviceBatch.' + what + ": opts.tensor.channels is 'rgb', 'bgr' or 'gray'");
+    const C = channels === 'gray' ? 1 : 3;
+    const coef = function (name, v, dflt) {
+      const out = new Float32Array(3);
+      if (v === undefined) v = dflt;
+      const list = typeof v === 'number' ? new Array(C).fill(v) : Array.from(v || []);
+      if (list.length !== C || list.some(function (x) { return typeof x !== 'number'; }))
+        throw new TypeError('DeviceBatch.' + what + ': opts.tensor.' + name + ' is a number or ' + C + ' numbers (one per output channel)');
+      list.forEach(function (x, c) { out[c] = x; });
+      return out;
+    };
+    return { dtype: TENSOR_DTYPES[dtype], layout: TENSOR_LAYOUTS[layout], channels: TENSOR_CHANNELS[channels], scale: coef('scale', t.scale, 1 / 255), bias: coef('bias', t.bias, 0),
+             names: { dtype: dtype, layout: layout, channels: channels }, C: C, esize: dtype === 'f32' ? 4 : 2 };
+  };
+  const tensorArg = function (t) { return { dtype: t.dtype, layout: t.layout, channels: t.channels, scale: t.scale, bias: t.bias }; };
+  const patchBytes = function (prm, t) { return t ? t.C * prm[0] * prm[1] * t.esize : prm[0] * prm[1] * 4; };
+  const patchStride = function (prm, t) { return (patchBytes(prm, t) + 3) & ~3; };
+  /* the downloaded patches of a tensor call: the elements of all n patches, without the padding behind an odd 16-bit patch */
+  const tensorResult = function (last, dev) {
+    const t = last.tensor, pb = t.C * last.width * last.height * t.esize, stride = (pb + 3) & ~3, raw = new Uint8Array(last.n * stride);
+    A.deviceDownload(ctxs[0], dev, 0, raw);
+    let bytes = raw;
+    if (stride !== pb) {
+      bytes = new Uint8Array(last.n * pb);
+      for (let i = 0; i < last.n; i++) bytes.set(raw.subarray(i * stride, i * stride + pb), i * pb);
+    }
+    const patches = t.esize === 4 ? new Float32Array(bytes.buffer, 0, bytes.length >> 2) : new Uint16Array(bytes.buffer, 0, bytes.length >> 1);
+    const shape = t.layout === 0 ? [last.n, t.C, last.height, last.width] : [last.n, last.height, last.width, t.C];
+    return { patches: patches, tensor: { dtype: t.names.dtype, layout: t.names.layout, channels: t.names.channels, shape: shape } };
+  };
   let cropDev = null, cropBytes = 0, lastCrop = null;
   const needCrop = function (what) {
     if (typeof A.cropPairsDevice !== 'function' || typeof A.cropSourcesDevice !== 'function' || typeof A.cropResult !== 'function')
@@ -856,31 +900,37 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     if (typeof margin !== 'number' || !(margin >= 0.25 && margin <= 4)) throw new RangeError('DeviceBatch.' + what + ': opts.margin is a number 0.25..4');
     return Int32Array.from([o.width, o.height, Math.round(margin * 256), o.square ? 1 : 0]);
   };
-  const cropOut = function (count, prm) { /* the patch buffer, grown on demand */
-    const need = count * prm[0] * prm[1] * 4;
+  const cropOut = function (count, prm, t) { /* the patch buffer, grown on demand */
+    const need = count * (t ? patchStride(prm, t) : prm[0] * prm[1] * 4);
     if (cropBytes < need) {
       if (cropDev) A.deviceFree(ctxs[0], cropDev); /* waits for the work in flight */
       cropDev = A.deviceAlloc(ctxs[0], need); cropBytes = need;
     }
-    lastCrop = { n: count, width: prm[0], height: prm[1] };
+    lastCrop = { n: count, width: prm[0], height: prm[1], tensor: t || null };
     return cropDev;
   };
   this.cropPairs = function (set, pairs, o) {
     needCrop('cropPairs'); pairList('cropPairs', pairs);
     if (pairs.length > 2 * 65535) throw new RangeError('DeviceBatch.cropPairs: at most 65535 pairs');
-    const prm = cropParams('cropPairs', o);
+    const prm = cropParams('cropPairs', o), t = tensorFormat('cropPairs', o.tensor, ['cropPairsTensorDevice']);
     bind0(set === undefined ? 0 : set);
-    A.cropPairsDevice(ctxs[0], pairs, prm, cropOut(pairs.length >> 1, prm), 0, 0, false);
+    if (t) A.cropPairsTensorDevice(ctxs[0], pairs, prm, tensorArg(t), cropOut(pairs.length >> 1, prm, t), 0, 0, false);
+    else A.cropPairsDevice(ctxs[0], pairs, prm, cropOut(pairs.length >> 1, prm), 0, 0, false);
   };
   this.cropFeeds = function (sset, streams, o) {
     needCrop('cropFeeds');
     if (!(streams instanceof Int32Array) || streams.length !== n) throw new TypeError('DeviceBatch.cropFeeds: streams is an Int32Array with one tracker per feed (' + n + ')');
-    const prm = cropParams('cropFeeds', o), entries = listEntries(sset, o.rects, 'cropFeeds');
-    A.cropSourcesDevice(ctxs[0], streams, entries, prm, cropOut(n, prm), 0, 0, false);
+    const prm = cropParams('cropFeeds', o), t = tensorFormat('cropFeeds', o.tensor, ['cropSourcesTensorDevice']), entries = listEntries(sset, o.rects, 'cropFeeds');
+    if (t) A.cropSourcesTensorDevice(ctxs[0], streams, entries, prm, tensorArg(t), cropOut(n, prm, t), 0, 0, false);
+    else A.cropSourcesDevice(ctxs[0], streams, entries, prm, cropOut(n, prm), 0, 0, false);
   };
   this.cropResult = function () {
     if (!lastCrop) throw new Error('DeviceBatch.cropResult: no cropPairs / cropFeeds yet');
     const r = A.cropResult(ctxs[0], lastCrop.n), bytes = lastCrop.n * lastCrop.width * lastCrop.height * 4;
+    if (lastCrop.tensor) {
+      const tr = tensorResult(lastCrop, cropDev);
+      return { n: lastCrop.n, width: lastCrop.width, height: lastCrop.height, records: r.records, ratios: r.ratios, patches: tr.patches, tensor: tr.tensor };
+    }
     const patches = new Uint8Array(bytes);
     A.deviceDownload(ctxs[0], cropDev, 0, patches);
     return { n: lastCrop.n, width: lastCrop.width, height: lastCrop.height, records: r.records, ratios: r.ratios, patches: patches };
@@ -898,31 +948,37 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
       throw new Error('DeviceBatch.' + what + ': this headtrackr_hip.node has no alignPairsDevice / alignSourcesDevice / alignResult (rebuild it)');
     if (!trackers) throw new Error('DeviceBatch.' + what + ': no trackers yet (initPairs, initTrackers or detectStep first)');
   };
-  const alignOut = function (count, prm) { /* the patch buffer, grown on demand */
-    const need = count * prm[0] * prm[1] * 4;
+  const alignOut = function (count, prm, t) { /* the patch buffer, grown on demand */
+    const need = count * (t ? patchStride(prm, t) : prm[0] * prm[1] * 4);
     if (alignBytes < need) {
       if (alignDev) A.deviceFree(ctxs[0], alignDev); /* waits for the work in flight */
       alignDev = A.deviceAlloc(ctxs[0], need); alignBytes = need;
     }
-    lastAlign = { n: count, width: prm[0], height: prm[1] };
+    lastAlign = { n: count, width: prm[0], height: prm[1], tensor: t || null };
     return alignDev;
   };
   this.alignPairs = function (set, pairs, o) {
     needAlign('alignPairs'); pairList('alignPairs', pairs);
     if (pairs.length > 2 * 65535) throw new RangeError('DeviceBatch.alignPairs: at most 65535 pairs');
-    const prm = cropParams('alignPairs', o);
+    const prm = cropParams('alignPairs', o), t = tensorFormat('alignPairs', o.tensor, ['alignPairsTensorDevice']);
     bind0(set === undefined ? 0 : set);
-    A.alignPairsDevice(ctxs[0], pairs, prm, alignOut(pairs.length >> 1, prm), 0, 0, false);
+    if (t) A.alignPairsTensorDevice(ctxs[0], pairs, prm, tensorArg(t), alignOut(pairs.length >> 1, prm, t), 0, 0, false);
+    else A.alignPairsDevice(ctxs[0], pairs, prm, alignOut(pairs.length >> 1, prm), 0, 0, false);
   };
   this.alignFeeds = function (sset, streams, o) {
     needAlign('alignFeeds');
     if (!(streams instanceof Int32Array) || streams.length !== n) throw new TypeError('DeviceBatch.alignFeeds: streams is an Int32Array with one tracker per feed (' + n + ')');
-    const prm = cropParams('alignFeeds', o), entries = listEntries(sset, o.rects, 'alignFeeds');
-    A.alignSourcesDevice(ctxs[0], streams, entries, prm, alignOut(n, prm), 0, 0, false);
+    const prm = cropParams('alignFeeds', o), t = tensorFormat('alignFeeds', o.tensor, ['alignSourcesTensorDevice']), entries = listEntries(sset, o.rects, 'alignFeeds');
+    if (t) A.alignSourcesTensorDevice(ctxs[0], streams, entries, prm, tensorArg(t), alignOut(n, prm, t), 0, 0, false);
+    else A.alignSourcesDevice(ctxs[0], streams, entries, prm, alignOut(n, prm), 0, 0, false);
   };
   this.alignResult = function () {
     if (!lastAlign) throw new Error('DeviceBatch.alignResult: no alignPairs / alignFeeds yet');
     const r = A.alignResult(ctxs[0], lastAlign.n), bytes = lastAlign.n * lastAlign.width * lastAlign.height * 4;
+    if (lastAlign.tensor) {
+      const tr = tensorResult(lastAlign, alignDev);
+      return { n: lastAlign.n, width: lastAlign.width, height: lastAlign.height, records: r.records, terms: r.terms, patches: tr.patches, tensor: tr.tensor };
+    }
     const patches = new Uint8Array(bytes);
     A.deviceDownload(ctxs[0], alignDev, 0, patches);
     return { n: lastAlign.n, width: lastAlign.width, height: lastAlign.height, records: r.records, terms: r.terms, patches: patches };

@@ -492,7 +492,7 @@ ht_status ht_camshift_crop_records_device(ht_ctx *ctx, const void **records, int
  * view, taps clamped to the source frame; a pixel whose sample centre lies outside the source frame is four zero bytes.  HT_ALIGN_EMPTY — a
  * lost 0 x 0 object, a stream that was never tracked, a box wider than 65536 or centred beyond +-2^20, an angle that is not finite or beyond
  * +-1024 — writes every byte of the patch as 0.  Not part of this: sub-pixel centres (x, y are floored as the crop calls floor them), a
- * prefilter for strong downscales, planar or float output. */
+ * prefilter for strong downscales.  (Planar or float output: the _tensor calls below.) */
 enum { HT_ALIGN_EMPTY = 0, HT_ALIGN_FACE = 1 };
 enum { HT_ALIGN_SQUARE = 1 };
 typedef struct ht_align_params {
@@ -518,6 +518,46 @@ ht_status ht_camshift_align_result(ht_ctx *ctx, int32_t n, ht_align_record *out)
 /* Device pointer of those records (*n of them), complete for work enqueued on the ctx stream behind the align call; valid until the next
  * align call of the context.  HT_ERR_STATE while there is none. */
 ht_status ht_camshift_align_records_device(ht_ctx *ctx, const void **records, int32_t *n);
+
+/* ---- model-input tensors from face crops: planar float patches on the device ------------------------------------------- */
+
+/* The crop and align calls above write RGBA8.  These four write the tensor a network reads, in the same single enqueue-only launch: f(patch),
+ * where `patch` is byte for byte what the call of the same name without `_tensor` gives for the same arguments on the same tracker state,
+ * and f is, per pixel and output channel c (headtrackr_amd/csrc/ht_patch_plan.h states the rule):
+ *   b = the source byte: HT_PATCH_RGB bytes R, G, B; HT_PATCH_BGR bytes B, G, R; HT_PATCH_GRAY one channel, the ccv.grayscale byte of
+ *       (R, G, B) (binary64, round half to even); alpha is dropped;
+ *   v = fl32(fl32((float)b * scale[c]) + bias[c]): two binary32 operations, round to nearest even, never fused, subnormals kept;
+ *   the element: the bits of v (HT_PATCH_F32), v rounded to binary16 (HT_PATCH_F16: nearest even, gradual underflow, overflow to infinity)
+ *       or to bfloat16 (HT_PATCH_BF16: nearest even);
+ *   HT_PATCH_CHW: C planes of out_height x out_width elements, packed; HT_PATCH_HWC: C elements per pixel, packed.
+ * An EMPTY entry, and a pixel of an aligned patch whose sample centre lies outside the source, is therefore f of the zero byte — bias[c]
+ * in the dtype —, not zero bytes; the record's `code` tells an empty entry from a black face.
+ * scale[c] and bias[c] must be finite and 0 or of a magnitude within 2^-64 .. 2^64 (then no binary32 intermediate is subnormal or NaN);
+ * the slots of channels the mode does not have (gray: 1 and 2) must be 0; pad must be 0.
+ * Not part of this: an alpha or validity-mask channel, sub-pixel centres, a prefilter for strong downscales, per-entry formats,
+ * integer-quantised (int8) output. */
+enum { HT_PATCH_F32 = 0, HT_PATCH_F16 = 1, HT_PATCH_BF16 = 2 };
+enum { HT_PATCH_CHW = 0, HT_PATCH_HWC = 1 };
+enum { HT_PATCH_RGB = 0, HT_PATCH_BGR = 1, HT_PATCH_GRAY = 2 };
+typedef struct ht_patch_format {
+    int32_t dtype, layout, channels, pad; /* HT_PATCH_F32 .., HT_PATCH_CHW .., HT_PATCH_RGB ..; 0 */
+    float scale[3], bias[3];              /* per output channel */
+} ht_patch_format;                        /* 40 bytes */
+/* Arguments, list rules, the "entry <i>" refusals, status codes and the enqueue-only contract are those of the call of the same name
+ * without `_tensor`; format is not NULL and is checked, with everything else, before anything is enqueued.  A patch is C * out_width *
+ * out_height * (4 or 2) bytes (C = 3, gray: 1); out_dev is 4-byte aligned; out_stride is 0 (a patch's bytes rounded up to 4) or a multiple
+ * of 4 that is at least a patch's bytes, so a 16-bit plane of odd out_width * out_height starts 2-byte aligned.  The overlap refusal
+ * uses the tensor's own byte range.  A tensor call IS the context's last crop (or align) call: ht_camshift_crop_result /
+ * ht_camshift_crop_records_device (ht_camshift_align_result / ht_camshift_align_records_device) report on it, with the records the RGBA
+ * call would have written. */
+ht_status ht_camshift_crop_pairs_tensor_device(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, const ht_crop_params *params, const ht_patch_format *format,
+                                               void *out_dev, size_t out_stride);
+ht_status ht_camshift_crop_sources_tensor_device(ht_ctx *ctx, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_crop_params *params,
+                                                 const ht_patch_format *format, void *out_dev, size_t out_stride);
+ht_status ht_camshift_align_pairs_tensor_device(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, const ht_align_params *params, const ht_patch_format *format,
+                                                void *out_dev, size_t out_stride);
+ht_status ht_camshift_align_sources_tensor_device(ht_ctx *ctx, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_align_params *params,
+                                                  const ht_patch_format *format, void *out_dev, size_t out_stride);
 
 /* ---- multi-GPU: fixed-size result records, all-gathered over RCCL/xGMI ------------------------------------ */
 
