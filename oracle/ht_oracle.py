@@ -65,6 +65,8 @@ def lib():
         L.ho_scale.argtypes = [C.c_int]
         L.ho_pyramid.restype = C.c_int
         L.ho_pyramid.argtypes = [u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Level), u8p, C.POINTER(C.c_int64)]
+        L.ho_pyramid_layout.restype = C.c_int
+        L.ho_pyramid_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Level), C.POINTER(C.c_int64)]
         L.ho_detect_raw.restype = C.c_int64
         L.ho_detect_raw.argtypes = [u8p, C.c_int, C.c_int, C.c_int, u8p, C.c_size_t, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         L.ho_hits_to_rects.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -114,6 +116,16 @@ def pyramid(rgba: np.ndarray, interval: int = 5, cw: int = 24, ch: int = 24, gra
     return lv, arena[: nbytes.value]
 
 
+def pyramid_layout(w: int, h: int, interval: int = 5, cw: int = 24, ch: int = 24):
+    """Level sizes only (ccv.js:110-127): list of (w, h) per level, without building a plane.  ValueError beyond MAX_LEVELS."""
+    levels = (Level * MAX_LEVELS)()
+    nbytes = C.c_int64(0)
+    n = lib().ho_pyramid_layout(w, h, interval, cw, ch, levels, C.byref(nbytes))
+    if n < 0:
+        raise ValueError("pyramid layout failed")
+    return [(levels[i].w, levels[i].h) for i in range(n)]
+
+
 def plane(levels, arena, i: int, slot: int = 0) -> np.ndarray:
     w, h, off = levels[i]
     return arena[off[slot] : off[slot] + w * h].reshape(h, w)
@@ -150,9 +162,10 @@ def group(rects: np.ndarray, min_neighbors: int = 1) -> np.ndarray:
     return out[:n].copy()
 
 
-def detect_objects(rgba, cascade_blob, interval=5, min_neighbors=1, gray_in_r=False):
-    hits = detect_raw(rgba, cascade_blob, interval, gray_in_r)
-    rects = hits_to_rects(hits, interval)
+def detect_objects(rgba, cascade_blob, interval=5, min_neighbors=1, gray_in_r=False, cw=24, ch=24, cap=1 << 16):
+    """cw, ch: the window of cascade_blob (the rects' size, ccv.js:710-711)"""
+    hits = detect_raw(rgba, cascade_blob, interval, gray_in_r, cap=cap)
+    rects = hits_to_rects(hits, interval, cw, ch)
     return group(rects, min_neighbors) if min_neighbors > 0 else rects
 
 

@@ -6,7 +6,8 @@
  *   node oracle/ref_harness.js job.json out.json
  *
  * job.json: { "cases": [ {name, kind, w, h, ...} ] } with raw RGBA frames in files (see tests/golden/make_golden.py).
- *   kind "detect":     {frame, interval?, ops:["gray","pyramid","raw","grouped","whitebalance"]}
+ *   kind "detect":     {frame, interval?, cascade?, ops:["gray","pyramid","raw","grouped","whitebalance"]}
+ *                      cascade = a cascade object in the shape of headtrackr.cascade, used instead of it (ccv.js:109: an argument)
  *                      gray/pyramid = CRC32 of byte 0 of every pixel of each pyramid canvas, in creation order
  *                      (ccv.js:117-147: levels 1..5, levels 6..38, then for i=12..38 variants 1,2,3)
  *   kind "camshift":   {frames:[...], rect:[x,y,w,h], calcAngles} -> per track() call searchWindow + trackObj
@@ -62,6 +63,7 @@ function rectOut(r) {
 function runDetect(cs, base) {
   const out = { name: cs.name, kind: 'detect', w: cs.w, h: cs.h };
   const interval = cs.interval === undefined ? 5 : cs.interval;
+  const cascade = cs.cascade === undefined ? headtrackr.cascade : cs.cascade;
   const ops = cs.ops || ['gray', 'pyramid', 'raw', 'grouped'];
   const input = loadCanvas(path.resolve(base, cs.frame), cs.w, cs.h);
   out.input_crc = crc32All(input._buf);
@@ -73,7 +75,7 @@ function runDetect(cs, base) {
   }
   if (ops.indexOf('raw') >= 0 || ops.indexOf('pyramid') >= 0) {
     shim.stats.trackCreated = true; shim.stats.created = [];
-    const seq = headtrackr.ccv.detect_objects(copyCanvas(gray), headtrackr.cascade, interval, 0);
+    const seq = headtrackr.ccv.detect_objects(copyCanvas(gray), cascade, interval, 0);
     shim.stats.trackCreated = false;
     if (ops.indexOf('pyramid') >= 0) {
       out.pyramid = shim.stats.created.map(function (c) { return { w: c.width, h: c.height, crc: crc32Channel0(c._buf) }; });
@@ -84,7 +86,7 @@ function runDetect(cs, base) {
   if (ops.indexOf('grouped') >= 0) {
     const mn = cs.min_neighbors === undefined ? 1 : cs.min_neighbors;
     out.min_neighbors = mn;
-    out.grouped = headtrackr.ccv.detect_objects(copyCanvas(gray), headtrackr.cascade, interval, mn).map(rectOut);
+    out.grouped = headtrackr.ccv.detect_objects(copyCanvas(gray), cascade, interval, mn).map(rectOut);
   }
   return out;
 }

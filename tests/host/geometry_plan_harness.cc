@@ -3,7 +3,8 @@
 //
 //   geometry_plan_harness plan <cases>   one case per line:
 //       name W H max_batch interval rs_rpt rs_nofast rs_nosort rs_notail rs_tailcap rs_tailcap_forced tail_table tail_table_forced
-//       early_scan aux_stream queue_capacity_cfg nlevel_dims [w h]...
+//       early_scan aux_stream queue_capacity_cfg nlevel_dims [w h]... [cw ch]
+//     (cw ch: the cascade's window, 24 24 when left out)
 //     plans every case, checks what the kernels rely on (check_plan below) and prints one JSON object per line: the scalar results, one
 //     CRC32 per table as ht_set_geometry uploads it, and the level sizes
 //   geometry_plan_harness taps <tuples>  one "i r s origin" per line (r as a C hex float): prints "a b t u" of ht_host_tap (t, u as hex floats)
@@ -158,6 +159,10 @@ static int run_plan(const char *path) {
         for (auto &d : dims) ss >> d;
         if (!ss) return fprintf(stderr, "bad case line: %s\n", line.c_str()), 2;
         in.next = in.interval + 1, in.cw = in.ch = 24;
+        {
+            uint32_t cw, ch;
+            if (ss >> cw >> ch) in.cw = cw, in.ch = ch;
+        }
         in.rs_nofast = nofast, in.rs_nosort = nosort, in.rs_notail = notail, in.rs_tailcap = tailcap, in.rs_tailcap_forced = tcf, in.tail_table_forced = ttf;
         in.early_scan = es, in.aux_stream = aux, in.queue_capacity_cfg = (uint32_t)qcfg;
         const int upto = (int)std::floor(std::log((double)std::min(in.cw, in.ch)) / std::log(ht_scale_of(in.interval)));  // as ht_set_geometry, ccv.js:112
