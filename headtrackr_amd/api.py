@@ -689,6 +689,56 @@ class Context:
         self._check(self._lib.ht_camshift_align_sources_tensor_device(self._h, st.ctypes.data if len(st) else None, self._draw_sources(entries), len(entries), C.byref(prm),
                                                                       C.byref(f), dev_ptr, stride))
 
+    # -- prefiltered face crops: each patch pixel the mean of a block of the unfiltered rule's samples ------------------------
+    @staticmethod
+    def _filter_format(fmt):
+        """(the struct to keep alive, the pointer argument): None is RGBA8"""
+        if fmt is None:
+            return None, None
+        f = PatchFormat.of(fmt).struct()
+        return f, C.byref(f)
+
+    def camshift_crop_pairs_filtered_device(self, dev_ptr: int, pairs, width: int, height: int, max_factor: int = 8, fmt=None, margin: float = 1.0, square: bool = False,
+                                            stride: int = 0):
+        """camshift_crop_pairs_device for strong downscales: every patch pixel is the rounded mean of an Nx x Ny block of the unfiltered
+        rule's samples (the patch that call gives at Nx * width x Ny * height), Nx = min(max_factor, max(1, ceil(w / width))) and Ny
+        likewise, chosen per entry on the device from the tracked box; max_factor 1..8.  With factors 1, 1 the patch is byte for byte the
+        unfiltered call's.  fmt None: RGBA8; otherwise a PatchFormat (or a dict of its arguments) and the output is the model-input tensor
+        of the filtered patch, as camshift_crop_pairs_tensor_device lays it out.  ONE enqueue-only launch; this IS the context's last crop
+        call (camshift_crop_result gives the unfiltered call's records; crop_filter_factors turns them into the factors)."""
+        p, (_f, fp) = self._pairs(pairs), self._filter_format(fmt)
+        prm = self._crop_params(width, height, margin, square)
+        self._check(self._lib.ht_camshift_crop_pairs_filtered_device(self._h, p.ctypes.data, len(p), C.byref(prm), int(max_factor), fp, dev_ptr, stride))
+
+    def camshift_crop_sources_filtered_device(self, dev_ptr: int, streams, entries, width: int, height: int, max_factor: int = 8, fmt=None, margin: float = 1.0,
+                                              square: bool = False, stride: int = 0):
+        """camshift_crop_sources_device with the block-mean prefilter (see camshift_crop_pairs_filtered_device)"""
+        if len(streams) != len(entries):
+            raise ValueError("camshift_crop_sources_filtered_device: one stream per entry")
+        st, (_f, fp) = np.ascontiguousarray(np.asarray(streams, dtype=np.int32).reshape(-1)), self._filter_format(fmt)
+        prm = self._crop_params(width, height, margin, square)
+        self._check(self._lib.ht_camshift_crop_sources_filtered_device(self._h, st.ctypes.data if len(st) else None, self._draw_sources(entries), len(entries), C.byref(prm),
+                                                                       int(max_factor), fp, dev_ptr, stride))
+
+    def camshift_align_pairs_filtered_device(self, dev_ptr: int, pairs, width: int, height: int, max_factor: int = 8, fmt=None, margin: float = 1.0, square: bool = False,
+                                             stride: int = 0):
+        """camshift_align_pairs_device with the block-mean prefilter: Nx = min(max_factor, max(1, ceil((|ux| + |uy|) / (width * 65536)))),
+        Ny the same with (vx, vy) and height, from the entry's align record; the patch's edge fades where fine samples fall outside the
+        frame.  This IS the context's last align call (align_filter_factors turns its records into the factors)."""
+        p, (_f, fp) = self._pairs(pairs), self._filter_format(fmt)
+        prm = self._align_params(width, height, margin, square)
+        self._check(self._lib.ht_camshift_align_pairs_filtered_device(self._h, p.ctypes.data, len(p), C.byref(prm), int(max_factor), fp, dev_ptr, stride))
+
+    def camshift_align_sources_filtered_device(self, dev_ptr: int, streams, entries, width: int, height: int, max_factor: int = 8, fmt=None, margin: float = 1.0,
+                                               square: bool = False, stride: int = 0):
+        """camshift_align_sources_device with the block-mean prefilter (see camshift_align_pairs_filtered_device)"""
+        if len(streams) != len(entries):
+            raise ValueError("camshift_align_sources_filtered_device: one stream per entry")
+        st, (_f, fp) = np.ascontiguousarray(np.asarray(streams, dtype=np.int32).reshape(-1)), self._filter_format(fmt)
+        prm = self._align_params(width, height, margin, square)
+        self._check(self._lib.ht_camshift_align_sources_filtered_device(self._h, st.ctypes.data if len(st) else None, self._draw_sources(entries), len(entries), C.byref(prm),
+                                                                        int(max_factor), fp, dev_ptr, stride))
+
     # -- measurement --------------------------------------------------------------------------------------------
     def profile(self, on: bool = True):
         self._check(self._lib.ht_profile(self._h, int(on)))
@@ -717,6 +767,29 @@ class Context:
     @property
     def stream(self) -> int:
         return int(self._lib.ht_stream(self._h) or 0)
+
+
+def _filter_factors(fn, records, dtype, width: int, height: int, max_factor: int) -> np.ndarray:
+    rec = np.ascontiguousarray(records, dtype=dtype).reshape(-1)
+    out = np.zeros((len(rec), 2), dtype=np.int32)
+    nx, ny = C.c_int32(), C.c_int32()
+    for i in range(len(rec)):
+        st = fn(rec[i:i + 1].ctypes.data, int(width), int(height), int(max_factor), C.byref(nx), C.byref(ny))
+        if st != 0:
+            raise HtError(st, "filter factors: out_width / out_height must be 1..1024 and max_factor 1..8")
+        out[i] = nx.value, ny.value
+    return out
+
+
+def crop_filter_factors(records, width: int, height: int, max_factor: int = 8) -> np.ndarray:
+    """int32 [n, 2]: the (Nx, Ny) a filtered crop call of (width, height, max_factor) takes for each CROP_RECORD_DTYPE record (what
+    camshift_crop_result returns); 0, 0 for an empty one.  The library's own rule (ht_camshift_crop_filter_factors): needs no device."""
+    return _filter_factors(native.lib().ht_camshift_crop_filter_factors, records, native.CROP_RECORD_DTYPE, width, height, max_factor)
+
+
+def align_filter_factors(records, width: int, height: int, max_factor: int = 8) -> np.ndarray:
+    """the same for ALIGN_RECORD_DTYPE records and the filtered align calls (ht_camshift_align_filter_factors)"""
+    return _filter_factors(native.lib().ht_camshift_align_filter_factors, records, native.ALIGN_RECORD_DTYPE, width, height, max_factor)
 
 
 def device_count() -> int:

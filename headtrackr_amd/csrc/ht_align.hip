@@ -46,18 +46,19 @@ struct AlDwordStore {
 };
 
 // the four rows of a thread's column, behind the barrier; every pixel ends in ONE output stage, store(o, x, y), o the pixel's RGBA8 dword
-// (k_align_list: AlDwordStore; ht_patch.hip: the model-input tensors)
-template <int FMT, class STORE>
+// (k_align_list: AlDwordStore; ht_patch.hip: the model-input tensors).  RPT rows per thread: a tile of RPT * 4 rows (ht_filter.hip takes 1)
+template <int FMT, class STORE, int RPT = IG_RPT>
 __device__ __forceinline__ void al_pixels(const DlDesc &d, int SW, int SH, const int64_t *s_cx, const int64_t *s_cy, const int64_t *s_rx, const int64_t *s_ry,
                                           const STORE &store, int dw, int dh) {
-    const int col = threadIdx.x & (IG_TW - 1), r0 = threadIdx.x / IG_TW, x = blockIdx.x * IG_TW + col, Y0 = blockIdx.y * IG_TH;
+    static_assert(RPT >= 1 && RPT <= IG_RPT, "al_pixels: 1 .. 4 rows per thread; the default is the 64 x 16 tile");
+    const int col = threadIdx.x & (IG_TW - 1), r0 = threadIdx.x / IG_TW, x = blockIdx.x * IG_TW + col, Y0 = blockIdx.y * (RPT * (IG_NT / IG_TW));
     if (x >= dw) return;
     const uint8_t *__restrict__ p0 = (const uint8_t *)d.p0, *__restrict__ p1 = (const uint8_t *)d.p1, *__restrict__ p2 = (const uint8_t *)d.p2;
     const size_t pitch0 = d.pitch0, pitch1 = d.pitch1;
     const HtYuvCoef kc = d.kc;
     const int64_t cfx = s_cx[col], cfy = s_cy[col];
 #pragma unroll
-    for (int k = 0; k < IG_RPT; k++) {
+    for (int k = 0; k < RPT; k++) {
         const int j = r0 + k * (IG_NT / IG_TW), y = Y0 + j;
         if (y >= dh) continue;
         const int64_t fx = cfx + s_rx[j], fy = cfy + s_ry[j];
@@ -153,6 +154,8 @@ ht_status align_reserve(ht_ctx *c, const char *fn, size_t n) {
 static_assert(HT_ALIGN_SQUARE == HT_CROP_SQUARE && sizeof(ht_align_params) == sizeof(ht_crop_params), "align params are crop params");
 void pt_launch_upright(ht_ctx *c, dim3 grid, const CrDesc *tab, const HtCsState *states, uint8_t *out, size_t ostride, const ht_align_params &p,
                        const ht_patch_format &fmt, ht_align_record *recs);  // ht_patch.hip
+void fm_launch_upright(ht_ctx *c, dim3 grid, const CrDesc *tab, const HtCsState *states, uint8_t *out, size_t ostride, const ht_align_params &p, int32_t max_factor,
+                       const ht_patch_format *fmt, ht_align_record *recs);  // ht_filter.hip: the prefiltered forms; fmt == nullptr is RGBA8
 
 ht_status align_check(ht_ctx *c, const std::string &f, bool pairs_form, const void *list, int32_t n, const ht_align_params *p, const void *out_dev, size_t out_stride,
                       size_t *pbytes, size_t *ostride, bool tensor = false, const ht_patch_format *fmt = nullptr) {
@@ -162,8 +165,9 @@ ht_status align_check(ht_ctx *c, const std::string &f, bool pairs_form, const vo
 }
 
 // everything has been checked: table, kernel, records to the pinned twin
+// max_factor != 0: a prefiltered call (ht_filter.hip)
 ht_status align_launch(ht_ctx *c, const char *fn, const std::vector<HtCropDesc> &desc, const ht_align_params &p, uint8_t *out, size_t ostride,
-                       const ht_patch_format *fmt = nullptr) {
+                       const ht_patch_format *fmt = nullptr, int32_t max_factor = 0) {
     const size_t n = desc.size(), need = n * sizeof(HtCropDesc);
     HT_HIP(c, hipSetDevice(c->device));
     ht_status st = align_reserve(c, fn, n);
@@ -176,7 +180,11 @@ ht_status align_launch(ht_ctx *c, const char *fn, const std::vector<HtCropDesc> 
     HT_HIP(c, hipEventRecord(c->ev_align_tab[k], c->stream));
     c->align_n = 0;  // until this call's copy is behind its kernel
     const dim3 grid((p.out_width + IG_TW - 1) / IG_TW, (p.out_height + IG_TH - 1) / IG_TH, (unsigned)n);
-    if (fmt) {
+    if (max_factor) {
+        HtProfScope ps(c, "upright_mean");
+        fm_launch_upright(c, grid, reinterpret_cast<const CrDesc *>(c->d_align_tab), (const HtCsState *)c->d_cs, out, ostride, p, max_factor, fmt, reinterpret_cast<ht_align_record *>(c->d_align_rec));
+        HT_HIP(c, hipGetLastError());
+    } else if (fmt) {
         HtProfScope ps(c, "upright_tensor");
         pt_launch_upright(c, grid, reinterpret_cast<const CrDesc *>(c->d_align_tab), (const HtCsState *)c->d_cs, out, ostride, p, *fmt, reinterpret_cast<ht_align_record *>(c->d_align_rec));
         HT_HIP(c, hipGetLastError());
@@ -194,7 +202,7 @@ ht_status align_launch(ht_ctx *c, const char *fn, const std::vector<HtCropDesc> 
 
 // both pairs-form calls: fn names the export; tensor: ht_camshift_align_pairs_tensor_device (ht_patch.hip)
 ht_status align_pairs(ht_ctx *c, const char *fn, const ht_cs_pair *pairs, int32_t n, const ht_align_params *params, bool tensor, const ht_patch_format *fmt, void *out_dev,
-                      size_t out_stride) {
+                      size_t out_stride, int32_t max_factor = 0) {
     if (!c) return HT_ERR_INVALID;
     HtRange range(fn);
     const std::string f(fn);
@@ -216,12 +224,12 @@ ht_status align_pairs(ht_ctx *c, const char *fn, const ht_cs_pair *pairs, int32_
         e.SW = c->W, e.SH = c->H, e.stream = s;
         desc[(size_t)i] = e;
     }
-    return align_launch(c, fn, desc, *params, static_cast<uint8_t *>(out_dev), ostride, fmt);
+    return align_launch(c, fn, desc, *params, static_cast<uint8_t *>(out_dev), ostride, fmt, max_factor);
 }
 
 // both sources-form calls
 ht_status align_sources(ht_ctx *c, const char *fn, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_align_params *params, bool tensor,
-                        const ht_patch_format *fmt, void *out_dev, size_t out_stride) {
+                        const ht_patch_format *fmt, void *out_dev, size_t out_stride, int32_t max_factor = 0) {
     if (!c) return HT_ERR_INVALID;
     HtRange range(fn);
     const std::string f(fn);
@@ -242,7 +250,7 @@ ht_status align_sources(ht_ctx *c, const char *fn, const int32_t *streams, const
     }
     const int32_t bad = ht_draw_list_overlap(ext.data(), n, out_dev, (size_t)(n - 1) * ostride + pbytes);
     if (bad >= 0) return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": a source plane and the output overlap");
-    return align_launch(c, fn, desc, *params, static_cast<uint8_t *>(out_dev), ostride, fmt);
+    return align_launch(c, fn, desc, *params, static_cast<uint8_t *>(out_dev), ostride, fmt, max_factor);
 }
 
 }  // namespace

@@ -115,6 +115,9 @@ ht_status crop_reserve(ht_ctx *c, const char *fn, size_t n) {
 // the tensor forms' launches (ht_patch.hip, behind ht_align.hip): the same grid and arguments, another output stage
 void pt_launch_cut(ht_ctx *c, dim3 grid, const CrDesc *tab, const HtCsState *states, uint8_t *out, size_t ostride, const ht_crop_params &p, const ht_patch_format &fmt,
                    ht_crop_record *recs);
+// the prefiltered forms' launch (ht_filter.hip, behind ht_patch.hip): fmt == nullptr is RGBA8
+void fm_launch_cut(ht_ctx *c, dim3 grid, const CrDesc *tab, const HtCsState *states, uint8_t *out, size_t ostride, const ht_crop_params &p, int32_t max_factor,
+                   const ht_patch_format *fmt, ht_crop_record *recs);
 
 // the checks both forms share, in front of their entries: the context's state first, then the call's own arguments.  tensor: the output
 // is fmt's tensor (ht_patch_plan.h) instead of RGBA8 — fmt is checked here and a patch's bytes and the default stride are the tensor's
@@ -142,8 +145,9 @@ ht_status crop_check(ht_ctx *c, const std::string &f, bool pairs_form, const voi
 }
 
 // everything has been checked: table, kernel, records to the pinned twin
+// max_factor != 0: a prefiltered call (ht_filter.hip)
 ht_status crop_launch(ht_ctx *c, const char *fn, const std::vector<HtCropDesc> &desc, const ht_crop_params &p, uint8_t *out, size_t ostride,
-                      const ht_patch_format *fmt = nullptr) {
+                      const ht_patch_format *fmt = nullptr, int32_t max_factor = 0) {
     const size_t n = desc.size(), need = n * sizeof(HtCropDesc);
     HT_HIP(c, hipSetDevice(c->device));
     ht_status st = crop_reserve(c, fn, n);
@@ -156,7 +160,11 @@ ht_status crop_launch(ht_ctx *c, const char *fn, const std::vector<HtCropDesc> &
     HT_HIP(c, hipEventRecord(c->ev_crop_tab[k], c->stream));
     c->crop_n = 0;  // until this call's copy is behind its kernel
     const dim3 grid((p.out_width + IG_TW - 1) / IG_TW, (p.out_height + IG_TH - 1) / IG_TH, (unsigned)n);
-    if (fmt) {
+    if (max_factor) {
+        HtProfScope ps(c, "cut_mean");
+        fm_launch_cut(c, grid, reinterpret_cast<const CrDesc *>(c->d_crop_tab), (const HtCsState *)c->d_cs, out, ostride, p, max_factor, fmt, reinterpret_cast<ht_crop_record *>(c->d_crop_rec));
+        HT_HIP(c, hipGetLastError());
+    } else if (fmt) {
         HtProfScope ps(c, "cut_tensor");
         pt_launch_cut(c, grid, reinterpret_cast<const CrDesc *>(c->d_crop_tab), (const HtCsState *)c->d_cs, out, ostride, p, *fmt, reinterpret_cast<ht_crop_record *>(c->d_crop_rec));
         HT_HIP(c, hipGetLastError());
@@ -174,7 +182,7 @@ ht_status crop_launch(ht_ctx *c, const char *fn, const std::vector<HtCropDesc> &
 
 // both pairs-form calls: fn names the export; tensor: ht_camshift_crop_pairs_tensor_device (ht_patch.hip)
 ht_status crop_pairs(ht_ctx *c, const char *fn, const ht_cs_pair *pairs, int32_t n, const ht_crop_params *params, bool tensor, const ht_patch_format *fmt, void *out_dev,
-                     size_t out_stride) {
+                     size_t out_stride, int32_t max_factor = 0) {
     if (!c) return HT_ERR_INVALID;
     HtRange range(fn);
     const std::string f(fn);
@@ -196,12 +204,12 @@ ht_status crop_pairs(ht_ctx *c, const char *fn, const ht_cs_pair *pairs, int32_t
         e.SW = c->W, e.SH = c->H, e.stream = s;
         desc[(size_t)i] = e;
     }
-    return crop_launch(c, fn, desc, *params, static_cast<uint8_t *>(out_dev), ostride, fmt);
+    return crop_launch(c, fn, desc, *params, static_cast<uint8_t *>(out_dev), ostride, fmt, max_factor);
 }
 
 // both sources-form calls
 ht_status crop_sources(ht_ctx *c, const char *fn, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_crop_params *params, bool tensor,
-                       const ht_patch_format *fmt, void *out_dev, size_t out_stride) {
+                       const ht_patch_format *fmt, void *out_dev, size_t out_stride, int32_t max_factor = 0) {
     if (!c) return HT_ERR_INVALID;
     HtRange range(fn);
     const std::string f(fn);
@@ -222,7 +230,7 @@ ht_status crop_sources(ht_ctx *c, const char *fn, const int32_t *streams, const 
     }
     const int32_t bad = ht_draw_list_overlap(ext.data(), n, out_dev, (size_t)(n - 1) * ostride + pbytes);
     if (bad >= 0) return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": a source plane and the output overlap");
-    return crop_launch(c, fn, desc, *params, static_cast<uint8_t *>(out_dev), ostride, fmt);
+    return crop_launch(c, fn, desc, *params, static_cast<uint8_t *>(out_dev), ostride, fmt, max_factor);
 }
 
 }  // namespace

@@ -199,3 +199,8 @@ void ht_ingest_free(ht_ctx *c) {  // ht_destroy (the stream has been synchronise
 #include "ht_align.hip"
 // model-input tensors from both: the same kernels with a planar / float output stage (ht_patch_plan.h states the rule)
 #include "ht_patch.hip"
+// prefiltered crops: each patch pixel the mean of a block of the unfiltered rule's samples (ht_filter_plan.h states the rule); the kernels
+// compile the pixel bodies of both siblings as text, with an accumulating output stage
+#define HT_FILTER_FN __host__ __device__ inline
+#include "ht_filter_plan.h"
+#include "ht_filter.hip"

@@ -1440,12 +1440,14 @@ struct CropOut {
     size_t stride = 0;
     bool wait = false;
 };
-// fmt (the tensor forms): a patch is the tensor's C * width * height elements and the default stride its bytes rounded up to 4
-bool get_crop_out(const Args &a, size_t i, size_t n, const char *usage, CropOut *c, const ht_patch_format *fmt = nullptr) {
+// fmt (the tensor forms, and the filtered forms with a format): a patch is the tensor's C * width * height elements and the default stride
+// its bytes rounded up to 4.  between: the arguments between the params and outDev (the tensor forms' format object: 1; the filtered forms'
+// maxFactor and format | null: 2)
+bool get_crop_out(const Args &a, size_t i, size_t n, const char *usage, CropOut *c, const ht_patch_format *fmt, size_t between) {
     View prm;
     DevBuf *out = nullptr;
     size_t off = 0;
-    const size_t o = i + (fmt ? 2 : 1);  // outDev: behind the params, or behind the tensor forms' format object
+    const size_t o = i + 1 + between;  // outDev: behind the params, or behind what the form has between the two
     if (!a.devbuf(o, &out)) return false;
     if (!a.i32s(i, 4, &prm) || prm.len != 4 || !a.offset(o + 1, &c->stride) || (a.argc > o + 2 && !a.offset(o + 2, &off))) return type_error(a.env, usage) != nullptr;
     a.opt_bool(o + 3, &c->wait);
@@ -1474,11 +1476,22 @@ bool get_patch_format(napi_env env, napi_value v, const char *usage, ht_patch_fo
     return true;
 }
 
-// cropPairsDevice and cropPairsTensorDevice: the tensor form has the format object in front of outDev
-napi_value crop_pairs_call(napi_env env, napi_callback_info info, bool tensor) {
-    const char *usage = tensor ? "cropPairsTensorDevice(ctx, Int32Array pairs[2n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)"
+// the filtered forms (ht_camshift_*_filtered_device) have maxFactor (1..8) and format | null behind the params: argument i and i + 1
+bool get_filter_args(const Args &a, size_t i, const char *usage, int32_t *max_factor, bool *has_fmt) {
+    napi_valuetype vt;
+    if (!a.i32(i, max_factor) || napi_typeof(a.env, a.argv[i + 1], &vt) != napi_ok) return type_error(a.env, usage) != nullptr;
+    if (*max_factor < 1 || *max_factor > 8) return range_error(a.env, (std::string(usage) + ": maxFactor is 1..8").c_str()) != nullptr;
+    *has_fmt = vt != napi_null && vt != napi_undefined;  // null: RGBA8
+    return true;
+}
+
+// cropPairsDevice, cropPairsTensorDevice (the format object in front of outDev) and cropPairsFilteredDevice (maxFactor and format | null there)
+napi_value crop_pairs_call(napi_env env, napi_callback_info info, int mode) {  // 0: RGBA8, 1: the tensor form, 2: the filtered form
+    const bool tensor = mode == 1, filtered = mode == 2;
+    const char *usage = filtered ? "cropPairsFilteredDevice(ctx, Int32Array pairs[2n], Int32Array params[4], maxFactor, format | null, outDev, outStride, outOffset = 0, wait = false)"
+                        : tensor ? "cropPairsTensorDevice(ctx, Int32Array pairs[2n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)"
                                : "cropPairsDevice(ctx, Int32Array pairs[2n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
-    const size_t t = tensor ? 1 : 0;
+    const size_t t = filtered ? 2 : tensor ? 1 : 0;  // arguments between the params and outDev
     Args a(env, info, 7 + t);
     Locked L;
     const ht_cs_pair *pairs = nullptr;
@@ -1488,21 +1501,28 @@ napi_value crop_pairs_call(napi_env env, napi_callback_info info, bool tensor) {
     if (!a.ctx(5 + t, &L)) return nullptr;
     if (!get_pairs(env, a.argv[1], &pairs, &n)) return type_error(env, usage);
     if (n > 65535) return range_error(env, (std::string(usage) + ": 1..65535 pairs").c_str());
-    if (tensor && !get_patch_format(env, a.argv[3], usage, &fmt)) return nullptr;
-    if (!get_crop_out(a, 2, (size_t)n, usage, &c, tensor ? &fmt : nullptr)) return nullptr;
-    ht_status st = tensor ? ht_camshift_crop_pairs_tensor_device(L.ctx, pairs, n, &c.prm, &fmt, c.out, c.stride) : ht_camshift_crop_pairs_device(L.ctx, pairs, n, &c.prm, c.out, c.stride);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, tensor ? "ht_camshift_crop_pairs_tensor_device" : "ht_camshift_crop_pairs_device");
+    int32_t max_factor = 0;
+    bool has_fmt = tensor;
+    if (filtered && !get_filter_args(a, 3, usage, &max_factor, &has_fmt)) return nullptr;
+    if (has_fmt && !get_patch_format(env, a.argv[3 + (filtered ? 1 : 0)], usage, &fmt)) return nullptr;
+    if (!get_crop_out(a, 2, (size_t)n, usage, &c, has_fmt ? &fmt : nullptr, t)) return nullptr;
+    ht_status st = filtered ? ht_camshift_crop_pairs_filtered_device(L.ctx, pairs, n, &c.prm, max_factor, has_fmt ? &fmt : nullptr, c.out, c.stride)
+                   : tensor ? ht_camshift_crop_pairs_tensor_device(L.ctx, pairs, n, &c.prm, &fmt, c.out, c.stride) : ht_camshift_crop_pairs_device(L.ctx, pairs, n, &c.prm, c.out, c.stride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, filtered ? "ht_camshift_crop_pairs_filtered_device" : tensor ? "ht_camshift_crop_pairs_tensor_device" : "ht_camshift_crop_pairs_device");
     if (c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
     return nullptr;
 }
 
-napi_value CropPairsDevice(napi_env env, napi_callback_info info) { return crop_pairs_call(env, info, false); }
-napi_value CropPairsTensorDevice(napi_env env, napi_callback_info info) { return crop_pairs_call(env, info, true); }
+napi_value CropPairsDevice(napi_env env, napi_callback_info info) { return crop_pairs_call(env, info, 0); }
+napi_value CropPairsTensorDevice(napi_env env, napi_callback_info info) { return crop_pairs_call(env, info, 1); }
+napi_value CropPairsFilteredDevice(napi_env env, napi_callback_info info) { return crop_pairs_call(env, info, 2); }
 
-napi_value crop_sources_call(napi_env env, napi_callback_info info, bool tensor) {
-    const char *usage = tensor ? "cropSourcesTensorDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)"
+napi_value crop_sources_call(napi_env env, napi_callback_info info, int mode) {  // 0: RGBA8, 1: the tensor form, 2: the filtered form
+    const bool tensor = mode == 1, filtered = mode == 2;
+    const char *usage = filtered ? "cropSourcesFilteredDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], maxFactor, format | null, outDev, outStride, outOffset = 0, wait = false)"
+                        : tensor ? "cropSourcesTensorDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)"
                                : "cropSourcesDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
-    const size_t t = tensor ? 1 : 0;
+    const size_t t = filtered ? 2 : tensor ? 1 : 0;  // arguments between the params and outDev
     Args a(env, info, 8 + t);
     Locked L;
     View streams;
@@ -1521,17 +1541,22 @@ napi_value crop_sources_call(napi_env env, napi_callback_info info, bool tensor)
         NAPI_OK(napi_get_element(env, a.argv[2], i, &e));
         if (!get_draw_entry(env, e, &srcs[i])) return nullptr;
     }
-    if (tensor && !get_patch_format(env, a.argv[4], usage, &fmt)) return nullptr;
-    if (!get_crop_out(a, 3, (size_t)n, usage, &c, tensor ? &fmt : nullptr)) return nullptr;
-    ht_status st = tensor ? ht_camshift_crop_sources_tensor_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &c.prm, &fmt, c.out, c.stride)
-                          : ht_camshift_crop_sources_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &c.prm, c.out, c.stride);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, tensor ? "ht_camshift_crop_sources_tensor_device" : "ht_camshift_crop_sources_device");
+    int32_t max_factor = 0;
+    bool has_fmt = tensor;
+    if (filtered && !get_filter_args(a, 4, usage, &max_factor, &has_fmt)) return nullptr;
+    if (has_fmt && !get_patch_format(env, a.argv[4 + (filtered ? 1 : 0)], usage, &fmt)) return nullptr;
+    if (!get_crop_out(a, 3, (size_t)n, usage, &c, has_fmt ? &fmt : nullptr, t)) return nullptr;
+    ht_status st = filtered ? ht_camshift_crop_sources_filtered_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &c.prm, max_factor, has_fmt ? &fmt : nullptr, c.out, c.stride)
+                   : tensor ? ht_camshift_crop_sources_tensor_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &c.prm, &fmt, c.out, c.stride)
+                            : ht_camshift_crop_sources_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &c.prm, c.out, c.stride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, filtered ? "ht_camshift_crop_sources_filtered_device" : tensor ? "ht_camshift_crop_sources_tensor_device" : "ht_camshift_crop_sources_device");
     if (c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
     return nullptr;
 }
 
-napi_value CropSourcesDevice(napi_env env, napi_callback_info info) { return crop_sources_call(env, info, false); }
-napi_value CropSourcesTensorDevice(napi_env env, napi_callback_info info) { return crop_sources_call(env, info, true); }
+napi_value CropSourcesDevice(napi_env env, napi_callback_info info) { return crop_sources_call(env, info, 0); }
+napi_value CropSourcesTensorDevice(napi_env env, napi_callback_info info) { return crop_sources_call(env, info, 1); }
+napi_value CropSourcesFilteredDevice(napi_env env, napi_callback_info info) { return crop_sources_call(env, info, 2); }
 
 // {records: Int32Array [6n] = code, stream, x, y, width, height per entry; ratios: Float64Array [2n] = rx, ry}
 napi_value CropResult(napi_env env, napi_callback_info info) {
@@ -1569,10 +1594,12 @@ ht_align_params align_params(const CropOut &c) {
     return p;
 }
 
-napi_value align_pairs_call(napi_env env, napi_callback_info info, bool tensor) {
-    const char *usage = tensor ? "alignPairsTensorDevice(ctx, Int32Array pairs[2n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)"
+napi_value align_pairs_call(napi_env env, napi_callback_info info, int mode) {  // 0: RGBA8, 1: the tensor form, 2: the filtered form
+    const bool tensor = mode == 1, filtered = mode == 2;
+    const char *usage = filtered ? "alignPairsFilteredDevice(ctx, Int32Array pairs[2n], Int32Array params[4], maxFactor, format | null, outDev, outStride, outOffset = 0, wait = false)"
+                        : tensor ? "alignPairsTensorDevice(ctx, Int32Array pairs[2n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)"
                                : "alignPairsDevice(ctx, Int32Array pairs[2n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
-    const size_t t = tensor ? 1 : 0;
+    const size_t t = filtered ? 2 : tensor ? 1 : 0;  // arguments between the params and outDev
     Args a(env, info, 7 + t);
     Locked L;
     const ht_cs_pair *pairs = nullptr;
@@ -1582,22 +1609,29 @@ napi_value align_pairs_call(napi_env env, napi_callback_info info, bool tensor) 
     if (!a.ctx(5 + t, &L)) return nullptr;
     if (!get_pairs(env, a.argv[1], &pairs, &n)) return type_error(env, usage);
     if (n > 65535) return range_error(env, (std::string(usage) + ": 1..65535 pairs").c_str());
-    if (tensor && !get_patch_format(env, a.argv[3], usage, &fmt)) return nullptr;
-    if (!get_crop_out(a, 2, (size_t)n, usage, &c, tensor ? &fmt : nullptr)) return nullptr;
+    int32_t max_factor = 0;
+    bool has_fmt = tensor;
+    if (filtered && !get_filter_args(a, 3, usage, &max_factor, &has_fmt)) return nullptr;
+    if (has_fmt && !get_patch_format(env, a.argv[3 + (filtered ? 1 : 0)], usage, &fmt)) return nullptr;
+    if (!get_crop_out(a, 2, (size_t)n, usage, &c, has_fmt ? &fmt : nullptr, t)) return nullptr;
     const ht_align_params prm = align_params(c);
-    ht_status st = tensor ? ht_camshift_align_pairs_tensor_device(L.ctx, pairs, n, &prm, &fmt, c.out, c.stride) : ht_camshift_align_pairs_device(L.ctx, pairs, n, &prm, c.out, c.stride);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, tensor ? "ht_camshift_align_pairs_tensor_device" : "ht_camshift_align_pairs_device");
+    ht_status st = filtered ? ht_camshift_align_pairs_filtered_device(L.ctx, pairs, n, &prm, max_factor, has_fmt ? &fmt : nullptr, c.out, c.stride)
+                   : tensor ? ht_camshift_align_pairs_tensor_device(L.ctx, pairs, n, &prm, &fmt, c.out, c.stride) : ht_camshift_align_pairs_device(L.ctx, pairs, n, &prm, c.out, c.stride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, filtered ? "ht_camshift_align_pairs_filtered_device" : tensor ? "ht_camshift_align_pairs_tensor_device" : "ht_camshift_align_pairs_device");
     if (c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
     return nullptr;
 }
 
-napi_value AlignPairsDevice(napi_env env, napi_callback_info info) { return align_pairs_call(env, info, false); }
-napi_value AlignPairsTensorDevice(napi_env env, napi_callback_info info) { return align_pairs_call(env, info, true); }
+napi_value AlignPairsDevice(napi_env env, napi_callback_info info) { return align_pairs_call(env, info, 0); }
+napi_value AlignPairsTensorDevice(napi_env env, napi_callback_info info) { return align_pairs_call(env, info, 1); }
+napi_value AlignPairsFilteredDevice(napi_env env, napi_callback_info info) { return align_pairs_call(env, info, 2); }
 
-napi_value align_sources_call(napi_env env, napi_callback_info info, bool tensor) {
-    const char *usage = tensor ? "alignSourcesTensorDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)"
+napi_value align_sources_call(napi_env env, napi_callback_info info, int mode) {  // 0: RGBA8, 1: the tensor form, 2: the filtered form
+    const bool tensor = mode == 1, filtered = mode == 2;
+    const char *usage = filtered ? "alignSourcesFilteredDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], maxFactor, format | null, outDev, outStride, outOffset = 0, wait = false)"
+                        : tensor ? "alignSourcesTensorDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)"
                                : "alignSourcesDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
-    const size_t t = tensor ? 1 : 0;
+    const size_t t = filtered ? 2 : tensor ? 1 : 0;  // arguments between the params and outDev
     Args a(env, info, 8 + t);
     Locked L;
     View streams;
@@ -1616,18 +1650,23 @@ napi_value align_sources_call(napi_env env, napi_callback_info info, bool tensor
         NAPI_OK(napi_get_element(env, a.argv[2], i, &e));
         if (!get_draw_entry(env, e, &srcs[i])) return nullptr;
     }
-    if (tensor && !get_patch_format(env, a.argv[4], usage, &fmt)) return nullptr;
-    if (!get_crop_out(a, 3, (size_t)n, usage, &c, tensor ? &fmt : nullptr)) return nullptr;
+    int32_t max_factor = 0;
+    bool has_fmt = tensor;
+    if (filtered && !get_filter_args(a, 4, usage, &max_factor, &has_fmt)) return nullptr;
+    if (has_fmt && !get_patch_format(env, a.argv[4 + (filtered ? 1 : 0)], usage, &fmt)) return nullptr;
+    if (!get_crop_out(a, 3, (size_t)n, usage, &c, has_fmt ? &fmt : nullptr, t)) return nullptr;
     const ht_align_params prm = align_params(c);
-    ht_status st = tensor ? ht_camshift_align_sources_tensor_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &prm, &fmt, c.out, c.stride)
-                          : ht_camshift_align_sources_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &prm, c.out, c.stride);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, tensor ? "ht_camshift_align_sources_tensor_device" : "ht_camshift_align_sources_device");
+    ht_status st = filtered ? ht_camshift_align_sources_filtered_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &prm, max_factor, has_fmt ? &fmt : nullptr, c.out, c.stride)
+                   : tensor ? ht_camshift_align_sources_tensor_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &prm, &fmt, c.out, c.stride)
+                            : ht_camshift_align_sources_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &prm, c.out, c.stride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, filtered ? "ht_camshift_align_sources_filtered_device" : tensor ? "ht_camshift_align_sources_tensor_device" : "ht_camshift_align_sources_device");
     if (c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
     return nullptr;
 }
 
-napi_value AlignSourcesDevice(napi_env env, napi_callback_info info) { return align_sources_call(env, info, false); }
-napi_value AlignSourcesTensorDevice(napi_env env, napi_callback_info info) { return align_sources_call(env, info, true); }
+napi_value AlignSourcesDevice(napi_env env, napi_callback_info info) { return align_sources_call(env, info, 0); }
+napi_value AlignSourcesTensorDevice(napi_env env, napi_callback_info info) { return align_sources_call(env, info, 1); }
+napi_value AlignSourcesFilteredDevice(napi_env env, napi_callback_info info) { return align_sources_call(env, info, 2); }
 
 // {records: Int32Array [4n] = code, stream, a12, 0 per entry; terms: Float64Array [6n] = cx, cy, ux, uy, vx, vy in Q16 source pixels
 // (|value| < 2^52: exact in a binary64)}
@@ -1658,6 +1697,46 @@ napi_value AlignResult(napi_env env, napi_callback_info info) {
     }
     return obj;
 }
+
+// cropFilterFactors(records Int32Array[6n] as cropResult gives them, width, height, maxFactor) and
+// alignFilterFactors(records Int32Array[4n], terms Float64Array[6n] as alignResult gives them, width, height, maxFactor)
+// -> Int32Array [2n] = Nx, Ny per entry (0, 0 for an empty one): the library's own rule (ht_camshift_*_filter_factors), no context
+napi_value filter_factors_call(napi_env env, napi_callback_info info, bool align) {
+    const char *usage = align ? "alignFilterFactors(Int32Array records[4n], Float64Array terms[6n], width, height, maxFactor)" : "cropFilterFactors(Int32Array records[6n], width, height, maxFactor)";
+    const size_t t = align ? 1 : 0, per = align ? 4 : 6;
+    Args a(env, info, 4 + t);
+    View rec, terms;
+    int32_t w = 0, h = 0, mf = 0;
+    if (!a.arity(4 + t)) return nullptr;
+    if (!a.i32s(0, 0, &rec) || rec.len % per || (align && (!a.f64s(1, 0, &terms) || terms.len * 4 != rec.len * 6)) || !a.i32(1 + t, &w) || !a.i32(2 + t, &h) || !a.i32(3 + t, &mf))
+        return type_error(env, usage);
+    if (w < 1 || w > 1024 || h < 1 || h > 1024 || mf < 1 || mf > 8) return range_error(env, (std::string(usage) + ": width and height are 1..1024, maxFactor is 1..8").c_str());
+    const size_t n = rec.len / per;
+    napi_value ab, ta;
+    void *p = nullptr;
+    NAPI_OK(napi_create_arraybuffer(env, n * 8, &p, &ab));
+    NAPI_OK(napi_create_typedarray(env, napi_int32_array, n * 2, ab, 0, &ta));
+    int32_t *out = static_cast<int32_t *>(p);
+    const int32_t *v = rec.as<int32_t>();
+    for (size_t i = 0; i < n; i++) {
+        ht_status st;
+        if (align) {
+            const double *q = terms.as<double>() + 6 * i;
+            ht_align_record r = {};
+            r.code = v[4 * i], r.stream = v[4 * i + 1], r.a12 = v[4 * i + 2];
+            r.cx = (int64_t)q[0], r.cy = (int64_t)q[1], r.ux = (int64_t)q[2], r.uy = (int64_t)q[3], r.vx = (int64_t)q[4], r.vy = (int64_t)q[5];
+            st = ht_camshift_align_filter_factors(&r, w, h, mf, out + 2 * i, out + 2 * i + 1);
+        } else {
+            ht_crop_record r = {};
+            r.code = v[6 * i], r.stream = v[6 * i + 1], r.rect.x = v[6 * i + 2], r.rect.y = v[6 * i + 3], r.rect.width = v[6 * i + 4], r.rect.height = v[6 * i + 5];
+            st = ht_camshift_crop_filter_factors(&r, w, h, mf, out + 2 * i, out + 2 * i + 1);
+        }
+        if (st != HT_OK) return range_error(env, usage);
+    }
+    return ta;
+}
+napi_value CropFilterFactors(napi_env env, napi_callback_info info) { return filter_factors_call(env, info, false); }
+napi_value AlignFilterFactors(napi_env env, napi_callback_info info) { return filter_factors_call(env, info, true); }
 
 napi_value ctx_counter(napi_env env, napi_callback_info info, int which) {
     Args a(env, info, 1);
@@ -1699,6 +1778,9 @@ napi_value Init(napi_env env, napi_value exports) {
                {"alignPairsDevice", AlignPairsDevice}, {"alignSourcesDevice", AlignSourcesDevice}, {"alignResult", AlignResult},
                {"cropPairsTensorDevice", CropPairsTensorDevice}, {"cropSourcesTensorDevice", CropSourcesTensorDevice},
                {"alignPairsTensorDevice", AlignPairsTensorDevice}, {"alignSourcesTensorDevice", AlignSourcesTensorDevice},
+               {"cropPairsFilteredDevice", CropPairsFilteredDevice}, {"cropSourcesFilteredDevice", CropSourcesFilteredDevice},
+               {"alignPairsFilteredDevice", AlignPairsFilteredDevice}, {"alignSourcesFilteredDevice", AlignSourcesFilteredDevice},
+               {"cropFilterFactors", CropFilterFactors}, {"alignFilterFactors", AlignFilterFactors},
                {"detectBestEnqueue", DetectBestEnqueue}, {"collectBestDevice", CollectBestDevice}, {"detectGrouped", DetectGrouped},
                {"detectBestRecords", DetectBestRecords}, {"groupHits", GroupHits},
                {"framesBound", FramesBound},     {"framesEnqueued", FramesEnqueued}, {"graphLaunches", GraphLaunches}};

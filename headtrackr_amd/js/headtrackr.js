@@ -870,6 +870,18 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     return { dtype: TENSOR_DTYPES[dtype], layout: TENSOR_LAYOUTS[layout], channels: TENSOR_CHANNELS[channels], scale: coef('scale', t.scale, 1 / 255), bias: coef('bias', t.bias, 0),
              names: { dtype: dtype, layout: layout, channels: channels }, C: C, esize: dtype === 'f32' ? 4 : 2 };
   };
+  /* Prefiltered patches for strong downscales: with opts.prefilter = 1..8 (the largest block factor) the four calls write each patch pixel as
+   * the rounded mean of an Nx x Ny block of the unfiltered rule's samples, Nx and Ny chosen per entry on the device from the tracked box
+   * (ht_camshift_*_filtered_device: one launch, RGBA8 or — together with opts.tensor — the network's input).  cropResult() / alignResult()
+   * then carry `factors`: Int32Array(2 n) [Nx, Ny] per entry (0, 0 for an empty one), from the addon's cropFilterFactors /
+   * alignFilterFactors.  Without opts.prefilter nothing changes. */
+  const prefilterOf = function (what, o, names) {
+    if (o.prefilter === undefined || o.prefilter === null) return 0;
+    if (!(Number.isInteger(o.prefilter) && o.prefilter >= 1 && o.prefilter <= 8)) throw new RangeError('DeviceBatch.' + what + ': opts.prefilter is an integer 1..8');
+    if (names.some(function (f) { return typeof A[f] !== 'function'; }))
+      throw new Error('DeviceBatch.' + what + ': this headtrackr_hip.node has no ' + names.join(' / ') + ' (rebuild it)');
+    return o.prefilter;
+  };
   const tensorArg = function (t) { return { dtype: t.dtype, layout: t.layout, channels: t.channels, scale: t.scale, bias: t.bias }; };
   const patchBytes = function (prm, t) { return t ? t.C * prm[0] * prm[1] * t.esize : prm[0] * prm[1] * 4; };
   const patchStride = function (prm, t) { return (patchBytes(prm, t) + 3) & ~3; };
@@ -900,40 +912,47 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     if (typeof margin !== 'number' || !(margin >= 0.25 && margin <= 4)) throw new RangeError('DeviceBatch.' + what + ': opts.margin is a number 0.25..4');
     return Int32Array.from([o.width, o.height, Math.round(margin * 256), o.square ? 1 : 0]);
   };
-  const cropOut = function (count, prm, t) { /* the patch buffer, grown on demand */
+  const cropOut = function (count, prm, t, mf) { /* the patch buffer, grown on demand */
     const need = count * (t ? patchStride(prm, t) : prm[0] * prm[1] * 4);
     if (cropBytes < need) {
       if (cropDev) A.deviceFree(ctxs[0], cropDev); /* waits for the work in flight */
       cropDev = A.deviceAlloc(ctxs[0], need); cropBytes = need;
     }
-    lastCrop = { n: count, width: prm[0], height: prm[1], tensor: t || null };
+    lastCrop = { n: count, width: prm[0], height: prm[1], tensor: t || null, prefilter: mf || 0 };
     return cropDev;
   };
   this.cropPairs = function (set, pairs, o) {
     needCrop('cropPairs'); pairList('cropPairs', pairs);
     if (pairs.length > 2 * 65535) throw new RangeError('DeviceBatch.cropPairs: at most 65535 pairs');
-    const prm = cropParams('cropPairs', o), t = tensorFormat('cropPairs', o.tensor, ['cropPairsTensorDevice']);
+    const prm = cropParams('cropPairs', o), mf = prefilterOf('cropPairs', o, ['cropPairsFilteredDevice', 'cropFilterFactors']);
+    const t = tensorFormat('cropPairs', o.tensor, [mf ? 'cropPairsFilteredDevice' : 'cropPairsTensorDevice']);
     bind0(set === undefined ? 0 : set);
-    if (t) A.cropPairsTensorDevice(ctxs[0], pairs, prm, tensorArg(t), cropOut(pairs.length >> 1, prm, t), 0, 0, false);
+    if (mf) A.cropPairsFilteredDevice(ctxs[0], pairs, prm, mf, t ? tensorArg(t) : null, cropOut(pairs.length >> 1, prm, t, mf), 0, 0, false);
+    else if (t) A.cropPairsTensorDevice(ctxs[0], pairs, prm, tensorArg(t), cropOut(pairs.length >> 1, prm, t), 0, 0, false);
     else A.cropPairsDevice(ctxs[0], pairs, prm, cropOut(pairs.length >> 1, prm), 0, 0, false);
   };
   this.cropFeeds = function (sset, streams, o) {
     needCrop('cropFeeds');
     if (!(streams instanceof Int32Array) || streams.length !== n) throw new TypeError('DeviceBatch.cropFeeds: streams is an Int32Array with one tracker per feed (' + n + ')');
-    const prm = cropParams('cropFeeds', o), t = tensorFormat('cropFeeds', o.tensor, ['cropSourcesTensorDevice']), entries = listEntries(sset, o.rects, 'cropFeeds');
-    if (t) A.cropSourcesTensorDevice(ctxs[0], streams, entries, prm, tensorArg(t), cropOut(n, prm, t), 0, 0, false);
+    const prm = cropParams('cropFeeds', o), mf = prefilterOf('cropFeeds', o, ['cropSourcesFilteredDevice', 'cropFilterFactors']);
+    const t = tensorFormat('cropFeeds', o.tensor, [mf ? 'cropSourcesFilteredDevice' : 'cropSourcesTensorDevice']), entries = listEntries(sset, o.rects, 'cropFeeds');
+    if (mf) A.cropSourcesFilteredDevice(ctxs[0], streams, entries, prm, mf, t ? tensorArg(t) : null, cropOut(n, prm, t, mf), 0, 0, false);
+    else if (t) A.cropSourcesTensorDevice(ctxs[0], streams, entries, prm, tensorArg(t), cropOut(n, prm, t), 0, 0, false);
     else A.cropSourcesDevice(ctxs[0], streams, entries, prm, cropOut(n, prm), 0, 0, false);
   };
   this.cropResult = function () {
     if (!lastCrop) throw new Error('DeviceBatch.cropResult: no cropPairs / cropFeeds yet');
     const r = A.cropResult(ctxs[0], lastCrop.n), bytes = lastCrop.n * lastCrop.width * lastCrop.height * 4;
+    const res = { n: lastCrop.n, width: lastCrop.width, height: lastCrop.height, records: r.records, ratios: r.ratios };
+    if (lastCrop.prefilter) res.factors = A.cropFilterFactors(r.records, lastCrop.width, lastCrop.height, lastCrop.prefilter);
     if (lastCrop.tensor) {
       const tr = tensorResult(lastCrop, cropDev);
-      return { n: lastCrop.n, width: lastCrop.width, height: lastCrop.height, records: r.records, ratios: r.ratios, patches: tr.patches, tensor: tr.tensor };
+      res.patches = tr.patches; res.tensor = tr.tensor;
+      return res;
     }
-    const patches = new Uint8Array(bytes);
-    A.deviceDownload(ctxs[0], cropDev, 0, patches);
-    return { n: lastCrop.n, width: lastCrop.width, height: lastCrop.height, records: r.records, ratios: r.ratios, patches: patches };
+    res.patches = new Uint8Array(bytes);
+    A.deviceDownload(ctxs[0], cropDev, 0, res.patches);
+    return res;
   };
   /* Angle-aligned face crops (ht_camshift_align_pairs_device / ht_camshift_align_sources_device): the ROTATED box of each tracker — width and
    * height along the blob's axes, turned by its angle as the overlay draws it — sampled upright into opts.width x opts.height RGBA; pixels
@@ -948,40 +967,47 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
       throw new Error('DeviceBatch.' + what + ': this headtrackr_hip.node has no alignPairsDevice / alignSourcesDevice / alignResult (rebuild it)');
     if (!trackers) throw new Error('DeviceBatch.' + what + ': no trackers yet (initPairs, initTrackers or detectStep first)');
   };
-  const alignOut = function (count, prm, t) { /* the patch buffer, grown on demand */
+  const alignOut = function (count, prm, t, mf) { /* the patch buffer, grown on demand */
     const need = count * (t ? patchStride(prm, t) : prm[0] * prm[1] * 4);
     if (alignBytes < need) {
       if (alignDev) A.deviceFree(ctxs[0], alignDev); /* waits for the work in flight */
       alignDev = A.deviceAlloc(ctxs[0], need); alignBytes = need;
     }
-    lastAlign = { n: count, width: prm[0], height: prm[1], tensor: t || null };
+    lastAlign = { n: count, width: prm[0], height: prm[1], tensor: t || null, prefilter: mf || 0 };
     return alignDev;
   };
   this.alignPairs = function (set, pairs, o) {
     needAlign('alignPairs'); pairList('alignPairs', pairs);
     if (pairs.length > 2 * 65535) throw new RangeError('DeviceBatch.alignPairs: at most 65535 pairs');
-    const prm = cropParams('alignPairs', o), t = tensorFormat('alignPairs', o.tensor, ['alignPairsTensorDevice']);
+    const prm = cropParams('alignPairs', o), mf = prefilterOf('alignPairs', o, ['alignPairsFilteredDevice', 'alignFilterFactors']);
+    const t = tensorFormat('alignPairs', o.tensor, [mf ? 'alignPairsFilteredDevice' : 'alignPairsTensorDevice']);
     bind0(set === undefined ? 0 : set);
-    if (t) A.alignPairsTensorDevice(ctxs[0], pairs, prm, tensorArg(t), alignOut(pairs.length >> 1, prm, t), 0, 0, false);
+    if (mf) A.alignPairsFilteredDevice(ctxs[0], pairs, prm, mf, t ? tensorArg(t) : null, alignOut(pairs.length >> 1, prm, t, mf), 0, 0, false);
+    else if (t) A.alignPairsTensorDevice(ctxs[0], pairs, prm, tensorArg(t), alignOut(pairs.length >> 1, prm, t), 0, 0, false);
     else A.alignPairsDevice(ctxs[0], pairs, prm, alignOut(pairs.length >> 1, prm), 0, 0, false);
   };
   this.alignFeeds = function (sset, streams, o) {
     needAlign('alignFeeds');
     if (!(streams instanceof Int32Array) || streams.length !== n) throw new TypeError('DeviceBatch.alignFeeds: streams is an Int32Array with one tracker per feed (' + n + ')');
-    const prm = cropParams('alignFeeds', o), t = tensorFormat('alignFeeds', o.tensor, ['alignSourcesTensorDevice']), entries = listEntries(sset, o.rects, 'alignFeeds');
-    if (t) A.alignSourcesTensorDevice(ctxs[0], streams, entries, prm, tensorArg(t), alignOut(n, prm, t), 0, 0, false);
+    const prm = cropParams('alignFeeds', o), mf = prefilterOf('alignFeeds', o, ['alignSourcesFilteredDevice', 'alignFilterFactors']);
+    const t = tensorFormat('alignFeeds', o.tensor, [mf ? 'alignSourcesFilteredDevice' : 'alignSourcesTensorDevice']), entries = listEntries(sset, o.rects, 'alignFeeds');
+    if (mf) A.alignSourcesFilteredDevice(ctxs[0], streams, entries, prm, mf, t ? tensorArg(t) : null, alignOut(n, prm, t, mf), 0, 0, false);
+    else if (t) A.alignSourcesTensorDevice(ctxs[0], streams, entries, prm, tensorArg(t), alignOut(n, prm, t), 0, 0, false);
     else A.alignSourcesDevice(ctxs[0], streams, entries, prm, alignOut(n, prm), 0, 0, false);
   };
   this.alignResult = function () {
     if (!lastAlign) throw new Error('DeviceBatch.alignResult: no alignPairs / alignFeeds yet');
     const r = A.alignResult(ctxs[0], lastAlign.n), bytes = lastAlign.n * lastAlign.width * lastAlign.height * 4;
+    const res = { n: lastAlign.n, width: lastAlign.width, height: lastAlign.height, records: r.records, terms: r.terms };
+    if (lastAlign.prefilter) res.factors = A.alignFilterFactors(r.records, r.terms, lastAlign.width, lastAlign.height, lastAlign.prefilter);
     if (lastAlign.tensor) {
       const tr = tensorResult(lastAlign, alignDev);
-      return { n: lastAlign.n, width: lastAlign.width, height: lastAlign.height, records: r.records, terms: r.terms, patches: tr.patches, tensor: tr.tensor };
+      res.patches = tr.patches; res.tensor = tr.tensor;
+      return res;
     }
-    const patches = new Uint8Array(bytes);
-    A.deviceDownload(ctxs[0], alignDev, 0, patches);
-    return { n: lastAlign.n, width: lastAlign.width, height: lastAlign.height, records: r.records, terms: r.terms, patches: patches };
+    res.patches = new Uint8Array(bytes);
+    A.deviceDownload(ctxs[0], alignDev, 0, res.patches);
+    return res;
   };
   this.graphLaunches = function () { return ctxs.reduce(function (s, c) { return s + A.graphLaunches(c); }, 0); };
   /* the frame buffer is shared by all `depth` contexts: the others go first (ht_device_free refuses while they have it bound) */

@@ -129,6 +129,8 @@ PATCH_DTYPES = {"f32": HT_PATCH_F32, "f16": HT_PATCH_F16, "bf16": HT_PATCH_BF16}
 PATCH_LAYOUTS = {"chw": HT_PATCH_CHW, "hwc": HT_PATCH_HWC}
 PATCH_CHANNELS = {"rgb": HT_PATCH_RGB, "bgr": HT_PATCH_BGR, "gray": HT_PATCH_GRAY}
 
+HT_FILTER_MAX_FACTOR = 8  # the largest max_factor of the _filtered calls
+
 HT_YUV_NV12, HT_YUV_I420 = 0, 1
 HT_DRAW_RGBA = 16  # ht_draw_source.format beside the two above (outside the range the YUV entry points take)
 HT_YUV_BT601_LIMITED, HT_YUV_BT709_LIMITED, HT_YUV_BT601_FULL, HT_YUV_BT709_FULL = 0, 1, 2, 3
@@ -142,7 +144,7 @@ SYMBOLS = [
     "ht_windows_per_frame", "ht_pyramid_bytes_per_frame", "ht_upload_frames", "ht_upload_frames_async", "ht_swap_frames", "ht_bind_frames_device", "ht_frames_bound", "ht_frames_enqueued", "ht_host_alloc", "ht_host_free", "ht_device_alloc", "ht_device_free", "ht_device_upload", "ht_device_download", "ht_draw_frames_device", "ht_draw_frames", "ht_draw_frames_yuv_device", "ht_draw_frames_yuv", "ht_draw_list_device", "ht_detect_enqueue",
     "ht_detect_collect", "ht_detect_batch", "ht_pyramid_readback", "ht_stage_counts", "ht_grayscale_batch",
     "ht_whitebalance_batch", "ht_detect_whitebalance", "ht_hits_to_rects", "ht_group_rects", "ht_best_faces", "ht_detect_collect_best", "ht_detect_collect_best_requeue", "ht_detect_best_enqueue", "ht_detect_best_collect", "ht_detect_best_collect_requeue", "ht_detect_grouped", "ht_detect_best_records_device", "ht_group_hits", "ht_camshift_reserve", "ht_camshift_init_batch",
-    "ht_camshift_track_batch", "ht_camshift_track_collect", "ht_camshift_init_pairs", "ht_camshift_track_pairs", "ht_camshift_init_best", "ht_camshift_init_best_result", "ht_camshift_track_sequence", "ht_camshift_sequence_collect", "ht_camshift_stats", "ht_camshift_debug_hist", "ht_camshift_backproject", "ht_camshift_backproject_device", "ht_camshift_backproject_pairs", "ht_camshift_backproject_pairs_device", "ht_camshift_crop_pairs_device", "ht_camshift_crop_sources_device", "ht_camshift_crop_result", "ht_camshift_crop_records_device", "ht_camshift_align_pairs_device", "ht_camshift_align_sources_device", "ht_camshift_align_result", "ht_camshift_align_records_device", "ht_camshift_crop_pairs_tensor_device", "ht_camshift_crop_sources_tensor_device", "ht_camshift_align_pairs_tensor_device", "ht_camshift_align_sources_tensor_device", "ht_allgather_records", "ht_allgather_best_faces", "ht_device_count", "ht_profile", "ht_kernel_times", "ht_stream", "ht_graph_launches", "ht_synchronize",
+    "ht_camshift_track_batch", "ht_camshift_track_collect", "ht_camshift_init_pairs", "ht_camshift_track_pairs", "ht_camshift_init_best", "ht_camshift_init_best_result", "ht_camshift_track_sequence", "ht_camshift_sequence_collect", "ht_camshift_stats", "ht_camshift_debug_hist", "ht_camshift_backproject", "ht_camshift_backproject_device", "ht_camshift_backproject_pairs", "ht_camshift_backproject_pairs_device", "ht_camshift_crop_pairs_device", "ht_camshift_crop_sources_device", "ht_camshift_crop_result", "ht_camshift_crop_records_device", "ht_camshift_align_pairs_device", "ht_camshift_align_sources_device", "ht_camshift_align_result", "ht_camshift_align_records_device", "ht_camshift_crop_pairs_tensor_device", "ht_camshift_crop_sources_tensor_device", "ht_camshift_align_pairs_tensor_device", "ht_camshift_align_sources_tensor_device", "ht_camshift_crop_pairs_filtered_device", "ht_camshift_crop_sources_filtered_device", "ht_camshift_align_pairs_filtered_device", "ht_camshift_align_sources_filtered_device", "ht_camshift_crop_filter_factors", "ht_camshift_align_filter_factors", "ht_allgather_records", "ht_allgather_best_faces", "ht_device_count", "ht_profile", "ht_kernel_times", "ht_stream", "ht_graph_launches", "ht_synchronize",
 ]
 
 _lib = None
@@ -300,6 +302,18 @@ def lib():
     L.ht_camshift_align_pairs_tensor_device.argtypes = [vp, vp, i32, C.POINTER(ALIGN_PARAMS), C.POINTER(PATCH_FORMAT), vp, sz]
     L.ht_camshift_align_sources_tensor_device.restype = i32
     L.ht_camshift_align_sources_tensor_device.argtypes = [vp, vp, C.POINTER(DRAW_SOURCE), i32, C.POINTER(ALIGN_PARAMS), C.POINTER(PATCH_FORMAT), vp, sz]
+    L.ht_camshift_crop_pairs_filtered_device.restype = i32
+    L.ht_camshift_crop_pairs_filtered_device.argtypes = [vp, vp, i32, C.POINTER(CROP_PARAMS), i32, C.POINTER(PATCH_FORMAT), vp, sz]
+    L.ht_camshift_crop_sources_filtered_device.restype = i32
+    L.ht_camshift_crop_sources_filtered_device.argtypes = [vp, vp, C.POINTER(DRAW_SOURCE), i32, C.POINTER(CROP_PARAMS), i32, C.POINTER(PATCH_FORMAT), vp, sz]
+    L.ht_camshift_align_pairs_filtered_device.restype = i32
+    L.ht_camshift_align_pairs_filtered_device.argtypes = [vp, vp, i32, C.POINTER(ALIGN_PARAMS), i32, C.POINTER(PATCH_FORMAT), vp, sz]
+    L.ht_camshift_align_sources_filtered_device.restype = i32
+    L.ht_camshift_align_sources_filtered_device.argtypes = [vp, vp, C.POINTER(DRAW_SOURCE), i32, C.POINTER(ALIGN_PARAMS), i32, C.POINTER(PATCH_FORMAT), vp, sz]
+    L.ht_camshift_crop_filter_factors.restype = i32
+    L.ht_camshift_crop_filter_factors.argtypes = [vp, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
+    L.ht_camshift_align_filter_factors.restype = i32
+    L.ht_camshift_align_filter_factors.argtypes = [vp, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
     L.ht_allgather_records.restype = i32
     L.ht_allgather_records.argtypes = [vp, i32, vp, sz]
     L.ht_allgather_best_faces.restype = i32

@@ -3,6 +3,7 @@
     fmt = PatchFormat.mean_std(mean, std, dtype="f16", layout="chw", channels="rgb")
     x = empty_patches(n, 112, 112, fmt, "cuda")          # [n, 3, 112, 112] float16
     align_sources_into(ctx, x, streams, entries, fmt)    # ONE launch behind the track step
+                                                         # (prefilter=8: block-mean patches for large faces, still one launch)
     ctx.synchronize()                                    # or order torch's stream behind ctx.stream
     y = model(x)
 
@@ -62,26 +63,38 @@ def _on_device(what: str, ctx, tensor):
         raise ValueError(f"{what}: the tensor lives on device {index}, the context on device {ctx.device}")
 
 
-def crop_pairs_into(ctx, tensor, pairs, fmt, margin: float = 1.0, square: bool = False):
+def crop_pairs_into(ctx, tensor, pairs, fmt, margin: float = 1.0, square: bool = False, prefilter=None):
     """Context.camshift_crop_pairs_tensor_device into `tensor` (empty_patches(len(pairs), w, h, fmt)): size and stride are the tensor's"""
     ptr, w, h, stride = _target("crop_pairs_into", tensor, len(pairs), fmt)
     _on_device("crop_pairs_into", ctx, tensor)
+    if prefilter is not None:  # the block-mean prefilter: max_factor 1..8 (Context.camshift_crop_pairs_filtered_device)
+        ctx.camshift_crop_pairs_filtered_device(ptr, pairs, w, h, max_factor=prefilter, fmt=fmt, margin=margin, square=square, stride=stride)
+        return
     ctx.camshift_crop_pairs_tensor_device(ptr, pairs, w, h, fmt, margin=margin, square=square, stride=stride)
 
 
-def crop_sources_into(ctx, tensor, streams, entries, fmt, margin: float = 1.0, square: bool = False):
+def crop_sources_into(ctx, tensor, streams, entries, fmt, margin: float = 1.0, square: bool = False, prefilter=None):
     ptr, w, h, stride = _target("crop_sources_into", tensor, len(entries), fmt)
     _on_device("crop_sources_into", ctx, tensor)
+    if prefilter is not None:  # the block-mean prefilter: max_factor 1..8 (Context.camshift_crop_sources_filtered_device)
+        ctx.camshift_crop_sources_filtered_device(ptr, streams, entries, w, h, max_factor=prefilter, fmt=fmt, margin=margin, square=square, stride=stride)
+        return
     ctx.camshift_crop_sources_tensor_device(ptr, streams, entries, w, h, fmt, margin=margin, square=square, stride=stride)
 
 
-def align_pairs_into(ctx, tensor, pairs, fmt, margin: float = 1.0, square: bool = False):
+def align_pairs_into(ctx, tensor, pairs, fmt, margin: float = 1.0, square: bool = False, prefilter=None):
     ptr, w, h, stride = _target("align_pairs_into", tensor, len(pairs), fmt)
     _on_device("align_pairs_into", ctx, tensor)
+    if prefilter is not None:  # the block-mean prefilter: max_factor 1..8 (Context.camshift_align_pairs_filtered_device)
+        ctx.camshift_align_pairs_filtered_device(ptr, pairs, w, h, max_factor=prefilter, fmt=fmt, margin=margin, square=square, stride=stride)
+        return
     ctx.camshift_align_pairs_tensor_device(ptr, pairs, w, h, fmt, margin=margin, square=square, stride=stride)
 
 
-def align_sources_into(ctx, tensor, streams, entries, fmt, margin: float = 1.0, square: bool = False):
+def align_sources_into(ctx, tensor, streams, entries, fmt, margin: float = 1.0, square: bool = False, prefilter=None):
     ptr, w, h, stride = _target("align_sources_into", tensor, len(entries), fmt)
     _on_device("align_sources_into", ctx, tensor)
+    if prefilter is not None:  # the block-mean prefilter: max_factor 1..8 (Context.camshift_align_sources_filtered_device)
+        ctx.camshift_align_sources_filtered_device(ptr, streams, entries, w, h, max_factor=prefilter, fmt=fmt, margin=margin, square=square, stride=stride)
+        return
     ctx.camshift_align_sources_tensor_device(ptr, streams, entries, w, h, fmt, margin=margin, square=square, stride=stride)

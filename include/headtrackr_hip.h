@@ -491,8 +491,8 @@ ht_status ht_camshift_crop_records_device(ht_ctx *ctx, const void **records, int
  * (headtrackr_amd/csrc/ht_align_plan.h states the rule).  Each pixel is a bilinear blend, with 8-bit weights, of the source's declared RGBA
  * view, taps clamped to the source frame; a pixel whose sample centre lies outside the source frame is four zero bytes.  HT_ALIGN_EMPTY — a
  * lost 0 x 0 object, a stream that was never tracked, a box wider than 65536 or centred beyond +-2^20, an angle that is not finite or beyond
- * +-1024 — writes every byte of the patch as 0.  Not part of this: sub-pixel centres (x, y are floored as the crop calls floor them), a
- * prefilter for strong downscales.  (Planar or float output: the _tensor calls below.) */
+ * +-1024 — writes every byte of the patch as 0.  Not part of this: sub-pixel centres (x, y are floored as the crop calls floor them).
+ * (Planar or float output: the _tensor calls below.  A prefilter for strong downscales: the _filtered calls below.) */
 enum { HT_ALIGN_EMPTY = 0, HT_ALIGN_FACE = 1 };
 enum { HT_ALIGN_SQUARE = 1 };
 typedef struct ht_align_params {
@@ -534,8 +534,8 @@ ht_status ht_camshift_align_records_device(ht_ctx *ctx, const void **records, in
  * in the dtype —, not zero bytes; the record's `code` tells an empty entry from a black face.
  * scale[c] and bias[c] must be finite and 0 or of a magnitude within 2^-64 .. 2^64 (then no binary32 intermediate is subnormal or NaN);
  * the slots of channels the mode does not have (gray: 1 and 2) must be 0; pad must be 0.
- * Not part of this: an alpha or validity-mask channel, sub-pixel centres, a prefilter for strong downscales, per-entry formats,
- * integer-quantised (int8) output. */
+ * Not part of this: an alpha or validity-mask channel, sub-pixel centres, per-entry formats, integer-quantised (int8) output.  (A prefilter
+ * for strong downscales: the _filtered calls below, which take a format too.) */
 enum { HT_PATCH_F32 = 0, HT_PATCH_F16 = 1, HT_PATCH_BF16 = 2 };
 enum { HT_PATCH_CHW = 0, HT_PATCH_HWC = 1 };
 enum { HT_PATCH_RGB = 0, HT_PATCH_BGR = 1, HT_PATCH_GRAY = 2 };
@@ -558,6 +558,44 @@ ht_status ht_camshift_align_pairs_tensor_device(ht_ctx *ctx, const ht_cs_pair *p
                                                 void *out_dev, size_t out_stride);
 ht_status ht_camshift_align_sources_tensor_device(ht_ctx *ctx, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_align_params *params,
                                                   const ht_patch_format *format, void *out_dev, size_t out_stride);
+
+/* ---- prefiltered face crops: block-mean patches for strong downscales ----------------------------------------------------- */
+
+/* The calls above sample one bilinear tap pair per patch pixel: a face 792 source pixels wide cut to 112 x 112 reads 2 of every 7 source
+ * rows and columns, and the rest aliases.  These four write each patch pixel as the mean of an Nx x Ny block of the UNFILTERED rule's
+ * samples, in the same single enqueue-only launch (headtrackr_amd/csrc/ht_filter_plan.h states the rule).  The factors are chosen per
+ * entry on the device, from the tracked box, with P x Q = out_width x out_height and max_factor 1..8:
+ *   crop:   Nx = min(max_factor, max(1, ceil(w / P))), Ny = min(max_factor, max(1, ceil(h / Q))), (l, t, w, h) the crop rule's rect;
+ *   align:  Nx = min(max_factor, max(1, ceil((|ux| + |uy|) / (P * 65536)))), Ny the same with (vx, vy) and Q: the L1 norm never
+ *           under-samples, and upright (a12 == 1024) it is the crop's w / P.
+ * The fine patch F is what the unfiltered call of the same name gives for the same entry at Nx * P x Ny * Q (crop: drawImage of the same
+ * rect with rx' = w / (Nx * P), ry' = h / (Ny * Q), one binary64 division each; align: the terms of column i of Nx * P and row j of
+ * Ny * Q with the same centre and vectors, the range test and the four zero bytes of a sample outside the frame as they are), and per
+ * channel, alpha included, with n = Nx * Ny:
+ *   out(x, y) = (sum of F(Nx * x + a, Ny * y + b) over a < Nx, b < Ny + (n >> 1)) / n        (integer division)
+ * So with Nx == Ny == 1 — max_factor 1, or a box that is not downscaled — the patch is byte for byte the unfiltered call's; where
+ * w == Nx * P and h == Ny * Q exactly it is the exact integer box mean of the source block; an empty entry is zeros; an aligned patch's edge
+ * fades where fine samples fall outside the frame.  format == NULL: RGBA8, the output layout of the RGBA calls.  Otherwise the output is
+ * f(filtered patch) with f, the layout, the stride rule and the format check of the _tensor calls (gray is taken from the filtered R, G, B).
+ * Arguments, list rules, the "entry <i>" refusals, the overlap refusal, status codes and the enqueue-only contract are those of the call of
+ * the same name without `_filtered`, whose table, ring and records are used: a filtered call IS the context's last crop (or align) call,
+ * and ht_camshift_crop_result / ht_camshift_align_result report the records the unfiltered call would have written (crop: rx = w / P).
+ * max_factor outside 1..8: HT_ERR_INVALID, before anything is enqueued.
+ * Not part of this: filters other than the block mean, factors above 8, sub-pixel centres, per-entry formats, int8 output, a prefilter for
+ * the canvas draw calls. */
+ht_status ht_camshift_crop_pairs_filtered_device(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, const ht_crop_params *params, int32_t max_factor,
+                                                 const ht_patch_format *format, void *out_dev, size_t out_stride);
+ht_status ht_camshift_crop_sources_filtered_device(ht_ctx *ctx, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_crop_params *params,
+                                                   int32_t max_factor, const ht_patch_format *format, void *out_dev, size_t out_stride);
+ht_status ht_camshift_align_pairs_filtered_device(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, const ht_align_params *params, int32_t max_factor,
+                                                  const ht_patch_format *format, void *out_dev, size_t out_stride);
+ht_status ht_camshift_align_sources_filtered_device(ht_ctx *ctx, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_align_params *params,
+                                                    int32_t max_factor, const ht_patch_format *format, void *out_dev, size_t out_stride);
+/* The factors a filtered call of (out_width, out_height, max_factor) takes for the entry of *record: a pure function of the record, so a
+ * caller never restates the rule.  No context, no device.  An empty record gives 0, 0.  HT_ERR_INVALID for a NULL argument, out_width or
+ * out_height outside 1..1024, max_factor outside 1..8. */
+ht_status ht_camshift_crop_filter_factors(const ht_crop_record *record, int32_t out_width, int32_t out_height, int32_t max_factor, int32_t *nx, int32_t *ny);
+ht_status ht_camshift_align_filter_factors(const ht_align_record *record, int32_t out_width, int32_t out_height, int32_t max_factor, int32_t *nx, int32_t *ny);
 
 /* ---- multi-GPU: fixed-size result records, all-gathered over RCCL/xGMI ------------------------------------ */
 
