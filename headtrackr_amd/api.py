@@ -584,24 +584,45 @@ class Context:
     def _crop_params(width: int, height: int, margin: float, square: bool):
         return native.CROP_PARAMS(int(width), int(height), int(round(float(margin) * 256)), native.HT_CROP_SQUARE if square else 0)
 
+    @staticmethod
+    def _face_extra(name: str, fmt, max_factor):
+        """what a form has between the params and the output: the tensor forms' format; the filtered forms' max_factor and format | NULL"""
+        if name.endswith("_tensor_device"):
+            return (C.byref(PatchFormat.of(fmt).struct()),)
+        if name.endswith("_filtered_device"):
+            fp = Context._filter_format(fmt)[1]
+            return (int(max_factor), fp)
+        return ()
+
+    def _face_pairs(self, name: str, dev_ptr: int, pairs, size, stride: int, fmt=None, max_factor=None):
+        """the pairs form of every face-patch call: ht_<name>(ctx, pairs, n, params, [max_factor,] [format,] out, stride); size = (width, height,
+        margin, square)"""
+        p = self._pairs(pairs)
+        extra = self._face_extra(name, fmt, max_factor)
+        prm = (self._align_params if "_align_" in name else self._crop_params)(*size)
+        self._check(getattr(self._lib, "ht_" + name)(self._h, p.ctypes.data, len(p), C.byref(prm), *extra, dev_ptr, stride))
+
+    def _face_sources(self, name: str, dev_ptr: int, streams, entries, size, stride: int, fmt=None, max_factor=None):
+        """the sources form: ht_<name>(ctx, streams, entries, n, params, [max_factor,] [format,] out, stride)"""
+        if len(streams) != len(entries):
+            raise ValueError(name + ": one stream per entry")
+        st = np.ascontiguousarray(np.asarray(streams, dtype=np.int32).reshape(-1))
+        extra = self._face_extra(name, fmt, max_factor)
+        prm = (self._align_params if "_align_" in name else self._crop_params)(*size)
+        self._check(getattr(self._lib, "ht_" + name)(self._h, st.ctypes.data if len(st) else None, self._draw_sources(entries), len(entries), C.byref(prm), *extra,
+                                                     dev_ptr, stride))
+
     def camshift_crop_pairs_device(self, dev_ptr: int, pairs, width: int, height: int, margin: float = 1.0, square: bool = False, stride: int = 0):
         """Patch i = the box of stream pairs[i][0]'s track object cut from BOUND frame pairs[i][1] and scaled to width x height RGBA by the
         declared resampler, into device memory at dev_ptr (patches `stride` bytes apart, 0 = packed).  margin widens the box around its
         centre (1.0 = as tracked; it becomes 1/256 steps, 0.25 .. 4); square grows the shorter side first.  A lost or never tracked stream
         gives zeros.  Enqueued behind the outstanding track steps: no copy, no wait.  Streams may repeat."""
-        p = self._pairs(pairs)
-        prm = self._crop_params(width, height, margin, square)
-        self._check(self._lib.ht_camshift_crop_pairs_device(self._h, p.ctypes.data, len(p), C.byref(prm), dev_ptr, stride))
+        self._face_pairs("camshift_crop_pairs_device", dev_ptr, pairs, (width, height, margin, square), stride)
 
     def camshift_crop_sources_device(self, dev_ptr: int, streams, entries, width: int, height: int, margin: float = 1.0, square: bool = False, stride: int = 0):
         """The same from the feeds' own frames: entries[i] as in draw_list, its "rect" the rect that was drawn onto the canvas stream
         streams[i] tracks on; the box is mapped back through it and may reach beyond it, up to the source's edges."""
-        if len(streams) != len(entries):
-            raise ValueError("camshift_crop_sources_device: one stream per entry")
-        st = np.ascontiguousarray(np.asarray(streams, dtype=np.int32).reshape(-1))
-        prm = self._crop_params(width, height, margin, square)
-        self._check(self._lib.ht_camshift_crop_sources_device(self._h, st.ctypes.data if len(st) else None, self._draw_sources(entries), len(entries), C.byref(prm),
-                                                              dev_ptr, stride))
+        self._face_sources("camshift_crop_sources_device", dev_ptr, streams, entries, (width, height, margin, square), stride)
 
     def camshift_crop_result(self, n: int) -> np.ndarray:
         """CROP_RECORD_DTYPE [n] of the LAST crop call (same n): code (native.HT_CROP_EMPTY / _FACE), stream, the rect in source pixels and
@@ -627,19 +648,12 @@ class Context:
         apart, 0 = packed).  margin and square as for camshift_crop_pairs_device; square makes both sides the longer one.  Pixels whose
         sample centre lies outside the frame are zeros, and so is the patch of a lost or never tracked stream.  Enqueued behind the
         outstanding track steps: no copy, no wait.  Streams may repeat."""
-        p = self._pairs(pairs)
-        prm = self._align_params(width, height, margin, square)
-        self._check(self._lib.ht_camshift_align_pairs_device(self._h, p.ctypes.data, len(p), C.byref(prm), dev_ptr, stride))
+        self._face_pairs("camshift_align_pairs_device", dev_ptr, pairs, (width, height, margin, square), stride)
 
     def camshift_align_sources_device(self, dev_ptr: int, streams, entries, width: int, height: int, margin: float = 1.0, square: bool = False, stride: int = 0):
         """The same from the feeds' own frames: entries[i] as in draw_list, its "rect" the rect that was drawn onto the canvas stream
         streams[i] tracks on; the box is mapped back through it (an affine image) and may reach beyond it, up to the source's edges."""
-        if len(streams) != len(entries):
-            raise ValueError("camshift_align_sources_device: one stream per entry")
-        st = np.ascontiguousarray(np.asarray(streams, dtype=np.int32).reshape(-1))
-        prm = self._align_params(width, height, margin, square)
-        self._check(self._lib.ht_camshift_align_sources_device(self._h, st.ctypes.data if len(st) else None, self._draw_sources(entries), len(entries), C.byref(prm),
-                                                               dev_ptr, stride))
+        self._face_sources("camshift_align_sources_device", dev_ptr, streams, entries, (width, height, margin, square), stride)
 
     def camshift_align_result(self, n: int) -> np.ndarray:
         """ALIGN_RECORD_DTYPE [n] of the LAST align call (same n): code (native.HT_ALIGN_EMPTY / _FACE), stream, the angle in 1/4096 turn,
@@ -660,34 +674,20 @@ class Context:
         tensor — fmt.nchannels * width * height elements of fmt.dtype, `stride` bytes apart (0 = a patch's bytes rounded up to 4) —, every
         element fl32(fl32(byte * scale[c]) + bias[c]) rounded to the dtype, in the same single launch.  A lost or never tracked stream gives
         bias[c] everywhere (read camshift_crop_result's code).  This IS the context's last crop call."""
-        p, f = self._pairs(pairs), PatchFormat.of(fmt).struct()
-        prm = self._crop_params(width, height, margin, square)
-        self._check(self._lib.ht_camshift_crop_pairs_tensor_device(self._h, p.ctypes.data, len(p), C.byref(prm), C.byref(f), dev_ptr, stride))
+        self._face_pairs("camshift_crop_pairs_tensor_device", dev_ptr, pairs, (width, height, margin, square), stride, fmt)
 
     def camshift_crop_sources_tensor_device(self, dev_ptr: int, streams, entries, width: int, height: int, fmt, margin: float = 1.0, square: bool = False, stride: int = 0):
         """camshift_crop_sources_device with fmt as the output (see camshift_crop_pairs_tensor_device)"""
-        if len(streams) != len(entries):
-            raise ValueError("camshift_crop_sources_tensor_device: one stream per entry")
-        st, f = np.ascontiguousarray(np.asarray(streams, dtype=np.int32).reshape(-1)), PatchFormat.of(fmt).struct()
-        prm = self._crop_params(width, height, margin, square)
-        self._check(self._lib.ht_camshift_crop_sources_tensor_device(self._h, st.ctypes.data if len(st) else None, self._draw_sources(entries), len(entries), C.byref(prm),
-                                                                     C.byref(f), dev_ptr, stride))
+        self._face_sources("camshift_crop_sources_tensor_device", dev_ptr, streams, entries, (width, height, margin, square), stride, fmt)
 
     def camshift_align_pairs_tensor_device(self, dev_ptr: int, pairs, width: int, height: int, fmt, margin: float = 1.0, square: bool = False, stride: int = 0):
         """camshift_align_pairs_device with fmt as the output; a pixel whose sample centre lies outside the source is bias[c], as every
         element of an empty entry is.  This IS the context's last align call."""
-        p, f = self._pairs(pairs), PatchFormat.of(fmt).struct()
-        prm = self._align_params(width, height, margin, square)
-        self._check(self._lib.ht_camshift_align_pairs_tensor_device(self._h, p.ctypes.data, len(p), C.byref(prm), C.byref(f), dev_ptr, stride))
+        self._face_pairs("camshift_align_pairs_tensor_device", dev_ptr, pairs, (width, height, margin, square), stride, fmt)
 
     def camshift_align_sources_tensor_device(self, dev_ptr: int, streams, entries, width: int, height: int, fmt, margin: float = 1.0, square: bool = False, stride: int = 0):
         """camshift_align_sources_device with fmt as the output (see camshift_align_pairs_tensor_device)"""
-        if len(streams) != len(entries):
-            raise ValueError("camshift_align_sources_tensor_device: one stream per entry")
-        st, f = np.ascontiguousarray(np.asarray(streams, dtype=np.int32).reshape(-1)), PatchFormat.of(fmt).struct()
-        prm = self._align_params(width, height, margin, square)
-        self._check(self._lib.ht_camshift_align_sources_tensor_device(self._h, st.ctypes.data if len(st) else None, self._draw_sources(entries), len(entries), C.byref(prm),
-                                                                      C.byref(f), dev_ptr, stride))
+        self._face_sources("camshift_align_sources_tensor_device", dev_ptr, streams, entries, (width, height, margin, square), stride, fmt)
 
     # -- prefiltered face crops: each patch pixel the mean of a block of the unfiltered rule's samples ------------------------
     @staticmethod
@@ -706,38 +706,24 @@ class Context:
         unfiltered call's.  fmt None: RGBA8; otherwise a PatchFormat (or a dict of its arguments) and the output is the model-input tensor
         of the filtered patch, as camshift_crop_pairs_tensor_device lays it out.  ONE enqueue-only launch; this IS the context's last crop
         call (camshift_crop_result gives the unfiltered call's records; crop_filter_factors turns them into the factors)."""
-        p, (_f, fp) = self._pairs(pairs), self._filter_format(fmt)
-        prm = self._crop_params(width, height, margin, square)
-        self._check(self._lib.ht_camshift_crop_pairs_filtered_device(self._h, p.ctypes.data, len(p), C.byref(prm), int(max_factor), fp, dev_ptr, stride))
+        self._face_pairs("camshift_crop_pairs_filtered_device", dev_ptr, pairs, (width, height, margin, square), stride, fmt, max_factor)
 
     def camshift_crop_sources_filtered_device(self, dev_ptr: int, streams, entries, width: int, height: int, max_factor: int = 8, fmt=None, margin: float = 1.0,
                                               square: bool = False, stride: int = 0):
         """camshift_crop_sources_device with the block-mean prefilter (see camshift_crop_pairs_filtered_device)"""
-        if len(streams) != len(entries):
-            raise ValueError("camshift_crop_sources_filtered_device: one stream per entry")
-        st, (_f, fp) = np.ascontiguousarray(np.asarray(streams, dtype=np.int32).reshape(-1)), self._filter_format(fmt)
-        prm = self._crop_params(width, height, margin, square)
-        self._check(self._lib.ht_camshift_crop_sources_filtered_device(self._h, st.ctypes.data if len(st) else None, self._draw_sources(entries), len(entries), C.byref(prm),
-                                                                       int(max_factor), fp, dev_ptr, stride))
+        self._face_sources("camshift_crop_sources_filtered_device", dev_ptr, streams, entries, (width, height, margin, square), stride, fmt, max_factor)
 
     def camshift_align_pairs_filtered_device(self, dev_ptr: int, pairs, width: int, height: int, max_factor: int = 8, fmt=None, margin: float = 1.0, square: bool = False,
                                              stride: int = 0):
         """camshift_align_pairs_device with the block-mean prefilter: Nx = min(max_factor, max(1, ceil((|ux| + |uy|) / (width * 65536)))),
         Ny the same with (vx, vy) and height, from the entry's align record; the patch's edge fades where fine samples fall outside the
         frame.  This IS the context's last align call (align_filter_factors turns its records into the factors)."""
-        p, (_f, fp) = self._pairs(pairs), self._filter_format(fmt)
-        prm = self._align_params(width, height, margin, square)
-        self._check(self._lib.ht_camshift_align_pairs_filtered_device(self._h, p.ctypes.data, len(p), C.byref(prm), int(max_factor), fp, dev_ptr, stride))
+        self._face_pairs("camshift_align_pairs_filtered_device", dev_ptr, pairs, (width, height, margin, square), stride, fmt, max_factor)
 
     def camshift_align_sources_filtered_device(self, dev_ptr: int, streams, entries, width: int, height: int, max_factor: int = 8, fmt=None, margin: float = 1.0,
                                                square: bool = False, stride: int = 0):
         """camshift_align_sources_device with the block-mean prefilter (see camshift_align_pairs_filtered_device)"""
-        if len(streams) != len(entries):
-            raise ValueError("camshift_align_sources_filtered_device: one stream per entry")
-        st, (_f, fp) = np.ascontiguousarray(np.asarray(streams, dtype=np.int32).reshape(-1)), self._filter_format(fmt)
-        prm = self._align_params(width, height, margin, square)
-        self._check(self._lib.ht_camshift_align_sources_filtered_device(self._h, st.ctypes.data if len(st) else None, self._draw_sources(entries), len(entries), C.byref(prm),
-                                                                        int(max_factor), fp, dev_ptr, stride))
+        self._face_sources("camshift_align_sources_filtered_device", dev_ptr, streams, entries, (width, height, margin, square), stride, fmt, max_factor)
 
     # -- measurement --------------------------------------------------------------------------------------------
     def profile(self, on: bool = True):

@@ -94,44 +94,25 @@ ht_status csp_plan(ht_ctx *c, const char *fn, const ht_cs_pair *pairs, int32_t n
     return HT_OK;
 }
 
-// the call's table -> device (entries, then the distinct frames): staged in a pinned buffer, copied on the context's stream in front of
-// the kernels that read it.  HT_CSP_STAGE staging buffers take turns, so a call practically never waits for an earlier call's copy.
+// the call's table -> device (entries, then the distinct frames): through the context's staged pair table (HtStagedTable, ht_internal.h),
+// copied on the context's stream in front of the kernels that read it.
 // ht_bp_pairs.hip sends its group records along (`extra`, extra_words 32-bit words behind the frame list; at most 8 per pair).
 ht_status csp_upload(ht_ctx *c, const char *fn, const CspPlan &plan, const CspEntry **d_entries, const int32_t **d_frames, const void *extra = nullptr,
                      size_t extra_words = 0, const int32_t **d_extra = nullptr) {
     const size_t n = plan.entries.size(), base_words = n * (sizeof(CspEntry) / 4) + plan.frames.size(), words = base_words + extra_words;
-    if (c->csp_tab_cap < words || c->h_csp_tab_cap < words) {
-        HT_HIP(c, hipStreamSynchronize(c->stream));
-        const size_t cap = std::max(words, (size_t)c->cs_streams * (2 * sizeof(CspEntry) / 4 + 1));  // entry + frame + group record per stream
-        if (c->d_csp_tab) (void)hipFree(c->d_csp_tab);
-        c->d_csp_tab = nullptr, c->csp_tab_cap = 0;
-        for (auto &h : c->h_csp_tab) {
-            if (h) (void)hipHostFree(h);
-            h = nullptr;
-        }
-        c->h_csp_tab_cap = 0;
-        bool ok = hipMalloc(reinterpret_cast<void **>(&c->d_csp_tab), cap * 4) == hipSuccess;
-        for (int k = 0; ok && k < ht_ctx::HT_CSP_STAGE; k++) {
-            ok = hipHostMalloc(reinterpret_cast<void **>(&c->h_csp_tab[k]), cap * 4, hipHostMallocDefault) == hipSuccess;
-            if (ok && !c->ev_csp_tab[k]) ok = hipEventCreateWithFlags(&c->ev_csp_tab[k], hipEventDisableTiming) == hipSuccess;
-        }
-        if (!ok) {
-            (void)hipGetLastError();
-            return ht_fail(c, HT_ERR_NOMEM, std::string(fn) + ": allocation of the pair table failed");
-        }
-        c->csp_tab_cap = c->h_csp_tab_cap = cap;
-    }
-    const int k = c->csp_stage_next;
-    c->csp_stage_next = (k + 1) % ht_ctx::HT_CSP_STAGE;
-    HT_HIP(c, hipEventSynchronize(c->ev_csp_tab[k]));  // never recorded: returns at once
-    std::memcpy(c->h_csp_tab[k], plan.entries.data(), n * sizeof(CspEntry));
-    std::memcpy(c->h_csp_tab[k] + n * (sizeof(CspEntry) / 4), plan.frames.data(), plan.frames.size() * 4);
-    if (extra_words) std::memcpy(c->h_csp_tab[k] + base_words, extra, extra_words * 4);
-    HT_HIP(c, hipMemcpyAsync(c->d_csp_tab, c->h_csp_tab[k], words * 4, hipMemcpyHostToDevice, c->stream));
-    HT_HIP(c, hipEventRecord(c->ev_csp_tab[k], c->stream));
-    *d_entries = reinterpret_cast<const CspEntry *>(c->d_csp_tab);
-    *d_frames = c->d_csp_tab + n * (sizeof(CspEntry) / 4);
-    if (d_extra) *d_extra = c->d_csp_tab + base_words;
+    const size_t minimum = (size_t)c->cs_streams * (2 * sizeof(CspEntry) / 4 + 1);  // entry + frame + group record per stream
+    ht_status st = ht_stage_reserve(c, &c->csp_tab, words * 4, minimum * 4, std::string(fn) + ": allocation of the pair table failed");
+    if (st != HT_OK) return st;
+    uint8_t *slot = nullptr;
+    if ((st = ht_stage_take(c, &c->csp_tab, &slot)) != HT_OK) return st;
+    std::memcpy(slot, plan.entries.data(), n * sizeof(CspEntry));
+    std::memcpy(slot + n * sizeof(CspEntry), plan.frames.data(), plan.frames.size() * 4);
+    if (extra_words) std::memcpy(slot + base_words * 4, extra, extra_words * 4);
+    if ((st = ht_stage_commit(c, &c->csp_tab, words * 4)) != HT_OK) return st;
+    const int32_t *d_tab = reinterpret_cast<const int32_t *>(c->csp_tab.d);
+    *d_entries = reinterpret_cast<const CspEntry *>(d_tab);
+    *d_frames = d_tab + n * (sizeof(CspEntry) / 4);
+    if (d_extra) *d_extra = d_tab + base_words;
     return HT_OK;
 }
 
@@ -266,15 +247,9 @@ extern "C" ht_status ht_camshift_track_pairs(ht_ctx *c, const ht_cs_pair *pairs,
 }
 
 void ht_cs_pairs_free(ht_ctx *c) {  // ht_destroy (the stream has been synchronised)
-    if (c->d_csp_tab) (void)hipFree(c->d_csp_tab);
+    ht_stage_free(&c->csp_tab);
     if (c->d_csp_hist) (void)hipFree(c->d_csp_hist);
-    for (auto &h : c->h_csp_tab)
-        if (h) (void)hipHostFree(h);
-    for (auto &e : c->ev_csp_tab)
-        if (e) (void)hipEventDestroy(e);
-    c->d_csp_tab = nullptr, c->d_csp_hist = nullptr, c->csp_tab_cap = c->h_csp_tab_cap = c->csp_hist_cap = 0;
-    for (auto &h : c->h_csp_tab) h = nullptr;
-    for (auto &e : c->ev_csp_tab) e = nullptr;
+    c->d_csp_hist = nullptr, c->csp_hist_cap = 0;
 }
 
 // The record-driven initTracker (ht_camshift_init_best, k_csb_resolve) is compiled right behind this file, whose plan, table upload and

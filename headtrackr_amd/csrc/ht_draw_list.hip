@@ -7,10 +7,9 @@
 // k_draw_list: grid (tile column, tile row, entry), 64 x 16 destination pixels and 256 threads per workgroup.  A workgroup reads its
 // entry's 104-byte descriptor (ht_draw_list_plan.h) — blockIdx.z is uniform and the table is const __restrict__, so these are scalar
 // loads —, computes the tile's 80 taps from that entry's ratios and rect into LDS, and behind the barrier takes a workgroup-uniform branch
-// into one of the three bodies.  The table reaches the device through a ring of pinned staging slots and one hipMemcpyAsync on the ctx
-// stream per call, as ht_cs_pairs.hip moves its pair tables: the copy and the kernel are ordered on the stream, so a later call's table
-// cannot reach the device before an earlier call's kernel has read its own, and a slot is written again only after the event behind
-// its copy.  DESIGN.md §2.3.2 gives the reasoning and the registers.
+// into one of the three bodies.  The table reaches the device
+// through a staged table (HtStagedTable, ht_internal.h: a ring of pinned slots and one hipMemcpyAsync on the ctx stream per call), as
+// every list call's table does.  DESIGN.md §2.3.2 gives the reasoning and the registers.
 #include <cstring>
 #include <vector>
 
@@ -56,36 +55,15 @@ __global__ __launch_bounds__(IG_NT) void k_draw_list(const DlDesc *__restrict__ 
     }
 }
 
-// the table of a call on the device: staged in the next pinned slot, copied behind everything enqueued so far
+// the table of a call on the device: through the context's staged descriptor table (HtStagedTable, ht_internal.h)
 ht_status dl_upload(ht_ctx *c, const char *fn, const std::vector<HtDrawDesc> &desc) {
     const size_t need = desc.size() * sizeof(HtDrawDesc);
-    if (c->dl_tab_cap < need) {  // a reallocation waits for the work in flight first, like every reallocation of the library
-        HT_HIP(c, hipStreamSynchronize(c->stream));
-        const size_t cap = std::max(need, (size_t)64 * sizeof(HtDrawDesc));
-        if (c->d_dl_tab) (void)hipFree(c->d_dl_tab);
-        c->d_dl_tab = nullptr, c->dl_tab_cap = 0;
-        for (auto &h : c->h_dl_tab) {
-            if (h) (void)hipHostFree(h);
-            h = nullptr;
-        }
-        bool ok = hipMalloc(reinterpret_cast<void **>(&c->d_dl_tab), cap) == hipSuccess;
-        for (int k = 0; ok && k < ht_ctx::HT_DL_STAGE; k++) {
-            ok = hipHostMalloc(reinterpret_cast<void **>(&c->h_dl_tab[k]), cap, hipHostMallocDefault) == hipSuccess;
-            if (ok && !c->ev_dl_tab[k]) ok = hipEventCreateWithFlags(&c->ev_dl_tab[k], hipEventDisableTiming) == hipSuccess;
-        }
-        if (!ok) {
-            (void)hipGetLastError();
-            return ht_fail(c, HT_ERR_NOMEM, std::string(fn) + ": allocation of the descriptor table failed");
-        }
-        c->dl_tab_cap = cap;
-    }
-    const int k = c->dl_stage_next;
-    c->dl_stage_next = (k + 1) % ht_ctx::HT_DL_STAGE;
-    HT_HIP(c, hipEventSynchronize(c->ev_dl_tab[k]));  // never recorded: returns at once
-    std::memcpy(c->h_dl_tab[k], desc.data(), need);
-    HT_HIP(c, hipMemcpyAsync(c->d_dl_tab, c->h_dl_tab[k], need, hipMemcpyHostToDevice, c->stream));
-    HT_HIP(c, hipEventRecord(c->ev_dl_tab[k], c->stream));
-    return HT_OK;
+    ht_status st = ht_stage_reserve(c, &c->dl_tab, need, 64 * sizeof(HtDrawDesc), std::string(fn) + ": allocation of the descriptor table failed");
+    if (st != HT_OK) return st;
+    uint8_t *slot = nullptr;
+    if ((st = ht_stage_take(c, &c->dl_tab, &slot)) != HT_OK) return st;
+    std::memcpy(slot, desc.data(), need);
+    return ht_stage_commit(c, &c->dl_tab, need);
 }
 
 ht_status dl_launch(ht_ctx *c, const char *fn, const std::vector<HtDrawDesc> &desc, uint8_t *dst, size_t dstride) {
@@ -93,7 +71,7 @@ ht_status dl_launch(ht_ctx *c, const char *fn, const std::vector<HtDrawDesc> &de
     if (st != HT_OK) return st;
     HtProfScope ps(c, "draw_list");
     const dim3 grid((c->W + IG_TW - 1) / IG_TW, (c->H + IG_TH - 1) / IG_TH, (unsigned)desc.size());
-    hipLaunchKernelGGL(k_draw_list, grid, dim3(IG_NT), 0, c->stream, reinterpret_cast<const DlDesc *>(c->d_dl_tab), dst, dstride, c->W, c->H);
+    hipLaunchKernelGGL(k_draw_list, grid, dim3(IG_NT), 0, c->stream, reinterpret_cast<const DlDesc *>(c->dl_tab.d), dst, dstride, c->W, c->H);
     HT_HIP(c, hipGetLastError());
     return HT_OK;
 }

@@ -173,17 +173,9 @@ extern "C" ht_status ht_draw_frames(ht_ctx *c, const uint8_t *host_rgba, int32_t
 void ht_ingest_free(ht_ctx *c) {  // ht_destroy (the stream has been synchronised)
     if (c->d_ingest_src) (void)hipFree(c->d_ingest_src);
     c->d_ingest_src = nullptr, c->ingest_src_cap = 0;
-    // ht_draw_list_device's descriptor table, its pinned staging slots and their events (ht_draw_list.hip)
-    if (c->d_dl_tab) (void)hipFree(c->d_dl_tab);
-    c->d_dl_tab = nullptr, c->dl_tab_cap = 0;
-    for (int k = 0; k < ht_ctx::HT_DL_STAGE; k++) {
-        if (c->h_dl_tab[k]) (void)hipHostFree(c->h_dl_tab[k]);
-        if (c->ev_dl_tab[k]) (void)hipEventDestroy(c->ev_dl_tab[k]);
-        c->h_dl_tab[k] = nullptr, c->ev_dl_tab[k] = nullptr;
-    }
-    c->dl_stage_next = 0;
-    ht_crop_free(c);  // the face crops' table, records and events (ht_crop.hip)
-    ht_align_free(c);  // the aligned crops' likewise (ht_align.hip)
+    ht_stage_free(&c->dl_tab);  // ht_draw_list_device's descriptor table (ht_draw_list.hip)
+    ht_crop_free(c);  // the face crops' table, records and events (ht_face_calls.hip)
+    ht_align_free(c);  // the aligned crops' likewise
 }
 
 #include "ht_ingest_yuv.hip"  // the same draw for YUV 4:2:0 frames (shares ig_channel and the tile constants)
@@ -192,7 +184,7 @@ void ht_ingest_free(ht_ctx *c) {  // ht_destroy (the stream has been synchronise
 // is host AND device text; ht_cs_pairs.hip, later in this code object, spells HT_CSB_FN with the same tokens
 #define HT_CSB_FN __host__ __device__ inline
 #define HT_CROP_FN __host__ __device__ inline
-#define HT_PATCH_FN __host__ __device__ inline  // ht_patch_plan.h: ht_crop.hip checks a tensor call's format, ht_patch.hip compiles the rule
+#define HT_PATCH_FN __host__ __device__ inline  // ht_patch_plan.h: ht_face_calls.hip checks a tensor call's format, ht_patch.hip compiles the rule
 #include "ht_crop.hip"
 // the aligned crops: the rotated box of each tracker, upright (a kernel of its own: a gather along tilted lines, integer blend)
 #define HT_ALIGN_FN __host__ __device__ inline
@@ -204,3 +196,5 @@ void ht_ingest_free(ht_ctx *c) {  // ht_destroy (the stream has been synchronise
 #define HT_FILTER_FN __host__ __device__ inline
 #include "ht_filter_plan.h"
 #include "ht_filter.hip"
+// the calls of the four files above — one host path for the crop and the align family in all their forms — and their extern "C" entry points
+#include "ht_face_calls.hip"

@@ -79,6 +79,30 @@ struct HtDetectGraph {
 };
 
 // ---------------------------------------------------------------------------------------------------------
+// A call's table on its way to the device: ONE device table and a ring of HT_STAGE_SLOTS pinned slots, each with an event.  A call takes
+// the next slot (waiting for the event behind that slot's previous copy), fills it, and commits: one hipMemcpyAsync on the context's stream
+// and the event behind it.  Copy and kernel are ordered on the stream, so a later call's table cannot reach the device before an earlier
+// call's kernel has read its own.  The draw list, the crop calls, the align calls and the camshift pair calls each have one
+// (ht_stage_reserve / _take / _commit / _free below; the arithmetic is ht_stage_plan.h).
+#include "ht_stage_plan.h"
+struct HtStagedTable {
+    uint8_t *d = nullptr;                  // the device table
+    uint8_t *h[HT_STAGE_SLOTS] = {};       // the pinned slots
+    hipEvent_t ev[HT_STAGE_SLOTS] = {};    // a slot's copy has left it
+    size_t cap = 0;                        // bytes the table and every slot hold
+    int next = 0, taken = 0;               // the slot the next call takes; the slot taken last (what commit copies)
+};
+
+// The buffers of one family of face-patch calls (crop, align): the descriptor table, the records of the last call on the device and in
+// a pinned twin the call copies them to; the event behind that copy is what ht_camshift_*_result waits for
+struct HtFaceCalls {
+    HtStagedTable tab;
+    uint8_t *d_rec = nullptr, *h_rec = nullptr;
+    size_t rec_cap = 0;       // records both hold
+    hipEvent_t ev = nullptr;
+    int n = 0;                // entries of the last call (0: none, or its record copy is not enqueued yet)
+};
+
 struct HtKernelTimer {
     std::string name;
     double ms = 0;
@@ -268,15 +292,9 @@ struct ht_ctx {
     size_t bp_hist_cap = 0, bp_lut_w_cap = 0, bp_lut_px_cap = 0, bp_out_cap = 0;
 
     // camshift on (stream, frame) pairs (ht_cs_pairs.hip): the call's pair table {stream, frame, histogram slot, rect} + list of distinct
-    // frames goes through a small ring of pinned staging buffers into ONE device table (copies and kernels are ordered by the stream);
+    // frames goes through a staged table (HtStagedTable: copies and kernels are ordered by the stream);
     // the chunk histograms of the distinct frames have scratch of their own, grown on demand.  Capacities in elements.
-    static constexpr int HT_CSP_STAGE = 4;
-    int32_t *d_csp_tab = nullptr;
-    size_t csp_tab_cap = 0;
-    int32_t *h_csp_tab[HT_CSP_STAGE] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_csp_tab[HT_CSP_STAGE] = {nullptr, nullptr, nullptr, nullptr};  // the staging buffer's copy has left it
-    size_t h_csp_tab_cap = 0;
-    int csp_stage_next = 0;
+    HtStagedTable csp_tab;
     uint32_t *d_csp_hist = nullptr;  // [distinct frames][chunks][4096]
     size_t csp_hist_cap = 0;
     bool csp_attr_set = false;       // > 64 KB dynamic LDS enabled for k_csp_meanshift on this context's device
@@ -297,33 +315,11 @@ struct ht_ctx {
     // ingest (ht_ingest.hip): device staging of ht_draw_frames' host-resident source frames, grown on demand
     uint8_t *d_ingest_src = nullptr;
     size_t ingest_src_cap = 0;
-    // ht_draw_list_device (ht_draw_list.hip): the descriptor table on the device and the ring of pinned slots a call's table is staged
-    // in; a slot's event is recorded behind its copy, and the slot is written again only after that event (both hold dl_tab_cap bytes)
-    static constexpr int HT_DL_STAGE = 4;
-    uint8_t *d_dl_tab = nullptr, *h_dl_tab[HT_DL_STAGE] = {};
-    hipEvent_t ev_dl_tab[HT_DL_STAGE] = {};
-    size_t dl_tab_cap = 0;
-    int dl_stage_next = 0;
-    // the face crops (ht_crop.hip): a descriptor table and staging ring of their OWN, moved as the draw list's is (a crop call and a draw
-    // call of one step never share a slot or the device table), and the records of the last call: on the device, and in a pinned twin the
-    // call copies them to; the event behind that copy is what ht_camshift_crop_result waits for
-    uint8_t *d_crop_tab = nullptr, *h_crop_tab[HT_DL_STAGE] = {};
-    hipEvent_t ev_crop_tab[HT_DL_STAGE] = {};
-    size_t crop_tab_cap = 0;
-    int crop_stage_next = 0;
-    uint8_t *d_crop_rec = nullptr, *h_crop_rec = nullptr;
-    size_t crop_rec_cap = 0;  // records both hold
-    hipEvent_t ev_crop = nullptr;
-    int crop_n = 0;           // entries of the last call (0: none)
-    // the aligned crops (ht_align.hip): the same again, their OWN — a crop call and an align call of one step share nothing
-    uint8_t *d_align_tab = nullptr, *h_align_tab[HT_DL_STAGE] = {};
-    hipEvent_t ev_align_tab[HT_DL_STAGE] = {};
-    size_t align_tab_cap = 0;
-    int align_stage_next = 0;
-    uint8_t *d_align_rec = nullptr, *h_align_rec = nullptr;
-    size_t align_rec_cap = 0;
-    hipEvent_t ev_align = nullptr;
-    int align_n = 0;
+    // ht_draw_list_device (ht_draw_list.hip): the call's descriptor table
+    HtStagedTable dl_tab;
+    // the face crops (ht_crop.hip) and the aligned crops (ht_align.hip), one host path for both (ht_face_calls.hip): each family has a
+    // descriptor table and the records of its last call of its OWN — a draw call, a crop call and an align call of one step share nothing
+    HtFaceCalls crop, align;
 
     std::vector<std::pair<void *, size_t>> user_allocs;  // ht_device_alloc buffers still alive (pointer, bytes): freed by ht_destroy at the latest
 
@@ -391,6 +387,56 @@ ht_status ht_grow_device(ht_ctx *c, T **p, size_t *cap, size_t need, const char 
     return HT_OK;
 }
 
+// The staged table's four steps.  reserve: the table and its slots hold >= need bytes afterwards (>= minimum when they have to be
+// allocated); a reallocation waits for the work in flight first.  `message`: the HT_ERR_NOMEM text (the table is then empty: cap == 0).
+inline ht_status ht_stage_reserve(ht_ctx *c, HtStagedTable *t, size_t need, size_t minimum, const std::string &message) {
+    const size_t cap = ht_stage_capacity(t->cap, need, minimum);
+    if (cap == t->cap) return HT_OK;
+    HT_HIP(c, hipStreamSynchronize(c->stream));
+    if (t->d) (void)hipFree(t->d);
+    t->d = nullptr, t->cap = 0;
+    for (auto &h : t->h) {
+        if (h) (void)hipHostFree(h);
+        h = nullptr;
+    }
+    bool ok = hipMalloc(reinterpret_cast<void **>(&t->d), cap) == hipSuccess;
+    for (int k = 0; ok && k < HT_STAGE_SLOTS; k++) {
+        ok = hipHostMalloc(reinterpret_cast<void **>(&t->h[k]), cap, hipHostMallocDefault) == hipSuccess;
+        if (ok && !t->ev[k]) ok = hipEventCreateWithFlags(&t->ev[k], hipEventDisableTiming) == hipSuccess;
+    }
+    if (!ok) {
+        (void)hipGetLastError();
+        return ht_fail(c, HT_ERR_NOMEM, message);
+    }
+    t->cap = cap;
+    return HT_OK;
+}
+
+// take: the next pinned slot, for the caller to fill (csp_upload fills it from three pieces); waits until that slot's previous copy has left it
+inline ht_status ht_stage_take(ht_ctx *c, HtStagedTable *t, uint8_t **slot) {
+    t->taken = t->next;
+    t->next = ht_stage_next_slot(t->next);
+    HT_HIP(c, hipEventSynchronize(t->ev[t->taken]));  // never recorded: returns at once
+    *slot = t->h[t->taken];
+    return HT_OK;
+}
+
+// commit: the first `bytes` of the slot taken last go to the device table, behind everything enqueued so far
+inline ht_status ht_stage_commit(ht_ctx *c, HtStagedTable *t, size_t bytes) {
+    HT_HIP(c, hipMemcpyAsync(t->d, t->h[t->taken], bytes, hipMemcpyHostToDevice, c->stream));
+    HT_HIP(c, hipEventRecord(t->ev[t->taken], c->stream));
+    return HT_OK;
+}
+
+inline void ht_stage_free(HtStagedTable *t) {  // the stream has been synchronised
+    if (t->d) (void)hipFree(t->d);
+    for (int k = 0; k < HT_STAGE_SLOTS; k++) {
+        if (t->h[k]) (void)hipHostFree(t->h[k]);
+        if (t->ev[k]) (void)hipEventDestroy(t->ev[k]);
+    }
+    *t = HtStagedTable();
+}
+
 // profiling scope: records a start/stop event pair around kernel launches when ctx->profiling
 struct HtProfScope {
     ht_ctx *ctx;
@@ -426,8 +472,8 @@ void ht_backproject_free(ht_ctx *ctx);                      // ht_backproject.hi
 void ht_cs_pairs_free(ht_ctx *ctx);                         // ht_cs_pairs.hip: pair table, staging and histogram scratch (ht_destroy)
 void ht_cs_best_free(ht_ctx *ctx);                          // ht_cs_best.hip: the result buffers of ht_camshift_init_best (ht_destroy)
 void ht_ingest_free(ht_ctx *ctx);                           // ht_ingest.hip: the host form's source staging, the draw list's table (ht_destroy)
-void ht_align_free(ht_ctx *ctx);                            // ht_align.hip: the aligned crops' table, records and events (called by ht_ingest_free)
-void ht_crop_free(ht_ctx *ctx);                             // ht_crop.hip: the face crops' table, records and events (called by ht_ingest_free)
+void ht_align_free(ht_ctx *ctx);                            // ht_face_calls.hip: the aligned crops' table, records and events (called by ht_ingest_free)
+void ht_crop_free(ht_ctx *ctx);                             // ht_face_calls.hip: the face crops' table, records and events (called by ht_ingest_free)
 void ht_group_free(ht_ctx *ctx);                            // ht_group.hip: the device grouping's buffers (ht_destroy)
 ht_status ht_detect_mark_collected(ht_ctx *ctx, bool wb_snap);  // ht_context.hip: the state every collect call leaves behind
 ht_status ht_frames_own_reserve(ht_ctx *ctx, size_t need, const char *fn);  // ht_context.hip: the context's own frame buffer holds >= need bytes

@@ -1429,9 +1429,9 @@ napi_value DrawListDevice(napi_env env, napi_callback_info info) {
     return nullptr;
 }
 
-// ---- face crops: each tracker's box cut from its feed (ht_camshift_crop_*_device) ---------------------------------------------------------
+// ---- face crops and angle-aligned face crops: each tracker's box cut from its feed (ht_camshift_crop_*_device / ht_camshift_align_*_device) ----
 
-// the arguments both crop forms share behind their lists: Int32Array params [width, height, marginQ8, flags] at argument i, then outDev, outStride,
+// the arguments every launching call shares behind its list: Int32Array params [width, height, marginQ8, flags] at argument i, then outDev, outStride,
 // outOffset = 0, wait = false.  The patch size is checked here because the range handed to the library with the buffer's pointer depends on it;
 // margin and flags are the library's to refuse.
 struct CropOut {
@@ -1485,52 +1485,92 @@ bool get_filter_args(const Args &a, size_t i, const char *usage, int32_t *max_fa
     return true;
 }
 
-// cropPairsDevice, cropPairsTensorDevice (the format object in front of outDev) and cropPairsFilteredDevice (maxFactor and format | null there)
-napi_value crop_pairs_call(napi_env env, napi_callback_info info, int mode) {  // 0: RGBA8, 1: the tensor form, 2: the filtered form
+// The 12 launching calls: family (crop, align) x list (pairs, sources) x mode (0: RGBA8; 1: the tensor form, the format object in front of
+// outDev; 2: the filtered form, maxFactor and format | null there).  ONE pairs call and ONE sources call read the arguments; FaceFns is the
+// table that gives each (family, mode) its C function and that function's name for throw_ht, FACE_USAGE the usage strings.
+template <class F>
+struct Named {
+    F *fn;
+    const char *name;
+};
+#define NAMED(f) {f, #f}
+template <class P>  // the family's params: ht_crop_params or ht_align_params, the same four fields
+struct FaceFns {
+    const char *word;  // the family's word, in front of every usage string
+    Named<ht_status(ht_ctx *, const ht_cs_pair *, int32_t, const P *, void *, size_t)> pairs;
+    Named<ht_status(ht_ctx *, const ht_cs_pair *, int32_t, const P *, const ht_patch_format *, void *, size_t)> pairs_tensor;
+    Named<ht_status(ht_ctx *, const ht_cs_pair *, int32_t, const P *, int32_t, const ht_patch_format *, void *, size_t)> pairs_filtered;
+    Named<ht_status(ht_ctx *, const int32_t *, const ht_draw_source *, int32_t, const P *, void *, size_t)> sources;
+    Named<ht_status(ht_ctx *, const int32_t *, const ht_draw_source *, int32_t, const P *, const ht_patch_format *, void *, size_t)> sources_tensor;
+    Named<ht_status(ht_ctx *, const int32_t *, const ht_draw_source *, int32_t, const P *, int32_t, const ht_patch_format *, void *, size_t)> sources_filtered;
+};
+const FaceFns<ht_crop_params> CROP_FNS = {"crop", NAMED(ht_camshift_crop_pairs_device), NAMED(ht_camshift_crop_pairs_tensor_device), NAMED(ht_camshift_crop_pairs_filtered_device),
+                                          NAMED(ht_camshift_crop_sources_device), NAMED(ht_camshift_crop_sources_tensor_device), NAMED(ht_camshift_crop_sources_filtered_device)};
+const FaceFns<ht_align_params> ALIGN_FNS = {"align", NAMED(ht_camshift_align_pairs_device), NAMED(ht_camshift_align_pairs_tensor_device), NAMED(ht_camshift_align_pairs_filtered_device),
+                                            NAMED(ht_camshift_align_sources_device), NAMED(ht_camshift_align_sources_tensor_device), NAMED(ht_camshift_align_sources_filtered_device)};
+const char *const FACE_USAGE[2][3] = {  // [list: 0 pairs, 1 sources][mode], behind the family's word
+    {"PairsDevice(ctx, Int32Array pairs[2n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)",
+     "PairsTensorDevice(ctx, Int32Array pairs[2n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)",
+     "PairsFilteredDevice(ctx, Int32Array pairs[2n], Int32Array params[4], maxFactor, format | null, outDev, outStride, outOffset = 0, wait = false)"},
+    {"SourcesDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)",
+     "SourcesTensorDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)",
+     "SourcesFilteredDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], maxFactor, format | null, outDev, outStride, outOffset = 0, wait = false)"}};
+
+// what every launching call has behind its list: the params at argument i, the mode's maxFactor and format, then the output
+struct FaceOut {
+    CropOut c;
+    int32_t max_factor = 0;
+    bool has_fmt = false;
+    ht_patch_format fmt;
+    const ht_patch_format *format() const { return has_fmt ? &fmt : nullptr; }
+    template <class P>
+    P params() const {
+        P p;
+        p.out_width = c.prm.out_width, p.out_height = c.prm.out_height, p.margin_q8 = c.prm.margin_q8, p.flags = c.prm.flags;
+        return p;
+    }
+};
+bool get_face_out(const Args &a, size_t i, size_t n, int mode, const char *usage, FaceOut *o) {
     const bool tensor = mode == 1, filtered = mode == 2;
-    const char *usage = filtered ? "cropPairsFilteredDevice(ctx, Int32Array pairs[2n], Int32Array params[4], maxFactor, format | null, outDev, outStride, outOffset = 0, wait = false)"
-                        : tensor ? "cropPairsTensorDevice(ctx, Int32Array pairs[2n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)"
-                               : "cropPairsDevice(ctx, Int32Array pairs[2n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
-    const size_t t = filtered ? 2 : tensor ? 1 : 0;  // arguments between the params and outDev
-    Args a(env, info, 7 + t);
+    o->has_fmt = tensor;
+    if (filtered && !get_filter_args(a, i + 1, usage, &o->max_factor, &o->has_fmt)) return false;
+    if (o->has_fmt && !get_patch_format(a.env, a.argv[i + 1 + (filtered ? 1 : 0)], usage, &o->fmt)) return false;
+    return get_crop_out(a, i, n, usage, &o->c, o->format(), filtered ? 2 : tensor ? 1 : 0);
+}
+
+template <class P>
+napi_value face_pairs_call(napi_env env, napi_callback_info info, const FaceFns<P> &f, int mode) {
+    const std::string usage_s = std::string(f.word) + FACE_USAGE[0][mode];
+    const char *usage = usage_s.c_str();
+    Args a(env, info, 7 + (size_t)mode);  // mode: also the number of arguments between the params and outDev
     Locked L;
     const ht_cs_pair *pairs = nullptr;
     int32_t n = 0;
-    CropOut c;
-    ht_patch_format fmt;
-    if (!a.ctx(5 + t, &L)) return nullptr;
+    FaceOut o;
+    if (!a.ctx(5 + (size_t)mode, &L)) return nullptr;
     if (!get_pairs(env, a.argv[1], &pairs, &n)) return type_error(env, usage);
     if (n > 65535) return range_error(env, (std::string(usage) + ": 1..65535 pairs").c_str());
-    int32_t max_factor = 0;
-    bool has_fmt = tensor;
-    if (filtered && !get_filter_args(a, 3, usage, &max_factor, &has_fmt)) return nullptr;
-    if (has_fmt && !get_patch_format(env, a.argv[3 + (filtered ? 1 : 0)], usage, &fmt)) return nullptr;
-    if (!get_crop_out(a, 2, (size_t)n, usage, &c, has_fmt ? &fmt : nullptr, t)) return nullptr;
-    ht_status st = filtered ? ht_camshift_crop_pairs_filtered_device(L.ctx, pairs, n, &c.prm, max_factor, has_fmt ? &fmt : nullptr, c.out, c.stride)
-                   : tensor ? ht_camshift_crop_pairs_tensor_device(L.ctx, pairs, n, &c.prm, &fmt, c.out, c.stride) : ht_camshift_crop_pairs_device(L.ctx, pairs, n, &c.prm, c.out, c.stride);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, filtered ? "ht_camshift_crop_pairs_filtered_device" : tensor ? "ht_camshift_crop_pairs_tensor_device" : "ht_camshift_crop_pairs_device");
-    if (c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
+    if (!get_face_out(a, 2, (size_t)n, mode, usage, &o)) return nullptr;
+    const P prm = o.template params<P>();
+    ht_status st = mode == 2   ? f.pairs_filtered.fn(L.ctx, pairs, n, &prm, o.max_factor, o.format(), o.c.out, o.c.stride)
+                   : mode == 1 ? f.pairs_tensor.fn(L.ctx, pairs, n, &prm, &o.fmt, o.c.out, o.c.stride)
+                               : f.pairs.fn(L.ctx, pairs, n, &prm, o.c.out, o.c.stride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, mode == 2 ? f.pairs_filtered.name : mode == 1 ? f.pairs_tensor.name : f.pairs.name);
+    if (o.c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
     return nullptr;
 }
 
-napi_value CropPairsDevice(napi_env env, napi_callback_info info) { return crop_pairs_call(env, info, 0); }
-napi_value CropPairsTensorDevice(napi_env env, napi_callback_info info) { return crop_pairs_call(env, info, 1); }
-napi_value CropPairsFilteredDevice(napi_env env, napi_callback_info info) { return crop_pairs_call(env, info, 2); }
-
-napi_value crop_sources_call(napi_env env, napi_callback_info info, int mode) {  // 0: RGBA8, 1: the tensor form, 2: the filtered form
-    const bool tensor = mode == 1, filtered = mode == 2;
-    const char *usage = filtered ? "cropSourcesFilteredDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], maxFactor, format | null, outDev, outStride, outOffset = 0, wait = false)"
-                        : tensor ? "cropSourcesTensorDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)"
-                               : "cropSourcesDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
-    const size_t t = filtered ? 2 : tensor ? 1 : 0;  // arguments between the params and outDev
-    Args a(env, info, 8 + t);
+template <class P>
+napi_value face_sources_call(napi_env env, napi_callback_info info, const FaceFns<P> &f, int mode) {
+    const std::string usage_s = std::string(f.word) + FACE_USAGE[1][mode];
+    const char *usage = usage_s.c_str();
+    Args a(env, info, 8 + (size_t)mode);
     Locked L;
     View streams;
     bool is_array = false;
     uint32_t n = 0;
-    CropOut c;
-    ht_patch_format fmt;
-    if (!a.ctx(6 + t, &L)) return nullptr;
+    FaceOut o;
+    if (!a.ctx(6 + (size_t)mode, &L)) return nullptr;
     if (!a.i32s(1, 0, &streams) || napi_is_array(env, a.argv[2], &is_array) != napi_ok || !is_array || napi_get_array_length(env, a.argv[2], &n) != napi_ok)
         return type_error(env, usage);
     if (n < 1 || n > 65535) return range_error(env, (std::string(usage) + ": 1..65535 entries").c_str());
@@ -1541,22 +1581,29 @@ napi_value crop_sources_call(napi_env env, napi_callback_info info, int mode) { 
         NAPI_OK(napi_get_element(env, a.argv[2], i, &e));
         if (!get_draw_entry(env, e, &srcs[i])) return nullptr;
     }
-    int32_t max_factor = 0;
-    bool has_fmt = tensor;
-    if (filtered && !get_filter_args(a, 4, usage, &max_factor, &has_fmt)) return nullptr;
-    if (has_fmt && !get_patch_format(env, a.argv[4 + (filtered ? 1 : 0)], usage, &fmt)) return nullptr;
-    if (!get_crop_out(a, 3, (size_t)n, usage, &c, has_fmt ? &fmt : nullptr, t)) return nullptr;
-    ht_status st = filtered ? ht_camshift_crop_sources_filtered_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &c.prm, max_factor, has_fmt ? &fmt : nullptr, c.out, c.stride)
-                   : tensor ? ht_camshift_crop_sources_tensor_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &c.prm, &fmt, c.out, c.stride)
-                            : ht_camshift_crop_sources_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &c.prm, c.out, c.stride);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, filtered ? "ht_camshift_crop_sources_filtered_device" : tensor ? "ht_camshift_crop_sources_tensor_device" : "ht_camshift_crop_sources_device");
-    if (c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
+    if (!get_face_out(a, 3, (size_t)n, mode, usage, &o)) return nullptr;
+    const P prm = o.template params<P>();
+    const int32_t *st_ids = streams.as<int32_t>();
+    ht_status st = mode == 2   ? f.sources_filtered.fn(L.ctx, st_ids, srcs.data(), (int32_t)n, &prm, o.max_factor, o.format(), o.c.out, o.c.stride)
+                   : mode == 1 ? f.sources_tensor.fn(L.ctx, st_ids, srcs.data(), (int32_t)n, &prm, &o.fmt, o.c.out, o.c.stride)
+                               : f.sources.fn(L.ctx, st_ids, srcs.data(), (int32_t)n, &prm, o.c.out, o.c.stride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, mode == 2 ? f.sources_filtered.name : mode == 1 ? f.sources_tensor.name : f.sources.name);
+    if (o.c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
     return nullptr;
 }
 
-napi_value CropSourcesDevice(napi_env env, napi_callback_info info) { return crop_sources_call(env, info, 0); }
-napi_value CropSourcesTensorDevice(napi_env env, napi_callback_info info) { return crop_sources_call(env, info, 1); }
-napi_value CropSourcesFilteredDevice(napi_env env, napi_callback_info info) { return crop_sources_call(env, info, 2); }
+napi_value CropPairsDevice(napi_env env, napi_callback_info info) { return face_pairs_call(env, info, CROP_FNS, 0); }
+napi_value CropPairsTensorDevice(napi_env env, napi_callback_info info) { return face_pairs_call(env, info, CROP_FNS, 1); }
+napi_value CropPairsFilteredDevice(napi_env env, napi_callback_info info) { return face_pairs_call(env, info, CROP_FNS, 2); }
+napi_value CropSourcesDevice(napi_env env, napi_callback_info info) { return face_sources_call(env, info, CROP_FNS, 0); }
+napi_value CropSourcesTensorDevice(napi_env env, napi_callback_info info) { return face_sources_call(env, info, CROP_FNS, 1); }
+napi_value CropSourcesFilteredDevice(napi_env env, napi_callback_info info) { return face_sources_call(env, info, CROP_FNS, 2); }
+napi_value AlignPairsDevice(napi_env env, napi_callback_info info) { return face_pairs_call(env, info, ALIGN_FNS, 0); }
+napi_value AlignPairsTensorDevice(napi_env env, napi_callback_info info) { return face_pairs_call(env, info, ALIGN_FNS, 1); }
+napi_value AlignPairsFilteredDevice(napi_env env, napi_callback_info info) { return face_pairs_call(env, info, ALIGN_FNS, 2); }
+napi_value AlignSourcesDevice(napi_env env, napi_callback_info info) { return face_sources_call(env, info, ALIGN_FNS, 0); }
+napi_value AlignSourcesTensorDevice(napi_env env, napi_callback_info info) { return face_sources_call(env, info, ALIGN_FNS, 1); }
+napi_value AlignSourcesFilteredDevice(napi_env env, napi_callback_info info) { return face_sources_call(env, info, ALIGN_FNS, 2); }
 
 // {records: Int32Array [6n] = code, stream, x, y, width, height per entry; ratios: Float64Array [2n] = rx, ry}
 napi_value CropResult(napi_env env, napi_callback_info info) {
@@ -1585,88 +1632,7 @@ napi_value CropResult(napi_env env, napi_callback_info info) {
     return obj;
 }
 
-// ---- angle-aligned face crops: each tracker's rotated box, upright (ht_camshift_align_*_device) -------------------------------------------
-// The arguments are the crop calls', read by the same reader (get_pairs, get_draw_entry, get_crop_out: ht_align_params has ht_crop_params' fields).
-
-ht_align_params align_params(const CropOut &c) {
-    ht_align_params p;
-    p.out_width = c.prm.out_width, p.out_height = c.prm.out_height, p.margin_q8 = c.prm.margin_q8, p.flags = c.prm.flags;
-    return p;
-}
-
-napi_value align_pairs_call(napi_env env, napi_callback_info info, int mode) {  // 0: RGBA8, 1: the tensor form, 2: the filtered form
-    const bool tensor = mode == 1, filtered = mode == 2;
-    const char *usage = filtered ? "alignPairsFilteredDevice(ctx, Int32Array pairs[2n], Int32Array params[4], maxFactor, format | null, outDev, outStride, outOffset = 0, wait = false)"
-                        : tensor ? "alignPairsTensorDevice(ctx, Int32Array pairs[2n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)"
-                               : "alignPairsDevice(ctx, Int32Array pairs[2n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
-    const size_t t = filtered ? 2 : tensor ? 1 : 0;  // arguments between the params and outDev
-    Args a(env, info, 7 + t);
-    Locked L;
-    const ht_cs_pair *pairs = nullptr;
-    int32_t n = 0;
-    CropOut c;
-    ht_patch_format fmt;
-    if (!a.ctx(5 + t, &L)) return nullptr;
-    if (!get_pairs(env, a.argv[1], &pairs, &n)) return type_error(env, usage);
-    if (n > 65535) return range_error(env, (std::string(usage) + ": 1..65535 pairs").c_str());
-    int32_t max_factor = 0;
-    bool has_fmt = tensor;
-    if (filtered && !get_filter_args(a, 3, usage, &max_factor, &has_fmt)) return nullptr;
-    if (has_fmt && !get_patch_format(env, a.argv[3 + (filtered ? 1 : 0)], usage, &fmt)) return nullptr;
-    if (!get_crop_out(a, 2, (size_t)n, usage, &c, has_fmt ? &fmt : nullptr, t)) return nullptr;
-    const ht_align_params prm = align_params(c);
-    ht_status st = filtered ? ht_camshift_align_pairs_filtered_device(L.ctx, pairs, n, &prm, max_factor, has_fmt ? &fmt : nullptr, c.out, c.stride)
-                   : tensor ? ht_camshift_align_pairs_tensor_device(L.ctx, pairs, n, &prm, &fmt, c.out, c.stride) : ht_camshift_align_pairs_device(L.ctx, pairs, n, &prm, c.out, c.stride);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, filtered ? "ht_camshift_align_pairs_filtered_device" : tensor ? "ht_camshift_align_pairs_tensor_device" : "ht_camshift_align_pairs_device");
-    if (c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
-    return nullptr;
-}
-
-napi_value AlignPairsDevice(napi_env env, napi_callback_info info) { return align_pairs_call(env, info, 0); }
-napi_value AlignPairsTensorDevice(napi_env env, napi_callback_info info) { return align_pairs_call(env, info, 1); }
-napi_value AlignPairsFilteredDevice(napi_env env, napi_callback_info info) { return align_pairs_call(env, info, 2); }
-
-napi_value align_sources_call(napi_env env, napi_callback_info info, int mode) {  // 0: RGBA8, 1: the tensor form, 2: the filtered form
-    const bool tensor = mode == 1, filtered = mode == 2;
-    const char *usage = filtered ? "alignSourcesFilteredDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], maxFactor, format | null, outDev, outStride, outOffset = 0, wait = false)"
-                        : tensor ? "alignSourcesTensorDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], format, outDev, outStride, outOffset = 0, wait = false)"
-                               : "alignSourcesDevice(ctx, Int32Array streams[n], entries[n], Int32Array params[4], outDev, outStride, outOffset = 0, wait = false)";
-    const size_t t = filtered ? 2 : tensor ? 1 : 0;  // arguments between the params and outDev
-    Args a(env, info, 8 + t);
-    Locked L;
-    View streams;
-    bool is_array = false;
-    uint32_t n = 0;
-    CropOut c;
-    ht_patch_format fmt;
-    if (!a.ctx(6 + t, &L)) return nullptr;
-    if (!a.i32s(1, 0, &streams) || napi_is_array(env, a.argv[2], &is_array) != napi_ok || !is_array || napi_get_array_length(env, a.argv[2], &n) != napi_ok)
-        return type_error(env, usage);
-    if (n < 1 || n > 65535) return range_error(env, (std::string(usage) + ": 1..65535 entries").c_str());
-    if (streams.len != n) return range_error(env, (std::string(usage) + ": one stream per entry").c_str());
-    std::vector<ht_draw_source> srcs(n);
-    for (uint32_t i = 0; i < n; i++) {  // an entry is drawListDevice's: {dev, offset, width, height, format, matrix, rect}
-        napi_value e;
-        NAPI_OK(napi_get_element(env, a.argv[2], i, &e));
-        if (!get_draw_entry(env, e, &srcs[i])) return nullptr;
-    }
-    int32_t max_factor = 0;
-    bool has_fmt = tensor;
-    if (filtered && !get_filter_args(a, 4, usage, &max_factor, &has_fmt)) return nullptr;
-    if (has_fmt && !get_patch_format(env, a.argv[4 + (filtered ? 1 : 0)], usage, &fmt)) return nullptr;
-    if (!get_crop_out(a, 3, (size_t)n, usage, &c, has_fmt ? &fmt : nullptr, t)) return nullptr;
-    const ht_align_params prm = align_params(c);
-    ht_status st = filtered ? ht_camshift_align_sources_filtered_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &prm, max_factor, has_fmt ? &fmt : nullptr, c.out, c.stride)
-                   : tensor ? ht_camshift_align_sources_tensor_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &prm, &fmt, c.out, c.stride)
-                            : ht_camshift_align_sources_device(L.ctx, streams.as<int32_t>(), srcs.data(), (int32_t)n, &prm, c.out, c.stride);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, filtered ? "ht_camshift_align_sources_filtered_device" : tensor ? "ht_camshift_align_sources_tensor_device" : "ht_camshift_align_sources_device");
-    if (c.wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
-    return nullptr;
-}
-
-napi_value AlignSourcesDevice(napi_env env, napi_callback_info info) { return align_sources_call(env, info, 0); }
-napi_value AlignSourcesTensorDevice(napi_env env, napi_callback_info info) { return align_sources_call(env, info, 1); }
-napi_value AlignSourcesFilteredDevice(napi_env env, napi_callback_info info) { return align_sources_call(env, info, 2); }
+// ---- angle-aligned face crops: each tracker's rotated box, upright (ht_camshift_align_*_device): the launching calls are above -------------
 
 // {records: Int32Array [4n] = code, stream, a12, 0 per entry; terms: Float64Array [6n] = cx, cy, ux, uy, vx, vy in Q16 source pixels
 // (|value| < 2^52: exact in a binary64)}

@@ -1,12 +1,12 @@
 // ht_patch.hip — model-input tensors from face crops: the crop and align calls with another output stage
 // (ht_camshift_crop_pairs_tensor_device / ht_camshift_crop_sources_tensor_device / ht_camshift_align_pairs_tensor_device /
-// ht_camshift_align_sources_tensor_device).
+// ht_camshift_align_sources_tensor_device; the calls themselves are ht_face_calls.hip, the family's one host path).
 //
 // A face embedder, landmark net or liveness net reads planar (or interleaved) floats in its own channel order and normalisation, not
 // RGBA8.  The rule — which bits an RGBA8 patch becomes — is ht_patch_plan.h, host and device text.  The kernels are k_crop_list and
 // k_align_list with the dword store at the end of a pixel replaced by ONE output stage, PtStore::operator()(o, x, y), o the pixel's
-// RGBA8 dword: the sampling bodies are shared as text (ht_ingest_bodies.inc's IG_STORE hook; al_pixels' STORE parameter), so the patch a
-// tensor is made of is the RGBA call's by construction.  Included at the end of ht_ingest.hip, behind ht_align.hip: same code object.
+// RGBA8 dword: the heads and the sampling bodies are shared as text (ht_list_parts.inc; ht_ingest_bodies.inc's IG_STORE hook; al_pixels'
+// STORE parameter), so the patch a tensor is made of is the RGBA call's by construction.  Included at the end of ht_ingest.hip, behind ht_align.hip: same code object.
 //
 // k_cut_tensor<DT> / k_upright_tensor<DT>: grid (tile column, tile row, entry), 64 x 16 patch pixels, 256 threads, four rows per thread —
 // the RGBA kernels' shape; a wavefront is one row of the tile, lane l holds column X0 + l.  The dtype is a template parameter (the element
@@ -72,17 +72,6 @@ struct PtStore {
             }
         }
     }
-
-    // f(0) for this thread's pixels of the tile: an empty entry, in front of the barrier
-    __device__ __forceinline__ void empty_tile() const {
-        const int x = blockIdx.x * IG_TW + (threadIdx.x & (IG_TW - 1)), y0 = blockIdx.y * IG_TH + threadIdx.x / IG_TW;
-        if (x < dw)
-#pragma unroll
-            for (int k = 0; k < IG_RPT; k++) {
-                const int y = y0 + k * (IG_NT / IG_TW);
-                if (y < dh) (*this)(0u, x, y);
-            }
-    }
 };
 
 #undef IG_STORE
@@ -94,47 +83,15 @@ __global__ __launch_bounds__(IG_NT) void k_cut_tensor(const CrDesc *__restrict__
                                                       int dw, int dh, int cw_canvas, int ch_canvas, int margin_q8, uint32_t flags, PtFormat pf,
                                                       ht_crop_record *__restrict__ recs) {
     __shared__ RsTap s_col[IG_TW], s_row[IG_TH];
-    const CrDesc &e = tab[blockIdx.z];
-    const DlDesc &d = e.d;
-    const int format = d.format, stream = e.stream;
-    const HtCsState &st = states[stream];
-    ht_cs_rect rc;
-    const int32_t code = ht_crop_rule(st.x, st.y, st.width, st.height, cw_canvas, ch_canvas, e.SW, e.SH, d.sx, d.sy, d.sw, d.sh, margin_q8, flags, &rc);
-    const int sx = rc.x, sy = rc.y, sw = rc.width, sh = rc.height;
-    const double rx = code == HT_CROP_FACE ? (double)sw / (double)dw : 0.0, ry = code == HT_CROP_FACE ? (double)sh / (double)dh : 0.0;
-    if ((blockIdx.x | blockIdx.y) == 0 && threadIdx.x == 0) {
-        ht_crop_record r;
-        r.code = code, r.stream = stream, r.rect = rc, r.rx = rx, r.ry = ry;
-        recs[blockIdx.z] = r;
-    }
+#define LP_PART 1  // LP_CUT_HEAD
+#include "ht_list_parts.inc"
     const PtStore<DT> store = {dst + (size_t)blockIdx.z * dst_stride, dw, dh, pf};
-    if (code != HT_CROP_FACE) {  // uniform
-        store.empty_tile();
-        return;
-    }
+    if (code != HT_CROP_FACE) return lp_empty_tile<IG_RPT>(store, dw, dh);  // uniform
 #define IG_BODY_PART 1  // IG_BODY_TAPS
 #include "ht_ingest_bodies.inc"
     __syncthreads();
-    if (format == HT_DRAW_RGBA) {
-        const uint8_t *__restrict__ src = (const uint8_t *)d.p0;
-        const size_t src_pitch = d.pitch0, src_stride = 0;
-#define IG_BODY_PART 2  // IG_BODY_RGBA
-#include "ht_ingest_bodies.inc"
-    } else {
-        const uint8_t *__restrict__ yp = (const uint8_t *)d.p0, *__restrict__ up = (const uint8_t *)d.p1, *__restrict__ vp = (const uint8_t *)d.p2;
-        const size_t y_pitch = d.pitch0, c_pitch = d.pitch1, stride = 0;
-        const int cw = d.cw;
-        const HtYuvCoef kc = d.kc;
-        if (format == HT_YUV_FMT_NV12) {
-            constexpr int FMT = HT_YUV_FMT_NV12;
-#define IG_BODY_PART 3  // IG_BODY_YUV
-#include "ht_ingest_bodies.inc"
-        } else {
-            constexpr int FMT = HT_YUV_FMT_I420;
-#define IG_BODY_PART 3  // IG_BODY_YUV
-#include "ht_ingest_bodies.inc"
-        }
-    }
+#define LP_PART 4  // LP_SCAFFOLD
+#include "ht_list_parts.inc"
 }
 
 #undef IG_STORE
@@ -146,37 +103,14 @@ __global__ __launch_bounds__(IG_NT) void k_upright_tensor(const CrDesc *__restri
                                                           int dw, int dh, int cw_canvas, int ch_canvas, int margin_q8, uint32_t flags, PtFormat pf,
                                                           ht_align_record *__restrict__ recs) {
     __shared__ int64_t s_cx[IG_TW], s_cy[IG_TW], s_rx[IG_TH], s_ry[IG_TH];
-    const CrDesc &e = tab[blockIdx.z];
-    const DlDesc &d = e.d;
-    const int format = d.format, stream = e.stream, SW = e.SW, SH = e.SH;
-    const HtCsState &st = states[stream];
-    HtAlignPlan pl;
-    const int32_t code = ht_align_rule(st.x, st.y, st.width, st.height, st.angle, cw_canvas, ch_canvas, SW, SH, d.sx, d.sy, d.sw, d.sh, margin_q8, flags, &pl);
-    if ((blockIdx.x | blockIdx.y) == 0 && threadIdx.x == 0) {
-        ht_align_record r;
-        r.code = code, r.stream = stream, r.a12 = pl.a12, r.pad = 0;
-        r.cx = pl.cx, r.cy = pl.cy, r.ux = pl.ux, r.uy = pl.uy, r.vx = pl.vx, r.vy = pl.vy;
-        recs[blockIdx.z] = r;
-    }
+#define LP_PART 2  // LP_UPRIGHT_HEAD
+#include "ht_list_parts.inc"
     const PtStore<DT> store = {dst + (size_t)blockIdx.z * dst_stride, dw, dh, pf};
-    if (code != HT_ALIGN_FACE) {  // uniform
-        store.empty_tile();
-        return;
-    }
-    const int X0 = blockIdx.x * IG_TW, Y0 = blockIdx.y * IG_TH;
-    if (threadIdx.x < IG_TW) {
-        const int i = min(X0 + (int)threadIdx.x, dw - 1);
-        s_cx[threadIdx.x] = pl.cx - 32768 + ht_align_term(i, dw, pl.ux);
-        s_cy[threadIdx.x] = pl.cy - 32768 + ht_align_term(i, dw, pl.uy);
-    } else if (threadIdx.x < IG_TW + IG_TH) {
-        const int j = min(Y0 + (int)threadIdx.x - IG_TW, dh - 1);
-        s_rx[threadIdx.x - IG_TW] = ht_align_term(j, dh, pl.vx);
-        s_ry[threadIdx.x - IG_TW] = ht_align_term(j, dh, pl.vy);
-    }
+    if (code != HT_ALIGN_FACE) return lp_empty_tile<IG_RPT>(store, dw, dh);  // uniform
+#define LP_PART 3  // LP_UPRIGHT_TERMS
+#include "ht_list_parts.inc"
     __syncthreads();
-    if (format == HT_DRAW_RGBA) al_pixels<HT_DRAW_RGBA>(d, SW, SH, s_cx, s_cy, s_rx, s_ry, store, dw, dh);
-    else if (format == HT_YUV_FMT_NV12) al_pixels<HT_YUV_FMT_NV12>(d, SW, SH, s_cx, s_cy, s_rx, s_ry, store, dw, dh);
-    else al_pixels<HT_YUV_FMT_I420>(d, SW, SH, s_cx, s_cy, s_rx, s_ry, store, dw, dh);
+    AL_PIXELS_ANY(PtStore<DT>, IG_RPT, s_cx, s_cy, s_rx, s_ry, store);
 }
 
 PtFormat pt_format(const ht_patch_format &f) {
@@ -186,38 +120,19 @@ PtFormat pt_format(const ht_patch_format &f) {
     return p;
 }
 
-void pt_launch_cut(ht_ctx *c, dim3 grid, const CrDesc *tab, const HtCsState *states, uint8_t *out, size_t ostride, const ht_crop_params &p, const ht_patch_format &fmt,
-                   ht_crop_record *recs) {
-    const PtFormat pf = pt_format(fmt);
-    auto k = fmt.dtype == HT_PATCH_F32 ? k_cut_tensor<HT_PATCH_F32> : fmt.dtype == HT_PATCH_F16 ? k_cut_tensor<HT_PATCH_F16> : k_cut_tensor<HT_PATCH_BF16>;
-    hipLaunchKernelGGL(k, grid, dim3(IG_NT), 0, c->stream, tab, states, out, ostride, (int)p.out_width, (int)p.out_height, c->W, c->H, (int)p.margin_q8, p.flags, pf, recs);
+// the tensor forms' launches: the RGBA kernels' grid and arguments, the format's floats in front of the records; one kernel per dtype
+template <class REC>
+using PtKernel = void (*)(const CrDesc *, const HtCsState *, uint8_t *, size_t, int, int, int, int, int, uint32_t, PtFormat, REC *);
+
+template <class REC>
+void pt_launch(const FaceLaunch &a, PtKernel<REC> f32, PtKernel<REC> f16, PtKernel<REC> bf16) {
+    PtKernel<REC> k = a.fmt->dtype == HT_PATCH_F32 ? f32 : a.fmt->dtype == HT_PATCH_F16 ? f16 : bf16;
+    hipLaunchKernelGGL(k, a.grid, dim3(IG_NT), 0, a.c->stream, FACE_KARGS(a), pt_format(*a.fmt), static_cast<REC *>(a.recs));
 }
 
-void pt_launch_upright(ht_ctx *c, dim3 grid, const CrDesc *tab, const HtCsState *states, uint8_t *out, size_t ostride, const ht_align_params &p,
-                       const ht_patch_format &fmt, ht_align_record *recs) {
-    const PtFormat pf = pt_format(fmt);
-    auto k = fmt.dtype == HT_PATCH_F32 ? k_upright_tensor<HT_PATCH_F32> : fmt.dtype == HT_PATCH_F16 ? k_upright_tensor<HT_PATCH_F16> : k_upright_tensor<HT_PATCH_BF16>;
-    hipLaunchKernelGGL(k, grid, dim3(IG_NT), 0, c->stream, tab, states, out, ostride, (int)p.out_width, (int)p.out_height, c->W, c->H, (int)p.margin_q8, p.flags, pf, recs);
+void pt_launch_cut(const FaceLaunch &a) { pt_launch<ht_crop_record>(a, k_cut_tensor<HT_PATCH_F32>, k_cut_tensor<HT_PATCH_F16>, k_cut_tensor<HT_PATCH_BF16>); }
+void pt_launch_upright(const FaceLaunch &a) {
+    pt_launch<ht_align_record>(a, k_upright_tensor<HT_PATCH_F32>, k_upright_tensor<HT_PATCH_F16>, k_upright_tensor<HT_PATCH_BF16>);
 }
 
 }  // namespace
-
-extern "C" ht_status ht_camshift_crop_pairs_tensor_device(ht_ctx *c, const ht_cs_pair *pairs, int32_t n, const ht_crop_params *params, const ht_patch_format *format,
-                                                          void *out_dev, size_t out_stride) {
-    return crop_pairs(c, "ht_camshift_crop_pairs_tensor_device", pairs, n, params, true, format, out_dev, out_stride);
-}
-
-extern "C" ht_status ht_camshift_crop_sources_tensor_device(ht_ctx *c, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_crop_params *params,
-                                                            const ht_patch_format *format, void *out_dev, size_t out_stride) {
-    return crop_sources(c, "ht_camshift_crop_sources_tensor_device", streams, srcs, n, params, true, format, out_dev, out_stride);
-}
-
-extern "C" ht_status ht_camshift_align_pairs_tensor_device(ht_ctx *c, const ht_cs_pair *pairs, int32_t n, const ht_align_params *params, const ht_patch_format *format,
-                                                           void *out_dev, size_t out_stride) {
-    return align_pairs(c, "ht_camshift_align_pairs_tensor_device", pairs, n, params, true, format, out_dev, out_stride);
-}
-
-extern "C" ht_status ht_camshift_align_sources_tensor_device(ht_ctx *c, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_align_params *params,
-                                                             const ht_patch_format *format, void *out_dev, size_t out_stride) {
-    return align_sources(c, "ht_camshift_align_sources_tensor_device", streams, srcs, n, params, true, format, out_dev, out_stride);
-}

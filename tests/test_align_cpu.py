@@ -369,9 +369,13 @@ def test_align_kernel_fits_its_budget_and_lives_in_the_ingest_code_object():
     assert len(objs) == 4
     home = [o for o in objs if b"k_align_list" in o]
     assert len(home) == 1 and b"k_draw_list" in home[0] and b"k_crop_list" in home[0]
-    text = {f: open(os.path.join(CSRC, f)).read() for f in ("ht_ingest.hip", "ht_align.hip", "ht_align_plan.h")}
+    family = ("ht_crop.hip", "ht_align.hip", "ht_patch.hip", "ht_filter.hip", "ht_face_calls.hip", "ht_list_parts.inc")
+    text = {f: open(os.path.join(CSRC, f)).read() for f in ("ht_ingest.hip", "ht_align_plan.h") + family}
+    whole = "".join(text[f] for f in family)
     assert text["ht_ingest.hip"].index('#include "ht_crop.hip"') < text["ht_ingest.hip"].index('#include "ht_align.hip"')
-    assert "ht_align_rule(" in text["ht_align.hip"] and "ht_draw_list_plan_entry(" in text["ht_align.hip"]  # the draw list's plan is asked, not restated
+    assert whole.count("ht_align_rule(") == 1 and "ht_align_rule(" in text["ht_list_parts.inc"] and whole.count("#define LP_PART 2  // LP_UPRIGHT_HEAD") == 3  # the upright head, once
+    assert whole.count("ht_draw_list_plan_entry(") == 1 and "ht_draw_list_plan_entry(" in text["ht_face_calls.hip"]  # the draw list's plan is asked, not restated: once for both families
+    assert "_reserve(" not in text["ht_align.hip"] and "extern" not in text["ht_align.hip"] and "hipMalloc" not in text["ht_align.hip"]  # no copy of the crop calls' host path
     plan = text["ht_align_plan.h"]
     assert "hip/" not in plan and "__global__" not in plan and "<math" not in plan and "<cmath" not in plan and plan.count("ht_csb_floor_i32(") == 5  # five floors
     body = plan.split("HT_ALIGN_FN int32_t ht_align_rule(")[1].split(") {", 1)[1].split("\n}\n", 1)[0]
@@ -433,7 +437,7 @@ def test_shim_passes_arguments_to_the_c_abi_and_refuses_malformed_calls(tmp_path
         assert thrown[what].startswith(kind + ": "), (what, thrown[what])
     napi = open(os.path.join(CSRC, "ht_napi.cc")).read()
     assert {"alignPairsDevice", "alignSourcesDevice", "alignResult"} <= set(re.findall(r'\{"(\w+)",\s*\w+\}', napi)) and '{"ALIGN_SQUARE", HT_ALIGN_SQUARE}' in napi
-    assert napi.count("get_crop_out(a, ") == 4 and napi.count("get_draw_entry(env, e, &srcs[i])") >= 2  # the one argument reader and range check, not a second one
+    assert napi.count("get_crop_out(a, ") == 1 and napi.count("get_draw_entry(env, e, &srcs[i])") == 2  # the one argument reader and range check, read in ONE place for every launching call
 
 
 # ---- the JavaScript facade on the mock addon ----------------------------------------------------------------------------------------------------

@@ -233,10 +233,19 @@ def test_crop_kernel_fits_its_budget_and_shares_the_text_of_the_draw_kernels():
     assert len(objs) == 4
     home = [o for o in objs if b"k_crop_list" in o]
     assert len(home) == 1 and b"k_draw_list" in home[0] and b"k_draw_frames" in home[0]
-    text = {f: open(os.path.join(CSRC, f)).read() for f in ("ht_ingest.hip", "ht_crop.hip", "ht_crop_plan.h", "ht_ingest_bodies.inc")}
-    assert '#include "ht_crop.hip"' in text["ht_ingest.hip"] and text["ht_crop.hip"].count('#include "ht_ingest_bodies.inc"') == 4
-    assert "rs_tap(" not in text["ht_crop.hip"] and "ig_channel(" not in text["ht_crop.hip"] and "ht_crop_rule(" in text["ht_crop.hip"]
-    assert "ht_draw_list_plan_entry(" in text["ht_crop.hip"]  # an entry's rules are asked of the draw list's plan, not restated
+    family = ("ht_crop.hip", "ht_align.hip", "ht_patch.hip", "ht_filter.hip", "ht_face_calls.hip", "ht_list_parts.inc")  # the face-patch calls' kernels, their one host path and the text the kernels share
+    text = {f: open(os.path.join(CSRC, f)).read() for f in ("ht_ingest.hip", "ht_crop_plan.h", "ht_ingest_bodies.inc") + family}
+    whole = "".join(text[f] for f in family)
+    assert '#include "ht_crop.hip"' in text["ht_ingest.hip"] and text["ht_ingest.hip"].index('#include "ht_filter.hip"') < text["ht_ingest.hip"].index('#include "ht_face_calls.hip"')
+    # the pixel bodies are ht_ingest_bodies.inc's text: the ONE format scaffold includes its three bodies, and the only other includes are the
+    # taps of the two kernels with the draw list's tile
+    assert text["ht_list_parts.inc"].count('#include "ht_ingest_bodies.inc"') == 3 and whole.count('#include "ht_ingest_bodies.inc"') == 3 + 2
+    assert text["ht_crop.hip"].count('#include "ht_ingest_bodies.inc"') == 1 and whole.count("#define LP_PART 4  // LP_SCAFFOLD") == 3
+    assert "ig_channel(" not in whole and whole.count("rs_tap(") == text["ht_filter.hip"].count("rs_tap(") == 2  # the fine patch's taps, as before
+    assert whole.count("ht_crop_rule(") == 1 and "ht_crop_rule(" in text["ht_list_parts.inc"]  # the cut head, written once
+    assert whole.count("#define LP_PART 1  // LP_CUT_HEAD") == 3
+    # an entry's rules are asked of the draw list's plan, not restated: once, in the family's one host path
+    assert whole.count("ht_draw_list_plan_entry(") == 1 and "ht_draw_list_plan_entry(" in text["ht_face_calls.hip"]
     assert "hip/" not in text["ht_crop_plan.h"] and "__global__" not in text["ht_crop_plan.h"] and "ht_csb_floor_i32(" in text["ht_crop_plan.h"]
     assert "double" not in text["ht_crop_plan.h"].split("HT_CROP_FN int32_t ht_crop_rule(")[1].split(") {", 1)[1]  # integer-only behind the four floors
 

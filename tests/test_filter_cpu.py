@@ -381,11 +381,17 @@ def test_filter_kernels_fit_their_budget_and_live_with_the_draw_kernels():
     assert len(objs) == 4
     home = [o for o in objs if b"k_cut_mean" in o]
     assert len(home) == 1 and b"k_upright_mean" in home[0] and b"k_draw_list" in home[0] and b"k_crop_list" in home[0]
-    text = {f: open(os.path.join(CSRC, f)).read() for f in ("ht_ingest.hip", "ht_filter.hip", "ht_filter_plan.h", "ht_crop.hip", "ht_patch.hip", "ht_ingest_bodies.inc")}
+    family = ("ht_crop.hip", "ht_align.hip", "ht_patch.hip", "ht_filter.hip", "ht_face_calls.hip", "ht_list_parts.inc")
+    text = {f: open(os.path.join(CSRC, f)).read() for f in ("ht_ingest.hip", "ht_filter_plan.h", "ht_ingest_bodies.inc") + family}
+    whole = "".join(text[f] for f in family)
     assert text["ht_ingest.hip"].index('#include "ht_patch.hip"') < text["ht_ingest.hip"].index('#include "ht_filter.hip"')
-    assert text["ht_filter.hip"].count('#include "ht_ingest_bodies.inc"') == 3 and text["ht_filter.hip"].count("al_pixels<") == 3
-    assert "ht_crop_rule(" in text["ht_filter.hip"] and "ht_align_rule(" in text["ht_filter.hip"] and "ig_channel(" not in text["ht_filter.hip"]
-    assert text["ht_crop.hip"].count('#include "ht_ingest_bodies.inc"') == 4 and text["ht_patch.hip"].count('#include "ht_ingest_bodies.inc"') == 4
+    # the pixel bodies are the siblings' text: the mean kernels include no body themselves, they take the ONE scaffold (with their loops over
+    # the fine slices in front of each body) and the ONE al_pixels dispatch, behind the ONE cut head and the ONE upright head
+    assert text["ht_filter.hip"].count('#include "ht_ingest_bodies.inc"') == 0 and text["ht_filter.hip"].count("#define LP_PART 4  // LP_SCAFFOLD") == 1
+    assert text["ht_filter.hip"].count("#define LP_EACH_PASS") == 1 and text["ht_filter.hip"].count("AL_PIXELS_ANY(") == 1 and whole.count("al_pixels<") == 3
+    assert text["ht_filter.hip"].count("#define LP_PART 1  // LP_CUT_HEAD") == 1 and text["ht_filter.hip"].count("#define LP_PART 2  // LP_UPRIGHT_HEAD") == 1
+    assert whole.count("ht_crop_rule(") == 1 and whole.count("ht_align_rule(") == 1 and "ig_channel(" not in whole
+    assert text["ht_list_parts.inc"].count('#include "ht_ingest_bodies.inc"') == 3 and whole.count('#include "ht_ingest_bodies.inc"') == 3 + 2
     assert text["ht_ingest_bodies.inc"].count("        IG_STORE(o, x, Y0 + ") == 2
     plan = text["ht_filter_plan.h"]
     assert "hip/" not in plan and "__global__" not in plan and "double" not in plan and "float" not in plan  # integers only
@@ -450,7 +456,7 @@ def test_shim_passes_max_factor_and_the_format_to_the_c_abi_and_refuses_malforme
     napi = open(os.path.join(CSRC, "ht_napi.cc")).read()
     assert {"cropPairsFilteredDevice", "cropSourcesFilteredDevice", "alignPairsFilteredDevice", "alignSourcesFilteredDevice", "cropFilterFactors", "alignFilterFactors"} <= set(
         re.findall(r'\{"(\w+)",\s*\w+\}', napi))
-    assert napi.count("get_crop_out(a, ") == 4 and napi.count("get_patch_format(env, ") == 4 and napi.count("get_filter_args(a, ") == 4  # the one reader and range check: no second one
+    assert napi.count("get_crop_out(a, ") == 1 and napi.count("get_patch_format(a.env, ") == 1 and napi.count("get_filter_args(a, ") == 1  # the one reader and range check: no second one, and ONE place that calls them
 
 
 # ---- the JavaScript facade on the mock addon ----------------------------------------------------------------------------------------------------

@@ -280,12 +280,21 @@ def test_tensor_kernels_have_no_spills_and_no_scratch_and_share_the_sampling_tex
     objs = _gfx950_code_objects(build.LIB)
     home = [o for o in objs if b"k_cut_tensor" in o]
     assert len(objs) == 4 and len(home) == 1 and b"k_crop_list" in home[0] and b"k_upright_tensor" in home[0] and b"k_align_list" in home[0]
-    text = {f: open(os.path.join(CSRC, f)).read() for f in ("ht_ingest.hip", "ht_patch.hip", "ht_patch_plan.h", "ht_ingest_bodies.inc", "ht_align.hip", "ht_pyramid.hip", "ht_gray.h", "ht_crop.hip")}
+    family = ("ht_crop.hip", "ht_align.hip", "ht_patch.hip", "ht_filter.hip", "ht_face_calls.hip", "ht_list_parts.inc")
+    text = {f: open(os.path.join(CSRC, f)).read() for f in ("ht_ingest.hip", "ht_patch_plan.h", "ht_ingest_bodies.inc", "ht_pyramid.hip", "ht_gray.h") + family}
+    whole = "".join(text[f] for f in family)
     assert text["ht_ingest.hip"].index('#include "ht_align.hip"') < text["ht_ingest.hip"].index('#include "ht_patch.hip"')
     assert text["ht_ingest_bodies.inc"].count("        IG_STORE(o, x, Y0 + ") == 2 and "out[(size_t)(Y0" not in text["ht_ingest_bodies.inc"]
-    assert text["ht_patch.hip"].count('#include "ht_ingest_bodies.inc"') == 4 and text["ht_patch.hip"].count("al_pixels<") == 3 and "ht_crop_rule(" in text["ht_patch.hip"]
+    # the tensor kernels compile the RGBA kernels' text: the cut head with the ONE crop rule, the ONE format scaffold around the pixel bodies
+    # (this file's only other include of them is the taps), the upright head and the ONE al_pixels dispatch
+    assert whole.count("ht_crop_rule(") == 1 and text["ht_list_parts.inc"].count('#include "ht_ingest_bodies.inc"') == 3 and text["ht_patch.hip"].count('#include "ht_ingest_bodies.inc"') == 1
+    assert text["ht_patch.hip"].count("#define LP_PART 1  // LP_CUT_HEAD") == 1 and text["ht_patch.hip"].count("#define LP_PART 4  // LP_SCAFFOLD") == 1
+    assert text["ht_patch.hip"].count("#define LP_PART 2  // LP_UPRIGHT_HEAD") == 1 and text["ht_patch.hip"].count("AL_PIXELS_ANY(") == 1
+    assert whole.count("al_pixels<") == text["ht_align.hip"].count("al_pixels<") == 3 and whole.count("#define AL_PIXELS_ANY(") == 1
     assert "store(o, x, y);" in text["ht_align.hip"] and "ht_gray_of(px)" in text["ht_pyramid.hip"] and "__dmul_rn" not in text["ht_pyramid.hip"].split("k_gray_linear")[0].split("xcd_item")[1]
-    assert "ht_patch_check_format(" in text["ht_crop.hip"] and text["ht_patch.hip"].count("crop_check(") == 0  # the checks are the crop calls' own
+    # the checks are the crop calls' own: ONE check of a call, ONE check of a format, in the family's one host path
+    assert whole.count("ht_patch_check_format(") == 1 and "ht_patch_check_format(" in text["ht_face_calls.hip"] and whole.count("ht_status face_check(") == 1
+    assert "_check(" not in text["ht_patch.hip"] and "extern" not in text["ht_patch.hip"]
     plan = text["ht_patch_plan.h"]
     assert "hip/" not in plan and "__global__" not in plan and "<math" not in plan and "<cmath" not in plan
 
@@ -389,7 +398,7 @@ def test_shim_passes_the_format_to_the_c_abi_and_refuses_malformed_calls(tmp_pat
         assert f"{sym}: status -1" in thrown[f"{n}: the library refuses"]
     napi = open(os.path.join(CSRC, "ht_napi.cc")).read()
     assert {"cropPairsTensorDevice", "cropSourcesTensorDevice", "alignPairsTensorDevice", "alignSourcesTensorDevice"} <= set(re.findall(r'\{"(\w+)",\s*\w+\}', napi))
-    assert napi.count("get_crop_out(a, ") == 4 and napi.count("get_patch_format(env, ") == 4  # the one argument reader and range check, one format reader
+    assert napi.count("get_crop_out(a, ") == 1 and napi.count("get_patch_format(a.env, ") == 1 and "get_patch_format(env, " not in napi  # the one argument reader and range check, one format reader, each called in ONE place
 
 
 # ---- the JavaScript facade on the mock addon ----------------------------------------------------------------------------------------------------
