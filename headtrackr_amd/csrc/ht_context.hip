@@ -704,18 +704,24 @@ static unsigned long long *wb_standalone_region(ht_ctx *c) {
     return reinterpret_cast<unsigned long long *>(c->d_scratch) + 4 * (size_t)std::max(c->max_batch, 1);
 }
 
-// the stream work of one detect batch: counters, (whitebalance sums,) gray, pyramid generations, cascade scan
-static ht_status detect_enqueue_body(ht_ctx *c, uint32_t flags) {
+// What a detect batch counts in, zeroed on the stream in front of its kernels: counters, (stage statistics, whitebalance sums).  Always
+// enqueued plainly, NEVER captured: a memset node of a captured sequence was replayed with a garbage fill value once other work had gone
+// through the process — a context's replay returned nhits = 0x682aa5da for 1517 hits after another context had merely been created, while
+// its plain launches counted right (LABLOG 2026-10-20).  The kernels' arguments belong to the graph; the fill pattern of a memset node does not.
+static ht_status detect_enqueue_zero(ht_ctx *c, uint32_t flags) {
     HT_HIP(c, hipMemsetAsync(c->d_counters, 0, sizeof(HtCounters), c->stream));
-    c->early_launched = false;
     if (flags & HT_SCAN_STATS) HT_HIP(c, hipMemsetAsync(c->d_stats, 0, sizeof(unsigned long long) * 64 * HT_STAT_SHARDS, c->stream));
+    if (flags & HT_DETECT_WHITEBALANCE) HT_HIP(c, hipMemsetAsync(c->d_scratch, 0, sizeof(unsigned long long) * 4 * (size_t)c->nframes, c->stream));
+    return HT_OK;
+}
+
+// the kernels of one detect batch behind detect_enqueue_zero: gray (with the whitebalance sums), pyramid generations, cascade scan
+static ht_status detect_enqueue_body(ht_ctx *c, uint32_t flags) {
+    c->early_launched = false;
     ht_status st;
     c->wb_fused = false;
     const bool wb = (flags & HT_DETECT_WHITEBALANCE) != 0;
-    if (wb) {  // channel sums ride along with the gray pass (no second read of the frames)
-        HT_HIP(c, hipMemsetAsync(c->d_scratch, 0, sizeof(unsigned long long) * 4 * (size_t)c->nframes, c->stream));
-        c->wb_fused = (c->W & 3) == 0;  // the linear gray kernel carries the sums; odd widths take the separate pass below
-    }
+    if (wb) c->wb_fused = (c->W & 3) == 0;  // the linear gray kernel carries the channel sums (no second read of the frames); odd widths take the separate pass below
     st = ht_launch_pyramid(c, flags);
     c->wb_fused = false;
     if (st != HT_OK) return st;
@@ -745,6 +751,7 @@ extern "C" ht_status ht_detect_enqueue(ht_ctx *c, uint32_t flags) {
     // one always runs plainly (it also sets the function attributes a capture must not).
     const bool graph_ok = c->graph_max_frames > 0 && c->nframes <= c->graph_max_frames && c->own_stream && !c->profiling && !c->early_scan &&
                           !(flags & HT_SCAN_STATS);
+    if ((st = detect_enqueue_zero(c, flags)) != HT_OK) return st;  // in front of the capture, the replay and the plain launches alike
     bool done = false;
     if (graph_ok) {
         HtDetectGraph *g = nullptr;

@@ -2,7 +2,10 @@
 tests/cs_cases.py.  Every list is built from seeds and small formulas here; what a case must return always comes from the CPU oracle
 (oracle.ht_oracle: hits_to_rects, group) — expected() below is the only judge, and tests/test_group_cases_cpu.py proves from the oracle
 alone that every case reaches the state it is named after.  All confidences are finite and all (frame, scale, q, y, x) keys distinct:
-that is what the scan emits."""
+that is what the scan emits.  The second half of cases() fills k_grp_frames<1024>'s workgroup (511 .. 1024 hits on a frame: many
+components, one long class, paths across wavefronts), launches it with 128 .. 512 threads, goes over the default cap and takes the
+bucket kernel's frame loop through three passes; cap_of / over_cap_frames restate the cap rule, and SCAN_BATCHES are real frames whose
+scan crowds one frame with 755 and 1473 raw hits."""
 import functools
 
 import numpy as np
@@ -90,6 +93,61 @@ def _concat(parts):
 
 SIZES = (0, 1, 63, 64, 65, 256, 257)
 
+# ---- the full-workgroup regimes: k_grp_frames<1024> near and at 1024 live threads, launched with 128 .. 1024 threads, frames over the
+# default cap, and batches the bucket kernel's frame loop needs more than one pass for ------------------------------------------------------
+WIDE = dict(w=1920, h=1080)  # a canvas the clustered() blobs do not fill: dozens of components per frame
+FULL_WIDE_SIZES = (511, 512, 513, 1023, 1024)
+FULL_DENSE_SIZES = (1024, 700)  # on the 320x240 default: one class takes most of the frame
+CHAIN_SIZES = (65, 200, 513, 1024)
+TWO_CHAINS = (500, 524)
+OVER_DEFAULT_SIZES = (1024, 1025, 1500, 9)
+CAPS_SIZES = (64, 65, 128, 129, 256, 257, 512, 513)
+CAPS_OPTIONS = (128, 256, 512, 300)  # 300 clamps to 256
+BUCKET_PASS = 1024  # frames k_grp_bucket scans per pass of its f0 loop
+FRAMES_SPECIAL = {1023: 65, 1024: 70}  # hits on the frames either side of the first pass boundary
+SEED_FULL = 20261020
+
+CAP_MIN, CAP_MAX = 64, 1024
+
+
+def cap_of(options):
+    """the per-frame cap of a context with these options (ht_grp_cap restated): the largest power of two <= group_cap=N, clamped to
+    [64, 1024]; 1024 without the option"""
+    n = None
+    for item in (options or "").split(","):
+        key, _, value = item.partition("=")
+        if key.strip() == "group_cap":
+            n = int(value)
+    if n is None or n >= CAP_MAX:
+        return CAP_MAX
+    cap = CAP_MIN
+    while cap * 2 <= n:
+        cap *= 2
+    return cap
+
+
+def frame_counts(name):
+    c = cases()[name]
+    return np.bincount(c["hits"]["frame"].astype(np.int64), minlength=c["nframes"])
+
+
+def over_cap_frames(name, options=Ellipsis):
+    """frames of a case with more hits than the cap (of its own options, or of the ones given): the ones the collect call finishes on the
+    host"""
+    return int((frame_counts(name) > cap_of(cases()[name]["options"] if options is Ellipsis else options)).sum())
+
+
+def _sparse_frames(rng, nframes, special):
+    """0-3 hits on most frames, whole runs of empty frames, `special` (frame -> hits) on top"""
+    parts = []
+    for f in range(nframes):
+        if f in special:
+            n = special[f]
+        else:
+            n = 0 if (f // 37) % 5 == 3 else int(rng.integers(0, 4))  # every fifth run of 37 frames stays empty
+        parts.append(clustered(rng, f, n))
+    return _concat(parts)
+
 
 @functools.lru_cache(maxsize=None)
 def cases():
@@ -112,6 +170,22 @@ def cases():
     add("last_of_257_only", clustered(rng, 256, 25), 257, (1,))
     add("empty", np.zeros(0, dtype=HIT), 2, (0, 1))
     add("overflow", _concat([clustered(rng, 0, 64), clustered(rng, 1, 65), clustered(rng, 2, 9)]), 3, (0, 1, 2), options="group_cap=64")
+    # a generator of their own: the cases above keep their bytes
+    rng = np.random.default_rng(SEED_FULL)
+    add("full_wide", _concat([clustered(rng, f, n, **WIDE) for f, n in enumerate(FULL_WIDE_SIZES)]), len(FULL_WIDE_SIZES), (0, 1, 2, 3))
+    add("full_dense", _concat([clustered(rng, f, n) for f, n in enumerate(FULL_DENSE_SIZES)]), len(FULL_DENSE_SIZES), (1, 3))
+    add("chains", _concat([chain_hits(f, n) for f, n in enumerate(CHAIN_SIZES)]), len(CHAIN_SIZES), (1, 2))
+    second = chain_hits(0, TWO_CHAINS[1])
+    second["y"] = 40
+    add("two_chains", _concat([chain_hits(0, TWO_CHAINS[0]), second]), 1, (1, 2))
+    add("over_default_cap", _concat([clustered(rng, f, n, **WIDE) for f, n in enumerate(OVER_DEFAULT_SIZES)]), len(OVER_DEFAULT_SIZES), (0, 1, 2))
+    caps = _shuffled(_concat([clustered(rng, f, n, **WIDE) for f, n in enumerate(CAPS_SIZES)]), 7)  # ONE hit list under four caps
+    for cap in CAPS_OPTIONS:
+        add("caps_%d" % cap, caps, len(CAPS_SIZES), (1,), options="group_cap=%d" % cap, shuffle=False)
+    # (frame 1024 is frames_1025's last frame: the second pass's only frame carries the 70 hits)
+    add("frames_1025", _sparse_frames(rng, 1025, FRAMES_SPECIAL), 1025, (1,))
+    add("frames_2500", _sparse_frames(rng, 2500, {**FRAMES_SPECIAL, 2300: 200, 2499: 30}), 2500, (1,))
+    add("last_of_2500_only", clustered(rng, 2499, 25), 2500, (1,))
     return out
 
 
@@ -143,10 +217,15 @@ def select_best(grouped):
 def expected(name, min_neighbors):
     """(best [nframes], grouped lists back to back in frame order, ngrouped [nframes]) from the oracle; computed once per (case, min_neighbors)"""
     c = cases()[name]
-    best = np.zeros(c["nframes"], dtype=ho.RECT_DTYPE)
-    lists, ng = [], np.zeros(c["nframes"], dtype=np.uint32)
-    for f in range(c["nframes"]):
-        seq = frame_seq(c["hits"], f)
+    return oracle_result(c["hits"], c["nframes"], min_neighbors)
+
+
+def oracle_result(hits, nframes, min_neighbors):
+    """expected() of any hit list"""
+    best = np.zeros(nframes, dtype=ho.RECT_DTYPE)
+    lists, ng = [], np.zeros(nframes, dtype=np.uint32)
+    for f in range(nframes):
+        seq = frame_seq(hits, f)
         g = ho.group(seq, min_neighbors) if (min_neighbors > 0 and len(seq)) else seq
         best[f] = select_best(g)
         ng[f] = len(g)
@@ -160,6 +239,59 @@ def expected(name, min_neighbors):
 def similar(seq, i, j):
     """are seq rects i and j joined by the reference (ccv.js:252-261, either direction)?  Asked of the oracle: a pair groups into one rect"""
     return len(ho.group(seq[[i, j]], 1)) == 1
+
+
+# ---- real frames whose scan crowds one frame: hundreds of hits to a frame, in the scan's atomic order from many workgroups ------------------
+
+
+def tiled_gen(w, h):
+    """48-pixel faces 56 pixels apart all over a w x h canvas"""
+    return {"family": "face", "faces": [[x, y, 48] for y in range(2, h - 48, 56) for x in range(2, w - 48, 56)]}
+
+
+SCAN_BATCHES = {
+    # frames 0 and 3 fill a k_grp_frames<1024> workgroup more than half (512 < raw <= 1024), frame 1 has one face, frame 2 none
+    "full_640x480": (640, 480, ("tiled", ("face", 200, 120, 120), ("noise", 77), "tiled")),
+    # frame 0 is over the default cap (raw > 1024): finished on the host behind a real scan
+    "over_960x540": (960, 540, ("tiled", ("face", 400, 200, 144))),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def scan_frames(batch):
+    from headtrackr_amd import synth
+
+    w, h, spec = SCAN_BATCHES[batch]
+    out = []
+    for s in spec:
+        if s == "tiled":
+            out.append(synth.make(tiled_gen(w, h), w, h))
+        elif s[0] == "face":
+            out.append(synth.face_frame(w, h, [s[1:]]))
+        else:
+            out.append(synth.noise_frame(w, h, s[1]))
+    out = np.ascontiguousarray(np.stack(out))
+    out.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def scan_raw(batch, cascade_blob):
+    """the oracle's raw hits per frame (interval 5); computed once"""
+    raw = tuple(ho.detect_raw(f, cascade_blob) for f in scan_frames(batch))
+    for r in raw:
+        r.setflags(write=False)
+    return raw
+
+
+@functools.lru_cache(maxsize=None)
+def scan_expected(batch, cascade_blob, min_neighbors):
+    """(best [nframes], grouped list per frame) of a scan batch from the oracle's detect_objects; computed once"""
+    lists = tuple(ho.detect_objects(f, cascade_blob, 5, min_neighbors) for f in scan_frames(batch))
+    best = np.array([select_best(g) for g in lists], dtype=ho.RECT_DTYPE)
+    for a in lists + (best,):
+        a.setflags(write=False)
+    return best, lists
 
 
 # ---- the JavaScript layer's job (tests/js/group_cpu.js on the mock addon, tests/js/group_gpu.js on the product addon) -----------------

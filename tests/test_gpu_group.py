@@ -1,6 +1,8 @@
 """The device grouping (ht_group.hip: ht_detect_best_enqueue / _collect / _collect_requeue, ht_detect_grouped,
 ht_detect_best_records_device, ht_group_hits) against the reference's recorded vectors, the CPU oracle and the host route.  Everything is
-compared byte for byte: grouped rects, best faces, the 64-byte records."""
+compared byte for byte: grouped rects, best faces, the 64-byte records.  The regimes of the per-frame kernel all run here: one wavefront,
+a full 1024-thread workgroup (synthetic and behind a real scan), the same template at 128 / 256 / 512 threads (group_cap), frames over
+the default cap finished on the host, and batches of more than 1024 frames through the bucket kernel's frame loop."""
 import ctypes as C
 import functools
 import json
@@ -163,8 +165,37 @@ def test_synthetic_case_through_group_hits(ctx_for, name, mn):
     assert np.array_equal(ng, wng), (ng, wng)
     assert grouped.tobytes() == wgrouped.tobytes()
     assert best.tobytes() == wbest.tobytes()
-    # the status word: only `overflow` has a frame above its context's cap (65 hits under group_cap=64), finished on the host
-    assert _over_cap_frames(c) == (1 if name == "overflow" else 0)
+    # the status words: exactly the frames with more hits than the context's cap are finished on the host
+    assert _over_cap_frames(c) == gc.over_cap_frames(name)
+
+
+def test_every_cap_route_returns_the_same_bytes(ctx, ctx_for):
+    """one hit list (frames of 64 .. 513 hits) on a default context and under group_cap=128, 256, 512 and 300 (k_grp_frames<1024> launched
+    with 128, 256, 512 and 256 threads): the frames above each cap go to the host, every route returns the oracle's bytes"""
+    case = gc.cases()["caps_128"]
+    want = gc.expected("caps_128", 1)
+    over = []
+    for options in (None, "group_cap=128", "group_cap=256", "group_cap=512", "group_cap=300"):
+        c = ctx if options is None else ctx_for(options)
+        _over_cap_frames(c)
+        best, grouped, ng = c.group_hits(case["hits"], case["nframes"], 1)
+        assert np.array_equal(ng, want[2]) and grouped.tobytes() == want[1].tobytes() and best.tobytes() == want[0].tobytes(), options
+        over.append(_over_cap_frames(c))
+        assert over[-1] == gc.over_cap_frames("caps_128", options)
+    # frames with MORE hits than the cap, of 64, 65, 128, 129, 256, 257, 512, 513: a frame of exactly `cap` hits is a full workgroup
+    assert over == [0, 5, 3, 1, 3]
+
+
+def test_a_batch_of_2500_frames_returns_the_last_frames_list(ctx):
+    """k_grp_bucket's frame loop runs three passes: the bucket starts carry over, and the last frame's list is the oracle's"""
+    for name in ("frames_2500", "last_of_2500_only"):
+        case = gc.cases()[name]
+        best, grouped, ng = ctx.group_hits(case["hits"], case["nframes"], 1)
+        wbest, wgrouped, wng = gc.expected(name, 1)
+        assert len(ng) == 2500 and wng[2499] > 0 and ng[2499] == wng[2499]
+        assert grouped[len(grouped) - int(ng[2499]):].tobytes() == wgrouped[len(wgrouped) - int(wng[2499]):].tobytes()
+        assert best[2499].tobytes() == wbest[2499].tobytes() and best[2499]["neighbors"] > 0
+        assert np.array_equal(ng, wng) and grouped.tobytes() == wgrouped.tobytes() and best.tobytes() == wbest.tobytes()
 
 
 def test_overflow_frame_is_flagged_only_under_the_lowered_cap(ctx, ctx_for):
@@ -195,6 +226,122 @@ def test_hits_with_a_frame_or_scale_out_of_range_are_reported_not_used(ctx):
     assert best.tobytes() == want[0].tobytes() and grouped.tobytes() == want[1].tobytes()
     with pytest.raises(HtError):
         ctx.group_hits(hits, 0, 1)
+
+
+# ---- behind a real scan that crowds a frame: the hits arrive in the scan's atomic order, hundreds to one frame ----------------------------
+
+
+def _assert_raw_equals_the_oracle(c, batch, blob):
+    """detect_raw per frame: keys and confidence bits (the scan's hit append at this density)"""
+    hits, counts = c.detect_raw(gc.scan_frames(batch))
+    want = gc.scan_raw(batch, blob)
+    assert [int(n) for n in counts] == [len(r) for r in want]
+    k = 0
+    for f, r in enumerate(want):
+        got = hits[k:k + len(r)]
+        k += len(r)
+        assert (got["frame"] == f).all()
+        for fld in ("scale", "q", "y", "x"):
+            assert np.array_equal(got[fld].astype(np.int64), r[fld].astype(np.int64)), (f, fld)
+        assert np.array_equal(got["sum"].view(np.uint64), r["sum"].view(np.uint64)), f
+
+
+def _assert_scan_batch(c, batch, blob, mn, over_cap, requeue=False):
+    """detect_enqueue, detect_best_enqueue(mn, 7), detect_best_collect, detect_grouped(f) on a scan batch: best faces, total, every grouped
+    list and the device's record buffer equal the oracle's; `over_cap`: the frames finished on the host"""
+    frames = gc.scan_frames(batch)
+    wbest, wlists = gc.scan_expected(batch, blob, mn)
+    wtotal = sum(len(r) for r in gc.scan_raw(batch, blob))
+    n, h, w, _ = frames.shape
+    c.set_geometry(w, h, n)
+    c.upload(frames)
+    _over_cap_frames(c)
+    c.detect_enqueue()
+    c.detect_best_enqueue(mn, 7)
+    if requeue:  # (the batch the requeue started owns the lists and the records until it is collected: best faces and total only)
+        best, total = c.detect_best_collect_requeue()
+        assert total == wtotal and best.tobytes() == wbest.tobytes()
+        assert _over_cap_frames(c) == over_cap
+    best, total = c.detect_best_collect()
+    best = best.copy()
+    assert total == wtotal
+    for f in range(n):
+        _assert_rects(c.detect_grouped(f), wlists[f], (batch, mn, f))
+    assert best.tobytes() == wbest.tobytes()
+    ptr, nrec = c.detect_best_records_ptr()
+    assert nrec == n
+    assert c.device_download(ptr, n * 64).tobytes() == hd.pack_best_records(wbest, 7).tobytes()
+    assert _over_cap_frames(c) == over_cap
+
+
+def test_real_scan_fills_a_workgroup(ctx, ctx_for, cascade):
+    """640x480, frames 0 and 3 tiled with faces (755 raw hits each, 88 grouped rects), one face on frame 1, noise on frame 2: raw hits,
+    grouped lists, best faces and records equal the oracle's on a default context; under group_cap=512 the two tiled frames are finished
+    on the host and the bytes are the same; a requeue round returns them twice"""
+    blob = cascade.blob
+    raw = gc.scan_raw("full_640x480", blob)
+    assert 512 < len(raw[0]) <= 1024 and len(raw[0]) == len(raw[3]) and len(raw[2]) == 0
+    _assert_raw_equals_the_oracle(ctx, "full_640x480", blob)
+    # the two contexts in turn: each replays its captured detect sequence after the other one has allocated its geometry and run a batch
+    # (LABLOG 2026-10-20: the replayed memset node of the counters once left a garbage hit count exactly here)
+    for mn in (1, 2):
+        _assert_scan_batch(ctx, "full_640x480", blob, mn, 0)
+        _assert_scan_batch(ctx_for("group_cap=512"), "full_640x480", blob, mn, 2)
+    _assert_scan_batch(ctx, "full_640x480", blob, 1, 0, requeue=True)
+    _assert_scan_batch(ctx_for("group_cap=512"), "full_640x480", blob, 1, 2, requeue=True)
+
+
+def test_real_scan_over_the_default_cap(ctx, cascade):
+    """960x540, frame 0 tiled with faces (1473 raw hits > 1024), one face on frame 1: frame 0 is flagged, finished by the collect call on
+    the host and its completed record written back to the device; detect_grouped(0) is the host's list, detect_grouped(1) the device's.
+    The second batch replays the context's captured detect sequence behind a collect call that finished a frame on the host."""
+    blob = cascade.blob
+    raw = gc.scan_raw("over_960x540", blob)
+    assert len(raw[0]) > 1024 and 0 < len(raw[1]) <= 64
+    _assert_raw_equals_the_oracle(ctx, "over_960x540", blob)
+    for mn in (1, 2):
+        _assert_scan_batch(ctx, "over_960x540", blob, mn, 1)
+    wbest, wlists = gc.scan_expected("over_960x540", blob, 1)
+    assert len(wlists[0]) == 153 and wbest[0]["neighbors"] > 0  # the record compared above is a face's, not the flagged frame's placeholder
+
+
+def test_hit_capacity_is_a_limit_not_a_fault(cascade):
+    """hit_capacity=100: a scan that finds 129 hits is reported by detect_best_collect with HT_ERR_CAPACITY and the next batch on the
+    context is exact; group_hits takes exactly hit_capacity hits and refuses one more"""
+    import init_best_cases as ib
+
+    blob = cascade.blob
+    tiled = ib.frames()[ib.TILED]
+    assert ib.raw_counts(blob)[ib.TILED] == 129
+    one = synth.face_frame(ib.W, ib.H, [(100, 60, 96)])
+    wone = ho.detect_objects(one, blob, 5, 1)
+    assert 0 < len(ho.detect_raw(one, blob)) < 100 and len(wone) == 1
+    c = Context(hit_capacity=100)
+    try:
+        c.set_geometry(ib.W, ib.H, 1)
+        c.upload(tiled[None])
+        c.detect_enqueue()
+        c.detect_best_enqueue(1, 0)
+        with pytest.raises(HtError) as e:
+            c.detect_best_collect()
+        assert e.value.status == native.HT_ERR_CAPACITY == -4
+        best, total = _device_route(c, one[None], 1)
+        assert total == len(ho.detect_raw(one, blob)) and best[0].tobytes() == gc.select_best(wone).tobytes()
+        _assert_rects(c.detect_grouped(0), wone, "after the capacity error")
+        rng = np.random.default_rng(100)
+        hits = np.concatenate([gc.clustered(rng, 0, 70), gc.clustered(rng, 1, 31)])
+        hits = hits[rng.permutation(len(hits))]
+        full = hits[:100]
+        want = gc.oracle_result(full, 2, 1)
+        best, grouped, ng = c.group_hits(full, 2, 1)
+        assert np.array_equal(ng, want[2]) and grouped.tobytes() == want[1].tobytes() and best.tobytes() == want[0].tobytes()
+        with pytest.raises(HtError) as e:
+            c.group_hits(hits, 2, 1)
+        assert len(hits) == 101 and e.value.status == -1
+        best, grouped, ng = c.group_hits(full, 2, 1)  # and the context is as good as before
+        assert grouped.tobytes() == want[1].tobytes() and best.tobytes() == want[0].tobytes()
+    finally:
+        c.close()
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,5 +1,5 @@
 """CPU-side checks of the device grouping (ht_group.hip): every synthetic hit list of tests/group_cases.py reaches the state it is named
-after — proven from oracle.ht_oracle alone —, the host part of the route (ht_group_plan.h) runs under AddressSanitizer + UBSan in a
+after — proven from oracle.ht_oracle alone, the full-workgroup, over-cap and > 1024-frame cases and the scan batches included —, the host part of the route (ht_group_plan.h) runs under AddressSanitizer + UBSan in a
 stand-alone harness and equals the oracle, the new entry points exist at every layer, and the new kernels sit in the fourth code object
 within their budgets.  No compute calls (no GPU here)."""
 import importlib.util
@@ -137,6 +137,190 @@ def test_size_overflow_and_layout_cases_have_the_stated_shapes():
     ng = np.concatenate([gc.expected(n, m)[2] for n, m in gc.case_ids()])
     assert (ng == 0).any() and (ng == 1).any() and (ng > 3).any()
     assert gc.expected("sizes", 3)[2].sum() < gc.expected("sizes", 1)[2].sum() < gc.expected("sizes", 0)[2].sum()
+
+
+# ---- the full-workgroup cases: k_grp_frames<1024> at 511 .. 1024 hits, every launch width, the default cap, > 1024 frames ------------------
+
+NEW_CASES = ("full_wide", "full_dense", "chains", "two_chains", "over_default_cap", "caps_128", "caps_256", "caps_512", "caps_300", "frames_1025",
+             "frames_2500", "last_of_2500_only")
+
+
+def _adjacency_matrix(seq):
+    """ccv.js:252-261 in either direction on the oracle's seq rects, as one boolean matrix (gc.similar pair by pair is a million oracle
+    calls at n = 1024): r2 is similar to r1 when it lies within floor(r1.width * 0.25 + 0.5) of it in x and y and the widths are within
+    a factor of 1.5 of each other, both rounded as the reference rounds them"""
+    x, y, w = seq["x"], seq["y"], seq["width"]
+    d, w15 = np.floor(w * 0.25 + 0.5), np.floor(w * 1.5 + 0.5)
+    p = ((x[None, :] <= (x + d)[:, None]) & (x[None, :] >= (x - d)[:, None]) & (y[None, :] <= (y + d)[:, None]) & (y[None, :] >= (y - d)[:, None])
+         & (w[None, :] <= w15[:, None]) & (w15[None, :] >= w[:, None]))  # p[i, j]: r1 = i, r2 = j
+    a = p | p.T
+    np.fill_diagonal(a, False)
+    return a
+
+
+def _kernel_rounds(adj):
+    """the kernel's label rounds in plain numpy: every rect takes the minimum label over itself and its similar rects, then jumps once
+    through the labels of the round's start; (final labels, rounds in which a label changed)"""
+    n = len(adj)
+    lab, rounds = np.arange(n), 0
+    while rounds <= n:
+        m = np.minimum(lab, np.where(adj, lab[None, :], n).min(axis=1))
+        new = lab[m]
+        if np.array_equal(new, lab):
+            break
+        lab, rounds = new, rounds + 1
+    return lab, rounds
+
+
+def _component_sizes(adj):
+    lab, _ = _kernel_rounds(adj)
+    roots = np.unique(lab)
+    assert np.array_equal(lab[roots], roots)  # every label is its class's smallest member
+    return np.sort(np.bincount(lab, minlength=len(adj))[roots])[::-1]
+
+
+def test_adjacency_matrix_is_the_oracles_pair_predicate():
+    """the vectorised predicate against oracle.group on pairs: every pair of the 65-hit chain and of a 129-hit blob frame, and seeded
+    pairs of the 1024-hit frames"""
+    cs = gc.cases()
+    for name, f, pairs in (("chains", 0, None), ("caps_128", 3, None), ("full_dense", 0, 3000), ("full_wide", 4, 3000)):
+        seq = gc.frame_seq(cs[name]["hits"], f)
+        adj, n = _adjacency_matrix(seq), len(seq)
+        if pairs is None:
+            ij = [(i, j) for i in range(n) for j in range(i + 1, n)]
+        else:
+            r = np.random.default_rng(n).integers(0, n, size=(pairs, 2))
+            near = np.argwhere(adj)[:: max(1, int(adj.sum()) // pairs)]  # and joined pairs, which a uniform draw seldom meets
+            ij = [(int(i), int(j)) for i, j in np.concatenate([r, near]) if i != j]
+        assert any(adj[i, j] for i, j in ij) and not all(adj[i, j] for i, j in ij)
+        for i, j in ij:
+            # (a class of two, not gc.similar's "one rect comes back": a rect nested in another one that is not similar to it is dropped
+            # by ccv.js:307-330 and leaves one rect of one member)
+            g = ho.group(seq[[i, j]], 1)
+            assert bool(adj[i, j]) == (len(g) == 1 and g[0]["neighbors"] == 2), (name, f, i, j)
+
+
+def test_full_workgroup_cases_have_the_stated_shapes():
+    cs = gc.cases()
+    assert list(cs)[-len(NEW_CASES):] == list(NEW_CASES)
+    counts = {name: gc.frame_counts(name).tolist() for name in NEW_CASES}
+    assert counts["full_wide"] == [511, 512, 513, 1023, 1024] and cs["full_wide"]["min_neighbors"] == (0, 1, 2, 3)
+    assert counts["full_dense"] == [1024, 700] and cs["full_dense"]["min_neighbors"] == (1, 3)
+    assert counts["chains"] == [65, 200, 513, 1024] and cs["chains"]["min_neighbors"] == (1, 2)
+    assert counts["two_chains"] == [1024]
+    assert counts["over_default_cap"] == [1024, 1025, 1500, 9] and cs["over_default_cap"]["min_neighbors"] == (0, 1, 2)
+    assert cs["over_default_cap"]["options"] is None
+    for cap in (128, 256, 512, 300):
+        c = cs["caps_%d" % cap]
+        assert counts["caps_%d" % cap] == [64, 65, 128, 129, 256, 257, 512, 513] and c["options"] == "group_cap=%d" % cap
+        assert c["hits"].tobytes() == cs["caps_128"]["hits"].tobytes()  # one hit list
+    for name, nfr in (("frames_1025", 1025), ("frames_2500", 2500)):
+        n = np.array(counts[name])
+        assert len(n) == nfr == cs[name]["nframes"] and n[1023] == 65 and n[1024] == 70
+        rest = np.delete(n, [1023, 1024, 2300, 2499][: 2 if nfr == 1025 else 4])
+        assert rest.max() == 3 and {0, 1, 2, 3} <= set(rest.tolist())
+        empty_runs = [r for r in range(nfr // 37) if not n[37 * r: 37 * r + 37].any()]
+        assert len(empty_runs) >= 3  # whole runs of frames without a hit
+        assert n[:1024].sum() < n.sum() and n[-1] > 0  # the second pass of the bucket kernel's frame loop carries a start, to the last frame
+    n = np.array(counts["frames_2500"])
+    assert n[2300] == 200 and n[2499] == 30 and n[2048:].sum() > 230  # the third pass
+    assert [k for k, v in enumerate(counts["last_of_2500_only"]) if v] == [2499] and cs["last_of_2500_only"]["nframes"] == 2500
+    for name in NEW_CASES:
+        h, nfr = cs[name]["hits"], cs[name]["nframes"]
+        assert np.isfinite(h["sum"]).all() and (h["frame"] < nfr).all() and (h["scale"] < 27).all(), name
+        assert (h["x"] < 1 << 16).all() and (h["y"] < 1 << 16).all() and (h["q"] < 4).all(), name  # the kernel's key fields
+        keys = set(zip(h["frame"].tolist(), h["scale"].tolist(), h["q"].tolist(), h["y"].tolist(), h["x"].tolist()))
+        assert len(keys) == len(h), name
+        if name not in ("two_chains", "last_of_2500_only") and not name.startswith("caps_"):
+            assert (np.diff(h["frame"].astype(np.int64)) < 0).any(), name  # arrival order: the frames interleaved
+
+
+def test_cap_rule_and_the_frames_each_case_leaves_to_the_host():
+    assert [gc.cap_of(o) for o in (None, "", "force_rccl=1", "group_cap=1024", "group_cap=5000")] == [1024] * 5
+    assert [gc.cap_of("group_cap=%d" % n) for n in (-5, 0, 1, 64, 65, 127, 128, 255, 256, 300, 511, 512, 1023)] == \
+        [64, 64, 64, 64, 64, 64, 128, 128, 256, 256, 256, 512, 512]  # (the rows of tests/host/group_harness.cc's plan checks among them)
+    assert gc.cap_of("force_rccl=1,group_cap=300") == 256
+    assert gc.over_cap_frames("overflow") == 1 and gc.over_cap_frames("overflow", None) == 0
+    assert gc.over_cap_frames("over_default_cap") == 2  # 1025 and 1500; 1024 is a full workgroup, not one over the cap
+    # more hits than the cap, counted by hand from 64, 65, 128, 129, 256, 257, 512, 513: a frame of exactly `cap` hits stays on the device
+    assert [gc.over_cap_frames("caps_%d" % cap) for cap in (128, 256, 512, 300)] == [5, 3, 1, 3]
+    assert gc.over_cap_frames("caps_128", None) == 0
+    for name in gc.cases():
+        if name not in ("overflow", "over_default_cap") and not name.startswith("caps_"):
+            assert gc.over_cap_frames(name) == 0, name
+
+
+def test_chains_are_paths_that_take_the_label_rounds_across_wavefronts():
+    cs = gc.cases()
+    for f, n in enumerate(gc.CHAIN_SIZES):
+        seq = gc.frame_seq(cs["chains"]["hits"], f)
+        assert len(seq) == n
+        adj = _adjacency_matrix(seq)
+        assert sorted(adj.sum(axis=1).tolist()) == [1, 1] + [2] * (n - 2)  # a path
+        for mn in (1, 2):
+            g = ho.group(seq, mn)
+            assert len(g) == 1 and g[0]["neighbors"] == n  # one class of n members
+        lab, rounds = _kernel_rounds(adj)
+        assert not lab.any() and rounds <= n
+        i, j = np.nonzero(adj)
+        # (emission order is q-major: a 6-pixel step's two windows are half a frame apart)
+        assert np.abs(i - j).max() > (64 if n > 128 else 16)  # neighbours in other wavefronts: label 0 travels through larger indices
+        if n == 1024:
+            assert rounds >= 8, rounds
+    assert int(cs["chains"]["hits"]["x"].max()) == 1278  # fits the key's 16-bit field
+
+
+def test_two_chains_are_two_components_the_second_rooted_far_from_index_zero():
+    seq = gc.frame_seq(gc.cases()["two_chains"]["hits"], 0)
+    adj = _adjacency_matrix(seq)
+    lab, _ = _kernel_rounds(adj)
+    assert sorted(np.bincount(lab)[np.unique(lab)].tolist()) == [500, 524]
+    assert np.unique(lab)[0] == 0 and np.unique(lab)[1] >= 100  # the second class's smallest member
+    g = ho.group(seq, 1)
+    assert sorted(int(r["neighbors"]) for r in g) == [500, 524]
+
+
+def test_full_wide_frames_have_many_components_of_every_size():
+    cs = gc.cases()
+    for f, n in enumerate(gc.FULL_WIDE_SIZES):
+        seq = gc.frame_seq(cs["full_wide"]["hits"], f)
+        sizes = _component_sizes(_adjacency_matrix(seq))
+        assert sizes.sum() == n
+        assert len(sizes) >= 30 and (sizes >= 3).sum() >= 20 and sizes[0] <= n // 4, (f, sizes)
+        assert len(ho.group(seq, 1)) <= len(sizes)
+        ng = [int(gc.expected("full_wide", mn)[2][f]) for mn in (1, 2, 3)]
+        assert ng[0] > ng[1] > ng[2] > 0, (f, ng)
+        assert int(gc.expected("full_wide", 0)[2][f]) == n
+    # labels above 255 are roots of classes (the uint16 label array), and the nested-rect pass sees dozens of averaged rects
+    seq = gc.frame_seq(cs["full_wide"]["hits"], 4)
+    lab, _ = _kernel_rounds(_adjacency_matrix(seq))
+    assert (np.unique(lab) > 255).sum() >= 10 and gc.expected("full_wide", 1)[2][4] >= 30
+
+
+def test_full_dense_frame_is_one_long_class_and_strays():
+    cs = gc.cases()
+    for f, n in enumerate(gc.FULL_DENSE_SIZES):
+        seq = gc.frame_seq(cs["full_dense"]["hits"], f)
+        sizes = _component_sizes(_adjacency_matrix(seq))
+        assert sizes.sum() == n and sizes[0] > n // 2 and len(sizes) >= 5, (f, sizes)
+        if f == 0:
+            assert sizes[0] > 512
+            assert max(int(r["neighbors"]) for r in ho.group(seq, 1)) == sizes[0]  # one thread sums it in order
+
+
+def test_scan_batches_crowd_a_frame_into_the_regimes_they_are_named_after(cascade):
+    """from the oracle alone: the tiled 640x480 frame fills more than half of a 1024-thread workgroup, the 960x540 one is over the cap"""
+    raw = gc.scan_raw("full_640x480", cascade.blob)
+    assert [len(r) for r in raw] == [755, len(raw[1]), 0, 755] and 512 < len(raw[0]) <= 1024 and 0 < len(raw[1]) < 64
+    _, lists = gc.scan_expected("full_640x480", cascade.blob, 1)
+    assert [len(g) for g in lists] == [88, 1, 0, 88]
+    raw = gc.scan_raw("over_960x540", cascade.blob)
+    assert len(raw[0]) == 1473 and len(raw[0]) > 1024 and 0 < len(raw[1]) < 64
+    assert [len(g) for g in gc.scan_expected("over_960x540", cascade.blob, 1)[1]] == [153, 1]
+    for batch in gc.SCAN_BATCHES:  # what the scan emits: distinct keys per frame, in emission order
+        for r in gc.scan_raw(batch, cascade.blob):
+            keys = list(zip(r["scale"].tolist(), r["q"].tolist(), r["y"].tolist(), r["x"].tolist()))
+            assert keys == sorted(set(keys))
 
 
 # ---- the host part of the route under the sanitizers -------------------------------------------------------------------------------------
