@@ -501,6 +501,25 @@ class Context:
         self._check(self._lib.ht_camshift_init_best_result(self._h, n, codes.ctypes.data, rects.ctypes.data))
         return codes, rects
 
+    def camshift_init_faces(self, pairs, min_confidence: float = -10.0, associate: bool = False):
+        """A tracker per grouped face, decided on the device: the pairs naming one BOUND frame are, in list order, that frame's slots (at
+        most native.HT_CSF_MAX_SLOTS), and the frame's grouped list of the device-grouped batch (detect_best_enqueue: in flight, or
+        collected) is dealt to them — the eligible faces (neighbors > 0, confidence > min_confidence) by confidence rank, or with
+        associate=True so that a tracker whose search window overlaps a face keeps its slot (largest overlap first; the other faces take
+        the slots that were never initialised, then the unmatched ones).  Slots without a face keep every byte; a frame that is not final
+        on the device yet defers its slots.  Enqueue only; camshift_init_faces_result tells what was decided."""
+        p = self._pairs(pairs)
+        flags = native.HT_CSF_ASSOCIATE if associate else 0
+        self._check(self._lib.ht_camshift_init_faces(self._h, p.ctypes.data, len(p), float(min_confidence), flags))
+
+    def camshift_init_faces_result(self, n: int):
+        """records native.CSF_RECORD_DTYPE [n] of the LAST camshift_init_faces (same n), in pair order: code (native.HT_CSB_UNTOUCHED /
+        _FACE / _DEFERRED), face (index in the frame's grouped list, or -1), the rect used (zeros without a face) and dropped (eligible
+        faces of the frame beyond its slots).  Waits for that call only."""
+        out = np.zeros(max(n, 0), dtype=native.CSF_RECORD_DTYPE)
+        self._check(self._lib.ht_camshift_init_faces_result(self._h, n, out.ctypes.data))
+        return out
+
     def camshift_track_pairs(self, pairs, calc_angles: bool = True, fetch: bool = True):
         """One track() of stream pairs[i][0] on bound frame pairs[i][1]; track objects in pair order.  The full-frame histogram is computed
         once per distinct frame.  fetch=False: enqueue only, collected with camshift_track_collect(len(pairs))."""

@@ -245,7 +245,8 @@ void ht_backproject_free(ht_ctx *c) {  // ht_destroy (the stream has been synchr
 
 // So are the pair forms of the camshift calls (ht_camshift_init_pairs / ht_camshift_track_pairs, k_csp_*): new kernels must not enter the
 // fingerprinted camshift object, and the library keeps four code objects.  (ht_cs_pairs.hip ends by including ht_cs_best.hip: the
-// record-driven initTracker, ht_camshift_init_best / k_csb_resolve, on this unit's grouping records and the pair unit's init kernels.)
+// record-driven initTracker, ht_camshift_init_best / k_csb_resolve, on this unit's grouping records and the pair unit's init kernels, and
+// behind it ht_cs_faces.hip: ht_camshift_init_faces / k_csf_resolve, the same for every grouped face of a frame.)
 #include "ht_cs_pairs.hip"
 
 // And the back-projection over pairs (ht_camshift_backproject_pairs / _device, k_bpp_*), behind the pair unit whose plan, table upload and

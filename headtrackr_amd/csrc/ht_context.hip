@@ -393,6 +393,7 @@ extern "C" void ht_destroy(ht_ctx *c) {
     ht_ingest_free(c);
     ht_cs_pairs_free(c);
     ht_cs_best_free(c);
+    ht_cs_faces_free(c);
     ht_group_free(c);
     if (c->d_gather) (void)hipFree(c->d_gather);
     for (auto &a : release) {

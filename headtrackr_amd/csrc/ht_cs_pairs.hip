@@ -255,3 +255,5 @@ void ht_cs_pairs_free(ht_ctx *c) {  // ht_destroy (the stream has been synchroni
 // The record-driven initTracker (ht_camshift_init_best, k_csb_resolve) is compiled right behind this file, whose plan, table upload and
 // init kernels it uses; ht_group.hip, whose records it reads, comes in front of both in ht_backproject.hip.
 #include "ht_cs_best.hip"
+// ... and behind it the same hand-off for every grouped face of a frame (ht_camshift_init_faces, k_csf_resolve).
+#include "ht_cs_faces.hip"

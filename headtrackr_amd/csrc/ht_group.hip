@@ -393,8 +393,9 @@ ht_status grp_launch(ht_ctx *c, const ht_hit *d_hits, const uint32_t *d_nhits, u
 }
 
 // After the result block has reached h_grp_out: the per-frame tables into the context, one rect per frame into best, and the frames the
-// kernel flagged finished on the host (their hits are fetched only here; their records on the device are completed too).
-ht_status grp_take_results(ht_ctx *c, uint32_t nframes, int32_t min_neighbors, int32_t frame_base, ht_rect *best, const char *fn) {
+// kernel flagged finished on the host (their hits are fetched only here; their records on the device are completed too,
+// and — lists_to_device: the collect, whose batch ht_camshift_init_faces may read afterwards — their grouped lists).
+ht_status grp_take_results(ht_ctx *c, uint32_t nframes, int32_t min_neighbors, int32_t frame_base, ht_rect *best, const char *fn, bool lists_to_device) {
     const HtGrpLayout L = ht_grp_layout(nframes);
     const double *records = reinterpret_cast<const double *>(c->h_grp_out + L.records);
     const uint32_t *status = reinterpret_cast<const uint32_t *>(c->h_grp_out + L.status), *ngrouped = reinterpret_cast<const uint32_t *>(c->h_grp_out + L.ngrouped);
@@ -426,6 +427,10 @@ ht_status grp_take_results(ht_ctx *c, uint32_t nframes, int32_t min_neighbors, i
         double rec[HT_GRP_REC_F64];
         ht_grp_rect_to_record(best[f], (double)(frame_base + (int32_t)f), rec);
         HT_HIP(c, hipMemcpy(c->d_grp_out + L.records + (size_t)f * sizeof(rec), rec, sizeof(rec), hipMemcpyHostToDevice));
+        if (!lists_to_device) continue;
+        // ... and so is its grouped list, for ht_camshift_init_faces: ng <= n rects into the frame's own bucket, the count next to them
+        if (ng) HT_HIP(c, hipMemcpy(c->d_grp_rects + start[f], g.data(), (size_t)ng * sizeof(ht_rect), hipMemcpyHostToDevice));
+        HT_HIP(c, hipMemcpy(c->d_grp_out + L.ngrouped + (size_t)f * sizeof(uint32_t), &ng, sizeof(ng), hipMemcpyHostToDevice));
     }
     return HT_OK;
 }
@@ -453,7 +458,7 @@ ht_status grp_collect(ht_ctx *c, ht_rect *best, uint32_t *total_hits, int64_t ne
     const int32_t mn = c->grp_min_neighbors, fb = c->grp_frame_base;
     if (head.nhits > c->hit_capacity) st = ht_fail(c, HT_ERR_CAPACITY, std::string(fn) + ": more raw hits than ht_config.hit_capacity; results incomplete");
     else if (head.bad) st = ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": a raw hit's frame or scale is out of range");
-    else if ((st = grp_take_results(c, nfr, mn, fb, best, fn)) == HT_OK) c->grp_valid = true;
+    else if ((st = grp_take_results(c, nfr, mn, fb, best, fn, true)) == HT_OK) c->grp_valid = true;
     if (st != HT_OK) return st;
     if (next_flags >= 0) {  // the next batch of the bound frames and its grouping, right behind the synchronisation
         if ((st = ht_detect_enqueue(c, (uint32_t)next_flags)) != HT_OK) return st;
@@ -543,7 +548,7 @@ extern "C" ht_status ht_group_hits(ht_ctx *c, const ht_hit *hits, uint32_t n, in
     HT_HIP(c, hipMemcpyAsync(c->h_grp_out, c->d_grp_out, L.bytes, hipMemcpyDeviceToHost, c->stream));
     HT_HIP(c, hipStreamSynchronize(c->stream));
     const HtGrpHead head = *reinterpret_cast<const HtGrpHead *>(c->h_grp_out);
-    if ((st = grp_take_results(c, nfr, min_neighbors, 0, best, "ht_group_hits")) != HT_OK) return st;
+    if ((st = grp_take_results(c, nfr, min_neighbors, 0, best, "ht_group_hits", false)) != HT_OK) return st;
     if (grouped) {  // the frames' lists back to back in frame order
         size_t k = 0;
         for (uint32_t f = 0; f < nfr; f++) {

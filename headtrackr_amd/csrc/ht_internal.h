@@ -311,6 +311,12 @@ struct ht_ctx {
     hipEvent_t ev_csb = nullptr;
     int csb_n = 0;                     // pairs of the last call (0: none)
     const void *csb_states = nullptr;  // d_cs at that call: a later ht_camshift_reserve that reallocated the trackers ends the result's life
+    // ht_camshift_init_faces (ht_cs_faces.hip): the same for its 32-byte records (ht_csf_record), one per pair
+    uint8_t *d_csf_res = nullptr, *h_csf_res = nullptr;
+    size_t csf_cap = 0;                // records both hold
+    hipEvent_t ev_csf = nullptr;
+    int csf_n = 0;                     // pairs of the last call (0: none)
+    const void *csf_states = nullptr;  // d_cs at that call
 
     // ingest (ht_ingest.hip): device staging of ht_draw_frames' host-resident source frames, grown on demand
     uint8_t *d_ingest_src = nullptr;
@@ -471,6 +477,7 @@ void ht_camshift_free(ht_ctx *ctx);                         // ht_camshift.hip: 
 void ht_backproject_free(ht_ctx *ctx);                      // ht_backproject.hip: its scratch (ht_destroy)
 void ht_cs_pairs_free(ht_ctx *ctx);                         // ht_cs_pairs.hip: pair table, staging and histogram scratch (ht_destroy)
 void ht_cs_best_free(ht_ctx *ctx);                          // ht_cs_best.hip: the result buffers of ht_camshift_init_best (ht_destroy)
+void ht_cs_faces_free(ht_ctx *ctx);                         // ht_cs_faces.hip: the result buffers of ht_camshift_init_faces (ht_destroy)
 void ht_ingest_free(ht_ctx *ctx);                           // ht_ingest.hip: the host form's source staging, the draw list's table (ht_destroy)
 void ht_align_free(ht_ctx *ctx);                            // ht_face_calls.hip: the aligned crops' table, records and events (called by ht_ingest_free)
 void ht_crop_free(ht_ctx *ctx);                             // ht_face_calls.hip: the face crops' table, records and events (called by ht_ingest_free)

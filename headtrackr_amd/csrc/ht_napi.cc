@@ -42,6 +42,9 @@
 //   camshiftInitBest(ctx, Int32Array pairs[2n], minConfidence, Int32Array fallback[4n] | null = null)   ht_camshift_init_best: initTracker from the
 //        device's best-face records of the device-grouped batch, enqueue only
 //   camshiftInitBestResult(ctx, n) -> {codes: Int32Array(n), rects: Int32Array(4n)}   ht_camshift_init_best_result: what the last such call decided
+//   camshiftInitFaces(ctx, Int32Array pairs[2n], minConfidence, flags = 0)   ht_camshift_init_faces: a tracker per grouped face of each frame (the
+//        frame's pairs are its slots; CSF_ASSOCIATE: a tracker that overlaps a face keeps its slot), enqueue only
+//   camshiftInitFacesResult(ctx, n) -> Int32Array(8n)   ht_camshift_init_faces_result: per pair code, face, x, y, width, height, dropped, 0
 //   camshiftTrackSequence(ctx, first, n, calcAngles, dev, Float64Array byteOffsets, frameStride, outAll, fetch) -> Float64Array | undefined
 //   camshiftSequenceCollect(ctx, n, ncalls, outAll) -> Float64Array
 //   camshiftBackProject(ctx, n, first, kind) -> Uint8Array(4 n w h) (BP_RGBA8) | Float64Array(n w h) (BP_F64): back-projection of the bound frames
@@ -792,6 +795,39 @@ napi_value CamshiftInitBestResult(napi_env env, napi_callback_info info) {
     NAPI_OK(napi_create_typedarray(env, napi_int32_array, (size_t)n * 4, ab, 0, &ta));
     NAPI_OK(napi_set_named_property(env, obj, "rects", ta));
     return obj;
+}
+
+napi_value CamshiftInitFaces(napi_env env, napi_callback_info info) {
+    Args a(env, info, 4);
+    Locked L;
+    const ht_cs_pair *pairs = nullptr;
+    int32_t n = 0, flags = 0;
+    double min_conf = 0;
+    const char *usage = "camshiftInitFaces(ctx, Int32Array pairs[2n], minConfidence, flags = 0)";
+    if (!a.ctx(3, &L)) return nullptr;
+    if (!get_pairs(env, a.argv[1], &pairs, &n) || napi_get_value_double(env, a.argv[2], &min_conf) != napi_ok) return type_error(env, usage);
+    napi_valuetype vt = napi_undefined;
+    if (a.argc > 3 && napi_typeof(env, a.argv[3], &vt) == napi_ok && vt != napi_undefined && vt != napi_null && !a.i32(3, &flags)) return type_error(env, usage);
+    ht_status st = ht_camshift_init_faces(L.ctx, pairs, n, min_conf, (uint32_t)flags);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_init_faces");
+    return nullptr;
+}
+
+napi_value CamshiftInitFacesResult(napi_env env, napi_callback_info info) {
+    Args a(env, info, 2);
+    Locked L;
+    int32_t n = 0;
+    if (!a.ctx(2, &L)) return nullptr;
+    if (!a.i32(1, &n) || n <= 0 || n > (1 << 24)) return type_error(env, "camshiftInitFacesResult(ctx, n)");
+    std::vector<ht_csf_record> recs((size_t)n);
+    ht_status st = ht_camshift_init_faces_result(L.ctx, n, recs.data());
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_camshift_init_faces_result");
+    napi_value ab, ta;
+    void *p = nullptr;
+    NAPI_OK(napi_create_arraybuffer(env, (size_t)n * sizeof(ht_csf_record), &p, &ab));
+    memcpy(p, recs.data(), (size_t)n * sizeof(ht_csf_record));
+    NAPI_OK(napi_create_typedarray(env, napi_int32_array, (size_t)n * 8, ab, 0, &ta));
+    return ta;
 }
 
 napi_value CamshiftTrackPairs(napi_env env, napi_callback_info info) {
@@ -1735,6 +1771,7 @@ napi_value Init(napi_env env, napi_value exports) {
                {"camshiftInitBound", CamshiftInitBound}, {"camshiftTrackBound", CamshiftTrackBound}, {"camshiftTrackCollect", CamshiftTrackCollect},
                {"camshiftInitPairs", CamshiftInitPairs}, {"camshiftTrackPairs", CamshiftTrackPairs},
                {"camshiftInitBest", CamshiftInitBest}, {"camshiftInitBestResult", CamshiftInitBestResult},
+               {"camshiftInitFaces", CamshiftInitFaces}, {"camshiftInitFacesResult", CamshiftInitFacesResult},
                {"camshiftTrackSequence", CamshiftTrackSequence}, {"camshiftSequenceCollect", CamshiftSequenceCollect},
                {"camshiftBackProject", CamshiftBackProject}, {"camshiftBackProjectDevice", CamshiftBackProjectDevice},
                {"camshiftBackProjectPairs", CamshiftBackProjectPairs}, {"camshiftBackProjectPairsDevice", CamshiftBackProjectPairsDevice},
@@ -1762,6 +1799,7 @@ napi_value Init(napi_env env, napi_value exports) {
                   {"SCAN_STATS", HT_SCAN_STATS},      {"BP_RGBA8", HT_BP_RGBA8},               {"BP_F64", HT_BP_F64},
                   {"YUV_NV12", HT_YUV_NV12},          {"YUV_I420", HT_YUV_I420},               {"DRAW_RGBA", HT_DRAW_RGBA},
                   {"CSB_UNTOUCHED", HT_CSB_UNTOUCHED}, {"CSB_FACE", HT_CSB_FACE},              {"CSB_FALLBACK", HT_CSB_FALLBACK}, {"CSB_DEFERRED", HT_CSB_DEFERRED},
+                  {"CSF_ASSOCIATE", HT_CSF_ASSOCIATE}, {"CSF_MAX_SLOTS", HT_CSF_MAX_SLOTS},
                   {"CROP_EMPTY", HT_CROP_EMPTY},      {"CROP_FACE", HT_CROP_FACE},             {"CROP_SQUARE", HT_CROP_SQUARE},
                   {"ALIGN_EMPTY", HT_ALIGN_EMPTY},    {"ALIGN_FACE", HT_ALIGN_FACE},           {"ALIGN_SQUARE", HT_ALIGN_SQUARE},
                   {"PATCH_F32", HT_PATCH_F32},        {"PATCH_F16", HT_PATCH_F16},             {"PATCH_BF16", HT_PATCH_BF16},

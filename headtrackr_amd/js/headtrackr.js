@@ -723,6 +723,54 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     reserve();
     A.camshiftInitPairs(ctxs[0], pairs, rects);
   };
+  /* A tracker per grouped face, decided on the device (ht_camshift_init_faces; needs grouping: 'device'): the pairs naming one frame are,
+   * in list order, that frame's slots (at most A.CSF_MAX_SLOTS), and the frame's grouped list of the device-grouped batch — the one
+   * detectStepEnqueue(set, min_neighbors) put in flight, or the one detectStepFinish collected last — is dealt to them: faces with confidence >
+   * minConfidence (default -10) by confidence rank, or with associate: true so that a tracker whose search window overlaps a face keeps its
+   * slot.  The slot is the identity of a tracker across re-detections.  Enqueue only: track steps may follow at once.
+   *   initFaces(pairs, {minConfidence, associate})
+   *   initFacesResult() -> Int32Array(8 pairs): code (A.CSB_UNTOUCHED / CSB_FACE / CSB_DEFERRED), face (index in the frame's grouped list or
+   *                        -1), x, y, width, height, dropped (eligible faces beyond the frame's slots), 0 per pair.  The slots of a frame
+   *                        that was not final on the device (over the grouping cap) are deferred: once the batch has been collected
+   *                        (detectStepFinish) initFacesResult() retries exactly those pairs, once, and returns the completed records
+   *                        of the WHOLE pair list — then and at every later read, without another call to the device.
+   * (camshift.MultiTracker.initFromDetection is not part of this: MultiTracker still initialises in list order from the host.) */
+  let facesCall = null; /* {pairs, minConfidence, flags, merged} of the last initFaces; merged: its records once deferred pairs have been retried */
+  const needFaces = function (what) {
+    if (!onDevice) throw new RangeError('DeviceBatch.' + what + ": needs grouping: 'device'");
+    if (typeof A.camshiftInitFaces !== 'function' || typeof A.camshiftInitFacesResult !== 'function')
+      throw new Error('DeviceBatch.' + what + ': this headtrackr_hip.node has no camshiftInitFaces / camshiftInitFacesResult (rebuild it)');
+  };
+  this.initFaces = function (pairs, o) {
+    needFaces('initFaces'); pairList('initFaces', pairs);
+    o = o || {};
+    const minConfidence = o.minConfidence === undefined ? -10 : o.minConfidence;
+    if (typeof minConfidence !== 'number' || minConfidence !== minConfidence) throw new RangeError('DeviceBatch.initFaces: minConfidence is a number, not NaN');
+    const flags = o.associate ? A.CSF_ASSOCIATE : 0;
+    reserve();
+    facesCall = null;
+    A.camshiftInitFaces(ctxs[0], pairs, minConfidence, flags);
+    facesCall = { pairs: new Int32Array(pairs), minConfidence: minConfidence, flags: flags, merged: null };
+  };
+  this.initFacesResult = function () {
+    needFaces('initFacesResult');
+    if (!facesCall) throw new Error('DeviceBatch.initFacesResult: no initFaces to report on');
+    const fcall = facesCall, np = fcall.pairs.length >> 1;
+    if (fcall.merged) return new Int32Array(fcall.merged); /* the library's last call is the retry now: its result names the late pairs only */
+    const rec = A.camshiftInitFacesResult(ctxs[0], np);
+    if (stepGrouped !== null) return rec; /* the batch is still in flight: deferred slots stay deferred until it has been collected */
+    const late = [];
+    for (let i = 0; i < np; i++) if (rec[8 * i] === A.CSB_DEFERRED) late.push(i);
+    if (!late.length) return rec;
+    const lp = new Int32Array(2 * late.length); /* every slot of a deferred frame is deferred: the frames keep their slots */
+    late.forEach(function (i, k) { lp[2 * k] = fcall.pairs[2 * i]; lp[2 * k + 1] = fcall.pairs[2 * i + 1]; });
+    A.camshiftInitFaces(ctxs[0], lp, fcall.minConfidence, fcall.flags);
+    const rec2 = A.camshiftInitFacesResult(ctxs[0], late.length);
+    const out = new Int32Array(rec);
+    late.forEach(function (i, k) { out.set(rec2.subarray(8 * k, 8 * k + 8), 8 * i); });
+    fcall.merged = out;
+    return new Int32Array(out);
+  };
   this.trackPairs = function (set, pairs, calcAngles) {
     needPairs('trackPairs'); pairList('trackPairs', pairs);
     bind0(set === undefined ? 0 : set);

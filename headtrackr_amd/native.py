@@ -31,6 +31,9 @@ HT_ERR_INVALID = -1
 HT_ERR_STATE = -6
 # ht_camshift_init_best's decision per pair
 HT_CSB_UNTOUCHED, HT_CSB_FACE, HT_CSB_FALLBACK, HT_CSB_DEFERRED = 0, 1, 2, 3
+# ht_camshift_init_faces: its flag, the slots one frame may have in a call
+HT_CSF_ASSOCIATE = 1
+HT_CSF_MAX_SLOTS = 16
 
 
 class Config(C.Structure):
@@ -53,6 +56,8 @@ RECT_DTYPE = np.dtype(
     [("x", "<f8"), ("y", "<f8"), ("width", "<f8"), ("height", "<f8"), ("confidence", "<f8"), ("neighbors", "<i4"), ("reserved", "<i4")]
 )
 CS_RECT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("width", "<i4"), ("height", "<i4")])
+# ht_csf_record (ht_camshift_init_faces_result), 32 bytes
+CSF_RECORD_DTYPE = np.dtype([("code", "<i4"), ("face", "<i4"), ("x", "<i4"), ("y", "<i4"), ("width", "<i4"), ("height", "<i4"), ("dropped", "<i4"), ("reserved", "<i4")])
 PAIR_DTYPE = np.dtype([("stream", "<i4"), ("frame", "<i4")])  # ht_cs_pair: tracker `stream` meets bound frame `frame`
 CS_TRACKOBJ_DTYPE = np.dtype(
     [("x", "<f8"), ("y", "<f8"), ("width", "<f8"), ("height", "<f8"), ("angle", "<f8"),
@@ -144,7 +149,7 @@ SYMBOLS = [
     "ht_windows_per_frame", "ht_pyramid_bytes_per_frame", "ht_upload_frames", "ht_upload_frames_async", "ht_swap_frames", "ht_bind_frames_device", "ht_frames_bound", "ht_frames_enqueued", "ht_host_alloc", "ht_host_free", "ht_device_alloc", "ht_device_free", "ht_device_upload", "ht_device_download", "ht_draw_frames_device", "ht_draw_frames", "ht_draw_frames_yuv_device", "ht_draw_frames_yuv", "ht_draw_list_device", "ht_detect_enqueue",
     "ht_detect_collect", "ht_detect_batch", "ht_pyramid_readback", "ht_stage_counts", "ht_grayscale_batch",
     "ht_whitebalance_batch", "ht_detect_whitebalance", "ht_hits_to_rects", "ht_group_rects", "ht_best_faces", "ht_detect_collect_best", "ht_detect_collect_best_requeue", "ht_detect_best_enqueue", "ht_detect_best_collect", "ht_detect_best_collect_requeue", "ht_detect_grouped", "ht_detect_best_records_device", "ht_group_hits", "ht_camshift_reserve", "ht_camshift_init_batch",
-    "ht_camshift_track_batch", "ht_camshift_track_collect", "ht_camshift_init_pairs", "ht_camshift_track_pairs", "ht_camshift_init_best", "ht_camshift_init_best_result", "ht_camshift_track_sequence", "ht_camshift_sequence_collect", "ht_camshift_stats", "ht_camshift_debug_hist", "ht_camshift_backproject", "ht_camshift_backproject_device", "ht_camshift_backproject_pairs", "ht_camshift_backproject_pairs_device", "ht_camshift_crop_pairs_device", "ht_camshift_crop_sources_device", "ht_camshift_crop_result", "ht_camshift_crop_records_device", "ht_camshift_align_pairs_device", "ht_camshift_align_sources_device", "ht_camshift_align_result", "ht_camshift_align_records_device", "ht_camshift_crop_pairs_tensor_device", "ht_camshift_crop_sources_tensor_device", "ht_camshift_align_pairs_tensor_device", "ht_camshift_align_sources_tensor_device", "ht_camshift_crop_pairs_filtered_device", "ht_camshift_crop_sources_filtered_device", "ht_camshift_align_pairs_filtered_device", "ht_camshift_align_sources_filtered_device", "ht_camshift_crop_filter_factors", "ht_camshift_align_filter_factors", "ht_allgather_records", "ht_allgather_best_faces", "ht_device_count", "ht_profile", "ht_kernel_times", "ht_stream", "ht_graph_launches", "ht_synchronize",
+    "ht_camshift_track_batch", "ht_camshift_track_collect", "ht_camshift_init_pairs", "ht_camshift_track_pairs", "ht_camshift_init_best", "ht_camshift_init_best_result", "ht_camshift_init_faces", "ht_camshift_init_faces_result", "ht_camshift_track_sequence", "ht_camshift_sequence_collect", "ht_camshift_stats", "ht_camshift_debug_hist", "ht_camshift_backproject", "ht_camshift_backproject_device", "ht_camshift_backproject_pairs", "ht_camshift_backproject_pairs_device", "ht_camshift_crop_pairs_device", "ht_camshift_crop_sources_device", "ht_camshift_crop_result", "ht_camshift_crop_records_device", "ht_camshift_align_pairs_device", "ht_camshift_align_sources_device", "ht_camshift_align_result", "ht_camshift_align_records_device", "ht_camshift_crop_pairs_tensor_device", "ht_camshift_crop_sources_tensor_device", "ht_camshift_align_pairs_tensor_device", "ht_camshift_align_sources_tensor_device", "ht_camshift_crop_pairs_filtered_device", "ht_camshift_crop_sources_filtered_device", "ht_camshift_align_pairs_filtered_device", "ht_camshift_align_sources_filtered_device", "ht_camshift_crop_filter_factors", "ht_camshift_align_filter_factors", "ht_allgather_records", "ht_allgather_best_faces", "ht_device_count", "ht_profile", "ht_kernel_times", "ht_stream", "ht_graph_launches", "ht_synchronize",
 ]
 
 _lib = None
@@ -260,6 +265,10 @@ def lib():
     L.ht_camshift_init_best.argtypes = [vp, vp, i32, C.c_double, vp]
     L.ht_camshift_init_best_result.restype = i32
     L.ht_camshift_init_best_result.argtypes = [vp, i32, vp, vp]
+    L.ht_camshift_init_faces.restype = i32
+    L.ht_camshift_init_faces.argtypes = [vp, vp, i32, C.c_double, C.c_uint32]
+    L.ht_camshift_init_faces_result.restype = i32
+    L.ht_camshift_init_faces_result.argtypes = [vp, i32, vp]
     L.ht_detect_whitebalance.restype = i32
     L.ht_detect_whitebalance.argtypes = [vp, vp, i32]
     L.ht_camshift_track_sequence.restype = i32

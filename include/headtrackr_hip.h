@@ -395,6 +395,38 @@ ht_status ht_camshift_init_best(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n,
  * per pair the code and the rect that was used (zeros for untouched and deferred pairs); either pointer may be NULL.  May be called
  * repeatedly.  HT_ERR_STATE when there is no such call, when n differs, or after an ht_camshift_reserve that grew the reservation. */
 ht_status ht_camshift_init_best_result(ht_ctx *ctx, int32_t n, int32_t *codes, ht_cs_rect *rects);
+/* The same hand-off for EVERY grouped face of a frame: one tracker per face, decided on the device from the frame's grouped list (what
+ * ht_detect_grouped returns) without copying it to the host.  The pairs of one frame, in list order, are that frame's slots S[0 .. k),
+ * 1 <= k <= HT_CSF_MAX_SLOTS.  Per frame: when the frame is not final on the device (the three conditions of HT_CSB_DEFERRED above) every
+ * slot gets HT_CSB_DEFERRED and keeps every byte.  Otherwise the eligible faces — neighbors > 0 && confidence > min_confidence, strict,
+ * so a NaN confidence never is — are ordered by confidence descending, then list index ascending; the first k are kept, `dropped` counts
+ * the eligible ones beyond them.  A face's rect is floor(x, y, width, height) as in ht_camshift_init_best.  Without HT_CSF_ASSOCIATE the
+ * face of rank r goes to slot r.  With it, a slot is live when its stream's search window (the int32 window the last enqueued init or
+ * track step left on the device; zeros since ht_camshift_reserve for a stream never initialised) has sw_width > 0 && sw_height > 0;
+ * overlap(slot, face) is the area of the intersection of that window with the face's rect, in 64-bit integers (a rect with width or
+ * height <= 0 has none); greedily, among unassigned live slots and unassigned faces with overlap > 0 the largest overlap is assigned —
+ * ties to the lowest slot position, then the lowest rank — until no such pair is left; the remaining faces in rank order then take the
+ * remaining slots: the not-live ones in ascending position first, then the unmatched live ones in ascending position.  So a tracker that
+ * overlaps a detection keeps its slot across re-detections: the slot is the identity.  A slot with a face: HT_CSB_FACE and initTracker
+ * (camshift.js:198-211) of its stream on the frame with the face's rect; any other slot: HT_CSB_UNTOUCHED, every byte kept.  Integer and
+ * binary64 comparisons only: no tolerance anywhere.
+ * Enqueue only; legal whenever ht_camshift_init_best is (HT_ERR_STATE otherwise); never waits in the steady state.  The pair list obeys
+ * the rules of ht_camshift_init_pairs; in addition HT_ERR_INVALID for a frame outside the grouped batch, more than HT_CSF_MAX_SLOTS
+ * slots on one frame, a NaN min_confidence and unknown flag bits; the message names the offending pair or frame.  Every check happens
+ * before anything is enqueued; a refused call changes nothing.  The models are the bits ht_camshift_init_pairs produces for the same
+ * rects. */
+enum { HT_CSF_ASSOCIATE = 1 };
+#define HT_CSF_MAX_SLOTS 16
+typedef struct ht_csf_record {
+    int32_t code, face;        /* HT_CSB_UNTOUCHED / _FACE / _DEFERRED; the face's index in the frame's grouped list, or -1 */
+    ht_cs_rect rect;           /* the rect used; zeros for untouched and deferred slots */
+    int32_t dropped, reserved; /* eligible faces of the frame beyond its slots (the same in every slot of the frame); 0 */
+} ht_csf_record;               /* 32 bytes */
+ht_status ht_camshift_init_faces(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, double min_confidence, uint32_t flags);
+/* What the LAST ht_camshift_init_faces of the context decided (same n), one record per pair in pair order: waits for that call only.  May
+ * be called repeatedly.  HT_ERR_STATE when there is no such call, when n differs, or after an ht_camshift_reserve that grew the
+ * reservation. */
+ht_status ht_camshift_init_faces_result(ht_ctx *ctx, int32_t n, ht_csf_record *out);
 /* ncalls successive track() calls (camshift.js:213-220 called once per video frame, main.js:168-180) for streams
  * [first, first+n) in ONE host call: call k uses the n device-resident frames at dev_frames[k] (frame_stride bytes apart;
  * same geometry as ht_set_geometry).  A stream's calls are sequentially dependent (its search window), so they are
