@@ -243,14 +243,18 @@ class Context:
             self.nframes = n
 
     # -- one launch for a list of per-feed sources ----------------------------------------------------------------
-    def draw_list(self, entries, dst: int | None = None, dst_stride: int = 0):
+    def draw_list(self, entries, dst: int | None = None, dst_stride: int = 0, prefilter: int | None = None):
         """entries: one dict per feed, drawn onto destination frame i in ONE launch (ht_draw_list_device) —
         {"format": 'rgba' | 'nv12' | 'i420' (or the code), "width", "height", "p0", "p1", "p2" (device pointers: RGBA p0; NV12 Y, UV; I420
         Y, U, V), "pitch0", "pitch1" (bytes per row, 0 = packed), "matrix" (as draw_frames_yuv_device, ignored for RGBA), "rect" (x, y,
         width, height) or None = the whole source}.  Every feed may have its own allocation, size, format, matrix and rect; pointers may
-        repeat.  dst as draw_frames_device()."""
+        repeat.  dst as draw_frames_device().  prefilter = 1..8: ht_draw_list_filtered_device with that max_factor — every canvas pixel the
+        mean of a block of the unfiltered draw's samples (draw_filter_factors gives the block per entry); None: the unfiltered call."""
         n = len(entries)
-        self._check(self._lib.ht_draw_list_device(self._h, self._draw_sources(entries), n, dst, dst_stride))
+        if prefilter is None:
+            self._check(self._lib.ht_draw_list_device(self._h, self._draw_sources(entries), n, dst, dst_stride))
+        else:
+            self._check(self._lib.ht_draw_list_filtered_device(self._h, self._draw_sources(entries), n, int(prefilter), dst, dst_stride))
         if dst is None:
             self.nframes = n
 
@@ -795,6 +799,25 @@ def crop_filter_factors(records, width: int, height: int, max_factor: int = 8) -
 def align_filter_factors(records, width: int, height: int, max_factor: int = 8) -> np.ndarray:
     """the same for ALIGN_RECORD_DTYPE records and the filtered align calls (ht_camshift_align_filter_factors)"""
     return _filter_factors(native.lib().ht_camshift_align_filter_factors, records, native.ALIGN_RECORD_DTYPE, width, height, max_factor)
+
+
+def draw_filter_factors(entries_or_sizes, width: int, height: int, max_factor: int = 8) -> np.ndarray:
+    """int32 [n, 2]: the (Nx, Ny) Context.draw_list(entries, prefilter=max_factor) takes for each entry on a width x height canvas.  An
+    item is a draw_list entry dict (its "rect" counts, else its whole "width" x "height") or a (source width, source height) pair.  The
+    library's own rule (ht_draw_filter_factors): needs no device."""
+    fn = native.lib().ht_draw_filter_factors
+    out = np.zeros((len(entries_or_sizes), 2), dtype=np.int32)
+    nx, ny = C.c_int32(), C.c_int32()
+    for i, e in enumerate(entries_or_sizes):
+        if isinstance(e, dict):
+            sw, sh = (e["rect"][2], e["rect"][3]) if e.get("rect") is not None else (e["width"], e["height"])
+        else:
+            sw, sh = e
+        st = fn(int(sw), int(sh), int(width), int(height), int(max_factor), C.byref(nx), C.byref(ny))
+        if st != 0:
+            raise HtError(st, f"draw filter factors: entry {i}: source width / height must be 1..16384, the canvas positive and max_factor 1..8")
+        out[i] = nx.value, ny.value
+    return out
 
 
 def device_count() -> int:

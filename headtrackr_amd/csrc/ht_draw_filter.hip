@@ -1,0 +1,121 @@
+// ht_draw_filter.hip — the draw list with a prefilter for strong downscales (ht_draw_list_filtered_device / ht_draw_filter_factors): each
+// canvas pixel the mean of an Nx x Ny block of the UNFILTERED draw's samples.  ht_draw_filter_plan.h states the rule and plans a call on the
+// host; the rounding is ht_filter_plan.h's.  Included at the end of ht_ingest.hip: same code object as k_draw_list and k_cut_mean, whose
+// helpers (fm_add, fm_finish, LpDwordStore) and shared text it takes.
+//
+// k_draw_list_mean_tile<RPT>: grid (tile column, tile row, entry), 256 threads; a tile is 64 columns by RPT * 4 rows, RPT rows per thread
+// (the library launches RPT 1, a 64 x 4 tile, at every max_factor: see dm_rpt_of).  A
+// workgroup reads its entry's 112-byte descriptor — HtDrawDesc with the FINE ratios, then Nx, Ny — with scalar loads (blockIdx.z is uniform,
+// the table const __restrict__).  The taps of the tile's fine columns and rows go to LDS, Nx * 64 + Ny * 4 RPT of them laid out [a][column]
+// and [b][row] (the arrays hold factor 8: 15 KB at RPT 4, 13 KB at RPT 1); one barrier; then for every (b, a) of the block — a
+// workgroup-uniform loop — the format's pixel body of ht_ingest_bodies.inc runs on tap slice a / b, through ht_list_parts.inc's scaffold,
+// with an IG_STORE that ADDS the sample's four bytes to the thread's sums.  A fine sample is therefore the unfiltered rule's byte by
+// construction: the binary64 blend of ig_channel, never contracted, rounded half to even; YUV taps converted first.  ht_filter_pixel
+// rounds the sums and the dword is stored.  Source rows are not staged in LDS: a block's Nx fine taps of one output pixel lie side by side
+// in the source, and the vector cache serves the neighbours (DESIGN.md §2.3.8 has the measurement).
+#include "ht_draw_filter_plan.h"
+
+namespace {
+
+typedef HtDrawMeanDescT<dl_gptr> DmDesc;
+static_assert(sizeof(DmDesc) == sizeof(HtDrawMeanDesc) && alignof(DmDesc) == alignof(HtDrawMeanDesc), "the kernel's view of a descriptor is the host's");
+
+#undef IG_STORE
+#define IG_STORE(o, x, y) ((void)out, (void)(x), (void)(y), fm_add(acc[k], o))  // k: the bodies' row index of the thread, a constant once unrolled
+
+// (the name: k_draw_list_mean with the tile behind it.  In a listing of the code object the kernels that END in _mean<..> are the face
+// crops' — tests/test_filter_cpu.py names them all — and a thin k_draw_list_mean over a tile function template was tried: it reordered
+// k_cut_mean<-1, 1>'s epilogue, which shares fm_finish.  As a kernel template of its own it leaves every neighbour's instructions alone.)
+template <int RPT>
+__global__ __launch_bounds__(IG_NT) void k_draw_list_mean_tile(const DmDesc *__restrict__ tab, uint8_t *__restrict__ dst, size_t dst_stride, int dw, int dh) {
+    constexpr int IG_RPT = RPT, IG_TH = RPT * FM_ROWS;  // the tile of THIS kernel: the shared text reads these two names
+    __shared__ RsTap s_colf[FM_MAXF * IG_TW], s_rowf[FM_MAXF * IG_TH];
+    const DmDesc &m = tab[blockIdx.z];  // uniform index into a read-only table: scalar loads
+    const DlDesc &d = m.d;
+    const int sx = d.sx, sy = d.sy, sw = d.sw, sh = d.sh, format = d.format;
+    const int nx = min(max(m.nx, 1), FM_MAXF), ny = min(max(m.ny, 1), FM_MAXF);  // the plan's 1 .. 8; the clamp keeps the LDS index in bounds whatever the table holds
+    const double rx = d.rx, ry = d.ry;  // the fine frame's: sw / (nx dw), sh / (ny dh), divided on the host
+    const int X0 = blockIdx.x * IG_TW, Y0 = blockIdx.y * IG_TH;
+    for (int t = threadIdx.x; t < nx * IG_TW; t += IG_NT)  // [a][column]: fine column nx * x + a
+        s_colf[t] = rs_tap(nx * min(X0 + (t & (IG_TW - 1)), dw - 1) + t / IG_TW, rx, sw, sx);
+    for (int t = threadIdx.x; t < ny * IG_TH; t += IG_NT)  // [b][row]
+        s_rowf[t] = rs_tap(ny * min(Y0 + (t & (IG_TH - 1)), dh - 1) + t / IG_TH, ry, sh, sy);
+    __syncthreads();
+    uint32_t acc[IG_RPT][4] = {};
+    // every (b, a) of the block runs the format's body on tap slice a / b
+#define LP_EACH_PASS                                   \
+    _Pragma("unroll 1") for (int b = 0; b < ny; b++)   \
+    _Pragma("unroll 1") for (int a = 0; a < nx; a++)   \
+    if (const RsTap *s_col = s_colf + a * IG_TW, *s_row = s_rowf + b * IG_TH; true)
+#define LP_PART 4  // LP_SCAFFOLD
+#include "ht_list_parts.inc"
+    fm_finish<RPT>(acc, (uint32_t)(nx * ny), LpDwordStore{reinterpret_cast<uint32_t *>(dst + (size_t)blockIdx.z * dst_stride), dw}, dw, dh);
+}
+
+#undef IG_STORE
+#define IG_STORE IG_STORE_DWORD  // the default again, for whatever is compiled behind this file
+
+// the tile of a call: 64 x 4 (RPT 1) at every max_factor.  Unlike the face crops' 112 x 112 patches a canvas has tiles enough for either form, and
+// the short workgroups won at every factor: on eight feeds -> 320 x 240, 74 against 100 us at max_factor 8, 18.5 against 20.9 us at 2, 9.2
+// against 10.0 us at 1 (profiles/draw_filter.txt).  The 64 x 16 form stays compiled behind the context option draw_filter_rows = 16, for
+// tools/gpu_draw_filter.py's comparison and the tests that pin both forms to the same bytes.
+int dm_rpt_of(const ht_ctx *c) { return c->draw_filter_rows ? c->draw_filter_rows / FM_ROWS : 1; }
+
+ht_status dm_launch(ht_ctx *c, const char *fn, const std::vector<HtDrawMeanDesc> &desc, uint8_t *dst, size_t dstride) {
+    ht_status st = dl_upload(c, fn, desc);  // the draw list's staged table (ht_draw_list.hip)
+    if (st != HT_OK) return st;
+    HtProfScope ps(c, "draw_list_mean");
+    const int rpt = dm_rpt_of(c);
+    const dim3 grid((c->W + IG_TW - 1) / IG_TW, (c->H + rpt * FM_ROWS - 1) / (rpt * FM_ROWS), (unsigned)desc.size());
+    const DmDesc *tab = reinterpret_cast<const DmDesc *>(c->dl_tab.d);
+    hipLaunchKernelGGL(rpt == 1 ? k_draw_list_mean_tile<1> : k_draw_list_mean_tile<IG_RPT>, grid, dim3(IG_NT), 0, c->stream, tab, dst, dstride, c->W, c->H);
+    HT_HIP(c, hipGetLastError());
+    return HT_OK;
+}
+
+}  // namespace
+
+// ht_draw_list_device's host path with ht_draw_filter_plan in the place of ht_draw_list_plan: everything is checked before anything is enqueued
+extern "C" ht_status ht_draw_list_filtered_device(ht_ctx *c, const ht_draw_source *srcs, int32_t n, int32_t max_factor, void *dst_dev, size_t dst_frame_stride) {
+    if (!c) return HT_ERR_INVALID;
+    HtRange range("ht_draw_list_filtered_device");
+    const char *fn = "ht_draw_list_filtered_device";
+    const std::string f(fn);
+    if (c->W == 0) return ht_fail(c, HT_ERR_STATE, f + ": call ht_set_geometry first");
+    if (!srcs || n <= 0 || n > HT_DRAW_LIST_MAX) return ht_fail(c, HT_ERR_INVALID, f + ": " + ht_draw_list_message(HT_DRAW_LIST_BAD_COUNT));
+    if (!ht_draw_filter_factor_ok(max_factor)) return ht_fail(c, HT_ERR_INVALID, f + ": " + ht_draw_filter_message(HT_DRAW_FILTER_BAD_FACTOR));
+    if ((uintptr_t)dst_dev & 3) return ht_fail(c, HT_ERR_INVALID, f + ": misaligned destination (4-byte alignment required)");
+    const size_t fbytes = (size_t)c->W * c->H * 4, dstride = dst_dev && dst_frame_stride ? dst_frame_stride : fbytes;
+    if ((dstride & 3) || dstride < fbytes) return ht_fail(c, HT_ERR_INVALID, f + ": destination frame stride smaller than a frame or not a multiple of 4");
+    std::vector<HtDrawMeanDesc> desc((size_t)n);
+    std::vector<HtDrawExtent> ext((size_t)n);
+    int32_t bad = -1;
+    const int ps = ht_draw_filter_plan(srcs, n, c->W, c->H, max_factor, desc.data(), ext.data(), &bad);
+    if (ps != HT_DRAW_LIST_OK) return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": " + ht_draw_filter_message(ps));
+    HT_HIP(c, hipSetDevice(c->device));
+    if (!dst_dev) {
+        if (n > c->max_batch)
+            return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(c->max_batch) + ": more entries than the geometry's batch capacity");
+        // the buffer as it is now and as far as this call writes it: defensive only, see ht_draw_frames_device
+        if ((bad = ht_draw_list_overlap(ext.data(), n, c->d_frames_own, std::max(c->d_frames_own_bytes, fbytes * (size_t)n))) >= 0)
+            return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": a source plane lies inside the context's own frame buffer");
+        ht_status st = ht_frames_own_reserve(c, fbytes * (size_t)n, fn);  // the contract of ig_draw_bound from here on
+        if (st != HT_OK) return st;
+        if ((st = dm_launch(c, fn, desc, c->d_frames_own, fbytes)) != HT_OK) return st;
+        ht_frames_bind_own(c, n);
+        return HT_OK;
+    }
+    if ((bad = ht_draw_list_overlap(ext.data(), n, dst_dev, (size_t)(n - 1) * dstride + fbytes)) >= 0)
+        return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": a source plane and the destination overlap");
+    return dm_launch(c, fn, desc, static_cast<uint8_t *>(dst_dev), dstride);
+}
+
+// the factors the filtered call takes for a source rect of src_width x src_height on a canvas: no context, no device
+extern "C" ht_status ht_draw_filter_factors(int32_t src_width, int32_t src_height, int32_t canvas_width, int32_t canvas_height, int32_t max_factor, int32_t *nx,
+                                            int32_t *ny) {
+    if (!nx || !ny || src_width <= 0 || src_height <= 0 || src_width > HT_YUV_MAX_DIM || src_height > HT_YUV_MAX_DIM || canvas_width <= 0 || canvas_height <= 0 ||
+        !ht_draw_filter_factor_ok(max_factor))
+        return HT_ERR_INVALID;
+    ht_draw_filter_factors_of(src_width, src_height, canvas_width, canvas_height, max_factor, nx, ny);
+    return HT_OK;
+}

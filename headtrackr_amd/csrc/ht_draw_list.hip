@@ -55,9 +55,11 @@ __global__ __launch_bounds__(IG_NT) void k_draw_list(const DlDesc *__restrict__ 
     }
 }
 
-// the table of a call on the device: through the context's staged descriptor table (HtStagedTable, ht_internal.h)
-ht_status dl_upload(ht_ctx *c, const char *fn, const std::vector<HtDrawDesc> &desc) {
-    const size_t need = desc.size() * sizeof(HtDrawDesc);
+// the table of a call on the device: through the context's staged descriptor table (HtStagedTable, ht_internal.h).  DESC: HtDrawDesc, or
+// the filtered draw's wider descriptor (ht_draw_filter.hip) — both calls are the draw list and share the table
+template <class DESC>
+ht_status dl_upload(ht_ctx *c, const char *fn, const std::vector<DESC> &desc) {
+    const size_t need = desc.size() * sizeof(DESC);
     ht_status st = ht_stage_reserve(c, &c->dl_tab, need, 64 * sizeof(HtDrawDesc), std::string(fn) + ": allocation of the descriptor table failed");
     if (st != HT_OK) return st;
     uint8_t *slot = nullptr;

@@ -198,3 +198,6 @@ void ht_ingest_free(ht_ctx *c) {  // ht_destroy (the stream has been synchronise
 #include "ht_filter.hip"
 // the calls of the four files above — one host path for the crop and the align family in all their forms — and their extern "C" entry points
 #include "ht_face_calls.hip"
+// the draw list with a prefilter: each canvas pixel the mean of a block of the unfiltered draw's samples (ht_draw_filter_plan.h states the
+// rule and plans a call on the host); the kernel compiles the three pixel bodies through the crops' scaffold, with ht_filter.hip's accumulating output stage
+#include "ht_draw_filter.hip"

@@ -322,7 +322,9 @@ struct ht_ctx {
     uint8_t *d_ingest_src = nullptr;
     size_t ingest_src_cap = 0;
     // ht_draw_list_device (ht_draw_list.hip): the call's descriptor table
+    // (ht_draw_list_filtered_device, ht_draw_filter.hip, stages its wider descriptors through the same table: both are the draw list)
     HtStagedTable dl_tab;
+    int draw_filter_rows = 0;  // option draw_filter_rows: the filtered draw's tile rows, 4 or 16 (0: the shipped 4) — for A-B measurements
     // the face crops (ht_crop.hip) and the aligned crops (ht_align.hip), one host path for both (ht_face_calls.hip): each family has a
     // descriptor table and the records of its last call of its OWN — a draw call, a crop call and an align call of one step share nothing
     HtFaceCalls crop, align;

@@ -62,6 +62,10 @@
 //   drawListDevice(ctx, entries, dstDev | null, dstStride, dstOffset = 0, wait = false)   ht_draw_list_device: ONE launch draws entries[i] onto
 //       frame i; an entry is {dev, offset, width, height, format (YUV_NV12 | YUV_I420 | DRAW_RGBA), matrix, rect: Int32Array[4] | null} and
 //       names ONE frame packed at byte `offset` of its own deviceAlloc() buffer (RGBA rows; Y, then UV or U, V)
+//   drawListFilteredDevice(ctx, entries, maxFactor, dstDev | null, dstStride, dstOffset = 0, wait = false)   ht_draw_list_filtered_device: the same
+//       draw with every canvas pixel the mean of a block of the unfiltered draw's samples, the block's factors up to maxFactor (1..8) per entry
+//   drawFilterFactors(Int32Array sizes[2n], canvasWidth, canvasHeight, maxFactor) -> Int32Array(2n)   ht_draw_filter_factors: Nx, Ny of entries
+//       whose source rect is sizes[2i] x sizes[2i + 1]
 //   framesBound(ctx), framesEnqueued(ctx), graphLaunches(ctx)
 #include <node_api.h>
 
@@ -1434,20 +1438,26 @@ bool get_draw_entry(napi_env env, napi_value e, ht_draw_source *s) {
     return true;
 }
 
-napi_value DrawListDevice(napi_env env, napi_callback_info info) {
-    static const char *usage = "drawListDevice(ctx, entries, dstDev | null, dstStride, dstOffset = 0, wait = false)";
-    Args a(env, info, 6);
+// drawListDevice and drawListFilteredDevice: ONE reader and ONE range check; the filtered form has maxFactor (1..8) behind the entries
+napi_value draw_list_call(napi_env env, napi_callback_info info, bool filtered) {
+    const char *usage = filtered ? "drawListFilteredDevice(ctx, entries, maxFactor, dstDev | null, dstStride, dstOffset = 0, wait = false)"
+                                 : "drawListDevice(ctx, entries, dstDev | null, dstStride, dstOffset = 0, wait = false)";
+    const char *cname = filtered ? "ht_draw_list_filtered_device" : "ht_draw_list_device";
+    const size_t k = filtered ? 1 : 0;  // the arguments behind maxFactor lie one further
+    Args a(env, info, 6 + k);
     Locked L;
     DevBuf *dst = nullptr;
     size_t dstride = 0, doff = 0;
     bool wait = false, is_array = false;
     uint32_t n = 0;
-    if (!a.ctx(4, &L) || !a.devbuf_or_null(2, &dst)) return nullptr;
-    if (napi_is_array(env, a.argv[1], &is_array) != napi_ok || !is_array || napi_get_array_length(env, a.argv[1], &n) != napi_ok || !a.offset(3, &dstride) ||
-        (a.argc > 4 && !a.offset(4, &doff)))
+    int32_t max_factor = 0;
+    if (!a.ctx(4 + k, &L) || !a.devbuf_or_null(2 + k, &dst)) return nullptr;
+    if (napi_is_array(env, a.argv[1], &is_array) != napi_ok || !is_array || napi_get_array_length(env, a.argv[1], &n) != napi_ok || (filtered && !a.i32(2, &max_factor)) ||
+        !a.offset(3 + k, &dstride) || (a.argc > 4 + k && !a.offset(4 + k, &doff)))
         return type_error(env, usage);
-    a.opt_bool(5, &wait);
+    a.opt_bool(5 + k, &wait);
     if (n < 1 || n > 65535) return range_error(env, (std::string(usage) + ": 1..65535 entries").c_str());
+    if (filtered && (max_factor < 1 || max_factor > 8)) return range_error(env, (std::string(usage) + ": maxFactor is 1..8").c_str());
     std::vector<ht_draw_source> srcs(n);
     for (uint32_t i = 0; i < n; i++) {
         napi_value e;
@@ -1455,14 +1465,40 @@ napi_value DrawListDevice(napi_env env, napi_callback_info info) {
         if (!get_draw_entry(env, e, &srcs[i])) return nullptr;
     }
     if (dst) {
-        const size_t fb = frame_bytes(env, L.ctx, 4, "drawListDevice");
+        const size_t fb = frame_bytes(env, L.ctx, 4, filtered ? "drawListFilteredDevice" : "drawListDevice");
         if (!fb) return nullptr;
         if (!frames_fit(doff, (size_t)n, dstride ? dstride : fb, fb, dst->bytes)) return range_error(env, (std::string(usage) + ": outside the device buffer").c_str());
     }
-    ht_status st = ht_draw_list_device(L.ctx, srcs.data(), (int32_t)n, dst ? static_cast<char *>(dst->ptr) + doff : nullptr, dstride);
-    if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_draw_list_device");
+    void *out = dst ? static_cast<char *>(dst->ptr) + doff : nullptr;
+    ht_status st = filtered ? ht_draw_list_filtered_device(L.ctx, srcs.data(), (int32_t)n, max_factor, out, dstride) : ht_draw_list_device(L.ctx, srcs.data(), (int32_t)n, out, dstride);
+    if (st != HT_OK) return throw_ht(env, L.ctx, st, cname);
     if (wait && (st = ht_synchronize(L.ctx)) != HT_OK) return throw_ht(env, L.ctx, st, "ht_synchronize");
     return nullptr;
+}
+napi_value DrawListDevice(napi_env env, napi_callback_info info) { return draw_list_call(env, info, false); }
+napi_value DrawListFilteredDevice(napi_env env, napi_callback_info info) { return draw_list_call(env, info, true); }
+
+// drawFilterFactors(Int32Array sizes[2n] = source (or rect) width, height per entry, canvasWidth, canvasHeight, maxFactor) -> Int32Array [2n] = Nx, Ny
+// per entry: the library's own rule (ht_draw_filter_factors), no context
+napi_value DrawFilterFactors(napi_env env, napi_callback_info info) {
+    static const char *usage = "drawFilterFactors(Int32Array sizes[2n], canvasWidth, canvasHeight, maxFactor)";
+    Args a(env, info, 4);
+    View sizes;
+    int32_t w = 0, h = 0, mf = 0;
+    if (!a.arity(4)) return nullptr;
+    if (!a.i32s(0, 0, &sizes) || sizes.len % 2 || !a.i32(1, &w) || !a.i32(2, &h) || !a.i32(3, &mf)) return type_error(env, usage);
+    if (w < 1 || h < 1 || mf < 1 || mf > 8) return range_error(env, (std::string(usage) + ": the canvas is positive, maxFactor is 1..8").c_str());
+    const size_t n = sizes.len / 2;
+    napi_value ab, ta;
+    void *p = nullptr;
+    NAPI_OK(napi_create_arraybuffer(env, n * 8, &p, &ab));
+    NAPI_OK(napi_create_typedarray(env, napi_int32_array, n * 2, ab, 0, &ta));
+    int32_t *out = static_cast<int32_t *>(p);
+    const int32_t *v = sizes.as<int32_t>();
+    for (size_t i = 0; i < n; i++)
+        if (ht_draw_filter_factors(v[2 * i], v[2 * i + 1], w, h, mf, out + 2 * i, out + 2 * i + 1) != HT_OK)
+            return range_error(env, (std::string(usage) + ": a source width / height is 1..16384").c_str());
+    return ta;
 }
 
 // ---- face crops and angle-aligned face crops: each tracker's box cut from its feed (ht_camshift_crop_*_device / ht_camshift_align_*_device) ----
@@ -1777,6 +1813,7 @@ napi_value Init(napi_env env, napi_value exports) {
                {"camshiftBackProjectPairs", CamshiftBackProjectPairs}, {"camshiftBackProjectPairsDevice", CamshiftBackProjectPairsDevice},
                {"drawFrames", DrawFrames},       {"drawFramesDevice", DrawFramesDevice},
                {"drawFramesYuv", DrawFramesYuv}, {"drawFramesYuvDevice", DrawFramesYuvDevice}, {"drawListDevice", DrawListDevice},
+               {"drawListFilteredDevice", DrawListFilteredDevice}, {"drawFilterFactors", DrawFilterFactors},
                {"cropPairsDevice", CropPairsDevice}, {"cropSourcesDevice", CropSourcesDevice}, {"cropResult", CropResult},
                {"alignPairsDevice", AlignPairsDevice}, {"alignSourcesDevice", AlignSourcesDevice}, {"alignResult", AlignResult},
                {"cropPairsTensorDevice", CropPairsTensorDevice}, {"cropSourcesTensorDevice", CropSourcesTensorDevice},

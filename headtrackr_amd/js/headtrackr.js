@@ -437,8 +437,10 @@ headtrackr.ccv.detect_objects_batch = function (frames, n, w, h, cascade, interv
  *   opts.sources = [{width, height, format = 'rgba' | 'nv12' | 'i420', matrix, sets = 1}, ...] (instead of opts.source): one entry per feed,
  *   every feed with its own device buffer, size and format; ONE launch draws them all (ht_draw_list_device)
  *     uploadSourceOf(i, frame, sset = 0)   feed i's packed frame host -> HBM
- *     drawList(sset, set, rects)           every feed onto its frame of frame set `set`; rects: null, or a rect / null per feed
- *     drawListBound(sset, rects)           the same into context 0's own frame buffer (bound): follow with the step functions at set = -1
+ *     drawList(sset, set, rects, opts)     every feed onto its frame of frame set `set`; rects: null, or a rect / null per feed;
+ *                                           opts.prefilter = 1..8: each canvas pixel the mean of a block of the draw's samples (ht_draw_list_filtered_device)
+ *     drawListBound(sset, rects, opts)     the same into context 0's own frame buffer (bound): follow with the step functions at set = -1
+ *     drawFilterFactors(rects, opts)       -> Int32Array(2 n): the block Nx, Ny opts.prefilter gives each feed under rects
  *     drawBound(sset, rect)                the same into context 0's own frame buffer, which becomes its bound frames: follow with the step
  *                                           functions at set = -1
  *     backProjectionPairs(set, pairs, kind) -> the same per (tracker, frame) pair, pair order: ht_camshift_backproject_pairs
@@ -873,12 +875,32 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
       return { dev: f.dev, offset: feedBase(f, sset, what), width: f.width, height: f.height, format: f.fmt, matrix: f.mat, rect: r || null };
     });
   };
-  this.drawList = function (sset, set, rects) {
-    A.drawListDevice(ctxs[0], listEntries(sset, rects, 'drawList'), dev, 0, (set || 0) * setBytes, depth > 1);
+  /* opts.prefilter = 1..8 (ht_draw_list_filtered_device): every canvas pixel the mean of an Nx x Ny block of the unfiltered draw's samples, the
+   * factors up to opts.prefilter per feed (drawFilterFactors gives them) — for strong downscales, where the plain draw reads 2 of every
+   * ratio rows and columns.  Without it nothing changes.  The rect -> canvas mapping does not depend on the filter: cropFeeds' opts.rects
+   * are the rects drawn, as before. */
+  const drawPrefilter = function (what, o) {
+    if (o !== undefined && o !== null && typeof o !== 'object') throw new TypeError('DeviceBatch.' + what + ': opts is an object ({prefilter})');
+    return prefilterOf(what, o || {}, ['drawListFilteredDevice']);
   };
-  this.drawListBound = function (sset, rects) {
-    A.drawListDevice(ctxs[0], listEntries(sset, rects, 'drawListBound'), null, 0, 0, false);
+  this.drawList = function (sset, set, rects, o) {
+    const mf = drawPrefilter('drawList', o), entries = listEntries(sset, rects, 'drawList');
+    if (mf) A.drawListFilteredDevice(ctxs[0], entries, mf, dev, 0, (set || 0) * setBytes, depth > 1);
+    else A.drawListDevice(ctxs[0], entries, dev, 0, (set || 0) * setBytes, depth > 1);
+  };
+  this.drawListBound = function (sset, rects, o) {
+    const mf = drawPrefilter('drawListBound', o), entries = listEntries(sset, rects, 'drawListBound');
+    if (mf) A.drawListFilteredDevice(ctxs[0], entries, mf, null, 0, 0, false);
+    else A.drawListDevice(ctxs[0], entries, null, 0, 0, false);
     bound = -1;
+  };
+  /* Int32Array(2 n): Nx, Ny a draw of `rects` with opts.prefilter takes for each feed (the library's rule; no device work) */
+  this.drawFilterFactors = function (rects, o) {
+    const mf = prefilterOf('drawFilterFactors', o || {}, ['drawFilterFactors']);
+    if (!mf) throw new RangeError('DeviceBatch.drawFilterFactors: opts.prefilter is an integer 1..8');
+    const sizes = new Int32Array(2 * n);
+    listEntries(0, rects, 'drawFilterFactors').forEach(function (e, i) { sizes[2 * i] = e.rect ? e.rect[2] : e.width; sizes[2 * i + 1] = e.rect ? e.rect[3] : e.height; });
+    return A.drawFilterFactors(sizes, w, h, mf);
   };
   /* Face crops on the device (ht_camshift_crop_pairs_device / ht_camshift_crop_sources_device): each tracker's box, as its last track step
    * — enqueue-only ones included — leaves it on the device, is cut from the frame and scaled to opts.width x opts.height RGBA.  Enqueue

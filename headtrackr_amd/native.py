@@ -146,7 +146,7 @@ YUV_MATRICES = {"bt601": HT_YUV_BT601_LIMITED, "bt709": HT_YUV_BT709_LIMITED, "b
 # every symbol include/headtrackr_hip.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = [
     "ht_create", "ht_destroy", "ht_last_error", "ht_abi_version", "ht_set_geometry", "ht_num_levels", "ht_plane",
-    "ht_windows_per_frame", "ht_pyramid_bytes_per_frame", "ht_upload_frames", "ht_upload_frames_async", "ht_swap_frames", "ht_bind_frames_device", "ht_frames_bound", "ht_frames_enqueued", "ht_host_alloc", "ht_host_free", "ht_device_alloc", "ht_device_free", "ht_device_upload", "ht_device_download", "ht_draw_frames_device", "ht_draw_frames", "ht_draw_frames_yuv_device", "ht_draw_frames_yuv", "ht_draw_list_device", "ht_detect_enqueue",
+    "ht_windows_per_frame", "ht_pyramid_bytes_per_frame", "ht_upload_frames", "ht_upload_frames_async", "ht_swap_frames", "ht_bind_frames_device", "ht_frames_bound", "ht_frames_enqueued", "ht_host_alloc", "ht_host_free", "ht_device_alloc", "ht_device_free", "ht_device_upload", "ht_device_download", "ht_draw_frames_device", "ht_draw_frames", "ht_draw_frames_yuv_device", "ht_draw_frames_yuv", "ht_draw_list_device", "ht_draw_list_filtered_device", "ht_draw_filter_factors", "ht_detect_enqueue",
     "ht_detect_collect", "ht_detect_batch", "ht_pyramid_readback", "ht_stage_counts", "ht_grayscale_batch",
     "ht_whitebalance_batch", "ht_detect_whitebalance", "ht_hits_to_rects", "ht_group_rects", "ht_best_faces", "ht_detect_collect_best", "ht_detect_collect_best_requeue", "ht_detect_best_enqueue", "ht_detect_best_collect", "ht_detect_best_collect_requeue", "ht_detect_grouped", "ht_detect_best_records_device", "ht_group_hits", "ht_camshift_reserve", "ht_camshift_init_batch",
     "ht_camshift_track_batch", "ht_camshift_track_collect", "ht_camshift_init_pairs", "ht_camshift_track_pairs", "ht_camshift_init_best", "ht_camshift_init_best_result", "ht_camshift_init_faces", "ht_camshift_init_faces_result", "ht_camshift_track_sequence", "ht_camshift_sequence_collect", "ht_camshift_stats", "ht_camshift_debug_hist", "ht_camshift_backproject", "ht_camshift_backproject_device", "ht_camshift_backproject_pairs", "ht_camshift_backproject_pairs_device", "ht_camshift_crop_pairs_device", "ht_camshift_crop_sources_device", "ht_camshift_crop_result", "ht_camshift_crop_records_device", "ht_camshift_align_pairs_device", "ht_camshift_align_sources_device", "ht_camshift_align_result", "ht_camshift_align_records_device", "ht_camshift_crop_pairs_tensor_device", "ht_camshift_crop_sources_tensor_device", "ht_camshift_align_pairs_tensor_device", "ht_camshift_align_sources_tensor_device", "ht_camshift_crop_pairs_filtered_device", "ht_camshift_crop_sources_filtered_device", "ht_camshift_align_pairs_filtered_device", "ht_camshift_align_sources_filtered_device", "ht_camshift_crop_filter_factors", "ht_camshift_align_filter_factors", "ht_allgather_records", "ht_allgather_best_faces", "ht_device_count", "ht_profile", "ht_kernel_times", "ht_stream", "ht_graph_launches", "ht_synchronize",
@@ -215,6 +215,10 @@ def lib():
     L.ht_draw_frames_yuv.argtypes = [vp, u8p, i32, i32, i32, i32, i32, sz, vp]
     L.ht_draw_list_device.restype = i32
     L.ht_draw_list_device.argtypes = [vp, C.POINTER(DRAW_SOURCE), i32, vp, sz]
+    L.ht_draw_list_filtered_device.restype = i32
+    L.ht_draw_list_filtered_device.argtypes = [vp, C.POINTER(DRAW_SOURCE), i32, i32, vp, sz]
+    L.ht_draw_filter_factors.restype = i32
+    L.ht_draw_filter_factors.argtypes = [i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
     L.ht_detect_enqueue.restype = i32
     L.ht_detect_enqueue.argtypes = [vp, u32]
     L.ht_detect_collect.restype = i32

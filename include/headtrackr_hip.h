@@ -85,6 +85,7 @@ typedef struct ht_config {
                              *   force_rccl=1         ht_allgather_* goes through RCCL even with one rank
                              *   group_cap=N          raw hits of one frame the device grouping takes (a power of two, 64 .. 1024 = default); frames above
                              *                        it are finished on the host by the collect call
+                             *   draw_filter_rows=4|16  ht_draw_list_filtered_device: the kernel's tile is 64 x 4 (the default) or 64 x 16 pixels
                              * Keys that make results incomplete by design (stop_stage, cs_iters, rs_maxgen) exist only in builds
                              * compiled with -DHT_DEBUG_KNOBS (tools/build_alt.py); the product library rejects them. */
 } ht_config;
@@ -255,6 +256,24 @@ typedef struct ht_draw_source {
  * hipMemcpyAsync on the ctx stream (a slot is reused only after an event shows its copy has run), so the call never copies to the host and
  * never waits in the steady state; the first call of a context, or a longer list, allocates. */
 ht_status ht_draw_list_device(ht_ctx *ctx, const ht_draw_source *srcs, int32_t n, void *dst_dev, size_t dst_frame_stride);
+
+/* The same draw with a prefilter for strong downscales.  ht_draw_list_device reads one bilinear tap pair per canvas pixel: 1920 x 1080 onto
+ * 320 x 240 touches 2 of every 6 columns and 2 of every 4.5 rows, and the rest aliases into everything downstream.  Here each canvas pixel
+ * is the mean of an Nx x Ny block of the UNFILTERED rule's samples.  For an entry whose source rect is sw x sh on the W x H canvas, with
+ * max_factor 1..8: Nx = min(max_factor, max(1, ceil(sw / W))), Ny likewise from sh and H.  The fine frame F is what ht_draw_list_device
+ * gives for the same entry on a canvas of Nx W x Ny H (the same rect, rx' = sw / (Nx W), ry' = sh / (Ny H) as one binary64 division each,
+ * the same edge clamps, YUV taps converted first); per channel, alpha included, with n = Nx Ny:
+ *   out(x, y) = (sum of F(Nx x + a, Ny y + b) over a < Nx, b < Ny  +  (n >> 1)) / n          (integer division)
+ * Factors (1, 1) — max_factor 1, a source rect not larger than the canvas, an upscale — give ht_draw_list_device's bytes; where sw == Nx W
+ * and sh == Ny H an RGBA entry's output is the exact integer box mean of the source block; a ratio above max_factor is clamped: the fine
+ * frame then decimates itself, and the result is defined all the same.  srcs, n, dst_dev, dst_frame_stride, the binding, the overlap
+ * refusals, the "entry <i>" messages and the enqueue-only contract are ht_draw_list_device's; max_factor outside 1..8 is HT_ERR_INVALID.
+ * ONE launch.  Not part of this: filters other than the block mean, factors above 8, the single-source calls (ht_draw_frames*). */
+ht_status ht_draw_list_filtered_device(ht_ctx *ctx, const ht_draw_source *srcs, int32_t n, int32_t max_factor, void *dst_dev, size_t dst_frame_stride);
+/* The factors that call takes for a source rect of src_width x src_height (1..16384 each) on a canvas_width x canvas_height canvas: the
+ * library's own rule, without a context or a device.  HT_ERR_INVALID (nothing written) for a NULL pointer or an argument out of range. */
+ht_status ht_draw_filter_factors(int32_t src_width, int32_t src_height, int32_t canvas_width, int32_t canvas_height, int32_t max_factor, int32_t *nx,
+                                 int32_t *ny);
 
 /* ---- detect: ccv.grayscale + ccv.detect_objects (ccv.js:22-32, 109-246) ---------------------------------- */
 
@@ -613,8 +632,8 @@ ht_status ht_camshift_align_sources_tensor_device(ht_ctx *ctx, const int32_t *st
  * the same name without `_filtered`, whose table, ring and records are used: a filtered call IS the context's last crop (or align) call,
  * and ht_camshift_crop_result / ht_camshift_align_result report the records the unfiltered call would have written (crop: rx = w / P).
  * max_factor outside 1..8: HT_ERR_INVALID, before anything is enqueued.
- * Not part of this: filters other than the block mean, factors above 8, sub-pixel centres, per-entry formats, int8 output, a prefilter for
- * the canvas draw calls. */
+ * Not part of this: filters other than the block mean, factors above 8, sub-pixel centres, per-entry formats, int8 output.  (The canvas
+ * draw has the same prefilter: ht_draw_list_filtered_device.) */
 ht_status ht_camshift_crop_pairs_filtered_device(ht_ctx *ctx, const ht_cs_pair *pairs, int32_t n, const ht_crop_params *params, int32_t max_factor,
                                                  const ht_patch_format *format, void *out_dev, size_t out_stride);
 ht_status ht_camshift_crop_sources_filtered_device(ht_ctx *ctx, const int32_t *streams, const ht_draw_source *srcs, int32_t n, const ht_crop_params *params,
