@@ -463,12 +463,11 @@ extern "C" ht_status ht_set_geometry(ht_ctx *c, int32_t width, int32_t height, i
     const int n = upto + c->next * 2;  // ccv.js:113
     if (n > HT_MAX_LEVELS) return ht_fail(c, HT_ERR_INVALID, "ht_set_geometry: too many pyramid levels");
     if (level_dims && nlevels_in != n) return ht_fail(c, HT_ERR_INVALID, "ht_set_geometry: level_dims has the wrong number of levels");
-    if (level_dims)  // everything that can be rejected is rejected before the current geometry is torn down
-        for (int i = 0; i < n; i++) {
-            const int lw = level_dims[2 * i], lh = level_dims[2 * i + 1];
-            if (lw < 0 || lh < 0 || lw > width || lh > height || (i == 0 && (lw != width || lh != height)))
-                return ht_fail(c, HT_ERR_INVALID, "ht_set_geometry: bad level_dims");
-        }
+    if (level_dims) {  // everything that can be rejected is rejected before the current geometry is torn down
+        std::string why;
+        const ht_status st = ht_check_level_dims(c->next, width, height, level_dims, n, &why);
+        if (st != HT_OK) return ht_fail(c, st, why);
+    }
     if (c->W == width && c->H == height && c->max_batch >= max_batch && c->nlevels == n && !level_dims) return HT_OK;
     HT_HIP(c, hipStreamSynchronize(c->stream));
     if (c->copy_stream) HT_HIP(c, hipStreamSynchronize(c->copy_stream));

@@ -38,6 +38,34 @@ static HtTap ht_host_tap(int i, double r, int s, int origin) {
     return tp;
 }
 
+// level_dims as ht_set_geometry takes them (n levels, 2 n values; checked on the host before the current geometry is torn down):
+// level 0 is the frame, no level is negative or larger than the frame, and level i + next is at most HALF of level i, floor(size / 2) in
+// both directions — ccv's own rule (ccv.js:126-127) with "at most" in place of "equal".  The scan relies on the last one and nothing on the
+// device clamps it: scale i takes its windows from level i + 2 next (qw = its width - cw / 4) and reads the same window at twice the
+// coordinates on level i + next and at four times on level i.  k_scan_simple, k_scan_deep and k_scan_deep_lds address those bytes straight
+// from the window origin (HT_WIN_SETUP: o0 = off + (4 y + 2 dy) stride + 4 x + 2 dx, ...), with no test against the plane's width or
+// height, so a level i + next wider or taller than half of level i puts the last windows' rows past the end of level i: into the planes
+// behind it, and for the last frame of a batch past the arena.  k_scan_tiles stages only rows and columns inside the planes (its loads are
+// predicated on L0.h / L1.h / the strides and clamped into L2), so there the same windows would read LDS bytes no load has written.
+// The resample kernels need no such relation: every tap is clamped into its source rect.
+static ht_status ht_check_level_dims(int next, int width, int height, const int32_t *level_dims, int n, std::string *why) {
+    for (int i = 0; i < n; i++) {
+        const int lw = level_dims[2 * i], lh = level_dims[2 * i + 1];
+        if (lw < 0 || lh < 0 || lw > width || lh > height || (i == 0 && (lw != width || lh != height)))
+            return *why = "ht_set_geometry: bad level_dims", HT_ERR_INVALID;
+    }
+    for (int i = 0; i + next < n; i++) {
+        const int j = i + next;
+        if (level_dims[2 * j] > level_dims[2 * i] / 2 || level_dims[2 * j + 1] > level_dims[2 * i + 1] / 2) {
+            *why = "ht_set_geometry: level_dims: level " + std::to_string(j) + " (" + std::to_string(level_dims[2 * j]) + "x" + std::to_string(level_dims[2 * j + 1]) +
+                   ") is larger than half of level " + std::to_string(i) + " (" + std::to_string(level_dims[2 * i]) + "x" + std::to_string(level_dims[2 * i + 1]) +
+                   "): the scan reads a window on levels i, i + next, i + 2 next at 4, 2 and 1 times its coordinates";
+            return HT_ERR_INVALID;
+        }
+    }
+    return HT_OK;
+}
+
 // level sizes, arena offsets, pyr_bytes and arena_stride
 static ht_status ht_plan_levels(const HtPlanInputs &in, int width, int height, const int32_t *level_dims, int n, HtGeometryPlan *p, std::string *why) {
     const int next = in.next;
@@ -45,7 +73,7 @@ static ht_status ht_plan_levels(const HtPlanInputs &in, int width, int height, c
     p->pyr_bytes = 0;
     for (int i = 0; i < n; i++) {
         HtDevLevel &L = p->levels[i];
-        if (level_dims) {  // validated by ht_set_geometry
+        if (level_dims) {  // validated by ht_set_geometry (ht_check_level_dims)
             L.w = level_dims[2 * i];
             L.h = level_dims[2 * i + 1];
         } else if (i == 0) {

@@ -149,7 +149,11 @@ int32_t ht_abi_version(void);
 
 /* Fixes frame size and batch capacity; (re)allocates the pyramid arena.  level_dims (optional, 2*nlevels int32:
  * w0,h0,w1,h1,...) lets a JavaScript host pass the sizes V8 computed with Math.pow/Math.floor (ccv.js:119-120,
- * 126-127); NULL = computed here (identical for interval 5, see oracle/ht_oracle.c HO_V8_SCALE6_POW). */
+ * 126-127); NULL = computed here (identical for interval 5, see oracle/ht_oracle.c HO_V8_SCALE6_POW).
+ * level_dims are refused (HT_ERR_INVALID, the current geometry stays) unless level 0 is the frame, every level lies within
+ * 0 .. the frame's size, and level i + interval + 1 is at most floor(size / 2) of level i in both directions: the scan
+ * reads one window on levels i, i + next and i + 2 next at 4, 2 and 1 times its coordinates, and nothing on the device
+ * clamps those reads into the planes (headtrackr_amd/csrc/ht_geometry_plan.h, ht_check_level_dims). */
 ht_status ht_set_geometry(ht_ctx *ctx, int32_t width, int32_t height, int32_t max_batch, const int32_t *level_dims,
                           int32_t nlevels);
 int32_t ht_num_levels(const ht_ctx *ctx);

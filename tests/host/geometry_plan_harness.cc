@@ -7,6 +7,8 @@
 //     (cw ch: the cascade's window, 24 24 when left out)
 //     plans every case, checks what the kernels rely on (check_plan below) and prints one JSON object per line: the scalar results, one
 //     CRC32 per table as ht_set_geometry uploads it, and the level sizes
+//   geometry_plan_harness dims <cases>   one "name W H interval nlevel_dims [w h]..." per line: prints {"name", "status", "why"} of ht_check_level_dims,
+//     the validation ht_set_geometry runs on level_dims before it touches the current geometry
 //   geometry_plan_harness taps <tuples>  one "i r s origin" per line (r as a C hex float): prints "a b t u" of ht_host_tap (t, u as hex floats)
 #include <cstdio>
 #include <cstdlib>
@@ -194,6 +196,24 @@ static int run_plan(const char *path) {
     return 0;
 }
 
+static int run_dims(const char *path) {
+    std::ifstream f(path);
+    std::string line;
+    while (std::getline(f, line)) {
+        if (line.empty() || line[0] == '#') continue;
+        std::istringstream ss(line);
+        int W, H, interval, nd;
+        ss >> g_case >> W >> H >> interval >> nd;
+        std::vector<int32_t> dims(2 * (size_t)std::max(nd, 0));
+        for (auto &d : dims) ss >> d;
+        if (!ss) return fprintf(stderr, "bad case line: %s\n", line.c_str()), 2;
+        std::string why;
+        const ht_status st = ht_check_level_dims(interval + 1, W, H, dims.data(), nd, &why);
+        printf("{\"name\":\"%s\",\"status\":%d,\"why\":\"%s\"}\n", g_case.c_str(), (int)st, why.c_str());
+    }
+    return 0;
+}
+
 static int run_taps(const char *path) {
     std::ifstream f(path);
     std::string rs;
@@ -207,7 +227,8 @@ static int run_taps(const char *path) {
 
 int main(int argc, char **argv) {
     if (argc == 3 && std::string(argv[1]) == "plan") return run_plan(argv[2]);
+    if (argc == 3 && std::string(argv[1]) == "dims") return run_dims(argv[2]);
     if (argc == 3 && std::string(argv[1]) == "taps") return run_taps(argv[2]);
-    fprintf(stderr, "usage: %s plan <cases> | taps <tuples>\n", argv[0]);
+    fprintf(stderr, "usage: %s plan <cases> | dims <cases> | taps <tuples>\n", argv[0]);
     return 2;
 }

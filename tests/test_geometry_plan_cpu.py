@@ -140,3 +140,106 @@ def test_the_plan_is_computed_in_one_place():
     for f in ("ht_geometry_plan.h", "ht_plan_types.h"):
         assert "#include <hip" not in texts[f] and '#include "ht_internal.h"' not in texts[f], f
     assert '#include "ht_plan_types.h"' in texts["ht_internal.h"] and "struct HtResampleJob" not in texts["ht_internal.h"]
+
+
+# ---- level_dims: what ht_set_geometry refuses, and the geometries of tests/test_gpu_pyramid_ties.py ----------------------------------------
+
+def run_dims(harness, tmp_path, cases):
+    """cases: [(name, W, H, interval, dims)] through ht_check_level_dims: {name: (status, why)}"""
+    path = str(tmp_path / "dims.txt")
+    with open(path, "w") as f:
+        for name, w, h, interval, dims in cases:
+            f.write(" ".join([name, str(w), str(h), str(interval), str(len(dims))] + [str(v) for wh in dims for v in wh]) + "\n")
+    r = subprocess.run([harness, "dims", path], capture_output=True, text=True, timeout=120, env=ENV)
+    assert r.returncode == 0 and not r.stderr, r.stderr[-3000:]
+    out = [json.loads(line) for line in r.stdout.splitlines()]
+    assert [o["name"] for o in out] == [c[0] for c in cases]
+    return {o["name"]: (o["status"], o["why"]) for o in out}
+
+
+def test_level_dims_the_scan_cannot_take_are_refused(harness, tmp_path):
+    """Scale i reads one window on levels i, i + next, i + 2 next at 4, 2 and 1 times its coordinates, unclamped (HT_WIN_SETUP in
+    ht_scan.hip): a level i + next larger than floor(size / 2) of level i would put the last windows past the end of level i.  Such
+    level_dims are refused on the host, with a message naming the two levels; ccv's own sizes, smaller ones and empty levels pass."""
+    import pyramid_cases as pc
+
+    ok = pc.ccv_dims(320, 240, 5)
+    cases = [("ccv", 320, 240, 5, ok), ("ccv_i2", 169, 125, 2, pc.ccv_dims(169, 125, 2))]
+
+    def with_level(i, wh):
+        d = list(ok)
+        d[i] = wh
+        return d
+
+    smaller = with_level(6, (100, 70))  # less than half of level 0, and the levels above it halved in turn
+    for i in range(12, 39, 6):
+        smaller[i] = (smaller[i - 6][0] // 2, smaller[i - 6][1] // 2)
+    cases += [("wider_half", 320, 240, 5, with_level(6, (161, 120))), ("taller_half", 320, 240, 5, with_level(6, (160, 121))),
+              ("quarter", 320, 240, 5, with_level(12, (81, 60))),                 # more than half of level 6, a quarter of level 0
+              ("odd_parent", 320, 240, 5, with_level(7, (143, 106))),             # level 1 is 285 x 213: floor(285 / 2) = 142
+              ("last_level", 320, 240, 5, with_level(38, (ok[32][0] // 2 + 1, ok[38][1]))),
+              ("smaller_is_fine", 320, 240, 5, smaller),
+              ("zeros_are_fine", 320, 240, 5, [(320, 240)] + [(0, 0)] * 38),
+              ("level0_is_the_frame", 320, 240, 5, with_level(0, (319, 240))), ("negative", 320, 240, 5, with_level(3, (-1, 5))),
+              ("beyond_the_frame", 320, 240, 5, with_level(1, (321, 10)))]
+    for (w, h) in pc.UNUSUAL_SIZES:
+        for k, dims in enumerate(pc.unusual_dims(w, h)):
+            cases.append((f"unusual_{w}_{k}", w, h, 5, dims))
+    for name, args in pc.COPY_CASES.items():
+        cases.append((name, args[0], args[1], 5, pc.copy_level_case(*args)["dims"]))
+    got = run_dims(harness, tmp_path, cases)
+    for name in ("ccv", "ccv_i2", "smaller_is_fine", "zeros_are_fine", "unusual_333_0", "unusual_333_1", "unusual_641_0", "unusual_641_1", "odd_169x125", "even_164x124"):
+        assert got[name] == (0, ""), (name, got[name])
+    for name, a, b in (("wider_half", 6, 0), ("taller_half", 6, 0), ("quarter", 12, 6), ("odd_parent", 7, 1), ("last_level", 38, 32)):
+        st, why = got[name]
+        assert st == -1 and f"level {a} (" in why and f"larger than half of level {b} (" in why, (name, got[name])
+    for name in ("level0_is_the_frame", "negative", "beyond_the_frame"):
+        assert got[name] == (-1, "ht_set_geometry: bad level_dims"), (name, got[name])
+
+
+def test_recorded_reference_level_sizes_are_accepted(harness, tmp_path):
+    """the level sizes recorded from the reference itself (tests/golden/detect_variants.json) obey the rule with equality"""
+    import detect_variant_cases as dv
+    from conftest import load_golden
+
+    cases = [(c["name"], c["w"], c["h"], c["interval"], dv.recorded_level_dims(c)) for c in load_golden("detect_variants.json")["cases"]]
+    assert len(cases) >= 8
+    got = run_dims(harness, tmp_path, cases)
+    assert all(v == (0, "") for v in got.values()), got
+    for _, _, _, interval, dims in cases:
+        assert all(tuple(dims[i + interval + 1]) == (dims[i][0] // 2, dims[i][1] // 2) for i in range(len(dims) - interval - 1))
+
+
+def test_set_geometry_checks_level_dims_before_it_tears_anything_down():
+    ctx = open(os.path.join(CSRC, "ht_context.hip")).read()
+    body = ctx[ctx.index('extern "C" ht_status ht_set_geometry('):]
+    assert 0 < body.index("ht_check_level_dims(") < body.index("free_geometry(c)")
+    assert len(re.findall(r"\bht_check_level_dims\(", "".join(open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".hip", ".inc", ".cc"))))) == 2  # defined once, called once
+
+
+def test_the_pyramid_tie_geometries_plan(harness, tmp_path):
+    """the geometries of tests/test_gpu_pyramid_ties.py through the planner and the harness's invariants (tiles cover each canvas once, extents
+    and bands hold their taps): the unusual level sizes, the ratio-1 copies, and a tail that starts at generation 1 in all three forms"""
+    import pyramid_cases as pc
+
+    lines = []
+    w, h, interval = pc.TAIL_CASE[:3]
+    for table in (0, 1, 2):
+        lines.append(f"tail{table} {w} {h} 3 {interval} 4 0 0 0 {pc.TAIL_CAP} 1 {table} 1 0 0 0 0")
+    with_dims = [(f"unusual_{w}_{k}", w, h, dims) for (w, h) in pc.UNUSUAL_SIZES for k, dims in enumerate(pc.unusual_dims(w, h))]
+    with_dims += [(name, a[0], a[1], pc.copy_level_case(*a)["dims"]) for name, a in pc.COPY_CASES.items()]
+    for name, w, h, dims in with_dims:
+        for rpt in (4, 2):
+            lines.append(f"{name}_rpt{rpt} {w} {h} 3 5 {rpt} 0 0 0 32768 0 1 0 0 0 0 {len(dims)} " + " ".join(f"{a} {b}" for a, b in dims))
+    path = str(tmp_path / "cases.txt")
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    r = subprocess.run([harness, "plan", path], capture_output=True, text=True, timeout=300, env=ENV)
+    assert r.returncode == 0 and not r.stderr, r.stderr[-3000:]
+    out = {o["name"]: o for o in (json.loads(line) for line in r.stdout.splitlines())}
+    assert len(out) == len(lines) and all(o["status"] == 0 for o in out.values())
+    for table in (0, 1, 2):
+        assert out[f"tail{table}"]["tail_first_gen"] == 1 and out[f"tail{table}"]["tail_table"] == table
+        assert out[f"tail{table}"]["levels"] == [list(d) for d in pc.ccv_dims(pc.TAIL_CASE[0], pc.TAIL_CASE[1], 5)]
+    for name, w, h, dims in with_dims:
+        assert out[name + "_rpt4"]["levels"] == [list(d) for d in dims] and out[name + "_rpt4"]["windows_per_frame"] > 0

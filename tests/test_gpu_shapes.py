@@ -367,6 +367,11 @@ def test_failed_geometry_leaves_a_clean_context(cascade):
         with pytest.raises(HtError) as e:
             c.set_geometry(320, 240, 3, level_dims=np.full(2 * c.num_levels, 999999, dtype=np.int32))
         assert e.value.status == -1
+        half = np.array(ho.pyramid_layout(320, 240), dtype=np.int32)
+        half[6] = (161, 120)  # wider than half of level 0: the scan's windows would leave level 0 (ht_check_level_dims)
+        with pytest.raises(HtError) as e:
+            c.set_geometry(320, 240, 3, level_dims=half)
+        assert e.value.status == -1 and "level 6 (161x120) is larger than half of level 0 (320x240)" in str(e.value)
         c.upload(frames)  # bad level_dims are rejected BEFORE the current geometry is torn down
         c.detect_enqueue(0)
         got, _ = c.detect_collect()
