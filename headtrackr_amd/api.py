@@ -205,7 +205,7 @@ class Context:
         if dst is None:
             self.nframes = n
 
-    # -- the same draw for YUV 4:2:0 frames (NV12 / I420): conversion fused into the draw -------------------------
+    # -- the same draw for YUV frames (4:2:0 NV12 / I420, packed 4:2:2 YUYV / UYVY): conversion fused into the draw ----
     @staticmethod
     def _yuv_code(table, v, what):
         if isinstance(v, str):
@@ -214,11 +214,29 @@ class Context:
             return table[v]
         return int(v)
 
-    def draw_frames_yuv(self, planes, fmt="nv12", matrix="bt601", rect=None):
+    def draw_frames_yuv(self, planes, fmt="nv12", matrix="bt601", rect=None, width=None, height=None):
         """planes: host arrays of n frames — NV12: (y uint8 [n, h, w], uv uint8 [n, ch, cw, 2]); I420: (y, u [n, ch, cw], v [n, ch, cw]) with
         cw = ceil(w / 2), ch = ceil(h / 2) — packed frame by frame and drawn like draw_frames(): converted with the declared integer matrix
-        ('bt601', 'bt709', 'bt601-full', 'bt709-full' or 0 .. 3), scaled on the device, result bound."""
+        ('bt601', 'bt709', 'bt601-full', 'bt709-full' or 0 .. 3), scaled on the device, result bound.
+        fmt 'yuyv' / 'uyvy' (packed 4:2:2): planes is ONE uint8 array, [n, h, 4 cw] (rows of cw macropixels; width defaults to 2 cw, pass
+        width = 2 cw - 1 for an odd frame) or flat with width and height given (n = size / (4 cw h)); staged at 2 B/px."""
         fmt, matrix = self._yuv_code(native.YUV_FORMATS, fmt, "fmt"), self._yuv_code(native.YUV_MATRICES, matrix, "matrix")
+        if fmt in native.YUV_PACKED_422:
+            host = np.ascontiguousarray(planes, dtype=np.uint8)
+            if host.ndim == 3:
+                n, h, row = host.shape
+                w = int(width) if width is not None else row // 2
+                if height is not None and int(height) != h:
+                    raise ValueError("draw_frames_yuv: height differs from the array's rows")
+            else:
+                if host.ndim != 1 or width is None or height is None:
+                    raise ValueError("draw_frames_yuv: a packed 4:2:2 array is [n, h, 4 * ceil(w / 2)], or flat with width and height given")
+                w, h = int(width), int(height)
+                row = 4 * ((w + 1) // 2)
+                n = host.size // (row * h) if row * h > 0 else 0
+            if w <= 0 or h <= 0 or row != 4 * ((w + 1) // 2) or n <= 0 or host.size != n * row * h:
+                raise ValueError("draw_frames_yuv: a packed 4:2:2 frame is h rows of 4 * ceil(w / 2) bytes (width is 2 cw or 2 cw - 1)")
+            return self.draw_frames_yuv_ptr(host.ctypes.data, n, w, h, fmt, matrix, 0, rect)
         planes = [np.ascontiguousarray(p, dtype=np.uint8) for p in planes]
         n, h, w = planes[0].shape
         assert len(planes) == (2 if fmt == native.HT_YUV_NV12 else 3) and all(len(p) == n for p in planes)
@@ -227,7 +245,8 @@ class Context:
         self.draw_frames_yuv_ptr(host.ctypes.data, n, w, h, fmt, matrix, 0, rect)
 
     def draw_frames_yuv_ptr(self, host_ptr: int, n: int, w: int, h: int, fmt: int, matrix: int, frame_stride: int = 0, rect=None):
-        """ht_draw_frames_yuv on a raw host pointer: n tightly packed frames (Y, then UV or U, V), frame_stride bytes apart (0 = packed)"""
+        """ht_draw_frames_yuv on a raw host pointer: n tightly packed frames (Y, then UV or U, V; YUYV / UYVY: the one packed plane),
+        frame_stride bytes apart (0 = packed)"""
         r = self._cs_rect(rect)
         self._check(self._lib.ht_draw_frames_yuv(self._h, host_ptr, n, w, h, fmt, matrix, frame_stride, r.ctypes.data if r is not None else None))
         self.nframes = n
@@ -235,7 +254,8 @@ class Context:
     def draw_frames_yuv_device(self, y: int, u: int, v: int | None, n: int, w: int, h: int, fmt="nv12", matrix="bt601", y_pitch: int = 0, c_pitch: int = 0,
                                stride: int = 0, rect=None, dst: int | None = None, dst_stride: int = 0):
         """The same for planes resident in device memory at y / u / v (NV12: u = the interleaved plane, v None), rows y_pitch / c_pitch bytes
-        (0 = packed), frames `stride` bytes apart in every plane.  dst as draw_frames_device()."""
+        (0 = packed), frames `stride` bytes apart in every plane.  fmt 'yuyv' / 'uyvy': only y and y_pitch are read (the packed plane, base
+        and pitch multiples of 4); u, v and c_pitch are not looked at.  dst as draw_frames_device()."""
         d = native.YUV_FRAMES(y, u, v, y_pitch, c_pitch, stride, w, h, self._yuv_code(native.YUV_FORMATS, fmt, "fmt"), self._yuv_code(native.YUV_MATRICES, matrix, "matrix"))
         r = self._cs_rect(rect)
         self._check(self._lib.ht_draw_frames_yuv_device(self._h, C.byref(d), n, r.ctypes.data if r is not None else None, dst, dst_stride))
@@ -245,8 +265,8 @@ class Context:
     # -- one launch for a list of per-feed sources ----------------------------------------------------------------
     def draw_list(self, entries, dst: int | None = None, dst_stride: int = 0, prefilter: int | None = None):
         """entries: one dict per feed, drawn onto destination frame i in ONE launch (ht_draw_list_device) —
-        {"format": 'rgba' | 'nv12' | 'i420' (or the code), "width", "height", "p0", "p1", "p2" (device pointers: RGBA p0; NV12 Y, UV; I420
-        Y, U, V), "pitch0", "pitch1" (bytes per row, 0 = packed), "matrix" (as draw_frames_yuv_device, ignored for RGBA), "rect" (x, y,
+        {"format": 'rgba' | 'nv12' | 'i420' | 'yuyv' | 'uyvy' (or the code), "width", "height", "p0", "p1", "p2" (device pointers: RGBA p0;
+        NV12 Y, UV; I420 Y, U, V; YUYV / UYVY p0 alone — p1, p2 and pitch1 are not read), "pitch0", "pitch1" (bytes per row, 0 = packed), "matrix" (as draw_frames_yuv_device, ignored for RGBA), "rect" (x, y,
         width, height) or None = the whole source}.  Every feed may have its own allocation, size, format, matrix and rect; pointers may
         repeat.  dst as draw_frames_device().  prefilter = 1..8: ht_draw_list_filtered_device with that max_factor — every canvas pixel the
         mean of a block of the unfiltered draw's samples (draw_filter_factors gives the block per entry); None: the unfiltered call."""
@@ -265,7 +285,7 @@ class Context:
             s.p0, s.p1, s.p2 = e.get("p0"), e.get("p1"), e.get("p2")
             s.pitch0, s.pitch1 = int(e.get("pitch0", 0)), int(e.get("pitch1", 0))
             s.width, s.height = int(e["width"]), int(e["height"])
-            s.format = self._yuv_code(native.DRAW_FORMATS, e.get("format", "rgba"), "format")
+            s.format = self._yuv_code(native.DRAW_LIST_FORMATS, e.get("format", "rgba"), "format")
             s.matrix = self._yuv_code(native.YUV_MATRICES, e.get("matrix", "bt601"), "matrix")
             if e.get("rect") is not None:
                 s.rect = native.CS_RECT(*(int(v) for v in e["rect"]))

@@ -47,6 +47,10 @@ __global__ __launch_bounds__(IG_NT) void k_draw_list_mean_tile(const DmDesc *__r
     _Pragma("unroll 1") for (int b = 0; b < ny; b++)   \
     _Pragma("unroll 1") for (int a = 0; a < nx; a++)   \
     if (const RsTap *s_col = s_colf + a * IG_TW, *s_row = s_rowf + b * IG_TH; true)
+    // the 64 x 16 form draws YUYV / UYVY entries too: every draw of a packed 4:2:2 source is k_draw_list_mean_tile<IG_RPT>'s (dm_launch).  The
+    // 64 x 4 form, which every other filtered call takes, stays the instructions it was: with the branch it measured 10 - 17 % slower on lists
+    // WITHOUT a packed entry (81 against 74 us at max_factor 8, 57 against 49 us at 4)
+#define LP_PACKED_422 (RPT == 4)
 #define LP_PART 4  // LP_SCAFFOLD
 #include "ht_list_parts.inc"
     fm_finish<RPT>(acc, (uint32_t)(nx * ny), LpDwordStore{reinterpret_cast<uint32_t *>(dst + (size_t)blockIdx.z * dst_stride), dw}, dw, dh);
@@ -61,15 +65,69 @@ __global__ __launch_bounds__(IG_NT) void k_draw_list_mean_tile(const DmDesc *__r
 // tools/gpu_draw_filter.py's comparison and the tests that pin both forms to the same bytes.
 int dm_rpt_of(const ht_ctx *c) { return c->draw_filter_rows ? c->draw_filter_rows / FM_ROWS : 1; }
 
-ht_status dm_launch(ht_ctx *c, const char *fn, const std::vector<HtDrawMeanDesc> &desc, uint8_t *dst, size_t dstride) {
+// dw x dh: the destination frames' size — the canvas, or (dm_unpack_sources) a source's own size
+ht_status dm_launch(ht_ctx *c, const char *fn, const std::vector<HtDrawMeanDesc> &desc, uint8_t *dst, size_t dstride, int dw = 0, int dh = 0) {
     ht_status st = dl_upload(c, fn, desc);  // the draw list's staged table (ht_draw_list.hip)
     if (st != HT_OK) return st;
     HtProfScope ps(c, "draw_list_mean");
-    const int rpt = dm_rpt_of(c);
-    const dim3 grid((c->W + IG_TW - 1) / IG_TW, (c->H + rpt * FM_ROWS - 1) / (rpt * FM_ROWS), (unsigned)desc.size());
+    if (!dw) dw = c->W, dh = c->H;
+    const bool packed = std::any_of(desc.begin(), desc.end(), [](const HtDrawMeanDesc &m) { return ht_yuv_is_422(m.d.format); });
+    const int rpt = packed ? IG_RPT : dm_rpt_of(c);  // (LP_PACKED_422: the 64 x 16 form alone holds the packed pixel body)
+    const dim3 grid((dw + IG_TW - 1) / IG_TW, (dh + rpt * FM_ROWS - 1) / (rpt * FM_ROWS), (unsigned)desc.size());
     const DmDesc *tab = reinterpret_cast<const DmDesc *>(c->dl_tab.d);
-    hipLaunchKernelGGL(rpt == 1 ? k_draw_list_mean_tile<1> : k_draw_list_mean_tile<IG_RPT>, grid, dim3(IG_NT), 0, c->stream, tab, dst, dstride, c->W, c->H);
+    hipLaunchKernelGGL(rpt == 1 ? k_draw_list_mean_tile<1> : k_draw_list_mean_tile<IG_RPT>, grid, dim3(IG_NT), 0, c->stream, tab, dst, dstride, dw, dh);
     HT_HIP(c, hipGetLastError());
+    return HT_OK;
+}
+
+// The UNFILTERED draw of a list that holds packed 4:2:2 entries (ht_draw_list_device, ht_draw_frames_yuv*: declared in ht_ingest_yuv.hip).
+// k_draw_list, k_draw_yuv<> and the face-patch kernels are held to the registers they have (tests/golden/draw_filter_neighbours.json), so the
+// packed pixel body lives in this file's kernel alone, and factors (1, 1) are ht_draw_list_device's bytes by the declared rule: the same
+// taps and ratios, one sample per pixel, (s + 0) / 1.  It is not the shape one would build for it: profiles/ingest_422.txt has the cost
+// (10.7 against 9.2 us for k_draw_yuv<NV12> on eight 1080p feeds -> 320 x 240, 125 against 84 us at 1 : 1).
+ht_status dm_launch_unfiltered(ht_ctx *c, const char *fn, const HtDrawDesc *desc, size_t n, uint8_t *dst, size_t dstride) {
+    std::vector<HtDrawMeanDesc> m(n);
+    for (size_t i = 0; i < n; i++) m[i].d = desc[i], m[i].nx = m[i].ny = 1;
+    return dm_launch(c, fn, m, dst, dstride);
+}
+
+// The face-patch calls on packed 4:2:2 sources (declared in ht_crop.hip, called by ht_face_calls.hip behind every check of the call).  Their
+// kernels hold no packed body, so each packed entry's frame is first UNPACKED: drawn 1 : 1 onto an RGBA frame of its own size in the context's
+// staging buffer — at ratio 1 every tap weight is (1, 0), so that frame is the declared conversion itself —, and the entry is rewritten to
+// the RGBA entry of that frame (same size, rect, ratios, stream: the same bytes and the same record by the calls' own contract).  One launch
+// per packed entry (the frames have sizes of their own), the whole frame at 4 B/px: a pass the fused kernels exist to avoid, and what a list
+// without packed entries never pays.
+ht_status dm_unpack_sources(ht_ctx *c, const char *fn, std::vector<HtCropDesc> &desc) {
+    size_t need = 0;
+    for (const HtCropDesc &e : desc)
+        if (ht_yuv_is_422(e.d.format)) need += (size_t)e.SW * (size_t)e.SH * 4;
+    if (!need) return HT_OK;
+    HT_HIP(c, hipSetDevice(c->device));
+    if (c->ingest_src_cap < need) {  // a reallocation waits for the work in flight first, like every reallocation of the library
+        HT_HIP(c, hipStreamSynchronize(c->stream));
+        if (c->d_ingest_src) (void)hipFree(c->d_ingest_src);
+        c->d_ingest_src = nullptr, c->ingest_src_cap = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&c->d_ingest_src), need) != hipSuccess) {
+            (void)hipGetLastError();
+            return ht_fail(c, HT_ERR_NOMEM, std::string(fn) + ": hipMalloc failed (unpacked 4:2:2 sources)");
+        }
+        c->ingest_src_cap = need;
+    }
+    size_t at = 0;
+    std::vector<HtDrawMeanDesc> one(1);
+    for (HtCropDesc &e : desc) {
+        if (!ht_yuv_is_422(e.d.format)) continue;
+        HtDrawMeanDesc &m = one[0];
+        m = HtDrawMeanDesc{};
+        m.d.p0 = (const uint8_t *)e.d.p0, m.d.pitch0 = e.d.pitch0, m.d.rx = m.d.ry = 1.0;
+        m.d.sx = m.d.sy = 0, m.d.sw = e.SW, m.d.sh = e.SH, m.d.cw = e.d.cw, m.d.format = e.d.format, m.d.kc = e.d.kc;
+        m.nx = m.ny = 1;
+        uint8_t *frame = c->d_ingest_src + at;
+        const ht_status st = dm_launch(c, fn, one, frame, 0, e.SW, e.SH);
+        if (st != HT_OK) return st;
+        e.d.p0 = frame, e.d.p1 = e.d.p2 = nullptr, e.d.pitch0 = (size_t)e.SW * 4, e.d.pitch1 = 0, e.d.cw = 0, e.d.format = HT_DRAW_RGBA, e.d.kc = HtYuvCoef{};
+        at += (size_t)e.SW * (size_t)e.SH * 4;
+    }
     return HT_OK;
 }
 

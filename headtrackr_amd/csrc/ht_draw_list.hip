@@ -1,5 +1,5 @@
 // ht_draw_list.hip — the K-feed form of the video -> canvas draw: ONE launch draws a list of sources that share nothing (the reference's
-// loop is one drawImage per feed, main.js:170).  Every entry has its own device allocation(s), size, pitches, format (RGBA, NV12, I420),
+// loop is one drawImage per feed, main.js:170).  Every entry has its own device allocation(s), size, pitches, format (RGBA, NV12, I420; YUYV and UYVY: see dl_launch),
 // matrix and source rect; entry i goes onto destination frame i with the bytes ht_draw_frames_device / ht_draw_frames_yuv_device give for
 // it alone.  Included at the end of ht_ingest.hip, so it is part of the same code object and shares that file's and ht_ingest_yuv.hip's
 // text: the tile constants, ig_channel, ig_chroma_read and, through ht_ingest_bodies.inc, the taps and the three pixel bodies.
@@ -69,6 +69,9 @@ ht_status dl_upload(ht_ctx *c, const char *fn, const std::vector<DESC> &desc) {
 }
 
 ht_status dl_launch(ht_ctx *c, const char *fn, const std::vector<HtDrawDesc> &desc, uint8_t *dst, size_t dstride) {
+    // a list with a packed 4:2:2 entry (YUYV / UYVY) is drawn by the filtered draw's kernel at factors (1, 1): the same bytes, and the one
+    // kernel that holds the packed pixel body (ht_draw_filter.hip)
+    if (std::any_of(desc.begin(), desc.end(), [](const HtDrawDesc &d) { return ht_yuv_is_422(d.format); })) return dm_launch_unfiltered(c, fn, desc.data(), desc.size(), dst, dstride);
     ht_status st = dl_upload(c, fn, desc);
     if (st != HT_OK) return st;
     HtProfScope ps(c, "draw_list");

@@ -1,6 +1,6 @@
 // ht_draw_list_plan.h — the host side of ht_draw_list_device (one launch draws a list of per-feed sources, each with an allocation, size,
 // format, matrix and rect of its own): a list is validated here and turned into the descriptors k_draw_list reads, without HIP.  The rules
-// of an entry are those of ht_draw_frames_device (RGBA) and of ht_draw_frames_yuv_device (NV12 / I420) with n = 1; the YUV rules are not
+// of an entry are those of ht_draw_frames_device (RGBA) and of ht_draw_frames_yuv_device (NV12 / I420 / YUYV / UYVY) with n = 1; the YUV rules are not
 // restated: ht_yuv_plan (ht_yuv_plan.h) is asked.  The ratios rx = sw / W and ry = sh / H are ONE binary64 division each, done here, as
 // oracle/canvas_shim.js divides them and as the single-source calls do on the host.
 //
@@ -15,17 +15,17 @@
 #include "ht_yuv_plan.h"
 
 constexpr int32_t HT_DRAW_LIST_MAX = 65535;  // entries of one call: the grid's z extent
-static_assert(HT_DRAW_RGBA >= HT_YUV_NFORMATS, "the RGBA format number lies outside the YUV range");
+static_assert(!ht_yuv_format_ok(HT_DRAW_RGBA), "the RGBA format number is no YUV format's");
 
 // what a workgroup of k_draw_list reads for its entry (blockIdx.z): 104 bytes, pointers first.  PLANE: how a plane pointer is spelled — the
 // host writes plain pointers, the kernel reads the same bytes as global-address-space pointers (ht_draw_list.hip)
 template <class PLANE>
 struct HtDrawDescT {
-    PLANE p0, p1, p2;             // RGBA: p0.  NV12: Y, UV (p2 = p1).  I420: Y, U, V
+    PLANE p0, p1, p2;             // RGBA: p0.  NV12: Y, UV (p2 = p1).  I420: Y, U, V.  YUYV / UYVY: p0 (p1 = p2 = NULL)
     size_t pitch0, pitch1;        // effective pitches
     double rx, ry;                // sw / W, sh / H
     int32_t sx, sy, sw, sh;       // the source rect
-    int32_t cw, format;           // chroma samples per row of the source (0 for RGBA)
+    int32_t cw, format;           // chroma samples per row of the source (0 for RGBA; YUYV / UYVY: macropixels per row)
     HtYuvCoef kc;                 // the entry's matrix (zeros for RGBA)
 };
 typedef HtDrawDescT<const uint8_t *> HtDrawDesc;
@@ -48,7 +48,7 @@ enum HtDrawListStatus {
     HT_DRAW_LIST_BAD_PITCH0,
     HT_DRAW_LIST_BAD_PITCH1,
     HT_DRAW_LIST_NULL_PLANE,
-    HT_DRAW_LIST_MISALIGNED,   // RGBA base not a multiple of 4, NV12 chroma base odd
+    HT_DRAW_LIST_MISALIGNED,   // RGBA / YUYV / UYVY base not a multiple of 4, NV12 chroma base odd
     HT_DRAW_LIST_BAD_RECT,
 };
 
@@ -57,13 +57,13 @@ inline const char *ht_draw_list_message(int st) {
         case HT_DRAW_LIST_OK: return "ok";
         case HT_DRAW_LIST_BAD_COUNT: return "the list must hold 1..65535 entries";
         case HT_DRAW_LIST_BAD_CANVAS: return "no canvas geometry";
-        case HT_DRAW_LIST_BAD_FORMAT: return "format must be HT_YUV_NV12, HT_YUV_I420 or HT_DRAW_RGBA";
+        case HT_DRAW_LIST_BAD_FORMAT: return "format must be HT_YUV_NV12, HT_YUV_I420, HT_YUV_YUYV, HT_YUV_UYVY or HT_DRAW_RGBA";
         case HT_DRAW_LIST_BAD_SIZE: return "source width/height must be 1..16384";
         case HT_DRAW_LIST_BAD_MATRIX: return "matrix must be 0..3 (HT_YUV_BT601_LIMITED .. HT_YUV_BT709_FULL)";
-        case HT_DRAW_LIST_BAD_PITCH0: return "pitch0 smaller than a row (RGBA: or not a multiple of 4)";
+        case HT_DRAW_LIST_BAD_PITCH0: return "pitch0 smaller than a row (RGBA, YUYV, UYVY: or not a multiple of 4)";
         case HT_DRAW_LIST_BAD_PITCH1: return "chroma pitch smaller than a chroma row, or odd for NV12";
         case HT_DRAW_LIST_NULL_PLANE: return "NULL plane";
-        case HT_DRAW_LIST_MISALIGNED: return "misaligned plane (RGBA: 4-byte alignment, NV12 chroma: an even address)";
+        case HT_DRAW_LIST_MISALIGNED: return "misaligned plane (RGBA, YUYV, UYVY: 4-byte alignment, NV12 chroma: an even address)";
         case HT_DRAW_LIST_BAD_RECT: return "source rect must lie wholly inside the source frame";
     }
     return "unknown";
@@ -93,14 +93,20 @@ inline int ht_draw_list_plan_entry(const ht_draw_source &s, int32_t W, int32_t H
             default: return HT_DRAW_LIST_BAD_FORMAT;  // (count and stride cannot fail for n = 1)
         }
         const bool nv12 = s.format == HT_YUV_FMT_NV12;
-        if (!s.p0 || !s.p1 || (!nv12 && !s.p2)) return HT_DRAW_LIST_NULL_PLANE;
-        if (nv12 && ((uintptr_t)s.p1 & 1)) return HT_DRAW_LIST_MISALIGNED;
-        o.p0 = static_cast<const uint8_t *>(s.p0), o.p1 = static_cast<const uint8_t *>(s.p1);
-        o.p2 = nv12 ? o.p1 : static_cast<const uint8_t *>(s.p2);
+        if (ht_yuv_is_422(s.format)) {  // one plane: p1, p2 and pitch1 are not looked at
+            if (!s.p0) return HT_DRAW_LIST_NULL_PLANE;
+            if ((uintptr_t)s.p0 & 3) return HT_DRAW_LIST_MISALIGNED;
+            o.p0 = static_cast<const uint8_t *>(s.p0);
+        } else {
+            if (!s.p0 || !s.p1 || (!nv12 && !s.p2)) return HT_DRAW_LIST_NULL_PLANE;
+            if (nv12 && ((uintptr_t)s.p1 & 1)) return HT_DRAW_LIST_MISALIGNED;
+            o.p0 = static_cast<const uint8_t *>(s.p0), o.p1 = static_cast<const uint8_t *>(s.p1);
+            o.p2 = nv12 ? o.p1 : static_cast<const uint8_t *>(s.p2);
+            x.base[1] = s.p1, x.bytes[1] = p.c_extent;
+            if (!nv12) x.base[2] = s.p2, x.bytes[2] = p.c_extent;
+        }
         o.pitch0 = p.y_pitch, o.pitch1 = p.c_pitch, o.cw = p.cw, o.kc = HT_YUV_COEF[s.matrix];
         x.base[0] = s.p0, x.bytes[0] = p.y_extent;
-        x.base[1] = s.p1, x.bytes[1] = p.c_extent;
-        if (!nv12) x.base[2] = s.p2, x.bytes[2] = p.c_extent;
     }
     o.format = s.format;
     o.sx = o.sy = 0, o.sw = s.width, o.sh = s.height;

@@ -176,6 +176,8 @@ ht_status face_sources(ht_ctx *c, const FaceCall &k, const int32_t *streams, con
     }
     const int32_t bad = ht_draw_list_overlap(ext.data(), n, k.out_dev, (size_t)(n - 1) * ostride + pbytes);
     if (bad >= 0) return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": a source plane and the output overlap");
+    // packed 4:2:2 entries become the RGBA entries of their unpacked frames (ht_draw_filter.hip); a list without one is untouched
+    if ((st = dm_unpack_sources(c, k.fn, desc)) != HT_OK) return st;
     return k.launch(c, desc, ostride);
 }
 

@@ -1,14 +1,18 @@
 // ht_ingest_bodies.inc — the text of the draw kernels' tile, written once and compiled by every kernel that draws: k_draw_frames
-// (ht_ingest.hip), k_draw_yuv<NV12 | I420> (ht_ingest_yuv.hip) and k_draw_list (ht_draw_list.hip), which holds all three pixel bodies
-// behind one workgroup-uniform branch.  Included INSIDE a kernel, with IG_BODY_PART naming the piece:
+// (ht_ingest.hip), k_draw_yuv<NV12 | I420> (ht_ingest_yuv.hip), k_draw_list (ht_draw_list.hip), which holds all three pixel bodies behind one
+// workgroup-uniform branch, and through ht_list_parts.inc's scaffold the face-patch kernels and k_draw_list_mean_tile (ht_draw_filter.hip).
+// Included INSIDE a kernel, with IG_BODY_PART naming the piece:
 //
 //   IG_BODY_TAPS   X0, Y0 and the tile's 64 column and 16 row taps into s_col / s_row (the kernel declares the arrays and places the barrier)
 //   IG_BODY_RGBA   the RGBA pixel body, behind the barrier
-//   IG_BODY_YUV    the NV12 / I420 pixel body, behind the barrier; FMT is the template parameter or a constant of the enclosing scope
+//   IG_BODY_YUV    the NV12 / I420 / YUYV / UYVY pixel body, behind the barrier; FMT is the template parameter, a constant of the enclosing
+//                  scope or — where one inclusion serves several formats (k_draw_list_mean_tile alone: I420 and the packed 4:2:2,
+//                  LP_PACKED_422) — the entry's format, a workgroup-uniform value.  With a constant NV12 / I420 the packed branches fold away
 //
 // The text reads the names the single-source kernels give their parameters — src, src_pitch, src_stride (RGBA); yp, up, vp, y_pitch,
-// c_pitch, stride, cw, kc (YUV); dst, dst_stride, sx, sy, sw, sh, dw, dh, rx, ry — and k_draw_list binds the same names to its entry's
-// descriptor before it includes a piece (frame strides 0: an entry is one frame).
+// c_pitch, stride, cw, kc (YUV; 4:2:2 reads yp, y_pitch, stride, cw, kc: cw is then the row's macropixel count); dst, dst_stride, sx,
+// sy, sw, sh, dw, dh, rx, ry — and k_draw_list binds the same names to its entry's descriptor before it includes a piece (frame strides
+// 0: an entry is one frame).
 //
 // Shared as TEXT on purpose, as ht_cs_kernels.inc is.  The same bodies as __device__ __forceinline__ functions called from thin kernels
 // compile to other machine code: the extra inlining level reorders the optimiser's passes, and k_draw_frames went from 50 to 74 VGPRs —
@@ -89,35 +93,66 @@
     const int col = threadIdx.x & (IG_TW - 1), r0 = threadIdx.x / IG_TW, x = X0 + col;
     if (x >= dw) return;
     const RsTap cx = s_col[col];
+    // packed 4:2:2 (YUYV / UYVY): ONE plane (yp, y_pitch) of 4-byte macropixels, cw of them per row; up, vp and c_pitch are not read
+    const bool packed = ht_yuv_is_422(FMT);
     const bool pair = sw >= 2;
     const int xa = pair ? min(cx.a, sx + sw - 2) : cx.a;  // the Y pair's anchor, inside the rect
     const int ya_sel = cx.a - xa, yb_sel = cx.b - xa;      // 0 / 1: which byte of the pair each tap takes
     const bool cpair = cw >= 2;
-    const int ca = cpair ? min(cx.a >> 1, cw - 2) : 0;     // the chroma pair's anchor, inside the frame's chroma row
+    // the chroma pair's anchor, inside the frame's chroma row.  4:2:2: the MACROPIXEL pair's — the tap pair (a, b), b == a or a + 1, names
+    // at most two adjacent macropixels, (a >> 1) and (a >> 1) + 1, and a row holds cw whole ones whatever the rect is
+    const int ca = cpair ? min(cx.a >> 1, cw - 2) : 0;
     const int ca_sel = (cx.a >> 1) - ca, cb_sel = (cx.b >> 1) - ca;
+    // a macropixel as a dword, low byte first: YUYV Y0 U Y1 V, UYVY U Y0 V Y1
+    const int ush = FMT == HT_YUV_FMT_UYVY ? 0 : 8, ma_sh = 8 - ush + 16 * (cx.a & 1), mb_sh = 8 - ush + 16 * (cx.b & 1);
     const size_t foff = (size_t)blockIdx.z * stride;
-    const uint8_t *yf = yp + foff + (size_t)xa, *uf = up + foff, *vf = FMT == HT_YUV_FMT_NV12 ? uf : vp + foff;
-    uint32_t ytop[IG_RPT], ybot[IG_RPT], ctop[IG_RPT], cbot[IG_RPT];
+    const uint8_t *yf = yp + foff + (packed ? (size_t)ca * 4 : (size_t)xa), *uf = up + foff, *vf = FMT == HT_YUV_FMT_NV12 ? uf : vp + foff;
+    uint32_t ytop[IG_RPT], ybot[IG_RPT], ctop[IG_RPT], cbot[IG_RPT];  // 4:2:2: macropixel 0 of the pair in y.., macropixel 1 in c..
     double ru[IG_RPT], rt[IG_RPT];
     bool on[IG_RPT];
+    // (the format is tested ONCE around each row loop, not per row: where it is a run-time value the planar loop stays the straight-line
+    // code it is with a constant format, all its reads in front of the first use)
+    if (packed) {
 #pragma unroll
-    for (int k = 0; k < IG_RPT; k++) {
-        const int j = r0 + k * (IG_NT / IG_TW);
-        on[k] = Y0 + j < dh;
-        const RsTap ty = s_row[j];
-        ru[k] = ty.u, rt[k] = ty.t;
-        ytop[k] = ybot[k] = ctop[k] = cbot[k] = 0u;
-        if (on[k]) {
-            const uint8_t *pa = yf + (size_t)ty.a * y_pitch, *pb = yf + (size_t)ty.b * y_pitch;
-            if (pair) {
-                ytop[k] = *reinterpret_cast<const ig_u16b *>(pa);
-                ybot[k] = *reinterpret_cast<const ig_u16b *>(pb);
-            } else {
-                ytop[k] = *pa;
-                ybot[k] = *pb;
+        for (int k = 0; k < IG_RPT; k++) {
+            const int j = r0 + k * (IG_NT / IG_TW);
+            on[k] = Y0 + j < dh;
+            const RsTap ty = s_row[j];
+            ru[k] = ty.u, rt[k] = ty.t;
+            ytop[k] = ybot[k] = ctop[k] = cbot[k] = 0u;
+            if (on[k]) {
+                // ONE 8-byte read per row at a 4-byte-aligned address (the plan requires base and pitch to be multiples of 4), the form the
+                // RGBA body reads its pixel pair in; a frame of 1 or 2 pixels' width has one macropixel and is read as a single dword
+                const uint8_t *pa = yf + (size_t)ty.a * y_pitch, *pb = yf + (size_t)ty.b * y_pitch;
+                if (cpair) {
+                    const ig_u32x2 t2 = *reinterpret_cast<const ig_u32x2 *>(pa), b2 = *reinterpret_cast<const ig_u32x2 *>(pb);
+                    ytop[k] = t2.x, ctop[k] = t2.y, ybot[k] = b2.x, cbot[k] = b2.y;
+                } else {
+                    ytop[k] = ctop[k] = *reinterpret_cast<const uint32_t *>(pa);
+                    ybot[k] = cbot[k] = *reinterpret_cast<const uint32_t *>(pb);
+                }
             }
-            ctop[k] = ig_chroma_read<FMT>(uf, vf, (size_t)(ty.a >> 1) * (FMT == HT_YUV_FMT_NV12 ? c_pitch / 2 : c_pitch) + (size_t)ca, cpair);
-            cbot[k] = ig_chroma_read<FMT>(uf, vf, (size_t)(ty.b >> 1) * (FMT == HT_YUV_FMT_NV12 ? c_pitch / 2 : c_pitch) + (size_t)ca, cpair);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < IG_RPT; k++) {
+            const int j = r0 + k * (IG_NT / IG_TW);
+            on[k] = Y0 + j < dh;
+            const RsTap ty = s_row[j];
+            ru[k] = ty.u, rt[k] = ty.t;
+            ytop[k] = ybot[k] = ctop[k] = cbot[k] = 0u;
+            if (on[k]) {
+                const uint8_t *pa = yf + (size_t)ty.a * y_pitch, *pb = yf + (size_t)ty.b * y_pitch;
+                if (pair) {
+                    ytop[k] = *reinterpret_cast<const ig_u16b *>(pa);
+                    ybot[k] = *reinterpret_cast<const ig_u16b *>(pb);
+                } else {
+                    ytop[k] = *pa;
+                    ybot[k] = *pb;
+                }
+                ctop[k] = ig_chroma_read(FMT, uf, vf, (size_t)(ty.a >> 1) * (FMT == HT_YUV_FMT_NV12 ? c_pitch / 2 : c_pitch) + (size_t)ca, cpair);
+                cbot[k] = ig_chroma_read(FMT, uf, vf, (size_t)(ty.b >> 1) * (FMT == HT_YUV_FMT_NV12 ? c_pitch / 2 : c_pitch) + (size_t)ca, cpair);
+            }
         }
     }
     uint32_t *out = reinterpret_cast<uint32_t *>(dst + (size_t)blockIdx.z * dst_stride) + x;
@@ -125,11 +160,22 @@
     for (int k = 0; k < IG_RPT; k++) {
         if (!on[k]) continue;
         // the four tap pixels as the RGBA8 dwords k_draw_frames would have read
-        const uint32_t ta = ctop[k] >> (16 * ca_sel), tb = ctop[k] >> (16 * cb_sel), ba = cbot[k] >> (16 * ca_sel), bb = cbot[k] >> (16 * cb_sel);
-        const uint32_t p00 = ht_yuv_to_rgba((ytop[k] >> (8 * ya_sel)) & 0xffu, ta & 0xffu, (ta >> 8) & 0xffu, kc);
-        const uint32_t p01 = ht_yuv_to_rgba((ytop[k] >> (8 * yb_sel)) & 0xffu, tb & 0xffu, (tb >> 8) & 0xffu, kc);
-        const uint32_t p10 = ht_yuv_to_rgba((ybot[k] >> (8 * ya_sel)) & 0xffu, ba & 0xffu, (ba >> 8) & 0xffu, kc);
-        const uint32_t p11 = ht_yuv_to_rgba((ybot[k] >> (8 * yb_sel)) & 0xffu, bb & 0xffu, (bb >> 8) & 0xffu, kc);
+        uint32_t p00, p01, p10, p11;
+        if (packed) {  // each tap's macropixel, then Y, U and V by shifts out of the lane's registers
+            // (selected by a per-lane mask word, 0 or ~0, not by a lane-mask register pair: the list kernels with a tensor output are short of SGPRs)
+            const uint32_t am = 0u - (uint32_t)ca_sel, bm = 0u - (uint32_t)cb_sel, tx = ytop[k] ^ ctop[k], bx = ybot[k] ^ cbot[k];
+            const uint32_t ta = ytop[k] ^ (tx & am), tb = ytop[k] ^ (tx & bm), ba = ybot[k] ^ (bx & am), bb = ybot[k] ^ (bx & bm);
+            p00 = ht_yuv_to_rgba((ta >> ma_sh) & 0xffu, (ta >> ush) & 0xffu, (ta >> ush >> 16) & 0xffu, kc);
+            p01 = ht_yuv_to_rgba((tb >> mb_sh) & 0xffu, (tb >> ush) & 0xffu, (tb >> ush >> 16) & 0xffu, kc);
+            p10 = ht_yuv_to_rgba((ba >> ma_sh) & 0xffu, (ba >> ush) & 0xffu, (ba >> ush >> 16) & 0xffu, kc);
+            p11 = ht_yuv_to_rgba((bb >> mb_sh) & 0xffu, (bb >> ush) & 0xffu, (bb >> ush >> 16) & 0xffu, kc);
+        } else {
+            const uint32_t ta = ctop[k] >> (16 * ca_sel), tb = ctop[k] >> (16 * cb_sel), ba = cbot[k] >> (16 * ca_sel), bb = cbot[k] >> (16 * cb_sel);
+            p00 = ht_yuv_to_rgba((ytop[k] >> (8 * ya_sel)) & 0xffu, ta & 0xffu, (ta >> 8) & 0xffu, kc);
+            p01 = ht_yuv_to_rgba((ytop[k] >> (8 * yb_sel)) & 0xffu, tb & 0xffu, (tb >> 8) & 0xffu, kc);
+            p10 = ht_yuv_to_rgba((ybot[k] >> (8 * ya_sel)) & 0xffu, ba & 0xffu, (ba >> 8) & 0xffu, kc);
+            p11 = ht_yuv_to_rgba((ybot[k] >> (8 * yb_sel)) & 0xffu, bb & 0xffu, (bb >> 8) & 0xffu, kc);
+        }
         uint32_t o = 0;
 #pragma unroll
         for (int ch = 0; ch < 4; ch++) o |= ig_channel(p00, p01, p10, p11, 8 * ch, cx.u, cx.t, ru[k], rt[k]);

@@ -14,9 +14,19 @@
 //           bytes U V U V at a 2-byte-aligned address (the chroma base and pitch are even), I420 2 bytes from each of the two planes;
 //           a frame of 1 or 2 pixels' width has one chroma column and is read sample by sample.
 // All 16 (NV12) or 24 (I420) reads of a thread are issued before the first use.  DESIGN.md §2.3 gives the reasoning.
+//
+// Packed 4:2:2 (YUYV, UYVY: one plane of 4-byte macropixels, ht_yuv_plan.h) takes the same calls, the same plan and the same pixel body
+// (IG_BODY_YUV: per row pair ONE 8-byte read of the two macropixels the tap pair can name, anchored at min(a >> 1, cw - 2) at a
+// 4-byte-aligned address, 8 reads per thread in front of the first use; Y, U and V by shifts out of the lane's registers), but not a
+// k_draw_yuv<> of its own: the frames become n descriptors of the one list kernel that is compiled with the packed body,
+// k_draw_list_mean_tile at factors (1, 1) (ht_draw_filter.hip; DESIGN.md §2.3.1 says why).
+#include <vector>
+
+#include "ht_draw_list_plan.h"
 #include "ht_yuv_plan.h"
 
-static_assert(HT_YUV_NV12 == HT_YUV_FMT_NV12 && HT_YUV_I420 == HT_YUV_FMT_I420, "format numbers of the header and of the plan");
+static_assert(HT_YUV_NV12 == HT_YUV_FMT_NV12 && HT_YUV_I420 == HT_YUV_FMT_I420 && HT_YUV_YUYV == HT_YUV_FMT_YUYV && HT_YUV_UYVY == HT_YUV_FMT_UYVY,
+              "format numbers of the header and of the plan");
 static_assert(HT_YUV_BT601_LIMITED == 0 && HT_YUV_BT709_LIMITED == 1 && HT_YUV_BT601_FULL == 2 && HT_YUV_BT709_FULL == 3, "matrix numbers");
 
 namespace {
@@ -25,10 +35,10 @@ namespace {
 typedef uint16_t ig_u16b __attribute__((aligned(1)));
 typedef uint32_t ig_u32h __attribute__((aligned(2)));
 
-// the chroma of one source row at the anchor column: NV12 form, bytes U0 V0 U1 V1 (sample 0 = the anchor, 1 = its right neighbour)
-template <int FMT>
-__device__ __forceinline__ uint32_t ig_chroma_read(const uint8_t *u, const uint8_t *v, size_t off, bool cpair) {
-    if (FMT == HT_YUV_FMT_NV12) {
+// the chroma of one source row at the anchor column: NV12 form, bytes U0 V0 U1 V1 (sample 0 = the anchor, 1 = its right neighbour).  fmt:
+// NV12, or I420 for every other value; a constant wherever the kernel's format is one
+__device__ __forceinline__ uint32_t ig_chroma_read(const int fmt, const uint8_t *u, const uint8_t *v, size_t off, bool cpair) {
+    if (fmt == HT_YUV_FMT_NV12) {
         if (cpair) return *reinterpret_cast<const ig_u32h *>(u + 2 * off);
         return *reinterpret_cast<const uint16_t *>(u + 2 * off);
     }
@@ -51,6 +61,9 @@ __global__ __launch_bounds__(IG_NT) void k_draw_yuv(const uint8_t *__restrict__ 
 #define IG_BODY_PART 3  // IG_BODY_YUV: the four tap pixels converted by ht_yuv_to_rgba, then ig_channel(p00, p01, p10, p11, ..) per channel
 #include "ht_ingest_bodies.inc"
 }
+
+// the unfiltered draw of descriptors that may hold packed 4:2:2 entries: ht_draw_filter.hip, behind the kernel it launches
+ht_status dm_launch_unfiltered(ht_ctx *c, const char *fn, const HtDrawDesc *desc, size_t n, uint8_t *dst, size_t dstride);
 
 struct IgYuvCall {  // a validated call: the source as the device will see it
     HtYuvPlan plan;
@@ -77,12 +90,22 @@ ht_status igy_check(ht_ctx *c, const char *fn, int32_t n, int32_t width, int32_t
     return HT_OK;
 }
 
-ht_status igy_launch(ht_ctx *c, const IgYuvCall &q, const uint8_t *y, const uint8_t *u, const uint8_t *v, int32_t n, uint8_t *dst, size_t dstride) {
-    HtProfScope ps(c, "draw_yuv");
+ht_status igy_launch(ht_ctx *c, const char *fn, const IgYuvCall &q, const uint8_t *y, const uint8_t *u, const uint8_t *v, int32_t n, uint8_t *dst, size_t dstride) {
     const double rx = (double)q.sw / (double)c->W, ry = (double)q.sh / (double)c->H;  // canvas_shim.js: one binary64 division each
-    const dim3 grid((c->W + IG_TW - 1) / IG_TW, (c->H + IG_TH - 1) / IG_TH, n);
     const HtYuvPlan &p = q.plan;
     const HtYuvCoef kc = HT_YUV_COEF[q.matrix];
+    if (ht_yuv_is_422(q.format)) {  // one descriptor per frame through the one kernel that holds the packed pixel body (ht_draw_filter.hip; its timer)
+        std::vector<HtDrawDesc> desc((size_t)n);
+        for (int32_t f = 0; f < n; f++) {
+            HtDrawDesc &d = desc[(size_t)f];
+            d = HtDrawDesc{};
+            d.p0 = y + (size_t)f * p.stride, d.pitch0 = p.y_pitch, d.rx = rx, d.ry = ry;
+            d.sx = q.sx, d.sy = q.sy, d.sw = q.sw, d.sh = q.sh, d.cw = p.cw, d.format = q.format, d.kc = kc;
+        }
+        return dm_launch_unfiltered(c, fn, desc.data(), desc.size(), dst, dstride);
+    }
+    HtProfScope ps(c, "draw_yuv");
+    const dim3 grid((c->W + IG_TW - 1) / IG_TW, (c->H + IG_TH - 1) / IG_TH, n);
     if (q.format == HT_YUV_FMT_NV12)
         hipLaunchKernelGGL(k_draw_yuv<HT_YUV_FMT_NV12>, grid, dim3(IG_NT), 0, c->stream, y, u, u, p.y_pitch, p.c_pitch, p.stride, dst, dstride, q.sx, q.sy, q.sw,
                            q.sh, p.cw, c->W, c->H, rx, ry, kc);
@@ -97,7 +120,7 @@ ht_status igy_launch(ht_ctx *c, const IgYuvCall &q, const uint8_t *y, const uint
 ht_status igy_draw_bound(ht_ctx *c, const char *fn, const IgYuvCall &q, const uint8_t *y, const uint8_t *u, const uint8_t *v, int32_t n) {
     ht_status st = ht_frames_own_reserve(c, q.fbytes * (size_t)n, fn);
     if (st != HT_OK) return st;
-    if ((st = igy_launch(c, q, y, u, v, n, c->d_frames_own, q.fbytes)) != HT_OK) return st;
+    if ((st = igy_launch(c, fn, q, y, u, v, n, c->d_frames_own, q.fbytes)) != HT_OK) return st;
     ht_frames_bind_own(c, n);
     return HT_OK;
 }
@@ -112,11 +135,13 @@ extern "C" ht_status ht_draw_frames_yuv_device(ht_ctx *c, const ht_yuv_frames *s
     IgYuvCall q;
     ht_status st = igy_check(c, fn, n, s->width, s->height, s->format, s->matrix, s->y_pitch, s->c_pitch, s->frame_stride, src_rect, &q);
     if (st != HT_OK) return st;
-    const bool nv12 = q.format == HT_YUV_FMT_NV12;
-    if (!s->y || !s->u || (!nv12 && !s->v)) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": NULL plane");
+    const bool nv12 = q.format == HT_YUV_FMT_NV12, packed = ht_yuv_is_422(q.format);  // packed: one plane, u and v are not looked at
+    if (!s->y || (!packed && (!s->u || (!nv12 && !s->v)))) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": NULL plane");
     if (nv12 && ((uintptr_t)s->u & 1)) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": the NV12 chroma plane must start at an even address");
+    if (packed && ((uintptr_t)s->y & 3)) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": misaligned YUYV / UYVY plane (4-byte alignment required)");
     if ((uintptr_t)dst_dev & 3) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": misaligned destination (4-byte alignment required)");
-    const uint8_t *y = static_cast<const uint8_t *>(s->y), *u = static_cast<const uint8_t *>(s->u), *v = nv12 ? nullptr : static_cast<const uint8_t *>(s->v);
+    const uint8_t *y = static_cast<const uint8_t *>(s->y), *u = packed ? nullptr : static_cast<const uint8_t *>(s->u),
+                  *v = nv12 || packed ? nullptr : static_cast<const uint8_t *>(s->v);
     const HtYuvPlan &p = q.plan;
     const auto overlaps = [&](const void *d, size_t nd) { return ig_overlap(y, p.y_extent, d, nd) || ig_overlap(u, p.c_extent, d, nd) || ig_overlap(v, p.c_extent, d, nd); };
     HT_HIP(c, hipSetDevice(c->device));
@@ -129,7 +154,7 @@ extern "C" ht_status ht_draw_frames_yuv_device(ht_ctx *c, const ht_yuv_frames *s
     const size_t dstride = dst_frame_stride ? dst_frame_stride : q.fbytes;
     if ((dstride & 3) || dstride < q.fbytes) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": destination frame stride smaller than a frame or not a multiple of 4");
     if (overlaps(dst_dev, (size_t)(n - 1) * dstride + q.fbytes)) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": a source plane and the destination overlap");
-    return igy_launch(c, q, y, u, v, n, static_cast<uint8_t *>(dst_dev), dstride);
+    return igy_launch(c, fn, q, y, u, v, n, static_cast<uint8_t *>(dst_dev), dstride);
 }
 
 extern "C" ht_status ht_draw_frames_yuv(ht_ctx *c, const uint8_t *host, int32_t n, int32_t width, int32_t height, int32_t format, int32_t matrix,
@@ -139,7 +164,7 @@ extern "C" ht_status ht_draw_frames_yuv(ht_ctx *c, const uint8_t *host, int32_t 
     const char *fn = "ht_draw_frames_yuv";
     // staged tightly packed, Y then chroma, at 1.5 B/px.  NV12 wants its chroma plane at an even address: a frame of odd width AND odd
     // height has an odd Y plane, so it is staged one byte into the buffer (the Y plane needs no alignment) and frames one byte further
-    // apart
+    // apart.  A packed 4:2:2 frame is 4 cw h bytes at 2 B/px, a multiple of 4 already: no lead, and every frame starts on a macropixel
     HtYuvPlan p0;
     const size_t fsz = ht_yuv_plan(width, height, format, matrix, 0, 0, 0, 1, &p0) == HT_YUV_PLAN_OK ? p0.packed_frame : 0;
     const size_t lead = (format == HT_YUV_FMT_NV12) ? (fsz & 1) : 0, dstep = fsz + lead;
@@ -168,6 +193,8 @@ extern "C" ht_status ht_draw_frames_yuv(ht_ctx *c, const uint8_t *host, int32_t 
     if (n == 1 || (sstep == fsz && dstep == fsz)) HT_HIP(c, hipMemcpyAsync(stage, host, n == 1 ? fsz : fsz * (size_t)n, hipMemcpyHostToDevice, c->stream));
     else
         for (int32_t f = 0; f < n; f++) HT_HIP(c, hipMemcpyAsync(stage + (size_t)f * dstep, host + (size_t)f * sstep, fsz, hipMemcpyHostToDevice, c->stream));
-    const uint8_t *y = stage, *u = stage + (size_t)width * (size_t)height, *v = format == HT_YUV_FMT_NV12 ? nullptr : u + (size_t)q.plan.cw * (size_t)q.plan.ch;
+    const bool packed = ht_yuv_is_422(format);
+    const uint8_t *y = stage, *u = packed ? nullptr : stage + (size_t)width * (size_t)height,
+                  *v = format == HT_YUV_FMT_I420 ? u + (size_t)q.plan.cw * (size_t)q.plan.ch : nullptr;
     return igy_draw_bound(c, fn, q, y, u, v, n);
 }

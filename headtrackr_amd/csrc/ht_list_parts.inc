@@ -16,7 +16,10 @@
 //                     ht_ingest_bodies.inc, their parameter names bound to the entry's descriptor d (frame strides 0: an entry is one
 //                     frame).  LP_EACH_PASS, when the kernel defines it, stands in front of each body's block — statement heads that end
 //                     where a block may follow (ht_filter.hip: the loops over the fine patch's slices and, as an if's initialiser, the
-//                     slice's s_col / s_row); it is undefined again behind the scaffold
+//                     slice's s_col / s_row); it is undefined again behind the scaffold.  LP_PACKED_422, when the kernel defines it (as a constant expression that is true), makes the
+//                     third body take the packed 4:2:2 formats (YUYV, UYVY) besides I420 (ht_draw_filter.hip: the one kernel every draw of
+//                     a packed source goes through); without it a kernel is the instructions it was, and its host path hands it no such entry (the
+//                     face-patch calls unpack a packed entry's frame to RGBA first: dm_unpack_sources)
 //
 // The including kernel binds: tab, states, recs, dw, dh, cw_canvas, ch_canvas, margin_q8, flags (its parameters; dst and dst_stride for the
 // bodies), and the tile through IG_TW / IG_TH / IG_RPT / IG_NT as the pixel bodies read them (a kernel with another tile declares
@@ -112,7 +115,12 @@
 #include "ht_ingest_bodies.inc"
             }
         } else {
+#ifdef LP_PACKED_422  // (a constant expression of the kernel) I420, YUYV or UYVY in this ONE inclusion and ONE compiled body: the format is a
+            // workgroup-uniform value in it; where the expression is false FMT folds to the constant and the kernel is the instructions it was
+            const int FMT = (LP_PACKED_422) ? format : HT_YUV_FMT_I420;
+#else
             constexpr int FMT = HT_YUV_FMT_I420;
+#endif
             LP_EACH_PASS {
 #define IG_BODY_PART 3  // IG_BODY_YUV
 #include "ht_ingest_bodies.inc"
@@ -120,6 +128,7 @@
         }
     }
 #undef LP_EACH_PASS
+#undef LP_PACKED_422
 
 #else
 #error "LP_PART names no piece"

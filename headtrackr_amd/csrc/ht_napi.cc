@@ -650,14 +650,18 @@ napi_value DrawFrames(napi_env env, napi_callback_info info) {
     return nullptr;
 }
 
-// bytes of one tightly packed YUV 4:2:0 frame (Y, then the chroma planes); 0: no such frame
-size_t yuv_frame_bytes(int32_t w, int32_t h) {
+bool yuv_packed_422(int32_t format) { return format == HT_YUV_YUYV || format == HT_YUV_UYVY; }
+
+// bytes of one tightly packed YUV frame: 4:2:0 (Y, then the chroma planes) w h + 2 cw ch, packed 4:2:2 (YUYV / UYVY: one plane of 4-byte
+// macropixels) 4 cw h; 0: no such frame.  A format the library does not know is sized as 4:2:0 and refused by the library
+size_t yuv_frame_bytes(int32_t w, int32_t h, int32_t format) {
     if (w <= 0 || h <= 0 || w > 16384 || h > 16384) return 0;
+    if (yuv_packed_422(format)) return 4 * (size_t)((w + 1) / 2) * (size_t)h;
     return (size_t)w * h + 2 * (size_t)((w + 1) / 2) * ((h + 1) / 2);
 }
 
 napi_value DrawFramesYuv(napi_env env, napi_callback_info info) {
-    static const char *usage = "drawFramesYuv(ctx, Uint8Array planes, n, w, h, format, matrix, Int32Array rect[4] | null) with planes.length >= n * (w*h + 2*ceil(w/2)*ceil(h/2))";
+    static const char *usage = "drawFramesYuv(ctx, Uint8Array planes, n, w, h, format, matrix, Int32Array rect[4] | null) with planes.length >= n * (w*h + 2*ceil(w/2)*ceil(h/2)), YUYV / UYVY: n * 4*ceil(w/2)*h";
     Args a(env, info, 8);
     Locked L;
     uint8_t *data = nullptr;
@@ -668,7 +672,7 @@ napi_value DrawFramesYuv(napi_env env, napi_callback_info info) {
     if (!a.ctx(7, &L)) return nullptr;
     if (!a.bytes(1, &data, &len) || !a.i32(2, &n) || !a.i32(3, &w) || !a.i32(4, &h) || !a.i32(5, &format) || !a.i32(6, &matrix) || !get_rect(env, a.argv[7], &r, &rp) || n <= 0)
         return type_error(env, usage);
-    const size_t fsz = yuv_frame_bytes(w, h);
+    const size_t fsz = yuv_frame_bytes(w, h, format);
     if (!fsz || !frames_fit(0, (size_t)n, fsz, fsz, len)) return range_error(env, usage);
     ht_status st = ht_draw_frames_yuv(L.ctx, data, n, w, h, format, matrix, 0, rp);
     if (st != HT_OK) return throw_ht(env, L.ctx, st, "ht_draw_frames_yuv");
@@ -1380,7 +1384,9 @@ napi_value DrawFramesYuvDevice(napi_env env, napi_callback_info info) {
         return type_error(env, usage);
     a.opt_bool(13, &wait);
     // what the library checks itself — format, matrix, strides smaller than a plane, alignment, overlap — is left to it
-    const size_t fsz = yuv_frame_bytes(w, h);
+    const size_t fsz = yuv_frame_bytes(w, h, format);
+    const bool packed = yuv_packed_422(format);
+    if (packed && (soff & 3)) return range_error(env, "drawFramesYuvDevice: srcOffset of a YUYV / UYVY frame must be a multiple of 4");
     bool inside = fsz && frames_fit(soff, (size_t)n, stride ? stride : fsz, fsz, src->bytes);
     if (dst) {
         const size_t fb = frame_bytes(env, L.ctx, 4, "drawFramesYuvDevice");
@@ -1392,7 +1398,8 @@ napi_value DrawFramesYuvDevice(napi_env env, napi_callback_info info) {
     std::memset(&d, 0, sizeof(d));
     const char *base = static_cast<char *>(src->ptr) + soff;
     const size_t cplane = (size_t)((w + 1) / 2) * ((h + 1) / 2);
-    d.y = base, d.u = base + (size_t)w * h, d.v = format == HT_YUV_I420 ? base + (size_t)w * h + cplane : nullptr;
+    d.y = base;  // YUYV / UYVY: the one packed plane; u and v stay NULL
+    if (!packed) d.u = base + (size_t)w * h, d.v = format == HT_YUV_I420 ? base + (size_t)w * h + cplane : nullptr;
     d.frame_stride = stride ? stride : (n > 1 ? fsz : 0);
     d.width = w, d.height = h, d.format = format, d.matrix = matrix;
     ht_status st = ht_draw_frames_yuv_device(L.ctx, &d, n, rp, dst ? static_cast<char *>(dst->ptr) + doff : nullptr, dstride);
@@ -1416,7 +1423,7 @@ bool get_draw_entry(napi_env env, napi_value e, ht_draw_source *s) {
     }
     if (!get_prop(env, e, "width", &v) || !get_i32(env, v, &s->width) || !get_prop(env, e, "height", &v) || !get_i32(env, v, &s->height))
         return type_error(env, "drawListDevice: entry.width and entry.height are integers") != nullptr;
-    if (!get_prop(env, e, "format", &v) || !get_i32(env, v, &s->format)) return type_error(env, "drawListDevice: entry.format is YUV_NV12, YUV_I420 or DRAW_RGBA") != nullptr;
+    if (!get_prop(env, e, "format", &v) || !get_i32(env, v, &s->format)) return type_error(env, "drawListDevice: entry.format is YUV_NV12, YUV_I420, YUV_YUYV, YUV_UYVY or DRAW_RGBA") != nullptr;
     // optional like the trailing arguments of the entry points: absent or undefined is 0; anything else has to be a byte offset
     if (get_prop(env, e, "offset", &v) && napi_typeof(env, v, &vt) == napi_ok && vt != napi_undefined && !get_offset(env, v, &off))
         return type_error(env, "drawListDevice: entry.offset is a byte offset") != nullptr;
@@ -1427,11 +1434,13 @@ bool get_draw_entry(napi_env env, napi_value e, ht_draw_source *s) {
     // what the library checks itself — format, matrix, alignment, the rect, overlap — is left to it
     const bool rgba = s->format == HT_DRAW_RGBA;
     const size_t ysz = s->width > 0 && s->height > 0 && s->width <= 16384 && s->height <= 16384 ? (size_t)s->width * (size_t)s->height : 0;
-    const size_t fsz = rgba ? ysz * 4 : yuv_frame_bytes(s->width, s->height);
+    const bool packed = yuv_packed_422(s->format);
+    const size_t fsz = rgba ? ysz * 4 : yuv_frame_bytes(s->width, s->height, s->format);
     if (!fsz || !frames_fit(off, 1, fsz, fsz, dev->bytes)) return range_error(env, "drawListDevice: an entry's frame lies outside its device buffer") != nullptr;
+    if (packed && (off & 3)) return range_error(env, "drawListDevice: entry.offset of a YUYV / UYVY frame must be a multiple of 4") != nullptr;
     const char *base = static_cast<char *>(dev->ptr) + off;
     s->p0 = base;
-    if (!rgba) {
+    if (!rgba && !packed) {
         s->p1 = base + ysz;
         s->p2 = s->format == HT_YUV_I420 ? base + ysz + (size_t)((s->width + 1) / 2) * ((s->height + 1) / 2) : nullptr;
     }
@@ -1835,6 +1844,7 @@ napi_value Init(napi_env env, napi_value exports) {
     } consts[] = {{"abiVersion", ht_abi_version()},   {"INPUT_GRAY_IN_R", HT_INPUT_GRAY_IN_R}, {"INPUT_RGBA", HT_INPUT_RGBA}, {"DETECT_WHITEBALANCE", HT_DETECT_WHITEBALANCE},
                   {"SCAN_STATS", HT_SCAN_STATS},      {"BP_RGBA8", HT_BP_RGBA8},               {"BP_F64", HT_BP_F64},
                   {"YUV_NV12", HT_YUV_NV12},          {"YUV_I420", HT_YUV_I420},               {"DRAW_RGBA", HT_DRAW_RGBA},
+                  {"YUV_YUYV", HT_YUV_YUYV},          {"YUV_UYVY", HT_YUV_UYVY},
                   {"CSB_UNTOUCHED", HT_CSB_UNTOUCHED}, {"CSB_FACE", HT_CSB_FACE},              {"CSB_FALLBACK", HT_CSB_FALLBACK}, {"CSB_DEFERRED", HT_CSB_DEFERRED},
                   {"CSF_ASSOCIATE", HT_CSF_ASSOCIATE}, {"CSF_MAX_SLOTS", HT_CSF_MAX_SLOTS},
                   {"CROP_EMPTY", HT_CROP_EMPTY},      {"CROP_FACE", HT_CROP_FACE},             {"CROP_SQUARE", HT_CROP_SQUARE},

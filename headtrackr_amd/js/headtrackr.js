@@ -24,7 +24,7 @@
  *                                        of the loop bench.py times; every C-ABI export has a JS name (INTEGRATION.md)
  *   hostAlloc(bytes)                     pinned host memory for frames that cross PCIe every call
  *   ccv.drawFrames(video, canvas[, rect])  the loop's video -> canvas drawImage (main.js:170) scaled on the device -> ht_draw_frames_device;
- *                                           video may be {width, height, format: 'nv12' | 'i420', matrix, data} -> ht_draw_frames_yuv_device
+ *                                           video may be {width, height, format: 'nv12' | 'i420' | 'yuyv' | 'uyvy', matrix, data} -> ht_draw_frames_yuv_device
  *
  * "canvas" is anything with width, height and getContext('2d') -> {getImageData, putImageData, drawImage,
  * createImageData}; ./canvas.js provides one for Node.  Failure conventions are the reference's: empty arrays,
@@ -156,15 +156,20 @@ headtrackr.ccv.grayscale = function (canvas) { /* ccv.js:22-32, in place, return
  * canvas.height), or with rect = [sx, sy, sw, sh] (wholly inside the video) the 9-argument form.  The video's pixels are uploaded, scaled
  * with the declared resampler (ht_draw_frames_device) and copied back into the canvas: the bytes canvas.js's drawImage writes.  With an
  * addon that lacks the calls the canvas's own drawImage does it. */
-/* YUV 4:2:0 sources (NV12 / I420): names -> the numbers of include/headtrackr_hip.h, and the packed layout every YUV call here uses: a
+/* YUV sources: names -> the numbers of include/headtrackr_hip.h, and the packed layout every YUV call here uses.  4:2:0 (NV12 / I420): a
  * frame is Y (w h bytes), then UV (NV12) or U, V (I420), ceil(w/2) x ceil(h/2) chroma samples.  NV12's chroma plane has to start at an
- * even device address: a frame of odd width and odd height is placed `lead` = 1 byte into its buffer, frames `step` = bytes + 1 apart. */
-const YUV_FORMATS = { nv12: 0, i420: 1 }, YUV_MATRICES = { bt601: 0, bt709: 1, 'bt601-full': 2, 'bt709-full': 3 };
+ * even device address: a frame of odd width and odd height is placed `lead` = 1 byte into its buffer, frames `step` = bytes + 1 apart.
+ * Packed 4:2:2 (YUYV / UYVY, what an uncompressed webcam or a capture card delivers): ONE plane of 4-byte macropixels, 4 ceil(w/2) h bytes
+ * at 2 B/px; a frame is a multiple of 4 bytes and starts at a multiple of 4, so lead = 0 and step = bytes.  The draw calls take them
+ * (drawFrames, DeviceBatch draw / drawList / drawListBound, with opts.prefilter too), and so do cropFeeds / alignFeeds (the library unpacks
+ * such a feed's frame to RGBA first). */
+const YUV_FORMATS = { nv12: 0, i420: 1, yuyv: 4, uyvy: 5 }, YUV_MATRICES = { bt601: 0, bt709: 1, 'bt601-full': 2, 'bt709-full': 3 };
 function yuvLayout(width, height, format, matrix, who) {
   const fmt = YUV_FORMATS[format], mat = YUV_MATRICES[matrix === undefined ? 'bt601' : matrix];
-  if (fmt === undefined) throw new RangeError(who + ": format is 'nv12' or 'i420'");
+  if (fmt === undefined) throw new RangeError(who + ": format is 'nv12', 'i420', 'yuyv' or 'uyvy'");
   if (mat === undefined) throw new RangeError(who + ": matrix is 'bt601', 'bt709', 'bt601-full' or 'bt709-full'");
   if (!(width > 0 && height > 0)) throw new RangeError(who + ': width and height must be positive');
+  if (fmt >= 4) { const packed = 4 * ((width + 1) >> 1) * height; return { fmt: fmt, mat: mat, bytes: packed, lead: 0, step: packed }; }
   const bytes = width * height + 2 * ((width + 1) >> 1) * ((height + 1) >> 1), lead = fmt === 0 ? (bytes & 1) : 0;
   return { fmt: fmt, mat: mat, bytes: bytes, lead: lead, step: bytes + lead };
 }
@@ -179,11 +184,11 @@ headtrackr.ccv.drawFrames = function (video, canvas, rect) {
     return c[key];
   };
   if (video.format !== undefined && video.format !== 'rgba') {
-    /* a video-like object {width, height, format: 'nv12' | 'i420', matrix, data: Uint8Array}: there is no host route — a canvas cannot
+    /* a video-like object {width, height, format: 'nv12' | 'i420' | 'yuyv' | 'uyvy', matrix, data: Uint8Array}: there is no host route — a canvas cannot
      * draw planes — so an addon without the call is an error */
     const L = yuvLayout(vw, vh, video.format, video.matrix, 'ccv.drawFrames');
     if (typeof A.drawFramesYuvDevice !== 'function') throw new Error('ccv.drawFrames: this headtrackr_hip.node has no drawFramesYuvDevice (rebuild it)');
-    if (!(video.data instanceof Uint8Array) || video.data.length < L.bytes) throw new RangeError('ccv.drawFrames: video.data is a Uint8Array of w*h + 2*ceil(w/2)*ceil(h/2) bytes');
+    if (!(video.data instanceof Uint8Array) || video.data.length < L.bytes) throw new RangeError('ccv.drawFrames: video.data is a Uint8Array of w*h + 2*ceil(w/2)*ceil(h/2) bytes (yuyv / uyvy: 4*ceil(w/2)*h)');
     if (!(w > 0 && h > 0)) return canvas;
     const c = contextFor(headtrackr.cascade, 5);
     ensureGeometry(c, w, h, 1, headtrackr.cascade, 5);
@@ -428,13 +433,13 @@ headtrackr.ccv.detect_objects_batch = function (frames, n, w, h, cascade, interv
  *   opts.source = {width, height, sets}: a second device buffer of `sets` SOURCE-size frame sets (n frames of width x height each) and the
  *   loop's video -> canvas drawImage (main.js:170) between the two buffers, on the device (ht_draw_frames_device):
  *     uploadSource(frames, sset = 0)       host -> HBM once (frames: Uint8Array of n*width*height*4 bytes)
- *   opts.sourceFormat = 'nv12' | 'i420' (+ opts.sourceMatrix = 'bt601' (default) | 'bt709' | 'bt601-full' | 'bt709-full'): the source sets
+ *   opts.sourceFormat = 'nv12' | 'i420' | 'yuyv' | 'uyvy' (+ opts.sourceMatrix = 'bt601' (default) | 'bt709' | 'bt601-full' | 'bt709-full'): the source sets
  *   hold YUV 4:2:0 frames, each packed Y, then UV or U, V (width*height + 2*ceil(width/2)*ceil(height/2) bytes): uploadSource, draw and
  *   drawBound then move and read 1.5 B/px, the colour conversion is fused into the draw (ht_draw_frames_yuv_device)
  *     draw(sset, set, rect)                source set `sset` scaled onto work set `set` (rect: Int32Array [x, y, width, height] inside a source
  *                                           frame, default the whole frame); enqueue only, except that with depth > 1 it waits — the other
  *                                           contexts read the work set on streams of their own
- *   opts.sources = [{width, height, format = 'rgba' | 'nv12' | 'i420', matrix, sets = 1}, ...] (instead of opts.source): one entry per feed,
+ *   opts.sources = [{width, height, format = 'rgba' | 'nv12' | 'i420' | 'yuyv' | 'uyvy', matrix, sets = 1}, ...] (instead of opts.source): one entry per feed,
  *   every feed with its own device buffer, size and format; ONE launch draws them all (ht_draw_list_device)
  *     uploadSourceOf(i, frame, sset = 0)   feed i's packed frame host -> HBM
  *     drawList(sset, set, rects, opts)     every feed onto its frame of frame set `set`; rects: null, or a rect / null per feed;
@@ -802,7 +807,8 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     return A.camshiftBackProjectPairs(ctxs[0], pairs, kind === 'f64' ? A.BP_F64 : A.BP_RGBA8);
   };
   const source = opts.source || null;
-  /* opts.sourceFormat 'nv12' | 'i420' (+ opts.sourceMatrix): the source sets hold YUV 4:2:0 frames at 1.5 B/px, packed as yuvLayout says */
+  /* opts.sourceFormat 'nv12' | 'i420' | 'yuyv' | 'uyvy' (+ opts.sourceMatrix): the source sets hold YUV frames at 1.5 B/px (4:2:0) or 2 B/px
+   * (packed 4:2:2), packed as yuvLayout says */
   const yuv = source && opts.sourceFormat !== undefined && opts.sourceFormat !== 'rgba' ? yuvLayout(source.width, source.height, opts.sourceFormat, opts.sourceMatrix, 'DeviceBatch') : null;
   if (yuv && typeof A.drawFramesYuvDevice !== 'function') throw new Error('DeviceBatch: this headtrackr_hip.node has no drawFramesYuvDevice (rebuild it) — needed for opts.sourceFormat');
   const sframeBytes = source ? (yuv ? yuv.bytes : source.width * source.height * 4) : 0;
@@ -829,7 +835,7 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     drawSource(sset, rect, null, 0, false);
     bound = -1;
   };
-  /* opts.sources = [{width, height, format = 'rgba' | 'nv12' | 'i420', matrix, sets = 1}, ...]: one entry per feed, each feed with a device
+  /* opts.sources = [{width, height, format = 'rgba' | 'nv12' | 'i420' | 'yuyv' | 'uyvy', matrix, sets = 1}, ...]: one entry per feed, each feed with a device
    * buffer of its own that holds `sets` packed frames (RGBA rows; Y, then UV or U, V — an odd x odd NV12 frame one byte into its slot, as
    * yuvLayout says).  drawList / drawListBound draw all n feeds in ONE launch (ht_draw_list_device), every feed under a rect of its own. */
   const DRAW_RGBA = 16; /* HT_DRAW_RGBA */

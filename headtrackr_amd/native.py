@@ -137,10 +137,13 @@ PATCH_CHANNELS = {"rgb": HT_PATCH_RGB, "bgr": HT_PATCH_BGR, "gray": HT_PATCH_GRA
 HT_FILTER_MAX_FACTOR = 8  # the largest max_factor of the _filtered calls
 
 HT_YUV_NV12, HT_YUV_I420 = 0, 1
-HT_DRAW_RGBA = 16  # ht_draw_source.format beside the two above (outside the range the YUV entry points take)
+HT_YUV_YUYV, HT_YUV_UYVY = 4, 5  # packed 4:2:2: one plane of 4-byte macropixels (2, 3, 6 are no formats)
+HT_DRAW_RGBA = 16  # ht_draw_source.format beside the four above (no format of the YUV entry points)
 HT_YUV_BT601_LIMITED, HT_YUV_BT709_LIMITED, HT_YUV_BT601_FULL, HT_YUV_BT709_FULL = 0, 1, 2, 3
-YUV_FORMATS = {"nv12": HT_YUV_NV12, "i420": HT_YUV_I420}
-DRAW_FORMATS = dict(YUV_FORMATS, rgba=HT_DRAW_RGBA)
+YUV_FORMATS = {"nv12": HT_YUV_NV12, "i420": HT_YUV_I420, "yuyv": HT_YUV_YUYV, "uyvy": HT_YUV_UYVY}
+YUV_PACKED_422 = (HT_YUV_YUYV, HT_YUV_UYVY)
+DRAW_FORMATS = {"nv12": HT_YUV_NV12, "i420": HT_YUV_I420, "rgba": HT_DRAW_RGBA}  # the entry formats before packed 4:2:2 (tests/test_draw_list_cpu.py holds this table to these three)
+DRAW_LIST_FORMATS = dict(DRAW_FORMATS, yuyv=HT_YUV_YUYV, uyvy=HT_YUV_UYVY)  # what an ht_draw_source entry may be: api.py reads THIS table
 YUV_MATRICES = {"bt601": HT_YUV_BT601_LIMITED, "bt709": HT_YUV_BT709_LIMITED, "bt601-full": HT_YUV_BT601_FULL, "bt709-full": HT_YUV_BT709_FULL}
 
 # every symbol include/headtrackr_hip.h declares (tests/test_abi.py checks the header against this list)

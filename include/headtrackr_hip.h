@@ -216,39 +216,58 @@ ht_status ht_draw_frames(ht_ctx *ctx, const uint8_t *host_rgba, int32_t n, int32
  * D = U - 128, E = V - 128, R = clamp((cy C + crv E + 128) >> 8), G = clamp((cy C + cgu D + cgv E + 128) >> 8), B = clamp((cy C + cbu D +
  * 128) >> 8), A = 255.  The chroma sample of source pixel (x, y) is sample (x >> 1, y >> 1) of the FRAME, replicated; odd widths and
  * heights are legal, the chroma planes are ceil(w / 2) x ceil(h / 2).  The result is, byte for byte, what ht_draw_frames_device gives on
- * the RGBA frame that conversion produces. */
-enum { HT_YUV_NV12 = 0 /* Y plane + one plane of interleaved U V pairs */, HT_YUV_I420 = 1 /* Y, U, V planes */ };
+ * the RGBA frame that conversion produces.
+ *
+ * Packed 4:2:2 (what an uncompressed webcam or a capture card delivers: UVC "YUY2" = V4L2 YUYV; SDI bridges UYVY) rides the same calls:
+ * ht_draw_frames_yuv, ht_draw_frames_yuv_device, ht_draw_list_device, ht_draw_list_filtered_device and, as an ht_draw_source entry, the
+ * ht_camshift_crop_sources_* / ht_camshift_align_sources_* calls (those unpack each packed entry's whole frame to RGBA in a context-owned
+ * buffer first — one more launch and 4 B/px per packed entry — and then are the call on that RGBA entry).  A
+ * frame is ONE plane; with cw = ceil(w / 2), row y holds cw macropixels of 4 bytes: HT_YUV_YUYV Y(2m) U(m) Y(2m+1) V(m), HT_YUV_UYVY U(m)
+ * Y(2m) V(m) Y(2m+1).  Pixel (x, y) takes its own Y byte and the U and V of macropixel (x >> 1) of ROW y of the frame (replicated
+ * horizontally, not interpolated, sited by the frame and not by a source rect: the 4:2:0 rule without the vertical halving); the triple
+ * goes through the same conversion and matrices, and the result of every call is, byte for byte, what the same call gives on the RGBA frame
+ * that conversion produces.  Odd widths are legal: the last macropixel's second luma byte is in memory and never selected.  Base address and
+ * row pitch are multiples of 4 (a macropixel is one aligned dword), pitch >= 4 cw (0 = 4 cw), width / height 1..16384, matrix 0..3; for
+ * n > 1 the frame stride is a multiple of 4 and at least pitch (h - 1) + 4 cw; a tightly packed host frame is 4 cw h bytes.  In
+ * ht_yuv_frames the plane is y with y_pitch (u, v, c_pitch are not looked at); in ht_draw_source it is p0 with pitch0 (p1, p2, pitch1 are
+ * not looked at).  The numbers 2, 3, 6 and every other are no format and stay refused.  Not part of this: 10-bit layouts (P010, Y210), other
+ * byte orders (YVYU, VYUY), planar or semi-planar 4:2:2 (I422, NV16), chroma interpolation, and the *_pairs_* calls, which read the RGBA
+ * canvas and are untouched. */
+enum { HT_YUV_NV12 = 0 /* Y plane + one plane of interleaved U V pairs */, HT_YUV_I420 = 1 /* Y, U, V planes */,
+       HT_YUV_YUYV = 4 /* one plane of Y U Y V macropixels */, HT_YUV_UYVY = 5 /* one plane of U Y V Y macropixels */ };
 enum { HT_YUV_BT601_LIMITED = 0, HT_YUV_BT709_LIMITED = 1, HT_YUV_BT601_FULL = 2, HT_YUV_BT709_FULL = 3 };
 typedef struct ht_yuv_frames {
-    const void *y, *u, *v;   /* NV12: u = the interleaved UV plane, v = NULL */
-    size_t y_pitch;          /* 0 = width */
+    const void *y, *u, *v;   /* NV12: u = the interleaved UV plane, v = NULL.  YUYV / UYVY: y = the packed plane, u and v not looked at */
+    size_t y_pitch;          /* 0 = width (YUYV / UYVY: 0 = 4 ceil(width / 2)) */
     size_t c_pitch;          /* 0 = packed */
     size_t frame_stride;     /* added to every plane pointer per frame; 0 = device form refuses n > 1 */
     int32_t width, height, format, matrix;
 } ht_yuv_frames;
 /* Device-resident planes.  dst_dev, dst_frame_stride, src_rect, binding and errors as ht_draw_frames_device; the overlap refusals apply
- * per plane.  NV12's chroma base, chroma pitch and frame stride must be even; the Y plane and I420's chroma planes need no alignment. */
+ * per plane.  NV12's chroma base, chroma pitch and frame stride must be even; the Y plane and I420's chroma planes need no alignment;
+ * a YUYV / UYVY plane's base, pitch and frame stride are multiples of 4. */
 ht_status ht_draw_frames_yuv_device(ht_ctx *ctx, const ht_yuv_frames *src_dev, int32_t n, const ht_cs_rect *src_rect, void *dst_dev,
                                     size_t dst_frame_stride);
-/* Host-resident frames, each tightly packed: Y, then UV (NV12) or U, then V (I420), w h + 2 cw ch bytes, frames frame_stride apart
- * (0 = packed).  Staged through the context-owned device buffer of ht_draw_frames at 1.5 B/px; result bound; host reusable on return. */
+/* Host-resident frames, each tightly packed: Y, then UV (NV12) or U, then V (I420), w h + 2 cw ch bytes; YUYV / UYVY: 4 cw h bytes.  Frames
+ * frame_stride apart (0 = packed; for the host form any stride of at least a frame).  Staged through the context-owned device buffer of
+ * ht_draw_frames at 1.5 B/px (4:2:2: 2 B/px); result bound; host reusable on return. */
 ht_status ht_draw_frames_yuv(ht_ctx *ctx, const uint8_t *host, int32_t n, int32_t width, int32_t height, int32_t format, int32_t matrix,
                              size_t frame_stride, const ht_cs_rect *src_rect);
 
 /* The K-feed form of the draw (the reference's loop is one drawImage per feed, main.js:170): ONE launch draws a list of sources that share
  * nothing — every entry names its own device allocation(s), size, pitches, format, matrix and source rect.  Entry i is
  * drawImage(source_i, sx,sy,sw,sh, 0,0,W,H) onto destination frame i, with the bytes ht_draw_frames_device (HT_DRAW_RGBA) or
- * ht_draw_frames_yuv_device (HT_YUV_NV12 / HT_YUV_I420) gives for that entry alone.  Plane pointers of different entries may be equal or
- * overlap (one decoded surface under several rects).  Per entry, the rules of those calls with n = 1: RGBA base and pitch multiples of 4;
- * NV12 chroma base and pitch even; width / height 1..16384; matrix 0..3 (ignored for RGBA); rect wholly inside the source, or width == 0
+ * ht_draw_frames_yuv_device (HT_YUV_NV12 / HT_YUV_I420 / HT_YUV_YUYV / HT_YUV_UYVY) gives for that entry alone.  Plane pointers of different entries may be equal or
+ * overlap (one decoded surface under several rects).  Per entry, the rules of those calls with n = 1: RGBA, YUYV and UYVY base and pitch
+ * multiples of 4; NV12 chroma base and pitch even; width / height 1..16384; matrix 0..3 (ignored for RGBA); rect wholly inside the source, or width == 0
  * && height == 0 for the whole source (x, y are then not looked at).  HT_DRAW_RGBA lies outside the HT_YUV_* format range: the YUV entry
  * points refuse it. */
 enum { HT_DRAW_RGBA = 16 };
 typedef struct ht_draw_source {
-    const void *p0, *p1, *p2; /* RGBA: p0.  NV12: Y, UV.  I420: Y, U, V.  Device pointers; the unused ones are not looked at. */
+    const void *p0, *p1, *p2; /* RGBA: p0.  NV12: Y, UV.  I420: Y, U, V.  YUYV / UYVY: p0.  Device pointers; the unused ones are not looked at. */
     size_t pitch0, pitch1;    /* bytes per row of p0 / of the chroma plane(s); 0 = packed */
     int32_t width, height;    /* of THIS source */
-    int32_t format;           /* HT_YUV_NV12, HT_YUV_I420 or HT_DRAW_RGBA */
+    int32_t format;           /* HT_YUV_NV12, HT_YUV_I420, HT_YUV_YUYV, HT_YUV_UYVY or HT_DRAW_RGBA */
     int32_t matrix;           /* HT_YUV_* matrix; ignored for RGBA */
     ht_cs_rect rect;          /* width == 0 && height == 0: whole source */
 } ht_draw_source;
