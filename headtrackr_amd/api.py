@@ -214,12 +214,20 @@ class Context:
             return table[v]
         return int(v)
 
-    def draw_frames_yuv(self, planes, fmt="nv12", matrix="bt601", rect=None, width=None, height=None):
+    @staticmethod
+    def _oriented(code: int, orientation) -> int:
+        """a format code with the orientation 0..7 in bits 8..10 (HT_ORIENT of headtrackr_hip.h)"""
+        return int(code) | orientation_bits(orientation)
+
+    def draw_frames_yuv(self, planes, fmt="nv12", matrix="bt601", rect=None, width=None, height=None, orientation=0):
         """planes: host arrays of n frames — NV12: (y uint8 [n, h, w], uv uint8 [n, ch, cw, 2]); I420: (y, u [n, ch, cw], v [n, ch, cw]) with
         cw = ceil(w / 2), ch = ceil(h / 2) — packed frame by frame and drawn like draw_frames(): converted with the declared integer matrix
         ('bt601', 'bt709', 'bt601-full', 'bt709-full' or 0 .. 3), scaled on the device, result bound.
         fmt 'yuyv' / 'uyvy' (packed 4:2:2): planes is ONE uint8 array, [n, h, 4 cw] (rows of cw macropixels; width defaults to 2 cw, pass
-        width = 2 cw - 1 for an odd frame) or flat with width and height given (n = size / (4 cw h)); staged at 2 B/px."""
+        width = 2 cw - 1 for an odd frame) or flat with width and height given (n = size / (4 cw h)); staged at 2 B/px.
+        orientation 0..7 (orientation_from_exif / orientation_from_rotation): the planes are the frames AS STORED, the draw is that of the
+        oriented frame and rect is in its coordinates."""
+        orient = orientation_bits(orientation)
         fmt, matrix = self._yuv_code(native.YUV_FORMATS, fmt, "fmt"), self._yuv_code(native.YUV_MATRICES, matrix, "matrix")
         if fmt in native.YUV_PACKED_422:
             host = np.ascontiguousarray(planes, dtype=np.uint8)
@@ -236,27 +244,28 @@ class Context:
                 n = host.size // (row * h) if row * h > 0 else 0
             if w <= 0 or h <= 0 or row != 4 * ((w + 1) // 2) or n <= 0 or host.size != n * row * h:
                 raise ValueError("draw_frames_yuv: a packed 4:2:2 frame is h rows of 4 * ceil(w / 2) bytes (width is 2 cw or 2 cw - 1)")
-            return self.draw_frames_yuv_ptr(host.ctypes.data, n, w, h, fmt, matrix, 0, rect)
+            return self.draw_frames_yuv_ptr(host.ctypes.data, n, w, h, fmt | orient, matrix, 0, rect)
         planes = [np.ascontiguousarray(p, dtype=np.uint8) for p in planes]
         n, h, w = planes[0].shape
         assert len(planes) == (2 if fmt == native.HT_YUV_NV12 else 3) and all(len(p) == n for p in planes)
         host = np.concatenate([p.reshape(n, -1) for p in planes], axis=1)
         assert host.shape[1] == w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2), "chroma planes are ceil(w / 2) x ceil(h / 2)"
-        self.draw_frames_yuv_ptr(host.ctypes.data, n, w, h, fmt, matrix, 0, rect)
+        self.draw_frames_yuv_ptr(host.ctypes.data, n, w, h, fmt | orient, matrix, 0, rect)
 
     def draw_frames_yuv_ptr(self, host_ptr: int, n: int, w: int, h: int, fmt: int, matrix: int, frame_stride: int = 0, rect=None):
         """ht_draw_frames_yuv on a raw host pointer: n tightly packed frames (Y, then UV or U, V; YUYV / UYVY: the one packed plane),
-        frame_stride bytes apart (0 = packed)"""
+        frame_stride bytes apart (0 = packed).  fmt: the format code, with HT_ORIENT bits if the frames are oriented"""
         r = self._cs_rect(rect)
         self._check(self._lib.ht_draw_frames_yuv(self._h, host_ptr, n, w, h, fmt, matrix, frame_stride, r.ctypes.data if r is not None else None))
         self.nframes = n
 
     def draw_frames_yuv_device(self, y: int, u: int, v: int | None, n: int, w: int, h: int, fmt="nv12", matrix="bt601", y_pitch: int = 0, c_pitch: int = 0,
-                               stride: int = 0, rect=None, dst: int | None = None, dst_stride: int = 0):
+                               stride: int = 0, rect=None, dst: int | None = None, dst_stride: int = 0, orientation=0):
         """The same for planes resident in device memory at y / u / v (NV12: u = the interleaved plane, v None), rows y_pitch / c_pitch bytes
         (0 = packed), frames `stride` bytes apart in every plane.  fmt 'yuyv' / 'uyvy': only y and y_pitch are read (the packed plane, base
-        and pitch multiples of 4); u, v and c_pitch are not looked at.  dst as draw_frames_device()."""
-        d = native.YUV_FRAMES(y, u, v, y_pitch, c_pitch, stride, w, h, self._yuv_code(native.YUV_FORMATS, fmt, "fmt"), self._yuv_code(native.YUV_MATRICES, matrix, "matrix"))
+        and pitch multiples of 4); u, v and c_pitch are not looked at.  dst as draw_frames_device().  orientation 0..7: w, h, the
+        pitches and the planes describe the frames as stored; rect is in the oriented frame's coordinates."""
+        d = native.YUV_FRAMES(y, u, v, y_pitch, c_pitch, stride, w, h, self._oriented(self._yuv_code(native.YUV_FORMATS, fmt, "fmt"), orientation), self._yuv_code(native.YUV_MATRICES, matrix, "matrix"))
         r = self._cs_rect(rect)
         self._check(self._lib.ht_draw_frames_yuv_device(self._h, C.byref(d), n, r.ctypes.data if r is not None else None, dst, dst_stride))
         if dst is None:
@@ -267,7 +276,8 @@ class Context:
         """entries: one dict per feed, drawn onto destination frame i in ONE launch (ht_draw_list_device) —
         {"format": 'rgba' | 'nv12' | 'i420' | 'yuyv' | 'uyvy' (or the code), "width", "height", "p0", "p1", "p2" (device pointers: RGBA p0;
         NV12 Y, UV; I420 Y, U, V; YUYV / UYVY p0 alone — p1, p2 and pitch1 are not read), "pitch0", "pitch1" (bytes per row, 0 = packed), "matrix" (as draw_frames_yuv_device, ignored for RGBA), "rect" (x, y,
-        width, height) or None = the whole source}.  Every feed may have its own allocation, size, format, matrix and rect; pointers may
+        width, height) or None = the whole source, "orientation" 0..7 (orientation_from_exif / orientation_from_rotation; default 0): width,
+        height, pitches and pointers describe the frame AS STORED, the entry is drawn as the oriented frame and rect is in ITS coordinates}.  Every feed may have its own allocation, size, format, matrix and rect; pointers may
         repeat.  dst as draw_frames_device().  prefilter = 1..8: ht_draw_list_filtered_device with that max_factor — every canvas pixel the
         mean of a block of the unfiltered draw's samples (draw_filter_factors gives the block per entry); None: the unfiltered call."""
         n = len(entries)
@@ -285,7 +295,7 @@ class Context:
             s.p0, s.p1, s.p2 = e.get("p0"), e.get("p1"), e.get("p2")
             s.pitch0, s.pitch1 = int(e.get("pitch0", 0)), int(e.get("pitch1", 0))
             s.width, s.height = int(e["width"]), int(e["height"])
-            s.format = self._yuv_code(native.DRAW_LIST_FORMATS, e.get("format", "rgba"), "format")
+            s.format = self._oriented(self._yuv_code(native.DRAW_LIST_FORMATS, e.get("format", "rgba"), "format"), e.get("orientation", 0))
             s.matrix = self._yuv_code(native.YUV_MATRICES, e.get("matrix", "bt601"), "matrix")
             if e.get("rect") is not None:
                 s.rect = native.CS_RECT(*(int(v) for v in e["rect"]))
@@ -838,6 +848,35 @@ def draw_filter_factors(entries_or_sizes, width: int, height: int, max_factor: i
             raise HtError(st, f"draw filter factors: entry {i}: source width / height must be 1..16384, the canvas positive and max_factor 1..8")
         out[i] = nx.value, ny.value
     return out
+
+
+# -- rotated and mirrored feeds: the orientation of a draw_list entry, of draw_frames_yuv* and of the face calls' entries -------------------
+# k = 0..7: k & 3 quarter turns CLOCKWISE bring the stored frame upright, k >> 2 mirrors it horizontally AFTER the turn
+# (numpy: np.rot90(stored, -(k & 3)), then np.fliplr if k >> 2).  It travels in bits 8..10 of the format number (HT_ORIENT).
+_EXIF_ORIENTATION = {1: 0, 2: 4, 3: 2, 4: 6, 5: 5, 6: 1, 7: 7, 8: 3}
+
+
+def orientation_bits(orientation) -> int:
+    """HT_ORIENT(k): the bits an orientation adds to a format number; anything but an integer 0..7 raises"""
+    k = int(orientation)
+    if k != orientation or not 0 <= k <= 7:
+        raise ValueError("orientation is an integer 0..7 (orientation_from_exif / orientation_from_rotation)")
+    return k << 8
+
+
+def orientation_from_exif(n: int) -> int:
+    """the orientation of an image whose EXIF Orientation tag is n (1..8)"""
+    if n not in _EXIF_ORIENTATION:
+        raise ValueError("an EXIF orientation is 1..8")
+    return _EXIF_ORIENTATION[n]
+
+
+def orientation_from_rotation(degrees: int, mirror: bool = False) -> int:
+    """the orientation of a feed that has to be turned `degrees` clockwise for display (a container's `rotate` / display matrix, WebRTC's
+    CVO; any multiple of 90, negative ones included) and, with mirror, flipped horizontally after the turn (a selfie camera)"""
+    if int(degrees) != degrees or int(degrees) % 90:
+        raise ValueError("a rotation is a multiple of 90 degrees")
+    return (int(degrees) // 90) % 4 | (4 if mirror else 0)
 
 
 def device_count() -> int:

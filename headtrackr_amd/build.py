@@ -16,6 +16,12 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libheadtrackr_hip.so")
 ADDON = os.path.join(HERE, "js", "headtrackr_hip.node")
+# the oriented draw's device code (csrc/ht_orient_kernels.hip): a code object of its OWN next to the library, which loads it with hipModuleLoad
+# on the first oriented call.  It is NOT one of HIP_SOURCES: the library's code objects, their kernels and registers are pinned by the CPU suite
+ORIENT_SOURCE = "ht_orient_kernels.hip"
+ORIENT_MODULE = os.path.join(HERE, "libheadtrackr_hip_orient.hsaco")
+# device code only, unbundled: the output is a plain gfx950 ELF (no offload bundle around it)
+ORIENT_FLAGS = ["--cuda-device-only", "--no-gpu-bundle-output"]
 
 HIP_SOURCES = ["ht_context.hip", "ht_pyramid.hip", "ht_scan.hip", "ht_camshift.hip", "ht_backproject.hip", "ht_allgather.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -64,7 +70,22 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
+    build_orient_module(force, verbose, deps)
     return LIB
+
+
+def build_orient_module(force: bool = False, verbose: bool = False, deps=None) -> str:
+    """the product flags (-ffp-contract=off: the blend is never contracted) plus ORIENT_FLAGS"""
+    src = os.path.join(CSRC, ORIENT_SOURCE)
+    if deps is None:
+        deps = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".inc", ".hip"))]
+        deps += [os.path.join(ROOT, "include", "headtrackr_hip.h"), os.path.abspath(__file__)]
+    if force or _newer(ORIENT_MODULE, deps):
+        cmd = [HIPCC, *HIP_FLAGS, *ORIENT_FLAGS, "-c", src, "-o", ORIENT_MODULE]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    return ORIENT_MODULE
 
 
 def build_addon(force: bool = False, verbose: bool = False) -> str | None:

@@ -212,6 +212,7 @@ static bool apply_options(ht_ctx *c, const std::string &opts, std::string &why) 
         else if (key == "force_rccl") c->force_rccl = iv != 0;
         else if (key == "group_cap") c->grp_cap_opt = std::max(1, iv);
         else if (key == "draw_filter_rows") { if (iv == 0 || iv == 4 || iv == 16) c->draw_filter_rows = iv; }  // k_draw_list_mean_tile's tile rows (0: the shipped 4)
+        else if (key == "orient_lanes") { if (iv >= 0 && iv <= 2) c->orient_lanes = iv; }  // the oriented draw's lane mapping for odd rot (0: the shipped one)
 #ifdef HT_DEBUG_KNOBS
         else if (key == "stop_stage") c->dbg_stop_stage = iv;                        // the tile kernel stops before this stage
         else if (key == "cs_iters") c->dbg_cs_iters = std::min(10, std::max(0, iv));   // mean-shift iterations (camshift.js:284 has 10)

@@ -97,26 +97,39 @@ ht_status dm_launch_unfiltered(ht_ctx *c, const char *fn, const HtDrawDesc *desc
 // the RGBA entry of that frame (same size, rect, ratios, stream: the same bytes and the same record by the calls' own contract).  One launch
 // per packed entry (the frames have sizes of their own), the whole frame at 4 B/px: a pass the fused kernels exist to avoid, and what a list
 // without packed entries never pays.
-ht_status dm_unpack_sources(ht_ctx *c, const char *fn, std::vector<HtCropDesc> &desc) {
+//
+// ORIENTED entries (orient[i] != 0, ht_orient_plan.h; any format) take the same route through the module's kernel (or_upright,
+// ht_draw_list.hip): the frame drawn is O, orient(convert(S)), of SW x SH — an oriented packed entry is ONE pass, not two — and the entry,
+// whose rect and size are O's already, becomes the RGBA entry of that frame.  The same cost in the same words: one more launch and the whole
+// frame at 4 B/px per oriented entry.
+ht_status dm_unpack_sources(ht_ctx *c, const char *fn, std::vector<HtCropDesc> &desc, const int32_t *orient) {
     size_t need = 0;
-    for (const HtCropDesc &e : desc)
-        if (ht_yuv_is_422(e.d.format)) need += (size_t)e.SW * (size_t)e.SH * 4;
+    const auto turned = [&](size_t i) { return orient && orient[i] != 0; };
+    for (size_t i = 0; i < desc.size(); i++)
+        if (turned(i) || ht_yuv_is_422(desc[i].d.format)) need += (size_t)desc[i].SW * (size_t)desc[i].SH * 4;
     if (!need) return HT_OK;
     HT_HIP(c, hipSetDevice(c->device));
-    if (c->ingest_src_cap < need) {  // a reallocation waits for the work in flight first, like every reallocation of the library
-        HT_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->d_ingest_src) (void)hipFree(c->d_ingest_src);
-        c->d_ingest_src = nullptr, c->ingest_src_cap = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&c->d_ingest_src), need) != hipSuccess) {
-            (void)hipGetLastError();
-            return ht_fail(c, HT_ERR_NOMEM, std::string(fn) + ": hipMalloc failed (unpacked 4:2:2 sources)");
-        }
-        c->ingest_src_cap = need;
-    }
+    ht_status rs = or_stage_reserve(c, fn, need, "unpacked 4:2:2 / oriented sources");
+    if (rs != HT_OK) return rs;
     size_t at = 0;
+    std::vector<HtOrientDesc> jobs;
+    std::vector<uint8_t *> frames;
+    for (size_t i = 0; i < desc.size(); i++) {
+        if (!turned(i)) continue;
+        HtCropDesc &e = desc[i];
+        HtOrientDesc o = {};
+        o.d.p0 = (const uint8_t *)e.d.p0, o.d.p1 = (const uint8_t *)e.d.p1, o.d.p2 = (const uint8_t *)e.d.p2, o.d.pitch0 = e.d.pitch0, o.d.pitch1 = e.d.pitch1;
+        o.d.cw = e.d.cw, o.d.format = e.d.format, o.d.kc = e.d.kc, o.orient = orient[i];
+        ht_orient_size(orient[i], e.SW, e.SH, &o.d.sw, &o.d.sh);  // the stored size back from O's (the swap is its own inverse)
+        jobs.push_back(ht_orient_whole(o));
+        frames.push_back(c->d_ingest_src + at);
+        e.d.p0 = frames.back(), e.d.p1 = e.d.p2 = nullptr, e.d.pitch0 = (size_t)e.SW * 4, e.d.pitch1 = 0, e.d.cw = 0, e.d.format = HT_DRAW_RGBA, e.d.kc = HtYuvCoef{};
+        at += (size_t)e.SW * (size_t)e.SH * 4;
+    }
+    if ((rs = or_upright(c, fn, jobs, frames)) != HT_OK) return rs;
     std::vector<HtDrawMeanDesc> one(1);
     for (HtCropDesc &e : desc) {
-        if (!ht_yuv_is_422(e.d.format)) continue;
+        if (!ht_yuv_is_422(e.d.format)) continue;  // (an oriented packed entry is RGBA by now)
         HtDrawMeanDesc &m = one[0];
         m = HtDrawMeanDesc{};
         m.d.p0 = (const uint8_t *)e.d.p0, m.d.pitch0 = e.d.pitch0, m.d.rx = m.d.ry = 1.0;
@@ -127,6 +140,38 @@ ht_status dm_unpack_sources(ht_ctx *c, const char *fn, std::vector<HtCropDesc> &
         if (st != HT_OK) return st;
         e.d.p0 = frame, e.d.p1 = e.d.p2 = nullptr, e.d.pitch0 = (size_t)e.SW * 4, e.d.pitch1 = 0, e.d.cw = 0, e.d.format = HT_DRAW_RGBA, e.d.kc = HtYuvCoef{};
         at += (size_t)e.SW * (size_t)e.SH * 4;
+    }
+    return HT_OK;
+}
+
+// The filtered draw of a list that holds oriented entries (odesc: ht_orient_plan's, every check of the call passed).  Each oriented entry's
+// frame is drawn 1 : 1 into the staging buffer (or_upright) and the entry planned as the RGBA entry of that O, with the rect it had — the
+// call's bytes by its own definition; the other entries are planned as they are.  The same cost as above: one more launch and the whole frame at
+// 4 B/px per oriented entry.
+ht_status dm_orient_first(ht_ctx *c, const char *fn, const ht_draw_source *srcs, int32_t max_factor, const std::vector<HtOrientDesc> &odesc, std::vector<HtDrawMeanDesc> &desc) {
+    size_t need = 0;
+    for (const HtOrientDesc &o : odesc)
+        if (o.orient) need += (size_t)o.d.sw * (size_t)o.d.sh * 4;
+    ht_status st = or_stage_reserve(c, fn, need, "oriented sources");
+    if (st != HT_OK) return st;
+    std::vector<HtOrientDesc> jobs;
+    std::vector<uint8_t *> frames;
+    size_t at = 0;
+    for (const HtOrientDesc &o : odesc) {
+        if (!o.orient) continue;
+        jobs.push_back(ht_orient_whole(o));
+        frames.push_back(c->d_ingest_src + at);
+        at += (size_t)o.d.sw * (size_t)o.d.sh * 4;
+    }
+    if ((st = or_upright(c, fn, jobs, frames)) != HT_OK) return st;
+    size_t j = 0;
+    for (size_t i = 0; i < odesc.size(); i++) {
+        ht_draw_source s = srcs[i];
+        if (odesc[i].orient) s = ht_orient_upright(srcs[i], odesc[i].orient, frames[j++]);
+        else s.format = HT_FORMAT_OF(s.format);
+        HtDrawExtent unused;
+        const int ps = ht_draw_filter_plan_entry(s, c->W, c->H, max_factor, &desc[i], &unused);
+        if (ps != HT_DRAW_LIST_OK) return ht_fail(c, HT_ERR_STATE, std::string(fn) + ": entry " + std::to_string(i) + ": " + ht_draw_filter_message(ps));  // (ht_orient_plan admitted it)
     }
     return HT_OK;
 }
@@ -148,9 +193,19 @@ extern "C" ht_status ht_draw_list_filtered_device(ht_ctx *c, const ht_draw_sourc
     std::vector<HtDrawMeanDesc> desc((size_t)n);
     std::vector<HtDrawExtent> ext((size_t)n);
     int32_t bad = -1;
-    const int ps = ht_draw_filter_plan(srcs, n, c->W, c->H, max_factor, desc.data(), ext.data(), &bad);
+    // a list with an oriented entry (ht_orient_plan.h) is checked by ht_orient_plan — the rects against O, the extents of the stored planes —
+    // and, behind every check of the call, ORIENTS FIRST (dm_orient_first): a list without one takes the path it always took
+    std::vector<HtOrientDesc> odesc;
+    const bool oriented = std::any_of(srcs, srcs + n, [](const ht_draw_source &s) { return ht_orient_present(s.format); });
+    if (oriented) odesc.resize((size_t)n);
+    const int ps = oriented ? ht_orient_plan(srcs, n, c->W, c->H, odesc.data(), ext.data(), &bad) : ht_draw_filter_plan(srcs, n, c->W, c->H, max_factor, desc.data(), ext.data(), &bad);
     if (ps != HT_DRAW_LIST_OK) return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": " + ht_draw_filter_message(ps));
     HT_HIP(c, hipSetDevice(c->device));
+    if (oriented) {  // a missing module is reported before anything is touched
+        const OrModule *m = nullptr;
+        const ht_status st = or_module(c, fn, &m);
+        if (st != HT_OK) return st;
+    }
     if (!dst_dev) {
         if (n > c->max_batch)
             return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(c->max_batch) + ": more entries than the geometry's batch capacity");
@@ -159,12 +214,17 @@ extern "C" ht_status ht_draw_list_filtered_device(ht_ctx *c, const ht_draw_sourc
             return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": a source plane lies inside the context's own frame buffer");
         ht_status st = ht_frames_own_reserve(c, fbytes * (size_t)n, fn);  // the contract of ig_draw_bound from here on
         if (st != HT_OK) return st;
+        if (oriented && (st = dm_orient_first(c, fn, srcs, max_factor, odesc, desc)) != HT_OK) return st;
         if ((st = dm_launch(c, fn, desc, c->d_frames_own, fbytes)) != HT_OK) return st;
         ht_frames_bind_own(c, n);
         return HT_OK;
     }
     if ((bad = ht_draw_list_overlap(ext.data(), n, dst_dev, (size_t)(n - 1) * dstride + fbytes)) >= 0)
         return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": a source plane and the destination overlap");
+    if (oriented) {
+        const ht_status st = dm_orient_first(c, fn, srcs, max_factor, odesc, desc);
+        if (st != HT_OK) return st;
+    }
     return dm_launch(c, fn, desc, static_cast<uint8_t *>(dst_dev), dstride);
 }
 

@@ -10,10 +10,18 @@
 // into one of the three bodies.  The table reaches the device
 // through a staged table (HtStagedTable, ht_internal.h: a ring of pinned slots and one hipMemcpyAsync on the ctx stream per call), as
 // every list call's table does.  DESIGN.md §2.3.2 gives the reasoning and the registers.
+//
+// A list with an ORIENTED entry (an orientation in bits 8..10 of its format: ht_orient_plan.h) is not k_draw_list's: the second half of this
+// file loads the oriented draw's kernels from a code object of their own and launches them.
+#include <dlfcn.h>
+
+#include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <vector>
 
 #include "ht_draw_list_plan.h"
+#include "ht_orient_plan.h"
 
 namespace {
 
@@ -81,6 +89,117 @@ ht_status dl_launch(ht_ctx *c, const char *fn, const std::vector<HtDrawDesc> &de
     return HT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The oriented draw (ht_orient_plan.h).  Its device code is NOT in this library: the code objects here are held to the kernels and registers
+// they have, so k_draw_list_oriented lives in a code object of its own, libheadtrackr_hip_orient.hsaco next to this library
+// (csrc/ht_orient_kernels.hip, built by build.py).  It is found through dladdr on a symbol of this library, loaded with hipModuleLoad on the
+// first oriented call — once per device and process, under a mutex, never reloaded or unloaded — and launched with hipModuleLaunchKernel on
+// the context's stream.  Without the file an oriented call is HT_ERR_STATE with the path in its message; nothing else depends on it.
+struct OrModule {
+    hipModule_t mod = nullptr;
+    hipFunction_t plain = nullptr, turn = nullptr;  // k_draw_list_oriented, k_draw_list_oriented_turn
+};
+constexpr int OR_MAX_DEVICES = 64;
+std::mutex or_mutex;
+OrModule or_modules[OR_MAX_DEVICES];
+
+std::string or_module_path() {
+    Dl_info info;
+    std::string dir = ".";
+    if (dladdr(reinterpret_cast<const void *>(&ht_draw_list_device), &info) && info.dli_fname) {
+        const std::string lib(info.dli_fname);
+        const size_t slash = lib.rfind('/');
+        if (slash != std::string::npos) dir = lib.substr(0, slash);
+    }
+    return dir + "/libheadtrackr_hip_orient.hsaco";
+}
+
+// the module of the context's device (the device is current)
+ht_status or_module(ht_ctx *c, const char *fn, const OrModule **out) {
+    if (c->device < 0 || c->device >= OR_MAX_DEVICES) return ht_fail(c, HT_ERR_STATE, std::string(fn) + ": the oriented draw serves devices 0..63");
+    std::lock_guard<std::mutex> lock(or_mutex);
+    OrModule &m = or_modules[c->device];
+    if (!m.mod) {
+        const std::string path = or_module_path();
+        FILE *fp = std::fopen(path.c_str(), "rb");
+        if (!fp) return ht_fail(c, HT_ERR_STATE, std::string(fn) + ": an oriented source needs the module " + path + ", which is missing (python -m headtrackr_amd.build makes it)");
+        std::fclose(fp);
+        OrModule l;
+        hipError_t e = hipModuleLoad(&l.mod, path.c_str());
+        if (e == hipSuccess) e = hipModuleGetFunction(&l.plain, l.mod, "k_draw_list_oriented");
+        if (e == hipSuccess) e = hipModuleGetFunction(&l.turn, l.mod, "k_draw_list_oriented_turn");
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            if (l.mod) (void)hipModuleUnload(l.mod);
+            return ht_fail(c, HT_ERR_STATE, std::string(fn) + ": the module " + path + " could not be loaded: " + hipGetErrorString(e));
+        }
+        m = l;
+    }
+    *out = &m;
+    return HT_OK;
+}
+
+// dw x dh: the destination frames' size — the canvas (dw == 0), or a source's own oriented size (the orient-first pass of the filtered draw
+// and the face-patch calls); first .. first + count: the descriptors of the table this launch takes
+ht_status or_launch_part(ht_ctx *c, const OrModule &m, bool turn, size_t first, size_t count, uint8_t *dst, size_t dstride, int dw, int dh) {
+    if (!count) return HT_OK;
+    const uint8_t *tab = c->dl_tab.d + first * sizeof(HtOrientDesc);
+    void *args[] = {&tab, &dst, &dstride, &dw, &dh};
+    const unsigned tw = turn ? 32 : IG_TW, th = turn ? 32 : IG_TH;
+    HT_HIP(c, hipModuleLaunchKernel(turn ? m.turn : m.plain, (dw + tw - 1) / tw, (dh + th - 1) / th, (unsigned)count, IG_NT, 1, 1, 0, c->stream, args, nullptr));
+    return HT_OK;
+}
+
+// entries of odd rot take the kernel that turns its tile through LDS when the context says so (option orient_lanes; OR_TURN_SHIPPED: what
+// the measurement of DESIGN.md §2.3.9 chose); even rot never transposes.  The table is ordered plain entries first — an entry names its
+// destination frame itself — and each kind is one launch
+constexpr bool OR_TURN_SHIPPED = true;
+ht_status or_launch(ht_ctx *c, const char *fn, std::vector<HtOrientDesc> &desc, uint8_t *dst, size_t dstride, int dw, int dh) {
+    const OrModule *m = nullptr;
+    ht_status st = or_module(c, fn, &m);
+    if (st != HT_OK) return st;
+    const bool use_turn = c->orient_lanes ? c->orient_lanes == 2 : OR_TURN_SHIPPED;
+    const auto plain = [use_turn](const HtOrientDesc &o) { return !(use_turn && (o.orient & 1)); };
+    const size_t nplain = (size_t)(std::stable_partition(desc.begin(), desc.end(), plain) - desc.begin());
+    if ((st = dl_upload(c, fn, desc)) != HT_OK) return st;
+    HtProfScope ps(c, "draw_list_oriented");
+    if (!dw) dw = c->W, dh = c->H;
+    if ((st = or_launch_part(c, *m, false, 0, nplain, dst, dstride, dw, dh)) != HT_OK) return st;
+    return or_launch_part(c, *m, true, nplain, desc.size() - nplain, dst, dstride, dw, dh);
+}
+
+// the context's staging buffer (ht_draw_frames' source staging) holds >= need bytes.  A reallocation waits for the work in flight first, like
+// every reallocation of the library
+ht_status or_stage_reserve(ht_ctx *c, const char *fn, size_t need, const char *what) {
+    if (c->ingest_src_cap >= need) return HT_OK;
+    HT_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->d_ingest_src) (void)hipFree(c->d_ingest_src);
+    c->d_ingest_src = nullptr, c->ingest_src_cap = 0;
+    if (hipMalloc(reinterpret_cast<void **>(&c->d_ingest_src), need) != hipSuccess) {
+        (void)hipGetLastError();
+        return ht_fail(c, HT_ERR_NOMEM, std::string(fn) + ": hipMalloc failed (" + what + ")");
+    }
+    c->ingest_src_cap = need;
+    return HT_OK;
+}
+
+// ORIENT FIRST: the calls whose kernels hold no orientation (the filtered draw, the face-patch calls) have each oriented entry's whole frame
+// drawn 1 : 1 (ht_orient_whole) onto frames[i], orw x orh packed rows, and then are the call on the RGBA entry of that O.  One table, one
+// launch per job (the frames have sizes of their own), the whole frame at 4 B/px: a pass the fused draw exists to avoid, and what a list
+// without oriented entries never pays.
+ht_status or_upright(ht_ctx *c, const char *fn, std::vector<HtOrientDesc> &jobs, const std::vector<uint8_t *> &frames) {
+    if (jobs.empty()) return HT_OK;
+    const OrModule *m = nullptr;
+    ht_status st = or_module(c, fn, &m);
+    if (st != HT_OK) return st;
+    if ((st = dl_upload(c, fn, jobs)) != HT_OK) return st;
+    HtProfScope ps(c, "draw_list_oriented");
+    const bool use_turn = c->orient_lanes ? c->orient_lanes == 2 : OR_TURN_SHIPPED;
+    for (size_t i = 0; i < jobs.size(); i++)
+        if ((st = or_launch_part(c, *m, use_turn && (jobs[i].orient & 1), i, 1, frames[i], 0, jobs[i].orw, jobs[i].orh)) != HT_OK) return st;
+    return HT_OK;
+}
+
 }  // namespace
 
 extern "C" ht_status ht_draw_list_device(ht_ctx *c, const ht_draw_source *srcs, int32_t n, void *dst_dev, size_t dst_frame_stride) {
@@ -96,9 +215,20 @@ extern "C" ht_status ht_draw_list_device(ht_ctx *c, const ht_draw_source *srcs, 
     std::vector<HtDrawDesc> desc((size_t)n);
     std::vector<HtDrawExtent> ext((size_t)n);
     int32_t bad = -1;
-    const int ps = ht_draw_list_plan(srcs, n, c->W, c->H, desc.data(), ext.data(), &bad);
+    // a list with an oriented entry (any bit above the format number) is planned by ht_orient_plan and drawn, all of it, by the module's
+    // kernel: `launch` below.  A list without one takes the path it always took
+    std::vector<HtOrientDesc> odesc;
+    const bool oriented = std::any_of(srcs, srcs + n, [](const ht_draw_source &s) { return ht_orient_present(s.format); });
+    if (oriented) odesc.resize((size_t)n);
+    const int ps = oriented ? ht_orient_plan(srcs, n, c->W, c->H, odesc.data(), ext.data(), &bad) : ht_draw_list_plan(srcs, n, c->W, c->H, desc.data(), ext.data(), &bad);
     if (ps != HT_DRAW_LIST_OK) return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": " + ht_draw_list_message(ps));
+    const auto launch = [&](uint8_t *dst, size_t stride) { return oriented ? or_launch(c, fn, odesc, dst, stride) : dl_launch(c, fn, desc, dst, stride); };
     HT_HIP(c, hipSetDevice(c->device));
+    if (oriented) {  // a missing module is reported before anything is touched
+        const OrModule *m = nullptr;
+        const ht_status st = or_module(c, fn, &m);
+        if (st != HT_OK) return st;
+    }
     if (!dst_dev) {
         if (n > c->max_batch)
             return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(c->max_batch) + ": more entries than the geometry's batch capacity");
@@ -108,11 +238,11 @@ extern "C" ht_status ht_draw_list_device(ht_ctx *c, const ht_draw_source *srcs, 
             return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": a source plane lies inside the context's own frame buffer");
         ht_status st = ht_frames_own_reserve(c, fbytes * (size_t)n, fn);  // the contract of ig_draw_bound from here on
         if (st != HT_OK) return st;
-        if ((st = dl_launch(c, fn, desc, c->d_frames_own, fbytes)) != HT_OK) return st;
+        if ((st = launch(c->d_frames_own, fbytes)) != HT_OK) return st;
         ht_frames_bind_own(c, n);
         return HT_OK;
     }
     if ((bad = ht_draw_list_overlap(ext.data(), n, dst_dev, (size_t)(n - 1) * dstride + fbytes)) >= 0)
         return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": a source plane and the destination overlap");
-    return dl_launch(c, fn, desc, static_cast<uint8_t *>(dst_dev), dstride);
+    return launch(static_cast<uint8_t *>(dst_dev), dstride);
 }

@@ -165,19 +165,33 @@ ht_status face_sources(ht_ctx *c, const FaceCall &k, const int32_t *streams, con
     if (!streams) return ht_fail(c, HT_ERR_INVALID, f + ": NULL streams");
     std::vector<HtCropDesc> desc((size_t)n);
     std::vector<HtDrawExtent> ext((size_t)n);
+    std::vector<int32_t> orient;  // filled only when an entry carries an orientation (ht_orient_plan.h)
     for (int32_t i = 0; i < n; i++) {
         if (streams[i] < 0 || streams[i] >= c->cs_streams)
             return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(i) + ": stream " + std::to_string(streams[i]) + " is not reserved");
         HtCropDesc e = {};
-        const int ps = ht_draw_list_plan_entry(srcs[i], c->W, c->H, &e.d, &ext[(size_t)i]);  // an entry's rules are the draw list's: asked, not restated
+        int ps;
+        if (ht_orient_present(srcs[i].format)) {  // the stored planes, with the rect and the size of O: the frame the entry becomes below
+            HtOrientDesc o;
+            if ((ps = ht_orient_plan_entry(srcs[i], c->W, c->H, &o, &ext[(size_t)i])) == HT_DRAW_LIST_OK) {
+                e.d = ht_orient_as_plain(o);
+                ht_orient_size(o.orient, srcs[i].width, srcs[i].height, &e.SW, &e.SH);
+                if (orient.empty()) orient.assign((size_t)n, 0);
+                orient[(size_t)i] = o.orient;
+            }
+        } else {
+            ps = ht_draw_list_plan_entry(srcs[i], c->W, c->H, &e.d, &ext[(size_t)i]);  // an entry's rules are the draw list's: asked, not restated
+            e.SW = srcs[i].width, e.SH = srcs[i].height;
+        }
         if (ps != HT_DRAW_LIST_OK) return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(i) + ": " + ht_draw_list_message(ps));
-        e.SW = srcs[i].width, e.SH = srcs[i].height, e.stream = streams[i];
+        e.stream = streams[i];
         desc[(size_t)i] = e;
     }
     const int32_t bad = ht_draw_list_overlap(ext.data(), n, k.out_dev, (size_t)(n - 1) * ostride + pbytes);
     if (bad >= 0) return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": a source plane and the output overlap");
-    // packed 4:2:2 entries become the RGBA entries of their unpacked frames (ht_draw_filter.hip); a list without one is untouched
-    if ((st = dm_unpack_sources(c, k.fn, desc)) != HT_OK) return st;
+    // packed 4:2:2 entries become the RGBA entries of their unpacked frames, oriented entries those of their oriented frames
+    // (ht_draw_filter.hip); a list without either is untouched
+    if ((st = dm_unpack_sources(c, k.fn, desc, orient.empty() ? nullptr : orient.data())) != HT_OK) return st;
     return k.launch(c, desc, ostride);
 }
 

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "ht_draw_list_plan.h"
+#include "ht_orient_plan.h"
 #include "ht_yuv_plan.h"
 
 static_assert(HT_YUV_NV12 == HT_YUV_FMT_NV12 && HT_YUV_I420 == HT_YUV_FMT_I420 && HT_YUV_YUYV == HT_YUV_FMT_YUYV && HT_YUV_UYVY == HT_YUV_FMT_UYVY,
@@ -65,10 +66,14 @@ __global__ __launch_bounds__(IG_NT) void k_draw_yuv(const uint8_t *__restrict__ 
 // the unfiltered draw of descriptors that may hold packed 4:2:2 entries: ht_draw_filter.hip, behind the kernel it launches
 ht_status dm_launch_unfiltered(ht_ctx *c, const char *fn, const HtDrawDesc *desc, size_t n, uint8_t *dst, size_t dstride);
 
+// the oriented draw (a format with HT_ORIENT bits, ht_orient_plan.h) through the module's kernel: ht_draw_list.hip.  dw == 0: onto the canvas
+ht_status or_launch(ht_ctx *c, const char *fn, std::vector<HtOrientDesc> &desc, uint8_t *dst, size_t dstride, int dw = 0, int dh = 0);
+
 struct IgYuvCall {  // a validated call: the source as the device will see it
     HtYuvPlan plan;
-    int32_t format, matrix;
-    int32_t sx, sy, sw, sh;
+    int32_t format, matrix;  // format: the bare number
+    int32_t orient, width, height;  // the orientation the format carried, and the STORED frame's size
+    int32_t sx, sy, sw, sh;  // the source rect: in O's coordinates (orientation 0: O is the stored frame)
     size_t fbytes;  // bytes of one destination frame
 };
 
@@ -77,11 +82,15 @@ ht_status igy_check(ht_ctx *c, const char *fn, int32_t n, int32_t width, int32_t
                     size_t frame_stride, const ht_cs_rect *rect, IgYuvCall *q) {
     const std::string f(fn);
     if (c->W == 0) return ht_fail(c, HT_ERR_STATE, f + ": call ht_set_geometry first");
+    ht_orient_split(format, &format, &q->orient);  // (a value with a bit from 11 up stays whole and is refused as no format)
     const int ps = ht_yuv_plan(width, height, format, matrix, y_pitch, c_pitch, frame_stride, n, &q->plan);
     if (ps != HT_YUV_PLAN_OK) return ht_fail(c, HT_ERR_INVALID, f + ": " + ht_yuv_plan_message(ps));
-    q->format = format, q->matrix = matrix;
+    q->format = format, q->matrix = matrix, q->width = width, q->height = height;
     q->sx = q->sy = 0, q->sw = width, q->sh = height;
-    if (rect) {
+    if (q->orient) {  // the rect is O's
+        if (!ht_orient_rect(q->orient, width, height, rect, &q->sx, &q->sy, &q->sw, &q->sh))
+            return ht_fail(c, HT_ERR_INVALID, f + ": source rect must lie wholly inside the oriented source frame");
+    } else if (rect) {
         if (rect->x < 0 || rect->y < 0 || rect->width <= 0 || rect->height <= 0 || rect->width > width - rect->x || rect->height > height - rect->y)
             return ht_fail(c, HT_ERR_INVALID, f + ": source rect must lie wholly inside the source frame");
         q->sx = rect->x, q->sy = rect->y, q->sw = rect->width, q->sh = rect->height;
@@ -94,6 +103,20 @@ ht_status igy_launch(ht_ctx *c, const char *fn, const IgYuvCall &q, const uint8_
     const double rx = (double)q.sw / (double)c->W, ry = (double)q.sh / (double)c->H;  // canvas_shim.js: one binary64 division each
     const HtYuvPlan &p = q.plan;
     const HtYuvCoef kc = HT_YUV_COEF[q.matrix];
+    if (q.orient) {  // one descriptor per frame through the module's kernel, as the packed formats go through theirs below
+        std::vector<HtOrientDesc> desc((size_t)n);
+        const bool nv12 = q.format == HT_YUV_FMT_NV12, packed = ht_yuv_is_422(q.format);
+        for (int32_t f = 0; f < n; f++) {
+            HtOrientDesc &o = desc[(size_t)f];
+            o = HtOrientDesc{};
+            HtDrawDesc &d = o.d;
+            d.p0 = y + (size_t)f * p.stride, d.pitch0 = p.y_pitch, d.rx = rx, d.ry = ry;
+            if (!packed) d.p1 = u + (size_t)f * p.stride, d.p2 = nv12 ? d.p1 : v + (size_t)f * p.stride, d.pitch1 = p.c_pitch;
+            d.sw = q.width, d.sh = q.height, d.cw = p.cw, d.format = q.format, d.kc = kc;
+            o.orient = q.orient, o.frame = f, o.ox = q.sx, o.oy = q.sy, o.orw = q.sw, o.orh = q.sh;
+        }
+        return or_launch(c, fn, desc, dst, dstride);
+    }
     if (ht_yuv_is_422(q.format)) {  // one descriptor per frame through the one kernel that holds the packed pixel body (ht_draw_filter.hip; its timer)
         std::vector<HtDrawDesc> desc((size_t)n);
         for (int32_t f = 0; f < n; f++) {
@@ -166,10 +189,13 @@ extern "C" ht_status ht_draw_frames_yuv(ht_ctx *c, const uint8_t *host, int32_t 
     // height has an odd Y plane, so it is staged one byte into the buffer (the Y plane needs no alignment) and frames one byte further
     // apart.  A packed 4:2:2 frame is 4 cw h bytes at 2 B/px, a multiple of 4 already: no lead, and every frame starts on a macropixel
     HtYuvPlan p0;
+    const int32_t given = format;  // with its orientation bits: igy_check takes them apart again
+    int32_t orient = 0;
+    ht_orient_split(given, &format, &orient);
     const size_t fsz = ht_yuv_plan(width, height, format, matrix, 0, 0, 0, 1, &p0) == HT_YUV_PLAN_OK ? p0.packed_frame : 0;
     const size_t lead = (format == HT_YUV_FMT_NV12) ? (fsz & 1) : 0, dstep = fsz + lead;
     IgYuvCall q;
-    ht_status st = igy_check(c, fn, n, width, height, format, matrix, 0, 0, dstep, src_rect, &q);  // (reports what made fsz 0, if anything did)
+    ht_status st = igy_check(c, fn, n, width, height, given, matrix, 0, 0, dstep, src_rect, &q);  // (reports what made fsz 0, if anything did)
     if (st != HT_OK) return st;
     if (frame_stride && frame_stride < fsz) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": source frame stride smaller than a frame");
     if (!host) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": NULL source");

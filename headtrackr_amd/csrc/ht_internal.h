@@ -325,6 +325,7 @@ struct ht_ctx {
     // (ht_draw_list_filtered_device, ht_draw_filter.hip, stages its wider descriptors through the same table: both are the draw list)
     HtStagedTable dl_tab;
     int draw_filter_rows = 0;  // option draw_filter_rows: the filtered draw's tile rows, 4 or 16 (0: the shipped 4) — for A-B measurements
+    int orient_lanes = 0;  // option orient_lanes: the oriented draw's kernel for entries of odd rot, 1 = k_draw_list_oriented, 2 = .._turn (0: the shipped one) — for A-B measurements
     // the face crops (ht_crop.hip) and the aligned crops (ht_align.hip), one host path for both (ht_face_calls.hip): each family has a
     // descriptor table and the records of its last call of its OWN — a draw call, a crop call and an align call of one step share nothing
     HtFaceCalls crop, align;

@@ -650,7 +650,11 @@ napi_value DrawFrames(napi_env env, napi_callback_info info) {
     return nullptr;
 }
 
-bool yuv_packed_422(int32_t format) { return format == HT_YUV_YUYV || format == HT_YUV_UYVY; }
+// a format number without the orientation it may carry in bits 8..10 (HT_ORIENT: the facade packs a feed's orientation there, and the layout
+// of a frame in memory does not depend on it); a value with a bit from 11 up is no format, stays whole and is refused by the library
+int32_t bare_format(int32_t format) { return (format & ~0x7ff) ? format : HT_FORMAT_OF(format); }
+
+bool yuv_packed_422(int32_t format) { return bare_format(format) == HT_YUV_YUYV || bare_format(format) == HT_YUV_UYVY; }
 
 // bytes of one tightly packed YUV frame: 4:2:0 (Y, then the chroma planes) w h + 2 cw ch, packed 4:2:2 (YUYV / UYVY: one plane of 4-byte
 // macropixels) 4 cw h; 0: no such frame.  A format the library does not know is sized as 4:2:0 and refused by the library
@@ -1399,7 +1403,7 @@ napi_value DrawFramesYuvDevice(napi_env env, napi_callback_info info) {
     const char *base = static_cast<char *>(src->ptr) + soff;
     const size_t cplane = (size_t)((w + 1) / 2) * ((h + 1) / 2);
     d.y = base;  // YUYV / UYVY: the one packed plane; u and v stay NULL
-    if (!packed) d.u = base + (size_t)w * h, d.v = format == HT_YUV_I420 ? base + (size_t)w * h + cplane : nullptr;
+    if (!packed) d.u = base + (size_t)w * h, d.v = bare_format(format) == HT_YUV_I420 ? base + (size_t)w * h + cplane : nullptr;
     d.frame_stride = stride ? stride : (n > 1 ? fsz : 0);
     d.width = w, d.height = h, d.format = format, d.matrix = matrix;
     ht_status st = ht_draw_frames_yuv_device(L.ctx, &d, n, rp, dst ? static_cast<char *>(dst->ptr) + doff : nullptr, dstride);
@@ -1432,7 +1436,7 @@ bool get_draw_entry(napi_env env, napi_value e, ht_draw_source *s) {
     if (get_prop(env, e, "rect", &v) && !get_rect(env, v, &s->rect, &rp)) return type_error(env, "drawListDevice: entry.rect is null or an Int32Array [x, y, width, height]") != nullptr;
     if (rp && rp->width == 0 && rp->height == 0) s->rect.width = -1;  // an empty rect is an error, not "the whole source": the library refuses it
     // what the library checks itself — format, matrix, alignment, the rect, overlap — is left to it
-    const bool rgba = s->format == HT_DRAW_RGBA;
+    const bool rgba = bare_format(s->format) == HT_DRAW_RGBA;
     const size_t ysz = s->width > 0 && s->height > 0 && s->width <= 16384 && s->height <= 16384 ? (size_t)s->width * (size_t)s->height : 0;
     const bool packed = yuv_packed_422(s->format);
     const size_t fsz = rgba ? ysz * 4 : yuv_frame_bytes(s->width, s->height, s->format);
@@ -1442,7 +1446,7 @@ bool get_draw_entry(napi_env env, napi_value e, ht_draw_source *s) {
     s->p0 = base;
     if (!rgba && !packed) {
         s->p1 = base + ysz;
-        s->p2 = s->format == HT_YUV_I420 ? base + ysz + (size_t)((s->width + 1) / 2) * ((s->height + 1) / 2) : nullptr;
+        s->p2 = bare_format(s->format) == HT_YUV_I420 ? base + ysz + (size_t)((s->width + 1) / 2) * ((s->height + 1) / 2) : nullptr;
     }
     return true;
 }

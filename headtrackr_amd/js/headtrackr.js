@@ -163,6 +163,15 @@ headtrackr.ccv.grayscale = function (canvas) { /* ccv.js:22-32, in place, return
  * at 2 B/px; a frame is a multiple of 4 bytes and starts at a multiple of 4, so lead = 0 and step = bytes.  The draw calls take them
  * (drawFrames, DeviceBatch draw / drawList / drawListBound, with opts.prefilter too), and so do cropFeeds / alignFeeds (the library unpacks
  * such a feed's frame to RGBA first). */
+/* Rotated and mirrored feeds: `orientation` = 0..7 on a drawFrames video or a DeviceBatch source.  k & 3 quarter turns clockwise bring the
+ * stored frame upright, k >> 2 mirrors it horizontally after the turn; width, height and the bytes describe the frame AS STORED, the draw is
+ * that of the oriented frame and rects are in ITS coordinates.  It travels in bits 8..10 of the format number the addon already passes
+ * (HT_ORIENT of headtrackr_hip.h). */
+function orientBits(orientation, who) {
+  if (orientation === undefined || orientation === null) return 0;
+  if (!(Number.isInteger(orientation) && orientation >= 0 && orientation <= 7)) throw new RangeError(who + ': orientation is an integer 0..7');
+  return orientation << 8;
+}
 const YUV_FORMATS = { nv12: 0, i420: 1, yuyv: 4, uyvy: 5 }, YUV_MATRICES = { bt601: 0, bt709: 1, 'bt601-full': 2, 'bt709-full': 3 };
 function yuvLayout(width, height, format, matrix, who) {
   const fmt = YUV_FORMATS[format], mat = YUV_MATRICES[matrix === undefined ? 'bt601' : matrix];
@@ -186,7 +195,7 @@ headtrackr.ccv.drawFrames = function (video, canvas, rect) {
   if (video.format !== undefined && video.format !== 'rgba') {
     /* a video-like object {width, height, format: 'nv12' | 'i420' | 'yuyv' | 'uyvy', matrix, data: Uint8Array}: there is no host route — a canvas cannot
      * draw planes — so an addon without the call is an error */
-    const L = yuvLayout(vw, vh, video.format, video.matrix, 'ccv.drawFrames');
+    const L = yuvLayout(vw, vh, video.format, video.matrix, 'ccv.drawFrames'), orient = orientBits(video.orientation, 'ccv.drawFrames');
     if (typeof A.drawFramesYuvDevice !== 'function') throw new Error('ccv.drawFrames: this headtrackr_hip.node has no drawFramesYuvDevice (rebuild it)');
     if (!(video.data instanceof Uint8Array) || video.data.length < L.bytes) throw new RangeError('ccv.drawFrames: video.data is a Uint8Array of w*h + 2*ceil(w/2)*ceil(h/2) bytes (yuyv / uyvy: 4*ceil(w/2)*h)');
     if (!(w > 0 && h > 0)) return canvas;
@@ -194,11 +203,13 @@ headtrackr.ccv.drawFrames = function (video, canvas, rect) {
     ensureGeometry(c, w, h, 1, headtrackr.cascade, 5);
     const out = ctx2d.createImageData(w, h), dsrc = grow(c, 'drawSrc', L.lead + L.bytes), ddst = grow(c, 'drawDst', w * h * 4);
     A.deviceUpload(c.handle, dsrc, L.lead, video.data.subarray(0, L.bytes));
-    A.drawFramesYuvDevice(c.handle, dsrc, L.lead, 1, vw, vh, L.fmt, L.mat, 0, rect ? Int32Array.from(rect) : null, ddst, 0, 0, false);
+    A.drawFramesYuvDevice(c.handle, dsrc, L.lead, 1, vw, vh, L.fmt | orient, L.mat, 0, rect ? Int32Array.from(rect) : null, ddst, 0, 0, false);
     A.deviceDownload(c.handle, ddst, 0, out.data);
     ctx2d.putImageData(out, 0, 0);
     return canvas;
   }
+  /* (the RGBA route has no format to carry an orientation: an oriented RGBA feed is a DeviceBatch source) */
+  if (orientBits(video.orientation, 'ccv.drawFrames')) throw new RangeError("ccv.drawFrames: orientation needs a video with format 'nv12', 'i420', 'yuyv' or 'uyvy' (an RGBA feed: DeviceBatch opts.sources)");
   if (typeof A.drawFramesDevice !== 'function' || typeof A.deviceDownload !== 'function' || !(w > 0 && h > 0 && vw > 0 && vh > 0)) {
     if (rect) ctx2d.drawImage(video, rect[0], rect[1], rect[2], rect[3], 0, 0, w, h); else ctx2d.drawImage(video, 0, 0, w, h);
     return canvas;
@@ -439,7 +450,7 @@ headtrackr.ccv.detect_objects_batch = function (frames, n, w, h, cascade, interv
  *     draw(sset, set, rect)                source set `sset` scaled onto work set `set` (rect: Int32Array [x, y, width, height] inside a source
  *                                           frame, default the whole frame); enqueue only, except that with depth > 1 it waits — the other
  *                                           contexts read the work set on streams of their own
- *   opts.sources = [{width, height, format = 'rgba' | 'nv12' | 'i420' | 'yuyv' | 'uyvy', matrix, sets = 1}, ...] (instead of opts.source): one entry per feed,
+ *   opts.sources = [{width, height, format = 'rgba' | 'nv12' | 'i420' | 'yuyv' | 'uyvy', matrix, orientation = 0..7, sets = 1}, ...] (instead of opts.source): one entry per feed,
  *   every feed with its own device buffer, size and format; ONE launch draws them all (ht_draw_list_device)
  *     uploadSourceOf(i, frame, sset = 0)   feed i's packed frame host -> HBM
  *     drawList(sset, set, rects, opts)     every feed onto its frame of frame set `set`; rects: null, or a rect / null per feed;
@@ -835,7 +846,7 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     drawSource(sset, rect, null, 0, false);
     bound = -1;
   };
-  /* opts.sources = [{width, height, format = 'rgba' | 'nv12' | 'i420' | 'yuyv' | 'uyvy', matrix, sets = 1}, ...]: one entry per feed, each feed with a device
+  /* opts.sources = [{width, height, format = 'rgba' | 'nv12' | 'i420' | 'yuyv' | 'uyvy', matrix, orientation = 0 (orientBits), sets = 1}, ...]: one entry per feed, each feed with a device
    * buffer of its own that holds `sets` packed frames (RGBA rows; Y, then UV or U, V — an odd x odd NV12 frame one byte into its slot, as
    * yuvLayout says).  drawList / drawListBound draw all n feeds in ONE launch (ht_draw_list_device), every feed under a rect of its own. */
   const DRAW_RGBA = 16; /* HT_DRAW_RGBA */
@@ -849,9 +860,10 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
       if (!(Number.isInteger(s.width) && Number.isInteger(s.height) && s.width > 0 && s.height > 0)) throw new RangeError('DeviceBatch: opts.sources[' + i + ']: width and height must be positive integers');
       const sets = s.sets === undefined ? 1 : s.sets;
       if (!(Number.isInteger(sets) && sets >= 1)) throw new RangeError('DeviceBatch: opts.sources[' + i + ']: sets must be >= 1');
-      if (s.format === undefined || s.format === 'rgba') return { width: s.width, height: s.height, fmt: DRAW_RGBA, mat: 0, bytes: s.width * s.height * 4, lead: 0, step: s.width * s.height * 4, sets: sets };
+      const orient = orientBits(s.orientation, 'DeviceBatch: opts.sources[' + i + ']');
+      if (s.format === undefined || s.format === 'rgba') return { width: s.width, height: s.height, fmt: DRAW_RGBA | orient, mat: 0, bytes: s.width * s.height * 4, lead: 0, step: s.width * s.height * 4, sets: sets };
       const L = yuvLayout(s.width, s.height, s.format, s.matrix, 'DeviceBatch: opts.sources[' + i + ']');
-      return { width: s.width, height: s.height, fmt: L.fmt, mat: L.mat, bytes: L.bytes, lead: L.lead, step: L.step, sets: sets };
+      return { width: s.width, height: s.height, fmt: L.fmt | orient, mat: L.mat, bytes: L.bytes, lead: L.lead, step: L.step, sets: sets };
     });
     feeds = layouts.map(function (f) { f.dev = A.deviceAlloc(ctxs[0], f.sets * f.step + 2 * f.lead); return f; });
   }
@@ -905,7 +917,10 @@ headtrackr.ccv.DeviceBatch = function (w, h, n, opts) {
     const mf = prefilterOf('drawFilterFactors', o || {}, ['drawFilterFactors']);
     if (!mf) throw new RangeError('DeviceBatch.drawFilterFactors: opts.prefilter is an integer 1..8');
     const sizes = new Int32Array(2 * n);
-    listEntries(0, rects, 'drawFilterFactors').forEach(function (e, i) { sizes[2 * i] = e.rect ? e.rect[2] : e.width; sizes[2 * i + 1] = e.rect ? e.rect[3] : e.height; });
+    listEntries(0, rects, 'drawFilterFactors').forEach(function (e, i) {
+      const odd = (e.format >> 8) & 1; /* an odd orientation: the whole source is height x width */
+      sizes[2 * i] = e.rect ? e.rect[2] : (odd ? e.height : e.width); sizes[2 * i + 1] = e.rect ? e.rect[3] : (odd ? e.width : e.height);
+    });
     return A.drawFilterFactors(sizes, w, h, mf);
   };
   /* Face crops on the device (ht_camshift_crop_pairs_device / ht_camshift_crop_sources_device): each tracker's box, as its last track step

@@ -86,6 +86,8 @@ typedef struct ht_config {
                              *   group_cap=N          raw hits of one frame the device grouping takes (a power of two, 64 .. 1024 = default); frames above
                              *                        it are finished on the host by the collect call
                              *   draw_filter_rows=4|16  ht_draw_list_filtered_device: the kernel's tile is 64 x 4 (the default) or 64 x 16 pixels
+                             *   orient_lanes=1|2     the oriented draw, entries of odd rot: lanes along O's x (1) or along the stored row with the tile
+                             *                        turned through LDS (2); 0 = the shipped choice.  Same bytes either way
                              * Keys that make results incomplete by design (stop_stage, cs_iters, rs_maxgen) exist only in builds
                              * compiled with -DHT_DEBUG_KNOBS (tools/build_alt.py); the product library rejects them. */
 } ht_config;
@@ -241,7 +243,7 @@ typedef struct ht_yuv_frames {
     size_t y_pitch;          /* 0 = width (YUYV / UYVY: 0 = 4 ceil(width / 2)) */
     size_t c_pitch;          /* 0 = packed */
     size_t frame_stride;     /* added to every plane pointer per frame; 0 = device form refuses n > 1 */
-    int32_t width, height, format, matrix;
+    int32_t width, height, format, matrix;  /* format: | HT_ORIENT(k) for rotated / mirrored frames (below, at ht_draw_source) */
 } ht_yuv_frames;
 /* Device-resident planes.  dst_dev, dst_frame_stride, src_rect, binding and errors as ht_draw_frames_device; the overlap refusals apply
  * per plane.  NV12's chroma base, chroma pitch and frame stride must be even; the Y plane and I420's chroma planes need no alignment;
@@ -263,11 +265,34 @@ ht_status ht_draw_frames_yuv(ht_ctx *ctx, const uint8_t *host, int32_t n, int32_
  * && height == 0 for the whole source (x, y are then not looked at).  HT_DRAW_RGBA lies outside the HT_YUV_* format range: the YUV entry
  * points refuse it. */
 enum { HT_DRAW_RGBA = 16 };
+/* Rotated and mirrored feeds (a phone in portrait: landscape surfaces plus a rotation flag — container `rotate` / display matrix, WebRTC CVO,
+ * EXIF on stills; a hardware decoder's surface as stored; a mirrored selfie camera).  An ORIENTATION k = 0..7 rides in bits 8..10 of the
+ * `format` field of ht_draw_source and ht_yuv_frames (and of ht_draw_frames_yuv's format argument): format = HT_YUV_NV12 | HT_ORIENT(5).
+ * rot = k & 3 counts the quarter turns clockwise that bring the stored frame upright, flip = k >> 2 is a horizontal mirror applied after the
+ * turn.  The stored frame S of w x h gives the oriented frame O of (w, h) for even rot, (h, w) for odd rot, a pure index permutation: with
+ * x' = flip ? ow - 1 - x : x, O(x, y) = S(u, v), (u, v) = (x', y) | (y, h - 1 - x') | (w - 1 - x', h - 1 - y) | (w - 1 - y, x') for rot 0 | 1 |
+ * 2 | 3 (numpy: np.rot90(S, -rot), then np.fliplr if flip; EXIF orientations 1..8 are k = 0, 4, 2, 6, 5, 1, 7, 3).  Every call that takes
+ * such a format gives, byte for byte, what it gives today on the RGBA frame O = orient(convert(S)): width, height, pitches and planes
+ * describe the STORED frame, YUV chroma is sited by the stored frame exactly as without an orientation (conversion first, permutation
+ * second), and source rects, crop boxes and records are in O's coordinates (a rect inside O but outside S is legal, the converse is
+ * refused).  Every value that was legal before means what it meant; a value with any bit from 11 up stays no format.
+ *   ht_draw_list_device, ht_draw_frames_yuv, ht_draw_frames_yuv_device: ONE fused launch (k_draw_list_oriented) — the permutation is applied
+ *     to the few source samples the draw reads.  A list without an oriented entry takes the path it took.
+ *   ht_draw_list_filtered_device and the ht_camshift_crop_sources_* / ht_camshift_align_sources_* calls orient each oriented entry's whole
+ *     frame into a context-owned buffer first — one more launch and 4 B/px per oriented entry (an oriented YUYV / UYVY entry: one pass, not
+ *     two) — and then are the call on that RGBA entry of O.
+ * The kernel lives in a code object of its own, libheadtrackr_hip_orient.hsaco NEXT TO the library, loaded on the first oriented call of a
+ * process (once per device); without that file every oriented call returns HT_ERR_STATE with the path in ht_last_error, and every other call
+ * works as before.  Not part of this: ht_draw_frames / ht_draw_frames_device (no format argument: an RGBA feed uses a one-entry list), the
+ * *_pairs_* calls (they read the canvas), arbitrary angles, a format-preserving rotation. */
+#define HT_ORIENT(k) ((int32_t)(k) << 8)
+#define HT_FORMAT_OF(f) ((int32_t)(f) & 0xff)
+#define HT_ORIENT_OF(f) (((int32_t)(f) >> 8) & 7)
 typedef struct ht_draw_source {
     const void *p0, *p1, *p2; /* RGBA: p0.  NV12: Y, UV.  I420: Y, U, V.  YUYV / UYVY: p0.  Device pointers; the unused ones are not looked at. */
     size_t pitch0, pitch1;    /* bytes per row of p0 / of the chroma plane(s); 0 = packed */
     int32_t width, height;    /* of THIS source */
-    int32_t format;           /* HT_YUV_NV12, HT_YUV_I420, HT_YUV_YUYV, HT_YUV_UYVY or HT_DRAW_RGBA */
+    int32_t format;           /* HT_YUV_NV12, HT_YUV_I420, HT_YUV_YUYV, HT_YUV_UYVY or HT_DRAW_RGBA; | HT_ORIENT(k) for a rotated / mirrored source */
     int32_t matrix;           /* HT_YUV_* matrix; ignored for RGBA */
     ht_cs_rect rect;          /* width == 0 && height == 0: whole source */
 } ht_draw_source;
