@@ -32,11 +32,6 @@ typedef HtCropDescT<dl_gptr> CrDesc;
 static_assert(sizeof(HtCropDesc) == 120 && sizeof(CrDesc) == sizeof(HtCropDesc) && alignof(CrDesc) == alignof(HtCropDesc), "crop descriptor layout");
 static_assert(sizeof(ht_crop_record) == 40, "ht_crop_record");
 
-// packed 4:2:2 entries (YUYV / UYVY) of a sources call rewritten to the RGBA entries of their unpacked frames: ht_draw_filter.hip, behind
-// the one kernel that holds the packed pixel body.  orient: per entry its orientation (ht_orient_plan.h), or NULL for none — an oriented entry
-// of ANY format becomes the RGBA entry of its oriented frame the same way
-ht_status dm_unpack_sources(ht_ctx *c, const char *fn, std::vector<HtCropDesc> &desc, const int32_t *orient = nullptr);
-
 // the RGBA8 output stage of the family: the pixel's dword into packed rows of dw pixels
 struct LpDwordStore {
     uint32_t *__restrict__ base;  // the entry's patch

@@ -1,7 +1,7 @@
 // ht_draw_list.hip — the K-feed form of the video -> canvas draw: ONE launch draws a list of sources that share nothing (the reference's
 // loop is one drawImage per feed, main.js:170).  Every entry has its own device allocation(s), size, pitches, format (RGBA, NV12, I420; YUYV and UYVY: see dl_launch),
 // matrix and source rect; entry i goes onto destination frame i with the bytes ht_draw_frames_device / ht_draw_frames_yuv_device give for
-// it alone.  Included at the end of ht_ingest.hip, so it is part of the same code object and shares that file's and ht_ingest_yuv.hip's
+// it alone.  Included by ht_ingest.hip, so it is part of the same code object and shares that file's and ht_ingest_yuv.hip's
 // text: the tile constants, ig_channel, ig_chroma_read and, through ht_ingest_bodies.inc, the taps and the three pixel bodies.
 //
 // k_draw_list: grid (tile column, tile row, entry), 64 x 16 destination pixels and 256 threads per workgroup.  A workgroup reads its
@@ -12,7 +12,8 @@
 // every list call's table does.  DESIGN.md §2.3.2 gives the reasoning and the registers.
 //
 // A list with an ORIENTED entry (an orientation in bits 8..10 of its format: ht_orient_plan.h) is not k_draw_list's: the second half of this
-// file loads the oriented draw's kernels from a code object of their own and launches them.
+// file loads the oriented draw's kernels from a code object of their own and launches them.  The entry point itself — one
+// function with ht_draw_list_filtered_device — is ht_draw_calls.hip, the draw family's one host path.
 #include <dlfcn.h>
 
 #include <cstdio>
@@ -76,10 +77,8 @@ ht_status dl_upload(ht_ctx *c, const char *fn, const std::vector<DESC> &desc) {
     return ht_stage_commit(c, &c->dl_tab, need);
 }
 
+// (a list with a packed 4:2:2 entry is not this kernel's: draw_list_call, ht_draw_calls.hip)
 ht_status dl_launch(ht_ctx *c, const char *fn, const std::vector<HtDrawDesc> &desc, uint8_t *dst, size_t dstride) {
-    // a list with a packed 4:2:2 entry (YUYV / UYVY) is drawn by the filtered draw's kernel at factors (1, 1): the same bytes, and the one
-    // kernel that holds the packed pixel body (ht_draw_filter.hip)
-    if (std::any_of(desc.begin(), desc.end(), [](const HtDrawDesc &d) { return ht_yuv_is_422(d.format); })) return dm_launch_unfiltered(c, fn, desc.data(), desc.size(), dst, dstride);
     ht_status st = dl_upload(c, fn, desc);
     if (st != HT_OK) return st;
     HtProfScope ps(c, "draw_list");
@@ -154,7 +153,7 @@ ht_status or_launch_part(ht_ctx *c, const OrModule &m, bool turn, size_t first, 
 // the measurement of DESIGN.md §2.3.9 chose); even rot never transposes.  The table is ordered plain entries first — an entry names its
 // destination frame itself — and each kind is one launch
 constexpr bool OR_TURN_SHIPPED = true;
-ht_status or_launch(ht_ctx *c, const char *fn, std::vector<HtOrientDesc> &desc, uint8_t *dst, size_t dstride, int dw, int dh) {
+ht_status or_launch(ht_ctx *c, const char *fn, std::vector<HtOrientDesc> &desc, uint8_t *dst, size_t dstride, int dw = 0, int dh = 0) {
     const OrModule *m = nullptr;
     ht_status st = or_module(c, fn, &m);
     if (st != HT_OK) return st;
@@ -168,25 +167,8 @@ ht_status or_launch(ht_ctx *c, const char *fn, std::vector<HtOrientDesc> &desc, 
     return or_launch_part(c, *m, true, nplain, desc.size() - nplain, dst, dstride, dw, dh);
 }
 
-// the context's staging buffer (ht_draw_frames' source staging) holds >= need bytes.  A reallocation waits for the work in flight first, like
-// every reallocation of the library
-ht_status or_stage_reserve(ht_ctx *c, const char *fn, size_t need, const char *what) {
-    if (c->ingest_src_cap >= need) return HT_OK;
-    HT_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->d_ingest_src) (void)hipFree(c->d_ingest_src);
-    c->d_ingest_src = nullptr, c->ingest_src_cap = 0;
-    if (hipMalloc(reinterpret_cast<void **>(&c->d_ingest_src), need) != hipSuccess) {
-        (void)hipGetLastError();
-        return ht_fail(c, HT_ERR_NOMEM, std::string(fn) + ": hipMalloc failed (" + what + ")");
-    }
-    c->ingest_src_cap = need;
-    return HT_OK;
-}
-
-// ORIENT FIRST: the calls whose kernels hold no orientation (the filtered draw, the face-patch calls) have each oriented entry's whole frame
-// drawn 1 : 1 (ht_orient_whole) onto frames[i], orw x orh packed rows, and then are the call on the RGBA entry of that O.  One table, one
-// launch per job (the frames have sizes of their own), the whole frame at 4 B/px: a pass the fused draw exists to avoid, and what a list
-// without oriented entries never pays.
+// ORIENT FIRST (dm_unpack_sources, ht_draw_calls.hip): each job's whole frame drawn 1 : 1 (ht_orient_whole) onto frames[i], orw x orh packed
+// rows.  One table, one launch per job (the frames have sizes of their own)
 ht_status or_upright(ht_ctx *c, const char *fn, std::vector<HtOrientDesc> &jobs, const std::vector<uint8_t *> &frames) {
     if (jobs.empty()) return HT_OK;
     const OrModule *m = nullptr;
@@ -201,48 +183,3 @@ ht_status or_upright(ht_ctx *c, const char *fn, std::vector<HtOrientDesc> &jobs,
 }
 
 }  // namespace
-
-extern "C" ht_status ht_draw_list_device(ht_ctx *c, const ht_draw_source *srcs, int32_t n, void *dst_dev, size_t dst_frame_stride) {
-    if (!c) return HT_ERR_INVALID;
-    HtRange range("ht_draw_list_device");
-    const char *fn = "ht_draw_list_device";
-    const std::string f(fn);
-    if (c->W == 0) return ht_fail(c, HT_ERR_STATE, f + ": call ht_set_geometry first");
-    if (!srcs || n <= 0 || n > HT_DRAW_LIST_MAX) return ht_fail(c, HT_ERR_INVALID, f + ": " + ht_draw_list_message(HT_DRAW_LIST_BAD_COUNT));
-    if ((uintptr_t)dst_dev & 3) return ht_fail(c, HT_ERR_INVALID, f + ": misaligned destination (4-byte alignment required)");
-    const size_t fbytes = (size_t)c->W * c->H * 4, dstride = dst_dev && dst_frame_stride ? dst_frame_stride : fbytes;
-    if ((dstride & 3) || dstride < fbytes) return ht_fail(c, HT_ERR_INVALID, f + ": destination frame stride smaller than a frame or not a multiple of 4");
-    std::vector<HtDrawDesc> desc((size_t)n);
-    std::vector<HtDrawExtent> ext((size_t)n);
-    int32_t bad = -1;
-    // a list with an oriented entry (any bit above the format number) is planned by ht_orient_plan and drawn, all of it, by the module's
-    // kernel: `launch` below.  A list without one takes the path it always took
-    std::vector<HtOrientDesc> odesc;
-    const bool oriented = std::any_of(srcs, srcs + n, [](const ht_draw_source &s) { return ht_orient_present(s.format); });
-    if (oriented) odesc.resize((size_t)n);
-    const int ps = oriented ? ht_orient_plan(srcs, n, c->W, c->H, odesc.data(), ext.data(), &bad) : ht_draw_list_plan(srcs, n, c->W, c->H, desc.data(), ext.data(), &bad);
-    if (ps != HT_DRAW_LIST_OK) return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": " + ht_draw_list_message(ps));
-    const auto launch = [&](uint8_t *dst, size_t stride) { return oriented ? or_launch(c, fn, odesc, dst, stride) : dl_launch(c, fn, desc, dst, stride); };
-    HT_HIP(c, hipSetDevice(c->device));
-    if (oriented) {  // a missing module is reported before anything is touched
-        const OrModule *m = nullptr;
-        const ht_status st = or_module(c, fn, &m);
-        if (st != HT_OK) return st;
-    }
-    if (!dst_dev) {
-        if (n > c->max_batch)
-            return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(c->max_batch) + ": more entries than the geometry's batch capacity");
-        // the buffer as it is now (it may be freed and reallocated for this call) and as far as this call writes it: defensive only, see
-        // ht_draw_frames_device
-        if ((bad = ht_draw_list_overlap(ext.data(), n, c->d_frames_own, std::max(c->d_frames_own_bytes, fbytes * (size_t)n))) >= 0)
-            return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": a source plane lies inside the context's own frame buffer");
-        ht_status st = ht_frames_own_reserve(c, fbytes * (size_t)n, fn);  // the contract of ig_draw_bound from here on
-        if (st != HT_OK) return st;
-        if ((st = launch(c->d_frames_own, fbytes)) != HT_OK) return st;
-        ht_frames_bind_own(c, n);
-        return HT_OK;
-    }
-    if ((bad = ht_draw_list_overlap(ext.data(), n, dst_dev, (size_t)(n - 1) * dstride + fbytes)) >= 0)
-        return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": a source plane and the destination overlap");
-    return launch(static_cast<uint8_t *>(dst_dev), dstride);
-}

@@ -142,7 +142,8 @@ ht_status face_pairs(ht_ctx *c, const FaceCall &k, const ht_cs_pair *pairs, int3
         if (s < 0 || s >= c->cs_streams) return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(i) + ": stream " + std::to_string(s) + " is not reserved");
         if (fr < 0 || fr >= c->nframes) return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(i) + ": frame " + std::to_string(fr) + " is not bound");
         const uint8_t *frame = c->d_frames + (size_t)fr * c->frame_stride;
-        if (ig_overlap(frame, fbytes, k.out_dev, total))
+        const HtDrawExtent bound = {{frame}, {fbytes}};
+        if (ht_draw_list_overlap(&bound, 1, k.out_dev, total) >= 0)
             return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(i) + ": the bound frame and the output overlap");
         HtCropDesc e = {};
         e.d.p0 = frame, e.d.pitch0 = (size_t)c->W * 4, e.d.format = HT_DRAW_RGBA;
@@ -152,6 +153,9 @@ ht_status face_pairs(ht_ctx *c, const FaceCall &k, const ht_cs_pair *pairs, int3
     }
     return k.launch(c, desc, ostride);
 }
+
+// packed 4:2:2 and oriented (orient[i] != 0) entries become the RGBA entries of their upright frames: ht_draw_calls.hip, behind ht_draw_filter.hip's launcher
+ht_status dm_unpack_sources(ht_ctx *c, const char *fn, std::vector<HtCropDesc> &desc, const int32_t *orient, bool packed_too);
 
 // every sources-form call
 ht_status face_sources(ht_ctx *c, const FaceCall &k, const int32_t *streams, const ht_draw_source *srcs, int32_t n) {
@@ -190,8 +194,8 @@ ht_status face_sources(ht_ctx *c, const FaceCall &k, const int32_t *streams, con
     const int32_t bad = ht_draw_list_overlap(ext.data(), n, k.out_dev, (size_t)(n - 1) * ostride + pbytes);
     if (bad >= 0) return ht_fail(c, HT_ERR_INVALID, f + ": entry " + std::to_string(bad) + ": a source plane and the output overlap");
     // packed 4:2:2 entries become the RGBA entries of their unpacked frames, oriented entries those of their oriented frames
-    // (ht_draw_filter.hip); a list without either is untouched
-    if ((st = dm_unpack_sources(c, k.fn, desc, orient.empty() ? nullptr : orient.data())) != HT_OK) return st;
+    // (ht_draw_calls.hip); a list without either is untouched
+    if ((st = dm_unpack_sources(c, k.fn, desc, orient.empty() ? nullptr : orient.data(), true)) != HT_OK) return st;
     return k.launch(c, desc, ostride);
 }
 

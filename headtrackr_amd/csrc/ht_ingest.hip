@@ -18,7 +18,8 @@
 // A file of its own, compiled into the back-projection unit's code object (ht_backproject.hip includes it at its end): profiles/traffic.json
 // ties the committed hardware counters to the machine code of the pyramid, scan and camshift code objects, which this code must not touch
 // (benchlib/fingerprint.py finds a unit by a kernel-name substring; no kernel here may carry one), and the library keeps exactly one
-// code object besides those three (tests/test_backproject_cpu.py).
+// code object besides those three (tests/test_backproject_cpu.py).  The kernel, a call's checks (ig_check) and the launch are here; the entry
+// points are ht_draw_calls.hip, the draw family's one host path, included last: behind every kernel file below and the launchers they define.
 #include <algorithm>
 #include <string>
 #include <type_traits>
@@ -59,10 +60,9 @@ struct IgPlan {  // a validated call
     int32_t sx, sy, sw, sh;
     size_t pitch, sstride;  // effective source pitch / frame stride
     size_t src_bytes;       // extent of the n source frames from src
-    size_t fbytes;          // bytes of one destination frame
 };
 
-// the checks both entry points share (the source described as the device will see it)
+// the checks both entry points share (ht_draw_calls.hip; the source described as the device will see it)
 ht_status ig_check(ht_ctx *c, const char *fn, int32_t n, int32_t src_width, int32_t src_height, size_t src_pitch, size_t src_frame_stride,
                    const ht_cs_rect *rect, IgPlan *p) {
     const std::string f(fn);
@@ -82,13 +82,7 @@ ht_status ig_check(ht_ctx *c, const char *fn, int32_t n, int32_t src_width, int3
         p->sx = rect->x, p->sy = rect->y, p->sw = rect->width, p->sh = rect->height;
     }
     p->src_bytes = (size_t)(n - 1) * p->sstride + p->pitch * (size_t)src_height;
-    p->fbytes = (size_t)c->W * c->H * 4;
     return HT_OK;
-}
-
-bool ig_overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return a && b && pa < pb + nb && pb < pa + na;
 }
 
 ht_status ig_launch(ht_ctx *c, const IgPlan &p, const uint8_t *src, int32_t n, uint8_t *dst, size_t dstride) {
@@ -100,75 +94,7 @@ ht_status ig_launch(ht_ctx *c, const IgPlan &p, const uint8_t *src, int32_t n, u
     return HT_OK;
 }
 
-// draws into the context's own frame buffer and binds the result.  Every argument error is reported before anything is touched; a HIP
-// failure here (the buffer has to grow and hipMalloc fails: HT_ERR_NOMEM; a failed launch: HT_ERR_HIP) leaves the context usable but,
-// when the buffer had to grow, without bound frames — the old buffer, and with it the old frames, is gone by then; the launch is ordered on the ctx stream behind every earlier reader
-// of that buffer (all of this context's work runs on that stream)
-ht_status ig_draw_bound(ht_ctx *c, const char *fn, const IgPlan &p, const uint8_t *src, int32_t n) {
-    ht_status st = ht_frames_own_reserve(c, p.fbytes * (size_t)n, fn);
-    if (st != HT_OK) return st;
-    if ((st = ig_launch(c, p, src, n, c->d_frames_own, p.fbytes)) != HT_OK) return st;
-    ht_frames_bind_own(c, n);
-    return HT_OK;
-}
-
 }  // namespace
-
-extern "C" ht_status ht_draw_frames_device(ht_ctx *c, const void *src_dev, int32_t n, int32_t src_width, int32_t src_height, size_t src_pitch,
-                                           size_t src_frame_stride, const ht_cs_rect *src_rect, void *dst_dev, size_t dst_frame_stride) {
-    if (!c) return HT_ERR_INVALID;
-    HtRange range("ht_draw_frames_device");
-    const char *fn = "ht_draw_frames_device";
-    IgPlan p;
-    ht_status st = ig_check(c, fn, n, src_width, src_height, src_pitch, src_frame_stride, src_rect, &p);
-    if (st != HT_OK) return st;
-    if (!src_dev || ((uintptr_t)src_dev & 3) || ((uintptr_t)dst_dev & 3))
-        return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": NULL source or misaligned pointer (4-byte alignment required)");
-    const uint8_t *src = static_cast<const uint8_t *>(src_dev);
-    HT_HIP(c, hipSetDevice(c->device));
-    if (!dst_dev) {
-        if (n > c->max_batch) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": more frames than the geometry's batch capacity");
-        // the buffer as it is now (it may be freed and reallocated for this call) and as far as this call writes it.  Defensive only: the
-        // library hands this buffer's address to nobody, so no caller can name a pointer into it except by accident
-        if (ig_overlap(src, p.src_bytes, c->d_frames_own, std::max(c->d_frames_own_bytes, p.fbytes * (size_t)n)))
-            return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": the source lies inside the context's own frame buffer");
-        return ig_draw_bound(c, fn, p, src, n);
-    }
-    const size_t dstride = dst_frame_stride ? dst_frame_stride : p.fbytes;
-    if ((dstride & 3) || dstride < p.fbytes) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": destination frame stride smaller than a frame or not a multiple of 4");
-    if (ig_overlap(src, p.src_bytes, dst_dev, (size_t)(n - 1) * dstride + p.fbytes))
-        return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": source and destination overlap");
-    return ig_launch(c, p, src, n, static_cast<uint8_t *>(dst_dev), dstride);
-}
-
-extern "C" ht_status ht_draw_frames(ht_ctx *c, const uint8_t *host_rgba, int32_t n, int32_t src_width, int32_t src_height, size_t src_frame_stride,
-                                    const ht_cs_rect *src_rect) {
-    if (!c) return HT_ERR_INVALID;
-    HtRange range("ht_draw_frames");
-    const char *fn = "ht_draw_frames";
-    IgPlan p;
-    const size_t sbytes = (size_t)(src_width > 0 ? src_width : 0) * (size_t)(src_height > 0 ? src_height : 0) * 4;
-    if (src_frame_stride && src_frame_stride < sbytes) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": source frame stride smaller than a frame");
-    ht_status st = ig_check(c, fn, n, src_width, src_height, 0, 0, src_rect, &p);  // staged packed: the caller's stride is applied by the copy
-    if (st != HT_OK) return st;
-    if (!host_rgba) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": NULL source");
-    if (n > c->max_batch) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": more frames than the geometry's batch capacity");
-    HT_HIP(c, hipSetDevice(c->device));
-    const size_t need = sbytes * (size_t)n;
-    if (c->ingest_src_cap < need) {  // a reallocation waits for the work in flight first, like every reallocation of the library
-        HT_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->d_ingest_src) (void)hipFree(c->d_ingest_src);
-        c->d_ingest_src = nullptr, c->ingest_src_cap = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&c->d_ingest_src), need) != hipSuccess) {
-            (void)hipGetLastError();
-            return ht_fail(c, HT_ERR_NOMEM, std::string(fn) + ": hipMalloc failed (source staging)");
-        }
-        c->ingest_src_cap = need;
-    }
-    if (!src_frame_stride || src_frame_stride == sbytes) HT_HIP(c, hipMemcpyAsync(c->d_ingest_src, host_rgba, need, hipMemcpyHostToDevice, c->stream));
-    else HT_HIP(c, hipMemcpy2DAsync(c->d_ingest_src, sbytes, host_rgba, src_frame_stride, sbytes, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    return ig_draw_bound(c, fn, p, c->d_ingest_src, n);
-}
 
 void ht_ingest_free(ht_ctx *c) {  // ht_destroy (the stream has been synchronised)
     if (c->d_ingest_src) (void)hipFree(c->d_ingest_src);
@@ -201,3 +127,5 @@ void ht_ingest_free(ht_ctx *c) {  // ht_destroy (the stream has been synchronise
 // the draw list with a prefilter: each canvas pixel the mean of a block of the unfiltered draw's samples (ht_draw_filter_plan.h states the
 // rule and plans a call on the host); the kernel compiles the three pixel bodies through the crops' scaffold, with ht_filter.hip's accumulating output stage
 #include "ht_draw_filter.hip"
+// the calls of the draw family: one host path for the six canvas-draw entry points, behind every launcher they end up in
+#include "ht_draw_calls.hip"

@@ -1,6 +1,7 @@
 // ht_ingest_yuv.hip — the video -> canvas draw for frames that arrive as YUV 4:2:0 (NV12 from hardware decoders, I420 from software
-// decoders): the colour conversion a browser's drawImage(video, ..) hides, fused into the draw.  Included at the end of ht_ingest.hip, so
-// it is part of the same code object and shares that file's text: the tile constants, ig_channel, ig_overlap.
+// decoders): the colour conversion a browser's drawImage(video, ..) hides, fused into the draw.  Included by ht_ingest.hip, so
+// it is part of the same code object and shares that file's text: the tile constants, ig_channel.  The kernel, a call's checks (igy_check) and
+// the planar launch are here; the two entry points and the routes below are ht_draw_calls.hip, the draw family's one host path.
 //
 // The result is DEFINED as what ht_draw_frames_device gives on the RGBA frame the declared conversion (ht_yuv_plan.h) makes of the
 // planes, byte for byte, for every rect, ratio and size: a destination pixel's four tap pixels are converted to RGBA8 dwords with the
@@ -63,21 +64,14 @@ __global__ __launch_bounds__(IG_NT) void k_draw_yuv(const uint8_t *__restrict__ 
 #include "ht_ingest_bodies.inc"
 }
 
-// the unfiltered draw of descriptors that may hold packed 4:2:2 entries: ht_draw_filter.hip, behind the kernel it launches
-ht_status dm_launch_unfiltered(ht_ctx *c, const char *fn, const HtDrawDesc *desc, size_t n, uint8_t *dst, size_t dstride);
-
-// the oriented draw (a format with HT_ORIENT bits, ht_orient_plan.h) through the module's kernel: ht_draw_list.hip.  dw == 0: onto the canvas
-ht_status or_launch(ht_ctx *c, const char *fn, std::vector<HtOrientDesc> &desc, uint8_t *dst, size_t dstride, int dw = 0, int dh = 0);
-
 struct IgYuvCall {  // a validated call: the source as the device will see it
     HtYuvPlan plan;
     int32_t format, matrix;  // format: the bare number
     int32_t orient, width, height;  // the orientation the format carried, and the STORED frame's size
     int32_t sx, sy, sw, sh;  // the source rect: in O's coordinates (orientation 0: O is the stored frame)
-    size_t fbytes;  // bytes of one destination frame
 };
 
-// the checks both entry points share
+// the checks both entry points share (ht_draw_calls.hip)
 ht_status igy_check(ht_ctx *c, const char *fn, int32_t n, int32_t width, int32_t height, int32_t format, int32_t matrix, size_t y_pitch, size_t c_pitch,
                     size_t frame_stride, const ht_cs_rect *rect, IgYuvCall *q) {
     const std::string f(fn);
@@ -95,38 +89,14 @@ ht_status igy_check(ht_ctx *c, const char *fn, int32_t n, int32_t width, int32_t
             return ht_fail(c, HT_ERR_INVALID, f + ": source rect must lie wholly inside the source frame");
         q->sx = rect->x, q->sy = rect->y, q->sw = rect->width, q->sh = rect->height;
     }
-    q->fbytes = (size_t)c->W * c->H * 4;
     return HT_OK;
 }
 
-ht_status igy_launch(ht_ctx *c, const char *fn, const IgYuvCall &q, const uint8_t *y, const uint8_t *u, const uint8_t *v, int32_t n, uint8_t *dst, size_t dstride) {
+// NV12 (u: the interleaved plane, v unused) and I420; a packed 4:2:2 or an oriented call is not this kernel's (igy_launch, ht_draw_calls.hip)
+ht_status igy_launch_planar(ht_ctx *c, const IgYuvCall &q, const uint8_t *y, const uint8_t *u, const uint8_t *v, int32_t n, uint8_t *dst, size_t dstride) {
     const double rx = (double)q.sw / (double)c->W, ry = (double)q.sh / (double)c->H;  // canvas_shim.js: one binary64 division each
     const HtYuvPlan &p = q.plan;
     const HtYuvCoef kc = HT_YUV_COEF[q.matrix];
-    if (q.orient) {  // one descriptor per frame through the module's kernel, as the packed formats go through theirs below
-        std::vector<HtOrientDesc> desc((size_t)n);
-        const bool nv12 = q.format == HT_YUV_FMT_NV12, packed = ht_yuv_is_422(q.format);
-        for (int32_t f = 0; f < n; f++) {
-            HtOrientDesc &o = desc[(size_t)f];
-            o = HtOrientDesc{};
-            HtDrawDesc &d = o.d;
-            d.p0 = y + (size_t)f * p.stride, d.pitch0 = p.y_pitch, d.rx = rx, d.ry = ry;
-            if (!packed) d.p1 = u + (size_t)f * p.stride, d.p2 = nv12 ? d.p1 : v + (size_t)f * p.stride, d.pitch1 = p.c_pitch;
-            d.sw = q.width, d.sh = q.height, d.cw = p.cw, d.format = q.format, d.kc = kc;
-            o.orient = q.orient, o.frame = f, o.ox = q.sx, o.oy = q.sy, o.orw = q.sw, o.orh = q.sh;
-        }
-        return or_launch(c, fn, desc, dst, dstride);
-    }
-    if (ht_yuv_is_422(q.format)) {  // one descriptor per frame through the one kernel that holds the packed pixel body (ht_draw_filter.hip; its timer)
-        std::vector<HtDrawDesc> desc((size_t)n);
-        for (int32_t f = 0; f < n; f++) {
-            HtDrawDesc &d = desc[(size_t)f];
-            d = HtDrawDesc{};
-            d.p0 = y + (size_t)f * p.stride, d.pitch0 = p.y_pitch, d.rx = rx, d.ry = ry;
-            d.sx = q.sx, d.sy = q.sy, d.sw = q.sw, d.sh = q.sh, d.cw = p.cw, d.format = q.format, d.kc = kc;
-        }
-        return dm_launch_unfiltered(c, fn, desc.data(), desc.size(), dst, dstride);
-    }
     HtProfScope ps(c, "draw_yuv");
     const dim3 grid((c->W + IG_TW - 1) / IG_TW, (c->H + IG_TH - 1) / IG_TH, n);
     if (q.format == HT_YUV_FMT_NV12)
@@ -139,88 +109,4 @@ ht_status igy_launch(ht_ctx *c, const char *fn, const IgYuvCall &q, const uint8_
     return HT_OK;
 }
 
-// into the context's own frame buffer, bound on success: the contract of ig_draw_bound
-ht_status igy_draw_bound(ht_ctx *c, const char *fn, const IgYuvCall &q, const uint8_t *y, const uint8_t *u, const uint8_t *v, int32_t n) {
-    ht_status st = ht_frames_own_reserve(c, q.fbytes * (size_t)n, fn);
-    if (st != HT_OK) return st;
-    if ((st = igy_launch(c, fn, q, y, u, v, n, c->d_frames_own, q.fbytes)) != HT_OK) return st;
-    ht_frames_bind_own(c, n);
-    return HT_OK;
-}
-
 }  // namespace
-
-extern "C" ht_status ht_draw_frames_yuv_device(ht_ctx *c, const ht_yuv_frames *s, int32_t n, const ht_cs_rect *src_rect, void *dst_dev, size_t dst_frame_stride) {
-    if (!c) return HT_ERR_INVALID;
-    HtRange range("ht_draw_frames_yuv_device");
-    const char *fn = "ht_draw_frames_yuv_device";
-    if (!s) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": NULL source description");
-    IgYuvCall q;
-    ht_status st = igy_check(c, fn, n, s->width, s->height, s->format, s->matrix, s->y_pitch, s->c_pitch, s->frame_stride, src_rect, &q);
-    if (st != HT_OK) return st;
-    const bool nv12 = q.format == HT_YUV_FMT_NV12, packed = ht_yuv_is_422(q.format);  // packed: one plane, u and v are not looked at
-    if (!s->y || (!packed && (!s->u || (!nv12 && !s->v)))) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": NULL plane");
-    if (nv12 && ((uintptr_t)s->u & 1)) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": the NV12 chroma plane must start at an even address");
-    if (packed && ((uintptr_t)s->y & 3)) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": misaligned YUYV / UYVY plane (4-byte alignment required)");
-    if ((uintptr_t)dst_dev & 3) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": misaligned destination (4-byte alignment required)");
-    const uint8_t *y = static_cast<const uint8_t *>(s->y), *u = packed ? nullptr : static_cast<const uint8_t *>(s->u),
-                  *v = nv12 || packed ? nullptr : static_cast<const uint8_t *>(s->v);
-    const HtYuvPlan &p = q.plan;
-    const auto overlaps = [&](const void *d, size_t nd) { return ig_overlap(y, p.y_extent, d, nd) || ig_overlap(u, p.c_extent, d, nd) || ig_overlap(v, p.c_extent, d, nd); };
-    HT_HIP(c, hipSetDevice(c->device));
-    if (!dst_dev) {
-        if (n > c->max_batch) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": more frames than the geometry's batch capacity");
-        if (overlaps(c->d_frames_own, std::max(c->d_frames_own_bytes, q.fbytes * (size_t)n)))  // defensive only: see ht_draw_frames_device
-            return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": a source plane lies inside the context's own frame buffer");
-        return igy_draw_bound(c, fn, q, y, u, v, n);
-    }
-    const size_t dstride = dst_frame_stride ? dst_frame_stride : q.fbytes;
-    if ((dstride & 3) || dstride < q.fbytes) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": destination frame stride smaller than a frame or not a multiple of 4");
-    if (overlaps(dst_dev, (size_t)(n - 1) * dstride + q.fbytes)) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": a source plane and the destination overlap");
-    return igy_launch(c, fn, q, y, u, v, n, static_cast<uint8_t *>(dst_dev), dstride);
-}
-
-extern "C" ht_status ht_draw_frames_yuv(ht_ctx *c, const uint8_t *host, int32_t n, int32_t width, int32_t height, int32_t format, int32_t matrix,
-                                        size_t frame_stride, const ht_cs_rect *src_rect) {
-    if (!c) return HT_ERR_INVALID;
-    HtRange range("ht_draw_frames_yuv");
-    const char *fn = "ht_draw_frames_yuv";
-    // staged tightly packed, Y then chroma, at 1.5 B/px.  NV12 wants its chroma plane at an even address: a frame of odd width AND odd
-    // height has an odd Y plane, so it is staged one byte into the buffer (the Y plane needs no alignment) and frames one byte further
-    // apart.  A packed 4:2:2 frame is 4 cw h bytes at 2 B/px, a multiple of 4 already: no lead, and every frame starts on a macropixel
-    HtYuvPlan p0;
-    const int32_t given = format;  // with its orientation bits: igy_check takes them apart again
-    int32_t orient = 0;
-    ht_orient_split(given, &format, &orient);
-    const size_t fsz = ht_yuv_plan(width, height, format, matrix, 0, 0, 0, 1, &p0) == HT_YUV_PLAN_OK ? p0.packed_frame : 0;
-    const size_t lead = (format == HT_YUV_FMT_NV12) ? (fsz & 1) : 0, dstep = fsz + lead;
-    IgYuvCall q;
-    ht_status st = igy_check(c, fn, n, width, height, given, matrix, 0, 0, dstep, src_rect, &q);  // (reports what made fsz 0, if anything did)
-    if (st != HT_OK) return st;
-    if (frame_stride && frame_stride < fsz) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": source frame stride smaller than a frame");
-    if (!host) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": NULL source");
-    if (n > c->max_batch) return ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": more frames than the geometry's batch capacity");
-    HT_HIP(c, hipSetDevice(c->device));
-    const size_t need = lead + dstep * (size_t)n;
-    if (c->ingest_src_cap < need) {  // a reallocation waits for the work in flight first, like every reallocation of the library
-        HT_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->d_ingest_src) (void)hipFree(c->d_ingest_src);
-        c->d_ingest_src = nullptr, c->ingest_src_cap = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&c->d_ingest_src), need) != hipSuccess) {
-            (void)hipGetLastError();
-            return ht_fail(c, HT_ERR_NOMEM, std::string(fn) + ": hipMalloc failed (source staging)");
-        }
-        c->ingest_src_cap = need;
-    }
-    uint8_t *stage = c->d_ingest_src + lead;
-    const size_t sstep = frame_stride ? frame_stride : fsz;
-    // one copy when both sides are packed; otherwise one per frame (a strided hipMemcpy2DAsync into the byte-offset staging left the head
-    // of frame 0 stale on the GPU tests' pageable sources, and n is a batch of feeds, not of pixels)
-    if (n == 1 || (sstep == fsz && dstep == fsz)) HT_HIP(c, hipMemcpyAsync(stage, host, n == 1 ? fsz : fsz * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    else
-        for (int32_t f = 0; f < n; f++) HT_HIP(c, hipMemcpyAsync(stage + (size_t)f * dstep, host + (size_t)f * sstep, fsz, hipMemcpyHostToDevice, c->stream));
-    const bool packed = ht_yuv_is_422(format);
-    const uint8_t *y = stage, *u = packed ? nullptr : stage + (size_t)width * (size_t)height,
-                  *v = format == HT_YUV_FMT_I420 ? u + (size_t)q.plan.cw * (size_t)q.plan.ch : nullptr;
-    return igy_draw_bound(c, fn, q, y, u, v, n);
-}

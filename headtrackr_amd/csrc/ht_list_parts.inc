@@ -19,7 +19,7 @@
 //                     slice's s_col / s_row); it is undefined again behind the scaffold.  LP_PACKED_422, when the kernel defines it (as a constant expression that is true), makes the
 //                     third body take the packed 4:2:2 formats (YUYV, UYVY) besides I420 (ht_draw_filter.hip: the one kernel every draw of
 //                     a packed source goes through); without it a kernel is the instructions it was, and its host path hands it no such entry (the
-//                     face-patch calls unpack a packed entry's frame to RGBA first: dm_unpack_sources)
+//                     face-patch calls unpack a packed entry's frame to RGBA first: dm_unpack_sources, ht_draw_calls.hip)
 //
 // The including kernel binds: tab, states, recs, dw, dh, cw_canvas, ch_canvas, margin_q8, flags (its parameters; dst and dst_stride for the
 // bodies), and the tile through IG_TW / IG_TH / IG_RPT / IG_NT as the pixel bodies read them (a kernel with another tile declares

@@ -279,7 +279,9 @@ def test_mean_kernels_fit_their_budget_and_leave_their_neighbours_alone():
     for unit in ("pyramid", "scan", "camshift"):
         assert now.get(unit) == recorded[unit], (unit, now.get(unit), recorded[unit])
     text = {f: open(os.path.join(CSRC, f)).read() for f in ("ht_ingest.hip", "ht_draw_filter.hip", "ht_draw_filter_plan.h", "ht_draw_list.hip")}
-    assert text["ht_ingest.hip"].rstrip().endswith('#include "ht_draw_filter.hip"') and text["ht_ingest.hip"].index('#include "ht_filter.hip"') < text["ht_ingest.hip"].index('#include "ht_draw_filter.hip"')
+    ingest = text["ht_ingest.hip"]  # the draw family's host path (ht_draw_calls.hip) is included last, behind this file's kernel and launcher
+    assert ingest.rstrip().endswith('#include "ht_draw_calls.hip"')
+    assert ingest.index('#include "ht_filter.hip"') < ingest.index('#include "ht_draw_filter.hip"') < ingest.index('#include "ht_draw_calls.hip"')
     # no second restatement of the blend or of the conversion: the kernel takes the ONE scaffold with its loops in front of each body
     f = text["ht_draw_filter.hip"]
     assert f.count("#define LP_PART 4  // LP_SCAFFOLD") == 1 and f.count("#define LP_EACH_PASS") == 1 and f.count('#include "ht_ingest_bodies.inc"') == 0

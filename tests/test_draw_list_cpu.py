@@ -230,11 +230,11 @@ def test_list_kernel_fits_its_budget_and_shares_the_text_of_the_draw_kernels():
     assert len(objs) == 4
     home = [o for o in objs if b"k_draw_list" in o]
     assert len(home) == 1 and b"k_draw_frames" in home[0] and b"k_draw_yuv" in home[0]
-    text = {f: open(os.path.join(CSRC, f)).read() for f in ("ht_ingest.hip", "ht_ingest_yuv.hip", "ht_draw_list.hip", "ht_ingest_bodies.inc", "ht_draw_list_plan.h")}
+    text = {f: open(os.path.join(CSRC, f)).read() for f in ("ht_ingest.hip", "ht_ingest_yuv.hip", "ht_draw_list.hip", "ht_draw_calls.hip", "ht_ingest_bodies.inc", "ht_draw_list_plan.h")}
     assert '#include "ht_draw_list.hip"' in text["ht_ingest.hip"]
-    assert [text[f].count('#include "ht_ingest_bodies.inc"') for f in ("ht_ingest.hip", "ht_ingest_yuv.hip", "ht_draw_list.hip")] == [2, 2, 4]
+    assert [text[f].count('#include "ht_ingest_bodies.inc"') for f in ("ht_ingest.hip", "ht_ingest_yuv.hip", "ht_draw_list.hip", "ht_draw_calls.hip")] == [2, 2, 4, 0]  # (the calls' host path holds no kernel)
     assert text["ht_ingest_bodies.inc"].count("ig_channel(") == 2 and text["ht_ingest_bodies.inc"].count("rs_tap(") == 2  # one per pixel body; column and row taps
-    for f in ("ht_ingest.hip", "ht_ingest_yuv.hip", "ht_draw_list.hip"):
+    for f in ("ht_ingest.hip", "ht_ingest_yuv.hip", "ht_draw_list.hip", "ht_draw_calls.hip"):
         assert "rs_tap(" not in text[f], f
     assert "hip/" not in text["ht_draw_list_plan.h"] and "__global__" not in text["ht_draw_list_plan.h"] and "ht_yuv_plan(" in text["ht_draw_list_plan.h"]
 

@@ -409,6 +409,21 @@ def test_error_statuses_leave_the_context_usable(cascade):
         ddst.free()
 
 
+def test_every_refusal_of_the_draw_calls_is_the_recorded_one():
+    """tests/draw_refusal_cases.py's table — every refusal of the six canvas-draw entry points, the adjacent double faults that pin each
+    call's check order, ht_set_geometry not yet called — replayed on the built library: status and ht_last_error text equal
+    tests/golden/draw_call_refusals.json, which was recorded before the calls' host path was written once.  No kernel runs."""
+    import draw_refusal_cases as drc
+
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "draw_call_refusals.json")))
+    got = drc.replay()
+    assert got["canvas"] == golden["canvas"]
+    assert sorted(got["cases"]) == sorted(golden["cases"]) and len(golden["cases"]) >= 180
+    for key, want in golden["cases"].items():
+        assert got["cases"][key] == want, (key, got["cases"][key], want)
+    assert all(st in (HT_ERR_INVALID, HT_ERR_STATE) and len(text) > 10 for st, text in golden["cases"].values())
+
+
 # ---- Node ----------------------------------------------------------------------------------------------------------------------------------
 
 def test_node_facade_draws_on_the_device(tmp_path):

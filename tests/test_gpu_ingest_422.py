@@ -323,6 +323,73 @@ def test_face_patches_from_a_packed_feed_equal_those_from_its_rgba_conversion(ki
         rarr.free()
 
 
+# ---- 5b: the staging buffer the routes share --------------------------------------------------------------------------------------------------
+
+def test_the_routes_share_one_staging_buffer():
+    """ONE context, a 40 x 30 canvas, sources of 34 x 18 at the most; every step against the CPU oracle of its case module, byte for byte.
+      1. ht_draw_frames from host RGBA: stages 2448 bytes into the context's ingest staging buffer (the first allocation);
+      2. at once, without a wait in between, crop_sources of [YUYV, NV12 under rot 1, RGBA]: the same buffer GROWS to 4896 bytes while step
+         1's draw may still read the old one, and is carved into the oriented job's frame (offset 0) and the unpacked YUYV frame (offset
+         2448).  (Freeing device memory waits by itself, so this does not prove the reserve's own wait; it pins the offsets and the order);
+      3. ht_draw_frames_yuv from host I420 and from host NV12 at 33 x 17 (odd x odd: NV12 is staged one byte into the buffer), two frames;
+      4. ht_draw_list_filtered_device of one oriented entry at max_factor 2 (factors (1, 2)): orient first, into the same buffer.
+    Step 1's frame is read back after step 2, every later step's result after the step: the routes do not tread on each other."""
+    import crop_cases as cr
+    import draw_filter_cases as dfc
+    import draw_list_cases as dl
+    import orient_cases as oc
+    from test_gpu_crop import record_tuples
+    from test_gpu_orient import Resident, upright_source
+
+    W, H, w, h, P, Q = 40, 30, 34, 18, 20, 11
+    scene = np.zeros((H, W, 4), dtype=np.uint8)
+    scene[...] = (30, 40, 90, 255)
+    scene[9:21, 12:28] = (230, 120, 60, 255)
+    host1 = ic.frames_of("noise", w, h, 1, seed=71)
+    yuyv, nv12, rgba = oc.source(y4.YUYV, w, h, seed=72, matrix=1), oc.source(yc.NV12, w, h, seed=73, matrix=2), oc.source(dl.RGBA, w, h, seed=74)
+    ups = [upright_source(yuyv.rgba), upright_source(oc.orient(nv12.rgba, 1)), rgba]  # what the three entries are to the crop: O of each
+    streams = [0, 1, 0]
+    res, sarr = Resident([yuyv, nv12, rgba]), DeviceArray(scene)
+    out = DeviceArray(np.full(3 * P * Q * 4 + 64, GUARD, dtype=np.uint8))
+    dst = DeviceArray(np.full(W * H * 4 + 64, GUARD, dtype=np.uint8))
+    try:
+        with fresh(W, H, 2) as c:
+            # the trackers, from frames drawn out of device memory: the staging buffer is not touched yet
+            c.draw_list([dict(format="rgba", width=W, height=H, p0=sarr.ptr)] * 2)
+            c.camshift_reserve(2)
+            c.camshift_init_pairs([(0, 0), (1, 1)], [(12, 9, 16, 12)] * 2)
+            objs = [tuple(float(v) for v in cr.obj_of(o)) for o in c.camshift_track_pairs([(0, 0), (1, 1)], calc_angles=True)]
+            # 1 and 2, back to back
+            c.draw_frames(host1)
+            c.camshift_crop_sources_device(out.ptr, streams, [res.entry(yuyv, 0), res.entry(nv12, 1), res.entry(rgba, 0)], P, Q)
+            rec = c.camshift_crop_result(3)
+            c.synchronize()
+            got = d2h(out.ptr, out.nbytes)
+            bound_equals(c, ic.expected(host1[0], None, W, H)[None], "step 1: the host RGBA frame, read after step 2 grew its staging buffer")
+            want = [cr.record(st, objs[st], W, H, up.w, up.h, None, 256, 0, P, Q) for up, st in zip(ups, streams)]
+            assert record_tuples(rec) == want and all(r[0] == cr.FACE for r in want), (record_tuples(rec), want)
+            for i, (up, st) in enumerate(zip(ups, streams)):
+                same(got[i * P * Q * 4:(i + 1) * P * Q * 4].reshape(Q, P, 4), cr.patch(up, objs[st], W, H, None, 256, 0, P, Q), f"step 2: entry {i}")
+            assert (got[3 * P * Q * 4:] == GUARD).all()
+            # 3: the host YUV forms, odd x odd
+            for fmt, matrix in ((yc.I420, 3), (yc.NV12, 0)):
+                frames = yc.from_rgb_frames("noise", 33, 17, 2, fmt, matrix, seed=75 + fmt)
+                c.draw_frames_yuv([np.stack([f[k] for f in frames]) for k in range(len(frames[0]))], fmt, matrix)
+                bound_equals(c, np.stack([yc.expected(f, 33, 17, fmt, matrix, None, W, H) for f in frames]), f"step 3: host format {fmt} at 33 x 17")
+            # 4: the filtered draw orients first
+            c.draw_list([res.entry(nv12, 1)], dst=dst.ptr, prefilter=2)
+            c.synchronize()
+            buf = d2h(dst.ptr, dst.nbytes)
+            want4, factors = dfc.expected_rgba(oc.orient(nv12.rgba, 1), None, W, H, 2)
+            assert factors == (1, 2), factors
+            same(buf[:W * H * 4].reshape(H, W, 4), want4, "step 4: the oriented entry, filtered")
+            assert (buf[W * H * 4:] == GUARD).all()
+    finally:
+        for x in (sarr, out, dst):
+            x.free()
+        res.free()
+
+
 # ---- 7: Node -------------------------------------------------------------------------------------------------------------------------------------
 
 def test_node_facade_draws_and_crops_packed_feeds_on_the_device(tmp_path):
