@@ -442,19 +442,14 @@ ht_status grp_collect(ht_ctx *c, ht_rect *best, uint32_t *total_hits, int64_t ne
     HT_HIP(c, hipSetDevice(c->device));
     const uint32_t nfr = (uint32_t)c->grp_nframes;
     const HtGrpLayout L = ht_grp_layout(nfr);
-    // nhits, records, status words and bucket tables in ONE pinned copy (+ the whitebalance sums of this batch, as in ht_detect_collect)
-    HT_HIP(c, hipMemcpyAsync(c->h_grp_out, c->d_grp_out, L.bytes, hipMemcpyDeviceToHost, c->stream));
-    const bool wb_snap = c->wb_enqueued && c->h_wb_pinned;
-    if (wb_snap)
-        HT_HIP(c, hipMemcpyAsync(c->h_wb_pinned, c->d_scratch, sizeof(unsigned long long) * 4 * (size_t)c->enq_nframes, hipMemcpyDeviceToHost, c->stream));
-    HT_HIP(c, hipStreamSynchronize(c->stream));
+    // nhits, records, status words and bucket tables in ONE pinned copy (+ the whitebalance sums of this batch): ht_detect_collect's head
+    ht_status st = ht_detect_fetch(c, c->h_grp_out, c->d_grp_out, L.bytes);
+    if (st != HT_OK) return st;
     const HtGrpHead head = *reinterpret_cast<const HtGrpHead *>(c->h_grp_out);
     c->grp_enqueued = false;
     c->h_counters = HtCounters{head.nhits, 0, 0, 0};
     c->spec_hint = head.nhits;
-    ht_status st = ht_detect_mark_collected(c, wb_snap);
     if (total_hits) *total_hits = head.nhits;
-    if (st != HT_OK) return st;
     const int32_t mn = c->grp_min_neighbors, fb = c->grp_frame_base;
     if (head.nhits > c->hit_capacity) st = ht_fail(c, HT_ERR_CAPACITY, std::string(fn) + ": more raw hits than ht_config.hit_capacity; results incomplete");
     else if (head.bad) st = ht_fail(c, HT_ERR_INVALID, std::string(fn) + ": a raw hit's frame or scale is out of range");

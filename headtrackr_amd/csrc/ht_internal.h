@@ -63,6 +63,9 @@ struct HtCounters {
 // without HIP as well, shared with the CPU suite's harness.
 #include "ht_cs_schedule.h"
 
+// A context's published frame binding (HtFrameSlot) and the process-wide registry of them: plain C++ too, shared with the CPU suite's harness.
+#include "ht_frame_registry.h"
+
 // A captured detect sequence (memsets + gray + pyramid generations + scan kernels: ~10 dependent launches) replayed with one
 // hipGraphLaunch.  Keyed by everything the kernels' arguments depend on besides the geometry (which owns the cache).
 // INVARIANT: a captured graph bakes in d_arena, d_counters, d_hits, d_queue, d_stats, the tile / job tables and d_scratch.  The first
@@ -179,9 +182,12 @@ struct ht_ctx {
     int back_n = 0;                    // frames in the back buffer (0 = nothing pending)
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_copy_done = nullptr, ev_front_free = nullptr;
+    // the binding: written by ht_frames_set (ht_frames.hip) and by nothing else, read by this context's own calls.  What OTHER contexts'
+    // threads may see of it is the copy ht_frames_set publishes in frame_slot (ht_frame_registry.h)
     const uint8_t *d_frames = nullptr;
     size_t frame_stride = 0;
     int nframes = 0;
+    HtFrameSlot frame_slot;
     // small batches (a live feed = 1 frame) are launch-bound: ~10 dependent launches cost more than their kernels.  Their sequence is
     // captured into a hipGraph per (frames pointer, count, flags) and replayed.  0 disables (option graph_max_frames)
     // set (under the cluster gate's lock: ht_capture_mark) while this context's stream is between hipStreamBeginCapture and EndCapture:
@@ -190,7 +196,6 @@ struct ht_ctx {
     int graph_max_frames = 256;  // round 4: replaying a 256-frame C2 batch instead of launching its 9 kernels: 0.2253 -> 0.2239 ms per step at three in flight (16 until then: only launch-bound small batches)
     std::vector<HtDetectGraph> graphs;
     uint64_t graph_launches = 0;  // measurement: enqueues served by a graph replay
-    int64_t requeue_flags = -1;   // >= 0: ht_detect_collect enqueues the next batch (these flags) as soon as the raw hits are on the host
     int enq_nframes = 0;  // frames of the batch enqueued last (what ht_detect_collect reports on)
 
     // scan outputs
@@ -210,8 +215,6 @@ struct ht_ctx {
     std::vector<uint32_t> h_frame_start;       // ... bucket offsets of the counting sort by frame
     bool stats_enqueued = false;
     bool enqueued = false;
-    bool collect_best_follows = false;  // set by ht_detect_collect_best around its ht_detect_collect: the per-frame ordering is left to its own per-frame pass
-    bool h_sort_deferred = false;       // ... and this says that it was
 
     // whitebalance / grayscale scratch
     double *d_scratch = nullptr;
@@ -485,9 +488,12 @@ void ht_ingest_free(ht_ctx *ctx);                           // ht_ingest.hip: th
 void ht_align_free(ht_ctx *ctx);                            // ht_face_calls.hip: the aligned crops' table, records and events (called by ht_ingest_free)
 void ht_crop_free(ht_ctx *ctx);                             // ht_face_calls.hip: the face crops' table, records and events (called by ht_ingest_free)
 void ht_group_free(ht_ctx *ctx);                            // ht_group.hip: the device grouping's buffers (ht_destroy)
-ht_status ht_detect_mark_collected(ht_ctx *ctx, bool wb_snap);  // ht_context.hip: the state every collect call leaves behind
-ht_status ht_frames_own_reserve(ht_ctx *ctx, size_t need, const char *fn);  // ht_context.hip: the context's own frame buffer holds >= need bytes
-void ht_frames_bind_own(ht_ctx *ctx, int n);                // ht_context.hip: binds its first n frames (packed), as after ht_upload_frames
+// ht_detect_step.hip: the head of every collect call — `bytes` from the device into pinned memory and the batch's whitebalance sums behind
+// them, one synchronisation, the state every collect call leaves behind
+ht_status ht_detect_fetch(ht_ctx *ctx, void *pinned_dst, const void *dev_src, size_t bytes);
+void ht_frames_set(ht_ctx *ctx, const uint8_t *frames, size_t frame_stride, int n);  // ht_frames.hip: THE binding setter (frames == nullptr: unbound)
+ht_status ht_frames_own_reserve(ht_ctx *ctx, size_t need, const char *fn);  // ht_frames.hip: the context's own frame buffer holds >= need bytes
+void ht_frames_bind_own(ht_ctx *ctx, int n);                // ht_frames.hip: binds its first n frames (packed), as after ht_upload_frames
 ht_status ht_launch_pyramid(ht_ctx *ctx, uint32_t flags);   // ht_pyramid.hip
 ht_status ht_launch_scan(ht_ctx *ctx, uint32_t flags);      // ht_scan.hip
 ht_status ht_launch_scan_early(ht_ctx *ctx, uint32_t flags); // ht_scan.hip: called by ht_launch_pyramid after generation early_gen

@@ -139,9 +139,16 @@ typedef struct ht_kernel_time { /* per-kernel device time of the last ht_detect_
  * = the `cascade` argument of ccv.detect_objects (ccv.js:109; data: cascade.js:19). */
 ht_status ht_create(const ht_config *cfg, const void *cascade_blob, size_t cascade_len, ht_ctx **out);
 /* Lifetime of shared frame buffers: a buffer of ht_device_alloc that OTHER live contexts still have frames bound inside
- * (ht_bind_frames_device) is not freed by its owner's ht_destroy — it stays alive and is released by the ht_destroy after which no
- * live context is bound inside it.  The recommended order is still binders first, owner last.  A context must not be re-bound
- * concurrently (another thread) with the destruction / ht_device_free of the buffer it is bound to. */
+ * (ht_bind_frames_device) is not freed by its owner's ht_destroy — it stays alive as an orphan.  Orphans are looked at whenever a
+ * context's frames move — at the end of ht_upload_frames, ht_swap_frames, ht_bind_frames_device, ht_device_free, the bind form of the
+ * draw calls — and in every ht_destroy: an orphan that no live context is bound inside any more is released by that call, whichever
+ * context makes it.  Such a release waits for the orphan's whole device first (hipDeviceSynchronize: work of any context may still
+ * read it), so the call that happens to release one is slow once; while no orphan exists these calls pay one relaxed load.  The
+ * recommended order is still binders first, owner last.
+ * Threads: every context publishes where it is bound, and only that is read by other contexts' calls — contexts used by one thread
+ * each need no lock between them for any of this.  What remains a caller error: binding a context INTO a buffer (another thread)
+ * concurrently with the call that releases it — the ht_device_free or ht_destroy of its owner or, for an orphan, the call after
+ * which no context is bound inside it.  The release may have decided before the binding was published. */
 void ht_destroy(ht_ctx *ctx);
 /* Message of the last failure on ctx (ctx == NULL: last failure of ht_create on this thread). Never NULL. */
 const char *ht_last_error(const ht_ctx *ctx);

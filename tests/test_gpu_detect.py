@@ -409,6 +409,59 @@ def test_collect_best_requeue_matches_collect_best(cascade):
         c.close()
 
 
+@pytest.mark.parametrize("n", [4, 1])
+def test_collect_forms_share_no_state(cascade, n):
+    """the three collect forms in turn on ONE context: what a call was asked for (leave the per-frame order to its own pass; enqueue the next
+    batch) is an argument of that call, nothing of it is left for the next.  A plain collect behind a collect-best returns the full
+    emission order, the requeue rounds replay the captured graph, a plain collect takes the batch the last requeue left in flight, a
+    caller's buffer that is too small gets the FIRST hits of the ordered list with HT_ERR_CAPACITY."""
+    import ctypes as C
+
+    from headtrackr_amd.native import HIT_DTYPE
+
+    w, h = 320, 240
+    frames = synth.mixed_batch(8, w, h, seed0=1234)[[2, 3, 5, 7][:n]] if n > 1 else synth.face_frame(w, h, [(100, 60, 96)])[None]
+    frames = np.ascontiguousarray(frames)
+    ref = np.concatenate([oracle_hits(frames[i], cascade, i) for i in range(n)])
+    want_counts = [int((ref["frame"] == i).sum()) for i in range(n)]
+    assert len(ref) >= 4
+    c = Context()
+    try:
+        c.set_geometry(w, h, n)
+        c.upload(frames)
+        c.detect_enqueue()
+        best, total = c.detect_collect_best(1)  # 1: its per-frame order is deferred to its own pass
+        best = best.copy()
+        assert total == len(ref)
+        c.detect_enqueue()
+        hits, counts = c.detect_collect()  # 2: full emission order although the call before it deferred its sort
+        assert_hits_equal(hits, ref)
+        assert [int(v) for v in counts] == want_counts
+        assert best.tobytes() == c.best_faces(hits, counts, 1).tobytes() and (best["neighbors"] > 0).any()
+        c.detect_enqueue()
+        launches = c.graph_launches
+        for k in range(3):  # 3: every call collects one batch and starts the next; the later ones are replays
+            got, tot = c.detect_collect_best_requeue(1)
+            assert tot == len(ref) and got.tobytes() == best.tobytes(), k
+        assert c.graph_launches >= launches + 2
+        hits, counts = c.detect_collect()  # 4: the batch the last requeue left in flight; no requeue is left over
+        assert_hits_equal(hits, ref)
+        assert [int(v) for v in counts] == want_counts and c._lib.ht_frames_enqueued(c._h) == 0
+        c.detect_enqueue()
+        cap = len(ref) // 2  # 5: a buffer that is too small
+        buf, cnt, tot = np.zeros(cap, dtype=HIT_DTYPE), np.zeros(n, dtype=np.uint32), C.c_uint32(0)
+        assert c._lib.ht_detect_collect(c._h, buf.ctypes.data, cap, cnt.ctypes.data, C.byref(tot)) == -4  # HT_ERR_CAPACITY
+        assert tot.value == len(ref) and [int(v) for v in cnt] == want_counts
+        assert_hits_equal(buf, ref[:cap])
+        assert c._lib.ht_frames_enqueued(c._h) == 0  # collected all the same
+        c.detect_enqueue()
+        hits, counts = c.detect_collect()  # 6: and the full result once more
+        assert_hits_equal(hits, ref)
+        assert [int(v) for v in counts] == want_counts
+    finally:
+        c.close()
+
+
 def test_tiny_hit_capacity_reports_overflow(cascade):
     from headtrackr_amd.api import HtError
 

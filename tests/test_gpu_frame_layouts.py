@@ -428,3 +428,26 @@ def test_bad_strides_and_pointers_are_refused_and_leave_the_binding(name):
         c.close()
         p.free()
         other.free()
+
+
+def test_every_refusal_of_the_frame_and_detect_step_calls_is_the_recorded_one():
+    """tests/frame_refusal_cases.py's script — every refusal of the frame calls (upload, async upload, swap, bind, the allocation calls,
+    ht_device_free under another context's binding) and of the detect-step calls (enqueue, the three collect forms, the batch call, both
+    whitebalance calls), the adjacent double faults that pin each call's check order, ht_set_geometry not yet called — replayed on the
+    built library: status, ht_last_error text and ht_frames_bound() afterwards equal tests/golden/frame_call_refusals.json, which was
+    recorded before the calls moved out of csrc/ht_context.hip."""
+    import json
+    import os
+
+    import frame_refusal_cases as frc
+    from conftest import GOLDEN
+
+    golden = json.load(open(os.path.join(GOLDEN, "frame_call_refusals.json")))
+    got = frc.replay()
+    assert got["canvas"] == golden["canvas"]
+    assert list(got["cases"]) == list(golden["cases"]) and len(golden["cases"]) >= 100  # the script's order is part of the record
+    for key, want in golden["cases"].items():
+        assert got["cases"][key] == want, (key, got["cases"][key], want)
+    refused = [v for v in golden["cases"].values() if v[0] != 0]
+    assert len(refused) >= 95 and all(st in (HT_ERR_INVALID, -6) for st, _, _ in refused)
+    assert len({text for _, text, _ in refused}) >= 15  # the messages of all the calls, not one repeated

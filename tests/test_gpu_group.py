@@ -464,6 +464,50 @@ def test_neighbours_are_undisturbed(cascade):
         ref.close()
 
 
+@pytest.mark.parametrize("n", [4, 1])
+def test_device_grouped_collect_carries_the_whitebalance_sums(cascade, n):
+    """ht_detect_best_collect and its requeue form with HT_DETECT_WHITEBALANCE: the head they share with ht_detect_collect (one pinned copy,
+    the batch's channel sums behind it, one wait) gives them the whitebalance values and best records that ht_detect_collect +
+    ht_detect_whitebalance + ht_best_faces give for the same frames — and the oracle's values.  A requeued batch reports its OWN flag."""
+    w, h = 320, 240
+    frames = np.ascontiguousarray(np.stack([synth.face_frame(w, h, [(100 + 7 * s, 60 + s, 96)], gray=90 + 20 * s) for s in range(n)]))
+    want_wb = np.array([ho.whitebalance(f) for f in frames])
+    assert len(set(want_wb)) == n
+    host, dev = Context(), Context()
+    try:
+        host.set_geometry(w, h, n)
+        host.upload(frames)
+        host.detect_enqueue(HT_DETECT_WHITEBALANCE)
+        hits, counts = host.detect_collect()
+        assert np.array_equal(host.detect_whitebalance(), want_wb)
+        want_best = host.best_faces(hits, counts, 1)
+        assert len(hits) > 0 and (want_best["neighbors"] > 0).any()
+
+        dev.set_geometry(w, h, n)
+        dev.upload(frames)
+        dev.detect_enqueue(HT_DETECT_WHITEBALANCE)
+        dev.detect_best_enqueue(1, 0)
+        best, total = dev.detect_best_collect()
+        assert total == len(hits) and best.tobytes() == want_best.tobytes()
+        assert np.array_equal(dev.detect_whitebalance(), want_wb)
+        dev.detect_enqueue(HT_DETECT_WHITEBALANCE)
+        dev.detect_best_enqueue(1, 0)
+        best, total = dev.detect_best_collect_requeue(next_flags=0)  # collects a batch WITH the sums, starts one without
+        assert total == len(hits) and best.tobytes() == want_best.tobytes()
+        assert np.array_equal(dev.detect_whitebalance(), want_wb)  # the collected batch's, although the one in flight has none
+        best, total = dev.detect_best_collect_requeue(next_flags=HT_DETECT_WHITEBALANCE)  # ... and the other way round
+        assert total == len(hits) and best.tobytes() == want_best.tobytes()
+        with pytest.raises(HtError) as e:
+            dev.detect_whitebalance()
+        assert e.value.status == -6
+        best, total = dev.detect_best_collect()
+        assert total == len(hits) and best.tobytes() == want_best.tobytes()
+        assert np.array_equal(dev.detect_whitebalance(), want_wb)
+    finally:
+        host.close()
+        dev.close()
+
+
 @pytest.mark.skipif(NODE is None, reason="node is not installed")
 def test_device_grouping_from_node(tmp_path, cascade):
     """tests/js/group_gpu.js on the product addon: new ccv.DeviceBatch(.., {grouping: 'device'}) against the default route, the oracle's best
