@@ -6,7 +6,7 @@
 //       early_scan aux_stream queue_capacity_cfg nlevel_dims [w h]... [cw ch]
 //     (cw ch: the cascade's window, 24 24 when left out)
 //     plans every case, checks what the kernels rely on (check_plan below) and prints one JSON object per line: the scalar results, one
-//     CRC32 per table as ht_set_geometry uploads it, and the level sizes
+//     CRC32 per table as ht_set_geometry uploads it, the level sizes, and the largest bx / pass0 / scan-tile origin of the tile records
 //   geometry_plan_harness dims <cases>   one "name W H interval nlevel_dims [w h]..." per line: prints {"name", "status", "why"} of ht_check_level_dims,
 //     the validation ht_set_geometry runs on level_dims before it touches the current geometry
 //   geometry_plan_harness taps <tuples>  one "i r s origin" per line (r as a C hex float): prints "a b t u" of ht_host_tap (t, u as hex floats)
@@ -189,7 +189,12 @@ static int run_plan(const char *path) {
                    crc_of(P.tail_jobs), crc_of(P.tail_prefix), crc_of(P.tail_taps), crc_of(P.tail_taps_fast), crc_of(P.tail_tapref), crc32(&P.tail, sizeof(P.tail)),
                    crc_of(P.scales), crc_of(P.tile_recs));
             for (int i = 0; i < n; i++) printf("%s[%d,%d]", i ? "," : "", P.levels[i].w, P.levels[i].h);
-            printf("]");
+            // the largest values the 16-bit tile-record fields bx and pass0 take, and the largest scan-tile origin
+            int max_bx = 0, max_pass0 = 0, max_x0 = 0, max_y0 = 0;
+            for (auto &g : P.gen_tiles)
+                for (auto &t : g) max_bx = std::max(max_bx, (int)t.bx), max_pass0 = std::max(max_pass0, (int)t.pass0);
+            for (auto &r : P.tile_recs) max_x0 = std::max(max_x0, (int)(r.origin & 0xffff)), max_y0 = std::max(max_y0, (int)(r.origin >> 16));
+            printf("],\"max_bx\":%d,\"max_pass0\":%d,\"max_tile_x0\":%d,\"max_tile_y0\":%d", max_bx, max_pass0, max_x0, max_y0);
         }
         printf("}\n");
     }
